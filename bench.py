@@ -14,6 +14,11 @@ N > 1   one rank per GPU.  `--gpus N` starts the N ranks itself (torch.distribut
         configs[3] -- ONE 1M-triangle 3840x2160 frame split by screen-tile rows across the ranks, the finished BGRA8
         bands exchanged over RCCL / xGMI through the C ABI (mirhi_comm_all_gather_bands): strong scaling of a frame.
         `--split none` measures alternate-frame rendering instead (whole frames per rank, no collective, weak scaling).
+
+A plain run sets up, warms up, times the --steps steps, writes the last step's frame if --dump-outputs is given and prints the line.
+Everything else it can measure or check -- the timed frames against the CPU oracle, the per-dispatch kernel passes behind the
+roofline, timelines and fragment statistics, the secondary loops (batched, re-recorded, resubmitted, two frames in flight), the
+other workloads, the one-GPU point of a split run and the CPU baseline -- runs only with --full.
 """
 from __future__ import annotations
 
@@ -95,7 +100,35 @@ def parse_args():
     ap.add_argument("--prewarm-seconds", type=float, default=1.0, help="untimed frame loop in front of the warm-up steps (GPU clock ramp)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: verification against the oracle, per-dispatch kernel passes (roofline, timelines, overdraw), "
+                         "the secondary measurements and the CPU baseline (--profile-pass-only runs the kernel passes without it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame the last timed step rendered to DIR/*.npy (float32; a fixed, seeded sample of its pixels "
+                         "when the whole frame would exceed 64 MB)")
+    args = ap.parse_args()
+    if args.timeline_out and not (args.full or args.profile_pass_only):
+        ap.error("--timeline-out comes from the per-dispatch passes: add --full")
+    return args
+
+
+DUMP_LIMIT_BYTES = 48 << 20          # under the 64 MB a dump may take
+
+
+def dump_frame(img, out_dir: str) -> None:
+    """The colour target the last timed frame rendered into, as a caller reads it back (B8G8R8A8 codes or linear RGBA floats), in
+    float32: DIR/color.npy (height x width x 4), or -- when that would exceed DUMP_LIMIT_BYTES -- DIR/color_sample.npy (pixels x 4) at
+    pixel indices drawn without replacement by numpy's default_rng(0), sorted (the same pixels for every run of the same shape)."""
+    import numpy as np
+    px = img.read().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    if px.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "color.npy"), px)
+        return
+    flat = px.reshape(-1, px.shape[-1])
+    keep = DUMP_LIMIT_BYTES // flat[0].nbytes
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=keep, replace=False))
+    np.save(os.path.join(out_dir, "color_sample.npy"), flat[idx])
 
 
 def spawn_ranks(args) -> int:
@@ -432,12 +465,16 @@ def main():
     barrier()
     dt = max_over_ranks(max(time.perf_counter() - t0, 1e-9))
     stats_after = dev.stats()
+    if args.dump_outputs and rank == 0 and not args.profile_pass_only:
+        last = floop.last_image()[0] if floop is not None else rig.groups[(rig.counter // per_submit - 1) % len(rig.groups)][-1].color
+        dump_frame(last, args.dump_outputs)
+    kernel_passes = args.full or args.profile_pass_only      # the per-dispatch passes and the figures taken from them
 
     # ---- the frames the timed region produced, against the oracle (the checker; never inside the timed region) ------------------------
     # every colour target the loop rendered into (the swapchain images of the re-recorded loop / each lane's target of the resubmitted one) is read
     # back and compared with the frame the CPU oracle renders of the same scene: <= 1 code per channel of the sRGB8 target, 1e-4 on a float one.
     verify = None
-    if world == 1 and not args.profile_pass_only and not split:
+    if args.full and world == 1 and not args.profile_pass_only and not split:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_binding as ob
@@ -458,7 +495,7 @@ def main():
         except Exception as e:
             verify = {"frames_verified": 0, "error": repr(e)}
 
-    if split and not args.profile_pass_only:
+    if args.full and split and not args.profile_pass_only:
         # every rank must now hold the same, complete frame
         chk = torch.stack([f[:scene.height].to(torch.int64).sum() for f in rig.frames]).cpu() if bpp == 4 else None
         if chk is not None and world > 1:
@@ -470,41 +507,42 @@ def main():
             if not torch.equal(lo.cpu(), hi.cpu()):
                 raise SystemExit("bench.py: the ranks disagree about the gathered frame (checksums differ): the band exchange is broken")
 
-    # ---- per-dispatch device time (event pair attached to each dispatch: begin -> end on the GPU clock) -------------------
-    prof_frames = max(64, min(1024, fps))
-    # (a) one frame in flight: isolated kernel durations (kernels of different frames cannot stretch each other)
-    dev.wait_idle()
-    dev.reset_kernel_times()
-    dev.set_profiling(m.Profile.TIMING)
-    for _ in range(prof_frames):
-        rig.slots[0].render()
-        if args.profile_pass_only:
-            dev.wait_idle()                   # (under a tracer / counter collection: strictly one frame on the GPU at a time)
-    dev.wait_idle()
-    iso = {name: dev.kernel_time(k) for k, name in enumerate(m.Kernel.NAMES)}
-    iso_tl = summarize_timeline(dev.timeline(), m.Kernel.NAMES)
-    # (b) the timed region's conditions: all lanes in flight (no band exchange: kernels only)
-    dev.reset_kernel_times()
-    flight_tl_raw = []
-    if not args.profile_pass_only:
-        for _ in range(prof_frames):
-            rig.slots[rig.next_slot()].render()
+    iso, iso_tl, flight_tl, shaded, covered, stat_frames = None, None, None, 0, 0, 2
+    if kernel_passes:
+        # ---- per-dispatch device time (event pair attached to each dispatch: begin -> end on the GPU clock) -------------------
+        prof_frames = max(64, min(1024, fps))
+        # (a) one frame in flight: isolated kernel durations (kernels of different frames cannot stretch each other)
         dev.wait_idle()
-        flight_tl_raw = dev.timeline()
-    flight_tl = summarize_timeline(flight_tl_raw, m.Kernel.NAMES)
-    dev.set_profiling(0)
-    if args.timeline_out and rank == 0:
-        with open(args.timeline_out, "w") as f:
-            json.dump({"kernels": m.Kernel.NAMES, "frames_in_flight": nfif, "dispatches": flight_tl_raw}, f)
-    # (c) fragment statistics: never part of a timed frame
-    dev.reset_kernel_times()
-    shaded, covered, stat_frames = 0, 0, 2
-    if not args.profile_pass_only:
-        dev.set_profiling(m.Profile.FRAGMENTS)
-        for _ in range(stat_frames):
+        dev.reset_kernel_times()
+        dev.set_profiling(m.Profile.TIMING)
+        for _ in range(prof_frames):
             rig.slots[0].render()
+            if args.profile_pass_only:
+                dev.wait_idle()                   # (under a tracer / counter collection: strictly one frame on the GPU at a time)
+        dev.wait_idle()
+        iso = {name: dev.kernel_time(k) for k, name in enumerate(m.Kernel.NAMES)}
+        iso_tl = summarize_timeline(dev.timeline(), m.Kernel.NAMES)
+        # (b) the timed region's conditions: all lanes in flight (no band exchange: kernels only)
+        dev.reset_kernel_times()
+        flight_tl_raw = []
+        if not args.profile_pass_only:
+            for _ in range(prof_frames):
+                rig.slots[rig.next_slot()].render()
+            dev.wait_idle()
+            flight_tl_raw = dev.timeline()
+        flight_tl = summarize_timeline(flight_tl_raw, m.Kernel.NAMES)
         dev.set_profiling(0)
-        shaded, covered, _scopes = dev.fragment_stats()
+        if args.timeline_out and rank == 0:
+            with open(args.timeline_out, "w") as f:
+                json.dump({"kernels": m.Kernel.NAMES, "frames_in_flight": nfif, "dispatches": flight_tl_raw}, f)
+        # (c) fragment statistics: never part of a timed frame
+        dev.reset_kernel_times()
+        if not args.profile_pass_only:
+            dev.set_profiling(m.Profile.FRAGMENTS)
+            for _ in range(stat_frames):
+                rig.slots[0].render()
+            dev.set_profiling(0)
+            shaded, covered, _scopes = dev.fragment_stats()
     dev.reset_kernel_times()
     stats = dev.stats()
     dispatch_path = dev.dispatch_path()
@@ -513,7 +551,7 @@ def main():
     if verify is not None:
         extras["frames_verified"] = verify.pop("frames_verified")
         extras["verification"] = verify
-    if world == 1 and per_submit == 1 and not args.no_extras and not args.profile_pass_only:
+    if args.full and world == 1 and per_submit == 1 and not args.no_extras and not args.profile_pass_only:
         # the same frame loop with 8 command buffers per mirhi_queue_submit call (vkQueueSubmit with several command buffers): the
         # frames of a call share one batch of launches.  Same device and queue lanes (a second device would be dealt other hardware
         # queues); reported beside the headline, which keeps one frame per submit.
@@ -564,7 +602,7 @@ def main():
                 "command_buffers": len(slots_), "queue_lanes": len(slots_), "fence_gated": False, "frames": frames_,
                 "note": "recorded once, resubmitted round-robin without waiting on fences (the lanes queue up)"}
 
-    if world == 1 and per_submit == 1 and not args.no_extras and not args.profile_pass_only:
+    if args.full and world == 1 and per_submit == 1 and not args.no_extras and not args.profile_pass_only:
         try:
             if floop is not None:
                 floop.destroy()
@@ -615,7 +653,7 @@ def main():
                 sl.cmd.set_queue_lane(i % nfif)
         except Exception as e:
             extras["frames_in_flight_2"] = {"error": repr(e)}
-    if world == 1 and per_submit == 1 and not args.no_extras and not args.profile_pass_only and args.other_workloads:
+    if args.full and world == 1 and per_submit == 1 and not args.no_extras and not args.profile_pass_only and args.other_workloads:
         # The other single-GPU BASELINE workloads, one short pass each on the same device and queue lanes (the headline fields above stay
         # the C2 figures): frame loop of pre-recorded command buffers with `nfif` frames in flight, the reference-shaped re-recorded loop,
         # and the isolated kernel durations behind their own roofline.
@@ -663,7 +701,7 @@ def main():
             except Exception as e:
                 wl_out[other] = {"error": repr(e)}
         extras["workloads"] = wl_out
-    if world > 1 and split and not args.no_extras and not args.profile_pass_only:
+    if args.full and world > 1 and split and not args.no_extras and not args.profile_pass_only:
         try:
             # the same workload, whole frame on ONE GPU (every rank renders its own unsplit copy, no exchange): the N = 1 point of the
             # curve.  Same device and queue lanes, re-recorded without the split.
@@ -691,20 +729,42 @@ def main():
     if rank == 0:
         frames_total = args.steps * fps * (1 if split or world == 1 else world)
         value = tris * frames_total / dt / 1e6
-        alg_bytes = scene.algorithmic_bytes(bpp_out=bpp)
-        if split:   # all geometry + this rank's share of the frame buffer
-            alg_bytes = alg_bytes - scene.width * scene.height * bpp + scene.width * scene.height * bpp // world
-        ras_ms, ras_n = iso["raster"]
-        geo_ms, geo_n = iso["geometry"]
-        vs_ms, vs_n = iso["vertex"]
-        ras_us = 1e3 * ras_ms / max(1, ras_n)
-        geo_us = 1e3 * geo_ms / max(1, geo_n)
-        vs_us = 1e3 * vs_ms / max(1, vs_n)
-        achieved = alg_bytes / (ras_us * 1e-6) / 1e9 if ras_us > 0 else 0.0
-        frame_us = ras_us + geo_us + vs_us
         src_hash = mbuild.source_hash()
-        traffic, traffic_note = (None, "split run") if split else measured_traffic(wname, src_hash)
-        shaded_per_frame = shaded / max(1, stat_frames)
+        figures = {}
+        if kernel_passes:
+            alg_bytes = scene.algorithmic_bytes(bpp_out=bpp)
+            if split:   # all geometry + this rank's share of the frame buffer
+                alg_bytes = alg_bytes - scene.width * scene.height * bpp + scene.width * scene.height * bpp // world
+            ras_ms, ras_n = iso["raster"]
+            geo_ms, geo_n = iso["geometry"]
+            vs_ms, vs_n = iso["vertex"]
+            ras_us = 1e3 * ras_ms / max(1, ras_n)
+            geo_us = 1e3 * geo_ms / max(1, geo_n)
+            vs_us = 1e3 * vs_ms / max(1, vs_n)
+            achieved = alg_bytes / (ras_us * 1e-6) / 1e9 if ras_us > 0 else 0.0
+            frame_us = ras_us + geo_us + vs_us
+            traffic, traffic_note = (None, "split run") if split else measured_traffic(wname, src_hash)
+            shaded_per_frame = shaded / max(1, stat_frames)
+            figures = {
+                "shaded_mpix_per_s": round(shaded_per_frame * frames_total / dt / 1e6, 1),
+                "overdraw": round(covered / shaded, 4) if shaded else None,
+                "shaded_pixels_per_frame": int(shaded_per_frame), "covered_fragments_per_frame": int(covered / max(1, stat_frames)),
+                "roofline": {"bound": "hbm", "kernel": "raster_kernel", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5),
+                             "traffic": traffic["frame_hbm_bytes"] if traffic else None, "traffic_scope": "whole frame: vertex + geometry + raster kernels",
+                             "traffic_structural": traffic.get("structural_bytes") if traffic else None,   # algorithmic bytes + the intermediate streams (shaded vertices, bin records) written once and read once
+                             "traffic_source": traffic_note, "kernel_source_sha16": src_hash,
+                             "algorithmic_bytes_per_launch": alg_bytes, "avg_kernel_us": round(ras_us, 3),
+                             "geometry_kernel_us": round(geo_us, 3), "vertex_kernel_us": round(vs_us, 3),
+                             "frame_kernels_us": round(frame_us, 3),
+                             "frame_frac": round(alg_bytes / (frame_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 5) if frame_us > 0 else None,
+                             "issue": issue_bound((traffic or {}).get("instructions", {}).get("raster_kernel"), ras_us),
+                             "timed_launches": ras_n,
+                             "how": "event pair attached to every dispatch (hipExtLaunchKernelGGL start/stop events = the dispatch's begin and end on "
+                                    "the GPU clock, as rocprofv3 --kernel-trace reports them; nothing subtracted); a pass of frames behind the timed "
+                                    "region with ONE frame in flight, so kernels of different frames do not stretch each other"},
+                "timeline_isolated": iso_tl, "timeline_in_flight": flight_tl,
+            }
         out = {
             "metric": "Mtris/s at 1920x1080 (input triangles per second, whole frame incl. shading + store)"
                       if scene.height == 1080 else "Mtris/s (input triangles per second, whole frame incl. shading + store)",
@@ -725,29 +785,12 @@ def main():
             "dispatch_path": dispatch_path, "native_dispatches": int(stats_after.native_dispatches - stats_before.native_dispatches) & 0xFFFFFFFF,
             "frames_submitted": int(stats_after.frames_submitted - stats_before.frames_submitted),
             "build_id": build_id, "build_matches_sources": build_id == src_hash,
-            "shaded_mpix_per_s": round(shaded_per_frame * frames_total / dt / 1e6, 1),
-            "overdraw": round(covered / shaded, 4) if shaded else None,
-            "shaded_pixels_per_frame": int(shaded_per_frame), "covered_fragments_per_frame": int(covered / max(1, stat_frames)),
             "target_mpix_per_s": round(scene.width * scene.height * frames_total / dt / 1e6, 1),
-            "roofline": {"bound": "hbm", "kernel": "raster_kernel", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic["frame_hbm_bytes"] if traffic else None, "traffic_scope": "whole frame: vertex + geometry + raster kernels",
-                         "traffic_structural": traffic.get("structural_bytes") if traffic else None,   # algorithmic bytes + the intermediate streams (shaded vertices, bin records) written once and read once
-                         "traffic_source": traffic_note, "kernel_source_sha16": src_hash,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_kernel_us": round(ras_us, 3),
-                         "geometry_kernel_us": round(geo_us, 3), "vertex_kernel_us": round(vs_us, 3),
-                         "frame_kernels_us": round(frame_us, 3),
-                         "frame_frac": round(alg_bytes / (frame_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 5) if frame_us > 0 else None,
-                         "issue": issue_bound((traffic or {}).get("instructions", {}).get("raster_kernel"), ras_us),
-                         "timed_launches": ras_n,
-                         "how": "event pair attached to every dispatch (hipExtLaunchKernelGGL start/stop events = the dispatch's begin and end on "
-                                "the GPU clock, as rocprofv3 --kernel-trace reports them; nothing subtracted); a pass of frames behind the timed "
-                                "region with ONE frame in flight, so kernels of different frames do not stretch each other"},
-            "timeline_isolated": iso_tl, "timeline_in_flight": flight_tl,
             "workspace_mb": round(stats.workspace_bytes / 1e6, 1), "big_list": stats.last_big_list,
         }
+        out.update(figures)
         out.update(extras)
-        if not args.no_cpu_baseline and world == 1 and not args.profile_pass_only:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.profile_pass_only:
             try:
                 out["cpu_baseline"] = cpu_baseline(scene, args.cpu_seconds)
             except Exception as e:  # the oracle is a reported baseline, never the measured path

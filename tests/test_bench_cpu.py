@@ -61,3 +61,43 @@ def test_world_size_mismatch_is_refused():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "refusing to report" in (r.stderr + r.stdout)
+
+
+def test_plain_run_is_the_default_and_full_is_asked_for(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert not args.full and args.steps == 7 and args.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse_args().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--timeline-out", "t.json"])   # the timeline comes from the passes --full runs
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
+class _Frame:
+    def __init__(self, px):
+        self.px = px
+
+    def read(self):
+        return self.px
+
+
+def test_dump_writes_the_frame_as_float32(tmp_path):
+    import numpy as np
+    px = np.random.default_rng(1).integers(0, 256, size=(9, 13, 4), dtype=np.uint8)
+    bench.dump_frame(_Frame(px), str(tmp_path / "d"))
+    got = np.load(tmp_path / "d" / "color.npy")
+    assert got.dtype == np.float32 and got.shape == (9, 13, 4) and np.array_equal(got, px.astype(np.float32))
+
+
+def test_dump_of_a_large_frame_is_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 100)            # 100 RGBA float32 pixels
+    px = np.arange(40 * 30 * 4, dtype=np.float32).reshape(40, 30, 4)
+    bench.dump_frame(_Frame(px), str(tmp_path / "a"))
+    bench.dump_frame(_Frame(px), str(tmp_path / "b"))
+    a, b = np.load(tmp_path / "a" / "color_sample.npy"), np.load(tmp_path / "b" / "color_sample.npy")
+    assert not (tmp_path / "a" / "color.npy").exists()
+    assert a.dtype == np.float32 and a.shape == (100, 4) and np.array_equal(a, b)
+    pix = a[:, 0] / 4                                                    # pixel index of each row (the values count up)
+    assert np.all(np.diff(pix) > 0) and np.array_equal(a, px.reshape(-1, 4)[pix.astype(np.int64)])

@@ -359,13 +359,15 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), n
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/assets/textures"), reason="reference assets are not on this machine")
 def test_reference_asset_textures_decode_like_pillow():
-    """every texture file the reference ships (assets/textures/*, the dancer's normal map): PNG and JPEG, bit for bit"""
+    """texture files the reference ships, one of each kind its assets/textures/* holds (tests/golden/textures: RGBA PNG, RGB and
+    greyscale baseline JPEG) and the dancer's normal map (RGB PNG): bit for bit"""
     import glob
     from PIL import Image
-    files = sorted(glob.glob("/root/reference/assets/textures/*/*.*") + glob.glob("/root/reference/assets/models/*/textures/*.*"))
-    assert len(files) >= 22                                           # includes the 4096x4096 normal map
+    golden = os.path.join(ROOT, "tests", "golden")
+    files = sorted(glob.glob(os.path.join(golden, "textures", "*.png")) + glob.glob(os.path.join(golden, "textures", "*.jpg"))
+                   + glob.glob(os.path.join(golden, "dancer", "textures", "*.png")))
+    assert len(files) == 5
     for f in files:
         got = images.load_image(f)
         ref = np.asarray(Image.open(f).convert("RGBA"))

@@ -119,19 +119,36 @@ def _split_worker(rank, world, port, out_dir, width=200, height=150):
     dist.destroy_process_group()
 
 
+def _spawn_ranks(world, *args):
+    """Runs _split_worker(rank, world, *args) for every rank, each in a fresh interpreter, and waits for all of them.  Not torch.multiprocessing:
+    importing torch into this process, after the GPU tests have loaded libmirhi.so and the HIP / ROCr runtimes it links, would load torch's own
+    copies of those runtimes beside them, and with a GPU present two copies in one process corrupt its heap when it exits.  The ranks import
+    torch themselves."""
+    import multiprocessing
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=_split_worker, args=(rank, world) + args) for rank in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(timeout=600)
+    for p in procs:
+        if p.is_alive():
+            p.kill()
+            p.join()
+    assert [p.exitcode for p in procs] == [0] * world
+
+
 def test_tile_row_split_all_gather_world2(tmp_path):
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_split_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    _spawn_ranks(2, port, str(tmp_path))
     assert open(tmp_path / "rank0.txt").read() == "ok" and open(tmp_path / "rank1.txt").read() == "ok"
 
 
 def test_tile_row_split_world4_uneven_last_band(tmp_path):
     """1080 rows = 34 tile rows over 4 ranks: bands of 9, 9, 9 and 7 tile rows (288, 288, 288, 216 pixel rows) -- the padded
     in-place all-gather and the direct exchange of unequal bands both reassemble the oracle's full frame on every rank."""
-    import torch.multiprocessing as mp
     from renderer_rs_amd import multigpu
     assert [multigpu.band_rows(1080, r, 4) for r in range(4)] == [(0, 288), (288, 576), (576, 864), (864, 1080)]
     port = _free_port()
-    mp.spawn(_split_worker, args=(4, port, str(tmp_path), 96, 1080), nprocs=4, join=True)
+    _spawn_ranks(4, port, str(tmp_path), 96, 1080)
     assert [open(tmp_path / f"rank{r}.txt").read() for r in range(4)] == ["ok"] * 4

@@ -4,7 +4,7 @@
 LIBS=$1; R=${2:-3}; shift 2
 for r in $(seq 1 $R); do
   for L in $LIBS; do
-    MIRHI_LIB_NAME=$L python bench.py --no-cpu-baseline --other-workloads c3 "$@" 2>/dev/null | python -c "
+    MIRHI_LIB_NAME=$L python bench.py --full --no-cpu-baseline --other-workloads c3 "$@" 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.readline()); rf=j['roofline']; w=j.get('workloads',{}).get('c3',{})
 print('%-20s' % '$L', 'round $r', 'c2', j['value'], 'rerec4', j['rerecorded_submit']['value'], 'rerec2', j['frames_in_flight_2']['rerecorded']['value'], 'lanes2', j['frames_in_flight_2']['resubmitted']['value'],

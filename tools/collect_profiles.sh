@@ -30,14 +30,14 @@ for w in $loads; do
 done
 if [ "$part" = a ]; then
   # the deep-queue loop (command buffers recorded once, resubmitted on four lanes) under the tracer: overlap of consecutive raster kernels
-  rocprofv3 --kernel-trace --output-format csv -d $out/trace -- python3 bench.py --gpus 1 --steps 4 --warmup 2 --no-cpu-baseline --no-extras --resubmit > $out/bench_traced.json 2> $out/trace.err
+  rocprofv3 --kernel-trace --output-format csv -d $out/trace -- python3 bench.py --full --gpus 1 --steps 4 --warmup 2 --no-cpu-baseline --no-extras --resubmit > $out/bench_traced.json 2> $out/trace.err
   # native dispatch (hand-written AQL packets) under counter collection: the queue the library gets is a tool's proxy (mirhi_api.hip, native_queue_is_proxy); with
   # MIRHI_NATIVE_DISPATCH=2 it dispatches natively all the same -- every wait bounded (MIRHI_NATIVE_TIMEOUT_MS) -- and the frames' kernels show up on a queue of their own
   MIRHI_NATIVE_DISPATCH=2 MIRHI_NATIVE_TIMEOUT_MS=5000 timeout -k 10 240 rocprofv3 --kernel-trace --pmc SQ_WAVES --output-format csv -d $out/pmc_native -- python3 bench.py --workload c2 --profile-pass-only --no-cpu-baseline > $out/bench_pmc_native.json 2> $out/pmc_native.err || echo "pmc_native run failed: rc $?"
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --timeline-out $out/timeline_in_flight.json > $out/bench_default.json 2> $out/bench_default.err
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --timeline-out $out/timeline_in_flight.json > $out/bench_default.json 2> $out/bench_default.err
   python3 tools/make_profile_summaries.py $tag $out/summary --workloads=c2,c3 > $out/summary_a.log 2>&1 || tail -5 $out/summary_a.log
 else
-  for w in c3 c4 c5; do python3 bench.py --workload $w --cpu-seconds 8 > $out/bench_$w.json 2>/dev/null; echo "bench $w done"; done
+  for w in c3 c4 c5; do python3 bench.py --full --workload $w --cpu-seconds 8 > $out/bench_$w.json 2>/dev/null; echo "bench $w done"; done
   # the tile split, every rank of world 2 / 4 / 8 in turn on this one GPU, both layouts (an emulation: tools/split_times.py)
   python3 tools/split_times.py --json $out/summary/${tag}_split_times_one_gpu_emulation.json > $out/summary/${tag}_split_times_one_gpu_emulation.txt 2>&1 || tail -3 $out/summary/${tag}_split_times_one_gpu_emulation.txt
   python3 tools/make_profile_summaries.py $tag $out/summary --workloads=c4,c5 --no-trace > $out/summary_b.log 2>&1 || tail -5 $out/summary_b.log
