@@ -10,9 +10,9 @@ use std::sync::Arc;
 #[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum StoreOp { Store = 0, DontCare = 1 }
 #[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum IndexType { Uint16 = 0, Uint32 = 1 }
 /// The registers of the HLSL the reference binds through descriptor sets (b0..b3, t0/t1 space1): INTEGRATION.md section 4.
-#[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum UniformSlot { Camera = 0, Object = 1, Lights = 2, Material = 3, PointLights = 4, SpotLights = 5 }
+#[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum UniformSlot { Camera = 0, Object = 1, Lights = 2, Material = 3, PointLights = 4, SpotLights = 5, ShadowData = 6 }
 /// model_pbr.hlsl:62-95 slot order
-#[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum TextureSlot { Albedo = 0, Normal = 1, MetallicRoughness = 2, Occlusion = 3, Emissive = 4 }
+#[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum TextureSlot { Albedo = 0, Normal = 1, MetallicRoughness = 2, Occlusion = 3, Emissive = 4, ShadowMap = 5 }
 
 #[derive(Clone, Copy, Debug)] pub struct Viewport { pub x: f32, pub y: f32, pub width: f32, pub height: f32, pub min_depth: f32, pub max_depth: f32 }
 #[derive(Clone, Copy, Debug)] pub struct Rect2D { pub x: i32, pub y: i32, pub width: u32, pub height: u32 }
@@ -68,6 +68,16 @@ impl CommandBuffer {
         ri.depth_image = info.depth.map_or(std::ptr::null_mut(), |d| d.raw);
         ri.depth_load_op = info.depth_load_op as i32; ri.depth_store_op = info.depth_store_op as i32; ri.clear_depth = info.clear_depth;
         ri.render_area = [info.render_area.x, info.render_area.y, info.render_area.width as i32, info.render_area.height as i32];
+        check(unsafe { mirhi_sys::mirhi_cmd_begin_rendering(self.raw, &ri) })
+    }
+    /// A depth-only scope (shadow pass, ShaderProgram::Shadow draws only): no colour attachment, `depth` stored; its extent is the render area.
+    pub fn begin_rendering_depth_only(&self, depth: &Image, depth_load_op: LoadOp, clear_depth: f32) -> RhiResult<()> {
+        let mut ri = std::mem::MaybeUninit::<mirhi_sys::mirhi_rendering_info>::zeroed();
+        unsafe { mirhi_sys::mirhi_rendering_info_default(ri.as_mut_ptr()) };
+        let mut ri = unsafe { ri.assume_init() };
+        ri.color_image = std::ptr::null_mut();
+        ri.depth_image = depth.raw;
+        ri.depth_load_op = depth_load_op as i32; ri.depth_store_op = StoreOp::Store as i32; ri.clear_depth = clear_depth;
         check(unsafe { mirhi_sys::mirhi_cmd_begin_rendering(self.raw, &ri) })
     }
     pub fn end_rendering(&self) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_cmd_end_rendering(self.raw) }) }  // :417

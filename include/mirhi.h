@@ -28,7 +28,9 @@ extern "C" {
 
 #define MIRHI_ABI_VERSION 5u     /* 3: mirhi_pipeline_desc.fragment_discard_enable; 4: mirhi_device_set_submit_thread; 5: mirhi_device_set_native_dispatch,
                                     mirhi_device_dispatch_path, mirhi_device_measure_roundtrip, mirhi_build_id, mirhi_device_set_tile_split_layout,
-                                    mirhi_device_split_rows, mirhi_device_stats grew four words */
+                                    mirhi_device_split_rows, mirhi_device_stats grew four words;
+                                    still 5 (new enum values only): MIRHI_PROGRAM_SHADOW, MIRHI_SLOT_SHADOW_DATA, MIRHI_TEXTURE_SHADOW_MAP, depth-only
+                                    pipelines (colour format UNDEFINED) and depth-only rendering scopes (color_image NULL) */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -75,7 +77,9 @@ mirhi_result mirhi_device_wait_idle(mirhi_device* dev);                   /* Dev
 mirhi_result mirhi_device_destroy(mirhi_device* dev);                     /* fails if children are alive */
 mirhi_result mirhi_device_name(mirhi_device* dev, char* out, uint32_t out_len);
 /* screen-tile-row split: this device rasterizes only the tile rows owned by `rank` of `world` (which ones: the
- * layout below); rank 0 / world 1 = whole frame.  Gathering the rows is mirhi_comm_all_gather_bands, or the caller's collective. */
+ * layout below); rank 0 / world 1 = whole frame.  Gathering the rows is mirhi_comm_all_gather_bands, or the caller's collective.
+ * Depth-only scopes (shadow maps, MIRHI_PROGRAM_SHADOW) are not split: every rank renders the whole depth image, because each rank's
+ * rows of a shadowed MODEL_PBR scope may sample any texel of it. */
 mirhi_result mirhi_device_set_tile_split(mirhi_device* dev, uint32_t rank, uint32_t world);
 /* Which tile rows a rank gets.  BANDS: one contiguous band of ceil(tile rows / world) rows per rank (the last rank's may be short).  INTERLEAVED (the
  * default; MIRHI_SPLIT=bands|interleaved in the environment sets another default): rank r owns tile rows r, r + world, r + 2 world, ... -- every rank then
@@ -161,7 +165,17 @@ typedef enum {   /* replaces Shader::from_spirv_file (shader.rs:244-330): precom
     MIRHI_PROGRAM_TRIANGLE = 0,     /* vertex/triangle.hlsl + pixel/triangle.hlsl */
     MIRHI_PROGRAM_MODEL = 1,        /* vertex/model.hlsl + pixel/model.hlsl (hard-coded fallback light/material) */
     MIRHI_PROGRAM_MODEL_FULL = 2,   /* vertex/model.hlsl + pixel/model_full.hlsl + lights.hlsli */
-    MIRHI_PROGRAM_MODEL_PBR = 3     /* vertex/model.hlsl + pixel/model_pbr.hlsl + pbr.hlsli (Cook-Torrance GGX; no shadow pass: shadow = 1) */
+    MIRHI_PROGRAM_MODEL_PBR = 3,    /* vertex/model.hlsl + pixel/model_pbr.hlsl + pbr.hlsli (Cook-Torrance GGX); the directional light is multiplied
+                                       by CalculateShadow (shadow.hlsli:49-121, model_pbr.hlsl:238-251) when MIRHI_TEXTURE_SHADOW_MAP is bound, else shadow = 1 */
+    MIRHI_PROGRAM_SHADOW = 4        /* vertex/shadow.hlsl + pixel/shadow.hlsl: depth-only pass in light space.  Reads ShadowConstants (vertex/shadow.hlsl:7-11:
+                                       lightSpaceMatrix @0, model @64, 128 B) from the b0 slot MIRHI_SLOT_CAMERA; position only, attribute_offsets[0] = 0 of
+                                       attribute_count 1, any vertex_stride >= 12 that is a multiple of 4 (a packed position stream or the 48-byte Vertex).
+                                       Clip = lightSpaceMatrix * (model * p), in the MODEL vertex path's operation order (vertex/model.hlsl:44-48): a SHADOW
+                                       draw and a MODEL draw with viewProjection = lightSpaceMatrix give the same depth bits.
+                                       Pipelines: vertex = fragment = SHADOW, color_attachment_count 1 with color_attachment_formats[0] = UNDEFINED (Vulkan's
+                                       "no attachment at this location"), depth D32_SFLOAT with test and write on and LESS / LESS_OR_EQUAL / GREATER /
+                                       GREATER_OR_EQUAL; no blending, no fragment discard.  SHADOW draws are recorded only in depth-only scopes
+                                       (mirhi_rendering_info.color_image NULL) and only SHADOW draws there. */
 } mirhi_program;
 typedef enum { MIRHI_TOPOLOGY_POINT_LIST = 0, MIRHI_TOPOLOGY_LINE_LIST = 1, MIRHI_TOPOLOGY_LINE_STRIP = 2,
                MIRHI_TOPOLOGY_TRIANGLE_LIST = 3, MIRHI_TOPOLOGY_TRIANGLE_STRIP = 4, MIRHI_TOPOLOGY_TRIANGLE_FAN = 5 } mirhi_topology;   /* pipeline.rs:274-300 */
@@ -224,7 +238,8 @@ typedef enum { MIRHI_STORE_OP_STORE = 0, MIRHI_STORE_OP_DONT_CARE = 1 } mirhi_st
 typedef enum { MIRHI_INDEX_UINT16 = 0, MIRHI_INDEX_UINT32 = 1 } mirhi_index_type;
 
 typedef struct {     /* RenderingConfig / ColorAttachment / DepthAttachment (rendering.rs:65-115,319-370,680-726) */
-    mirhi_image* color_image;        /* required */
+    mirhi_image* color_image;        /* required -- except in a depth-only scope (MIRHI_PROGRAM_SHADOW): NULL with a depth_image, whose extent is then the
+                                        render area; depth load CLEAR / LOAD, store STORE; no prim_id_image */
     int32_t      color_load_op;      /* default CLEAR  rendering.rs:106 */
     int32_t      color_store_op;     /* default STORE  :107 */
     float        clear_color[4];     /* default (0,0,0,1) :108-112 */
@@ -248,11 +263,20 @@ typedef enum {
     MIRHI_SLOT_MATERIAL = 3,      /* b3 MaterialData 32 B (model_full.hlsl:34-41); 80 B for MODEL_PBR (model_pbr.hlsl:36-59) */
     MIRHI_SLOT_POINT_LIGHTS = 4,  /* t0,space1 StructuredBuffer<PointLight> */
     MIRHI_SLOT_SPOT_LIGHTS = 5,   /* t1,space1 StructuredBuffer<SpotLight> */
-    MIRHI_SLOT_COUNT = 6
+    MIRHI_SLOT_SHADOW_DATA = 6,   /* ShadowData: ShadowParams 96 B (shadow.hlsli:20-30, model_pbr.hlsl:110-115): LightSpaceMatrix @0 (the convention of
+                                     CameraData.viewProjection), ShadowBias @64, NormalBias @68, ShadowMapSize @72, ShadowStrength @80.  Required (>= 96 B)
+                                     by a MODEL_PBR draw recorded with MIRHI_TEXTURE_SHADOW_MAP bound */
+    MIRHI_SLOT_COUNT = 7
 } mirhi_uniform_slot;
+/* MIRHI_TEXTURE_SHADOW_MAP: t7 / s5 of model_pbr.hlsl:103-108, D32_SFLOAT images only (D32 stays refused in the five colour slots).  The reference's
+ * sampler.rs is empty, so this build fixes the comparison sampler: compare op LESS_OR_EQUAL (shadow.hlsli:42), a tap is 1 when clamp(D_ref, 0, 1) <= texel;
+ * nearest texel i = clamp(floor(u * W), 0, W - 1), j = clamp(floor(v * H), 0, H - 1) with W x H the image's extent (clamp-to-edge addressing); the
+ * 3 x 3 tap offsets are 1 / ShadowMapSize of the UBO, as the shader has them.  MODEL / MODEL_FULL have no shadow term and ignore the slot.  A
+ * shadowed draw's pipeline may not blend, discard fragments or use a predicate depth state (depth test without write, EQUAL, NOT_EQUAL, ALWAYS). */
 typedef enum { MIRHI_TEXTURE_ALBEDO = 0 /* t0 */, MIRHI_TEXTURE_NORMAL = 1 /* t1 */,
                MIRHI_TEXTURE_METALLIC_ROUGHNESS = 2 /* t2 */, MIRHI_TEXTURE_OCCLUSION = 3 /* t3 */, MIRHI_TEXTURE_EMISSIVE = 4 /* t4 (model_pbr.hlsl:62-95) */,
-               MIRHI_TEXTURE_COUNT = 5 } mirhi_texture_slot;
+               MIRHI_TEXTURE_SHADOW_MAP = 5 /* t7 / s5 (model_pbr.hlsl:103-108) */,
+               MIRHI_TEXTURE_COUNT = 6 } mirhi_texture_slot;
 
 mirhi_result mirhi_cmd_create(mirhi_device* dev, mirhi_cmd** out);                 /* CommandPool::new + CommandBuffer::new :89,:297 */
 mirhi_result mirhi_cmd_destroy(mirhi_cmd* cmd);

@@ -37,7 +37,7 @@ class Format:
 
 
 class Program:
-    NONE, TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR = -1, 0, 1, 2, 3
+    NONE, TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR, SHADOW = -1, 0, 1, 2, 3, 4
 
 
 class PrimitiveTopology:  # pipeline.rs:274-282
@@ -82,11 +82,11 @@ class IndexType:
 
 
 class Slot:
-    CAMERA, OBJECT, LIGHTS, MATERIAL, POINT_LIGHTS, SPOT_LIGHTS = range(6)
+    CAMERA, OBJECT, LIGHTS, MATERIAL, POINT_LIGHTS, SPOT_LIGHTS, SHADOW_DATA = range(7)
 
 
 class TextureSlot:
-    ALBEDO, NORMAL, METALLIC_ROUGHNESS, OCCLUSION, EMISSIVE = range(5)
+    ALBEDO, NORMAL, METALLIC_ROUGHNESS, OCCLUSION, EMISSIVE, SHADOW_MAP = range(6)
 
 
 class Kernel:
@@ -609,6 +609,7 @@ class Pipeline:
 
 
 TRIANGLE_VERTEX_STRIDE, TRIANGLE_VERTEX_OFFSETS = 24, (0, 12)        # vertex.rs:35-61
+SHADOW_VERTEX_OFFSETS = (0,)                                         # vertex/shadow.hlsl:13-16: position only, any stride >= 12
 VERTEX_STRIDE, VERTEX_OFFSETS = 48, (0, 12, 24, 32)                  # vertex.rs:130-170
 
 
@@ -632,12 +633,13 @@ class CommandBuffer:
     def reset(self):
         check(lib().mirhi_cmd_reset(self.handle))
 
-    def begin_rendering(self, color: Image, clear_color=(0.0, 0.0, 0.0, 1.0), color_load_op=LoadOp.CLEAR,
+    def begin_rendering(self, color: Optional[Image], clear_color=(0.0, 0.0, 0.0, 1.0), color_load_op=LoadOp.CLEAR,
                         depth: Optional[Image] = None, clear_depth: float = 1.0, depth_load_op=LoadOp.CLEAR,
                         depth_store_op=StoreOp.DONT_CARE, prim_id: Optional[Image] = None):
+        """color=None with a depth image: a depth-only scope (Program.SHADOW draws)."""
         info = RenderingInfo()
         lib().mirhi_rendering_info_default(C.byref(info))
-        info.color_image = color.handle
+        info.color_image = color.handle if color is not None else None
         info.color_load_op = color_load_op
         info.clear_color = (C.c_float * 4)(*clear_color)
         if depth is not None:
@@ -763,7 +765,10 @@ class SceneResources:
 
     def __init__(self, device: Device, scene, color_format: int = Format.R32G32B32A32_SFLOAT, want_prim: bool = False,
                  want_depth: bool = False, color_image: Optional[Image] = None, wrap_buffers=None,
-                 color_load_op: int = LoadOp.CLEAR):
+                 color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None):
+        """scene.shadow (scenes.ShadowSpec) adds a depth-only shadow scope ahead of the main scope: recorded into the same command
+        buffer, or with shadow_cmd=True into a command buffer of its own (self.shadow_cmd; render() submits both, the shadow one first --
+        put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames)."""
         self.device, self.scene = device, scene
         self.color_load_op = color_load_op
         self.owns_color = color_image is None
@@ -835,11 +840,54 @@ class SceneResources:
                       spot=buf(BufferUsage.Uniform, d.spot_lights or None, key=("u", d.spot_lights)),
                       textures=[tex(t) for t in d.textures], draw=d)
             self.draw_state.append(st)
+        self.shadow, self.shadow_cmd, self.shadow_state, self.owns_shadow_map = getattr(scene, "shadow", None), None, [], False
+        if self.shadow is not None:
+            sh = self.shadow
+            self.shadow_map = shadow_map
+            if self.shadow_map is None:
+                self.shadow_map, self.owns_shadow_map = Image(device, sh.size[0], sh.size[1], Format.D32_SFLOAT), True
+            self.shadow_data = buf(BufferUsage.Uniform, sh.params, key=("u", sh.params))
+            for c in sh.casters:
+                pb = (GraphicsPipelineBuilder().vertex_shader(Program.SHADOW).fragment_shader(Program.SHADOW)
+                      .vertex_binding(c.stride).vertex_attributes(SHADOW_VERTEX_OFFSETS)
+                      .color_attachment_format(Format.UNDEFINED).depth_attachment_format(Format.D32_SFLOAT)
+                      .cull_mode(c.cull_mode).front_face(c.front_face).depth_compare_op(c.depth_compare))
+                pipe = pb.build(device)
+                self.objs.append(pipe)
+                self.shadow_state.append(dict(pipe=pipe, vb=buf(BufferUsage.Vertex, c.vertices),
+                                              ib=buf(BufferUsage.Index, c.indices) if c.indices is not None else None,
+                                              camera=buf(BufferUsage.Uniform, c.camera, key=("u", c.camera)), draw=c))
+            if shadow_cmd:
+                self.shadow_cmd = CommandBuffer(device)
         self.record()
+
+    def _record_shadow(self, cmd: "CommandBuffer"):
+        sh = self.shadow
+        w, h = sh.size
+        cmd.begin_rendering(None, depth=self.shadow_map, clear_depth=sh.clear_depth, depth_load_op=sh.load_op, depth_store_op=StoreOp.STORE)
+        for st in self.shadow_state:
+            d = st["draw"]
+            cmd.set_viewport(*(d.viewport or (0.0, 0.0, float(w), float(h), 0.0, 1.0)))
+            cmd.set_scissor(*(d.scissor or (0, 0, w, h)))
+            cmd.bind_pipeline(st["pipe"])
+            cmd.bind_vertex_buffers(0, [st["vb"]], [0])
+            cmd.bind_uniform(Slot.CAMERA, st["camera"])
+            if st["ib"] is not None:
+                cmd.bind_index_buffer(st["ib"], 0, IndexType.UINT16 if d.index_type == 2 else IndexType.UINT32)
+                cmd.draw_indexed(d.count, 1, d.first, d.vertex_offset, 0)
+            else:
+                cmd.draw(d.count, 1, d.first, 0)
+        cmd.end_rendering()
 
     def record(self):
         s, cmd = self.scene, self.cmd
+        if self.shadow_cmd is not None:
+            self.shadow_cmd.begin_reusable()
+            self._record_shadow(self.shadow_cmd)
+            self.shadow_cmd.end()
         cmd.begin_reusable()
+        if self.shadow is not None and self.shadow_cmd is None:
+            self._record_shadow(cmd)
         cmd.begin_rendering(self.color, clear_color=s.clear_color, color_load_op=self.color_load_op, depth=self.depth, clear_depth=s.clear_depth,
                             depth_store_op=StoreOp.STORE if self.depth else StoreOp.DONT_CARE, prim_id=self.prim)
         for st in self.draw_state:
@@ -857,6 +905,11 @@ class SceneResources:
             for slot, img in enumerate(st["textures"]):
                 if img is not None or slot < 2:
                     cmd.bind_texture(slot, img)
+            if self.shadow is not None and d.program == scenes.PROGRAM_MODEL_PBR:
+                cmd.bind_uniform(Slot.SHADOW_DATA, self.shadow_data)
+                cmd.bind_texture(TextureSlot.SHADOW_MAP, self.shadow_map)
+            elif self.shadow is not None:
+                cmd.bind_texture(TextureSlot.SHADOW_MAP, None)
             if st["ib"] is not None:
                 cmd.bind_index_buffer(st["ib"], 0, IndexType.UINT16 if d.index_type == 2 else IndexType.UINT32)
                 cmd.draw_indexed(d.count, getattr(d, "instances", 1), d.first, d.vertex_offset, 0)
@@ -866,7 +919,7 @@ class SceneResources:
         cmd.end()
 
     def render(self, fence: Optional[Fence] = None):
-        self.device.submit([self.cmd], fence)
+        self.device.submit([self.shadow_cmd, self.cmd] if self.shadow_cmd is not None else [self.cmd], fence)
 
     def read(self):
         self.device.wait_idle()
@@ -880,6 +933,10 @@ class SceneResources:
     def destroy(self):
         self.device.wait_idle()
         self.cmd.destroy()
+        if self.shadow_cmd is not None:
+            self.shadow_cmd.destroy()
+        if self.owns_shadow_map:
+            self.shadow_map.destroy()
         for o in self.objs:
             o.destroy()
         for o in (self.prim, self.depth, self.color):

@@ -510,6 +510,8 @@ struct RecordedPass {
     uint32_t first_tri = 0;                // primitive ids continue across the segments of a scope
     bool carry_in = false, carry_out = false;
     int32_t area[4] = {0, 0, 0, 0};
+    bool depth_only = false;               // color_image NULL: SHADOW draws into the depth image (raster_kernel_depth)
+    std::vector<mirhi_image*> sampled;     // shadow maps the scope's draws sample (MIRHI_TEXTURE_SHADOW_MAP): ordered like attachments
 };
 
 // Words of the counter block that never move (a re-recorded frame of another shape finds them where the last frame's kernels
@@ -1128,16 +1130,29 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
     if (d->blend_attachment_count != 0 && d->blend_attachment_count != d->color_attachment_count)
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: Blend attachment count (%u) must match color attachment count (%u)", d->blend_attachment_count, d->color_attachment_count);
     // --- program selection replaces SPIR-V module creation (shader.rs:244-330) ---
-    if (d->vertex_program < 0 || d->vertex_program > MIRHI_PROGRAM_MODEL_PBR || d->fragment_program < 0 || d->fragment_program > MIRHI_PROGRAM_MODEL_PBR)
+    if (d->vertex_program < 0 || d->vertex_program > MIRHI_PROGRAM_SHADOW || d->fragment_program < 0 || d->fragment_program > MIRHI_PROGRAM_SHADOW)
         return fail(MIRHI_ERR_SHADER, "Shader error: unknown program id (vertex %d, fragment %d)", d->vertex_program, d->fragment_program);
+    const bool vs_shadow = d->vertex_program == MIRHI_PROGRAM_SHADOW, fs_shadow = d->fragment_program == MIRHI_PROGRAM_SHADOW;
     const bool vs_model = d->vertex_program != MIRHI_PROGRAM_TRIANGLE, fs_model = d->fragment_program != MIRHI_PROGRAM_TRIANGLE;
-    if (vs_model != fs_model)
+    if (vs_model != fs_model || vs_shadow != fs_shadow)
         return fail(MIRHI_ERR_SHADER, "Shader error: vertex program %d does not produce the inputs of fragment program %d", d->vertex_program, d->fragment_program);
     // --- what this rasterizer does not implement fails loudly instead of rendering something else ---
     if (d->color_attachment_count != 1) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: %u color attachments (exactly 1 supported)", d->color_attachment_count);
     const int32_t cf = d->color_attachment_formats[0];
-    if (cf != MIRHI_FORMAT_B8G8R8A8_SRGB && cf != MIRHI_FORMAT_R32G32B32A32_SFLOAT)
+    // depth-only pipelines (pixel/shadow.hlsl writes no colour): the one location holds no attachment (UNDEFINED), and only those
+    if (vs_shadow && cf != MIRHI_FORMAT_UNDEFINED)
+        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: the SHADOW program is depth-only: color attachment format must be UNDEFINED, got %d", cf);
+    if (!vs_shadow && cf == MIRHI_FORMAT_UNDEFINED)
+        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: color attachment format UNDEFINED (no attachment) is only supported for the depth-only SHADOW program");
+    if (!vs_shadow && cf != MIRHI_FORMAT_B8G8R8A8_SRGB && cf != MIRHI_FORMAT_R32G32B32A32_SFLOAT)
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported color attachment format %d", cf);
+    if (vs_shadow) {
+        const int32_t op = d->depth_compare_op;
+        if (!d->depth_test_enable || !d->depth_write_enable || !(op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL || op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL))
+            return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth-only pipelines need depth test and write with LESS, LESS_OR_EQUAL, GREATER or GREATER_OR_EQUAL");
+        if (d->blend_enable || d->fragment_discard_enable)
+            return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: blending or fragment discard in a depth-only pipeline");
+    }
     if (has_depth && d->depth_attachment_format != MIRHI_FORMAT_D32_SFLOAT)
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported depth attachment format %d (D32_SFLOAT only)", d->depth_attachment_format);
     if (d->topology != MIRHI_TOPOLOGY_TRIANGLE_LIST) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported topology %d (TriangleList only)", d->topology);
@@ -1156,10 +1171,10 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
             return fail(MIRHI_ERR_PIPELINE, "Pipeline error: invalid blend op");
     }
     if (d->depth_clamp_enable || d->depth_bias_enable) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth clamp / depth bias");
-    const uint32_t want_stride = vs_model ? 48u : 24u;      // vertex.rs:35-41 / :130-136
+    const uint32_t want_stride = vs_shadow ? 12u : (vs_model ? 48u : 24u);      // vertex.rs:35-41 / :130-136; vertex/shadow.hlsl:13-16 (position only)
     if (d->vertex_stride < want_stride || (d->vertex_stride & 3u))
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: vertex stride %u too small for program %d (needs >= %u, multiple of 4)", d->vertex_stride, d->vertex_program, want_stride);
-    const uint32_t want_attrs = vs_model ? 4u : 2u;
+    const uint32_t want_attrs = vs_shadow ? 1u : (vs_model ? 4u : 2u);
     static const uint32_t model_offsets[4] = {0, 12, 24, 32}, tri_offsets[2] = {0, 12};
     if (d->attribute_count != want_attrs) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: program %d expects %u vertex attributes, got %u", d->vertex_program, want_attrs, d->attribute_count);
     for (uint32_t i = 0; i < want_attrs; i++)
@@ -1307,6 +1322,26 @@ extern "C" mirhi_result mirhi_cmd_reset(mirhi_cmd* cmd) {
 extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_rendering_info* info) {
     REQUIRE_RECORDING(cmd); NULL_CHECK(info, "rendering_info");
     if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
+    if (!info->color_image && info->depth_image) {
+        // depth-only scope (MIRHI_PROGRAM_SHADOW): the depth image's extent is the render area; only SHADOW draws are recorded here
+        const mirhi_image* di = info->depth_image;
+        if (di->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: depth attachment is not D32_SFLOAT");
+        if (info->prim_id_image) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: prim_id_image in a depth-only rendering scope");
+        if (info->depth_store_op != MIRHI_STORE_OP_STORE)
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a depth-only rendering scope must store its depth (STORE)");
+        RecordedPass p;
+        p.info = *info;
+        p.depth_only = true;
+        p.color_t = {nullptr, di->width, di->height, (uint32_t)MIRHI_FORMAT_UNDEFINED};
+        p.depth_t = {di->ptr, di->width, di->height, (uint32_t)di->format};
+        if (info->render_area[2] <= 0 || info->render_area[3] <= 0) { p.area[0] = 0; p.area[1] = 0; p.area[2] = (int32_t)di->width; p.area[3] = (int32_t)di->height; }
+        else memcpy(p.area, info->render_area, sizeof p.area);
+        if (p.area[0] != 0 || p.area[1] != 0 || p.area[2] != (int32_t)di->width || p.area[3] != (int32_t)di->height)
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: render area must cover the whole depth attachment");
+        cmd->passes.push_back(std::move(p));
+        cmd->in_rendering = true;
+        return MIRHI_OK;
+    }
     NULL_CHECK(info->color_image, "color_image");
     const mirhi_image* ci = info->color_image;
     if (ci->format != MIRHI_FORMAT_B8G8R8A8_SRGB && ci->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT)
@@ -1375,6 +1410,11 @@ extern "C" mirhi_result mirhi_cmd_bind_uniform(mirhi_cmd* cmd, mirhi_uniform_slo
 extern "C" mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slot slot, mirhi_image* image) {
     REQUIRE_RECORDING(cmd);
     if ((int)slot < 0 || (int)slot >= MIRHI_TEXTURE_COUNT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unknown texture slot %d", (int)slot);
+    if (slot == MIRHI_TEXTURE_SHADOW_MAP) {       // t7 / s5 (model_pbr.hlsl:103-108): a depth image, sampled with the comparison sampler
+        if (image && image->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow map must be D32_SFLOAT");
+        cmd->textures[slot] = image;
+        return MIRHI_OK;
+    }
     if (image && image->format != MIRHI_FORMAT_R8G8B8A8_UNORM && image->format != MIRHI_FORMAT_R8G8B8A8_SRGB)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: sampled images must be R8G8B8A8_UNORM or R8G8B8A8_SRGB");
     cmd->textures[slot] = image;
@@ -1414,9 +1454,14 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         return MIRHI_OK;
     }
     const mirhi_pipeline_desc& pd = cmd->pipeline->desc;
-    const mirhi_image* ci = cmd->passes.back().info.color_image;
-    if (pd.color_attachment_formats[0] != (int32_t)ci->format)
-        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)ci->format);
+    const bool shadow_prog = pd.vertex_program == MIRHI_PROGRAM_SHADOW;
+    if (cmd->passes.back().depth_only && !shadow_prog)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: only SHADOW draws may be recorded in a depth-only rendering scope (program %d)", pd.vertex_program);
+    if (!cmd->passes.back().depth_only && shadow_prog)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: SHADOW draws need a depth-only rendering scope (color_image NULL, depth_image set)");
+    const RecordedPass::Target ci = cmd->passes.back().color_t;      // (a depth-only scope: the depth image's extent, format UNDEFINED)
+    if (pd.color_attachment_formats[0] != (int32_t)ci.format)
+        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)ci.format);
     // depth state must be uniform within a rendering scope (DESIGN.md "Depth key")
     const uint32_t dtest = pd.depth_test_enable ? 1u : 0u;
     const uint32_t dcmp = dtest ? (uint32_t)pd.depth_compare_op : (uint32_t)MIRHI_COMPARE_ALWAYS;
@@ -1446,6 +1491,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
             prev.carry_out = true;
             next.info = prev.info;
             next.color_t = prev.color_t; next.depth_t = prev.depth_t; next.prim_t = prev.prim_t;
+            next.depth_only = prev.depth_only;
             memcpy(next.area, prev.area, sizeof next.area);
             next.info.color_load_op = MIRHI_LOAD_OP_LOAD;
             next.carry_in = true;
@@ -1462,7 +1508,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     d.stride = pd.vertex_stride;
     d.vb = cmd->vb->ptr + cmd->vb_offset;
     const uint64_t vb_bytes = cmd->vb->size - cmd->vb_offset;
-    const uint32_t vsize = pd.vertex_program == MIRHI_PROGRAM_TRIANGLE ? 24u : 48u;
+    const uint32_t vsize = shadow_prog ? 12u : (pd.vertex_program == MIRHI_PROGRAM_TRIANGLE ? 24u : 48u);
     if (!indexed) {
         const uint64_t last = (uint64_t)first + 3ull * tri_count;   // one past the last vertex read
         if ((last - 1) * d.stride + vsize > vb_bytes)
@@ -1488,7 +1534,15 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         *out = u.buf->ptr + u.offset;
         return MIRHI_OK;
     };
-    if (d.program != MIRHI_PROGRAM_TRIANGLE) {
+    if (d.program == MIRHI_PROGRAM_SHADOW) {
+        // ShadowConstants (vertex/shadow.hlsl:7-11) in b0: lightSpaceMatrix @0, model @64 -- the vertex pre-pass reads the model matrix as a MODEL
+        // draw's object and the light matrix in place of viewProjection
+        const uint8_t* p = nullptr;
+        mirhi_result r;
+        if ((r = uptr(MIRHI_SLOT_CAMERA, 128, &p, "ShadowConstants (b0)")) != MIRHI_OK) return r;
+        d.camera = (const float*)p;
+        d.object = (const float*)(p + 64);
+    } else if (d.program != MIRHI_PROGRAM_TRIANGLE) {
         const uint8_t* p = nullptr;
         mirhi_result r;
         if ((r = uptr(MIRHI_SLOT_CAMERA, 208, &p, "CameraData (b0)")) != MIRHI_OK) return r;
@@ -1508,6 +1562,17 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                     if (ti->levels > 1) d.tex_any_mips = 1;
                     if (ti->levels > 1) d.tex_aniso |= (ti->max_anisotropy - 1u) << (4 * t);
                 }
+            if (d.program == MIRHI_PROGRAM_MODEL_PBR && cmd->textures[MIRHI_TEXTURE_SHADOW_MAP]) {
+                // CalculateShadow (model_pbr.hlsl:238-251): the map and its ShadowParams; the shadowed raster variant resolves ordered depth keys only
+                const mirhi_image* sm = cmd->textures[MIRHI_TEXTURE_SHADOW_MAP];
+                if ((r = uptr(MIRHI_SLOT_SHADOW_DATA, 96, &d.shadow_data, "ShadowParams (SHADOW_DATA)")) != MIRHI_OK) return r;
+                const uint32_t op = pd.depth_compare_op;
+                const bool keyed = !pd.depth_test_enable || (pd.depth_write_enable && (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL ||
+                                                                                       op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL));
+                if (pd.blend_enable || pd.fragment_discard_enable || !keyed)
+                    return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a shadow map with blending, fragment discard or a predicate depth state");
+                d.shadow_map = (const float*)sm->ptr; d.shadow_w = sm->width; d.shadow_h = sm->height;
+            }
         }
     }
     // viewport (Vulkan: xf = (w/2) xd + (x + w/2)), guard-band factors, scissor
@@ -1519,11 +1584,15 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     d.gy = (GUARD_PX - std::fabs(d.cy)) / d.hh;
     int64_t sx0 = cmd->scissor.x, sy0 = cmd->scissor.y;
     int64_t sx1 = sx0 + (int64_t)cmd->scissor.width - 1, sy1 = sy0 + (int64_t)cmd->scissor.height - 1;
-    if (sx1 > (int64_t)ci->width - 1) sx1 = (int64_t)ci->width - 1;
-    if (sy1 > (int64_t)ci->height - 1) sy1 = (int64_t)ci->height - 1;
+    if (sx1 > (int64_t)ci.width - 1) sx1 = (int64_t)ci.width - 1;
+    if (sy1 > (int64_t)ci.height - 1) sy1 = (int64_t)ci.height - 1;
     d.sx0 = (int32_t)sx0; d.sy0 = (int32_t)sy0; d.sx1 = (int32_t)sx1; d.sy1 = (int32_t)sy1;
-    d.scissor_partial = (sx0 > 0 || sy0 > 0 || sx1 < (int64_t)ci->width - 1 || sy1 < (int64_t)ci->height - 1) ? 1u : 0u;
+    d.scissor_partial = (sx0 > 0 || sy0 > 0 || sx1 < (int64_t)ci.width - 1 || sy1 < (int64_t)ci.height - 1) ? 1u : 0u;
     if (sx0 > sx1 || sy0 > sy1) return MIRHI_OK;    // empty scissor: nothing can be covered
+    if (d.shadow_map) {
+        mirhi_image* sm = cmd->textures[MIRHI_TEXTURE_SHADOW_MAP];
+        if (std::find(pass.sampled.begin(), pass.sampled.end(), sm) == pass.sampled.end()) pass.sampled.push_back(sm);
+    }
     pass.draws.push_back(d);
     pass.draw_vb_bytes.push_back(vb_bytes);
     pass.total_tris += tri_count;
@@ -1661,6 +1730,13 @@ static void depth_key_setup(PassParams& P, const RecordedPass& pass) {
 //               long as the queue of atomics on the hottest bin counter, which per-XCD counters cut (see reserve_bin_slots).
 //  MIRHI_TP_MAX_AREA (0 = off), MIRHI_TP_DENSITY, MIRHI_RASTER_TEAMS (1 / 2) override for A/B measurements.
 struct RasterMode { uint32_t tp_max_area, teams; bool tri_prog; bool wide_eligible; bool xcd_bins; uint32_t wide; };
+// Depth-only scopes and scopes with a shadowed draw have raster variants of their own (raster_kernel_depth / raster_kernel_shadow): one team of four
+// waves per tile, single-list bins -- the team and wide selectors below leave them alone.
+static bool pass_is_depth_or_shadowed(const RecordedPass& pass) {
+    if (pass.depth_only) return true;
+    for (const DrawDesc& dd : pass.draws) if (dd.shadow_map) return true;
+    return false;
+}
 // wide: what the command buffer's busy-tile feedback asks for (Workspace::wide: 0 / 8 / 16 waves per tile)
 static RasterMode raster_mode(const RecordedPass& pass, size_t tiles, bool spread = false, uint32_t wide = 0) {
     RasterMode m{0u, 1u, false, false, false, 0u};
@@ -1673,7 +1749,7 @@ static RasterMode raster_mode(const RecordedPass& pass, size_t tiles, bool sprea
     m.tp_max_area = getenv("MIRHI_TP_MAX_AREA") ? (uint32_t)atoi(getenv("MIRHI_TP_MAX_AREA")) : (dense ? 64u : 0u);
     if (key.pred) m.tp_max_area = 0;      // predicate scopes resolve pixel-parallel only (the LDS key array holds ordered keys)
     else if (pass_is_masked_plain(pass) && m.tp_max_area == 0u) m.tp_max_area = 1u;    // alpha-masked scope: its records need the triangle-parallel path (LDS key array)
-    const bool mesh_only = !m.tri_prog && !pass.draws.empty();
+    const bool mesh_only = !m.tri_prog && !pass.draws.empty() && !pass_is_depth_or_shadowed(pass);      // (their variants: one team of four waves)
     m.teams = getenv("MIRHI_RASTER_TEAMS") ? (uint32_t)atoi(getenv("MIRHI_RASTER_TEAMS")) : (avg < 16 ? 2u : 1u);
     if (!(m.tp_max_area && mesh_only && !pass_is_ordered(pass)) || m.teams != 2u) m.teams = 1u;
     if (spread && !getenv("MIRHI_RASTER_TEAMS")) m.teams = 1u;      // measured on an earlier submission of this command buffer (Workspace::spread)
@@ -1719,6 +1795,7 @@ static bool same_recording(const std::vector<RecordedPass>& a, const std::vector
         if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || x.key_set != y.key_set || x.depth_test != y.depth_test || x.depth_compare != y.depth_compare ||
             x.depth_write != y.depth_write || x.frag_discard != y.frag_discard || memcmp(x.blend, y.blend, sizeof x.blend) != 0 ||
             x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
+        if (x.depth_only != y.depth_only || x.sampled != y.sampled) return false;
         if (x.draws.size() != y.draws.size() || x.draw_vb_bytes != y.draw_vb_bytes) return false;
         if (!x.draws.empty() && memcmp(x.draws.data(), y.draws.data(), x.draws.size() * sizeof(DrawDesc)) != 0) return false;
     }
@@ -1744,7 +1821,8 @@ static bool recording_reads(const std::vector<RecordedPass>& passes, const uint8
     auto in = [&](const void* q) { return q && (const uint8_t*)q >= lo && (const uint8_t*)q < hi; };
     for (const RecordedPass& pass : passes)
         for (const DrawDesc& d : pass.draws) {
-            if (in(d.vb) || in(d.ib) || in(d.camera) || in(d.object) || in(d.lights) || in(d.material) || in(d.point_lights) || in(d.spot_lights)) return true;
+            if (in(d.vb) || in(d.ib) || in(d.camera) || in(d.object) || in(d.lights) || in(d.material) || in(d.point_lights) || in(d.spot_lights) ||
+                in(d.shadow_data)) return true;
         }
     return false;
 }
@@ -1897,6 +1975,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         Geo g;
         g.tiles_x = (ci.width + TILE - 1) / TILE; g.tiles_y = (ci.height + TILE - 1) / TILE;
         { uint32_t count; split_rows(dev->split_layout, dev->split_rank, dev->split_world, g.tiles_y, &g.r0, &g.rstep, &count); g.r1 = g.r0 + count; }
+        if (pass.depth_only) { g.r0 = 0; g.r1 = g.tiles_y; g.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
         const size_t tiles = (size_t)g.tiles_x * (g.r1 - g.r0);
         const RasterMode mode = raster_mode(pass, tiles, cmd->ws.spread, cmd->ws.wide);
         g.xcd_bins = mode.xcd_bins;
@@ -2004,13 +2083,14 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
             DrawDesc& dd = pass_draws[pi][di];
             dd.vs_words = 0; dd.vs_out = nullptr; dd.vs_attr = nullptr;
             if (dd.program == MIRHI_PROGRAM_TRIANGLE) continue;
-            const uint32_t words = dd.program == MIRHI_PROGRAM_MODEL ? 3u : 5u;
+            const uint32_t words = dd.program == MIRHI_PROGRAM_SHADOW ? 1u : (dd.program == MIRHI_PROGRAM_MODEL ? 3u : 5u);   // (SHADOW: the clip stream only)
             const uint64_t vbb = pass.draw_vb_bytes[di];
-            const uint32_t count = vbb >= 48 ? (uint32_t)((vbb - 48) / dd.stride + 1) : 0u;
+            const uint64_t vsz = dd.program == MIRHI_PROGRAM_SHADOW ? 12u : 48u;
+            const uint32_t count = vbb >= vsz ? (uint32_t)((vbb - vsz) / dd.stride + 1) : 0u;
             size_t found = SIZE_MAX;
             for (size_t j = 0; j < pass_jobs[pi].size(); j++) {
                 const VsJob& J = pass_jobs[pi][j].j;
-                if (J.vb == dd.vb && J.camera == dd.camera && J.object == dd.object && J.stride == dd.stride && J.words >= words && J.count >= count) { found = j; break; }
+                if (J.vb == dd.vb && J.camera == dd.camera && J.object == dd.object && J.stride == dd.stride && J.words >= words && (J.words == 1u) == (words == 1u) && J.count >= count) { found = j; break; }
             }
             if (found == SIZE_MAX) {
                 HostJob hj{};
@@ -2136,6 +2216,9 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
             P.count_stride = g.xcd_bins ? (uint32_t)max_tiles : 0u;
         }
         P.xcd_swizzle = getenv("MIRHI_XCD_RUN") ? (uint32_t)atoi(getenv("MIRHI_XCD_RUN")) : 1u;
+        P.depth_only = pass.depth_only ? 1u : 0u;
+        for (const DrawDesc& dd : draws) P.shadowed |= dd.shadow_map ? 1u : 0u;
+        if (P.depth_only || P.shadowed) { P.xcd_swizzle = 1u; P.raster_wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
         P.vs_jobs = dev_jobs + jobs_done;
         P.num_vs_jobs = (uint32_t)pass_jobs[pi].size();
         P.vs_total_slots = 0;
@@ -2157,7 +2240,9 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         cmd->plan.push_back(P);
         uint32_t progs = 0;
         for (const DrawDesc& dd : draws) progs |= dd.program == 0 ? 1u : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.tex_any_mips || dd.tex_srgb) ? 4u : 2u);
-        cmd->plan_programs.push_back(progs ? progs : 1u);
+        // 8: a shadowed MODEL_PBR draw (raster_kernel_shadow, with the Cook-Torrance variant's programs); 0: a depth-only scope (raster_kernel_depth)
+        if (P.shadowed) progs = 4u | 8u;
+        cmd->plan_programs.push_back(P.depth_only ? 0u : (progs ? progs : 1u));
         cmd->plan_tris += pass.total_tris - pass.first_tri;
         // the kernels read their parameters from the block: copy 2*pi + parity of scope pi appends large triangles to counter
         // `parity` and re-arms the other one for the scope that follows on this workspace
@@ -2228,9 +2313,14 @@ static mirhi_result timing_begin(mirhi_device* dev, uint32_t kernel, uint32_t la
 // Attachments of a command buffer's recording that are still live images (dev->mu held).
 template <typename F>
 static void for_each_attachment(mirhi_device* dev, const mirhi_cmd* c, F&& f) {
-    for (const RecordedPass& pass : c->planned)
+    for (const RecordedPass& pass : c->planned) {
         for (mirhi_image* img : {pass.info.color_image, pass.info.depth_image, pass.info.prim_id_image})
             if (img && std::find(dev->images.begin(), dev->images.end(), img) != dev->images.end()) f(img);
+        // the shadow maps the scope samples count as attachments: a read after another lane's write (the shadow scope) and a write after another lane's
+        // read (the next frame's shadow scope behind this frame's lit one) are both ordered
+        for (mirhi_image* img : pass.sampled)
+            if (img && std::find(dev->images.begin(), dev->images.end(), img) != dev->images.end()) f(img);
+    }
 }
 // `c` is about to run on `stream` (or, natively, on `nq`): anything that used one of its attachments last somewhere else, and is not known
 // to have finished, goes first.  Between two HIP streams that is an event; with an AQL queue on either side the host waits (a frame loop
@@ -2495,7 +2585,7 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             HIP_TRY(le);
             const bool has_tiles = P.tile_row_end > P.tile_row_begin && P.tiles_x;
             const uint32_t* winners = nullptr;
-            if (counted && has_tiles && !P.ordered_recs) {          // (ordered -- blended -- segments are not counted)
+            if (counted && has_tiles && !P.ordered_recs && !P.depth_only) {      // (ordered -- blended -- segments and depth-only scopes are not counted)
                 mirhi_result r;
                 if (timed && (r = timing_begin(dev, MIRHI_KERNEL_FRAGMENT_COUNT, c->lane, &tc)) != MIRHI_OK) return r;
                 HIP_TRY(launch_fragment_count(P, dp, big_count, stream, tc));

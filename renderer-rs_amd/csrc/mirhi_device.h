@@ -75,6 +75,10 @@ struct DrawDesc {
     uint32_t tex_aniso;           // bits 4t..4t+3: max_anisotropy - 1 of texture t (0 = trilinear; set only for textures with a chain)
     const void* vs_attr;          // shaded vertices, the other words (vs_words - 1 per vertex): see VsJob
     const void* vs_out;           // shaded vertices, clip positions (16 B per vertex), indexed like the vertex buffer: see VsJob
+    const float*   shadow_map;    // MODEL_PBR with MIRHI_TEXTURE_SHADOW_MAP bound: the D32 map (t7), else nullptr (shadow = 1)
+    const uint8_t* shadow_data;   // ShadowParams (96 B, shadow.hlsli:20-30) when shadow_map is set
+    uint32_t shadow_w, shadow_h;  // the map's extent
+    uint32_t shadow_pad[2];
 };
 static_assert(sizeof(DrawDesc) % 16 == 0, "DrawDesc must stay 16-byte sized");
 
@@ -85,6 +89,7 @@ static_assert(sizeof(DrawDesc) % 16 == 0, "DrawDesc must stay 16-byte sized");
 //   clip[v]  = clip position
 //   attr[v]  = { world.xyz, N.x }, { N.y, N.z, u, v }                     (vs_words - 1 = 2 words, MODEL)
 //              + { T.xyz, B.x }, { B.y, B.z, 0, 0 }                       (vs_words - 1 = 4 words, MODEL_FULL / MODEL_PBR)
+//              nothing                                                    (vs_words = 1, SHADOW: camera = ShadowConstants, object = its model @64)
 // A job's output is [count x 16 B clip, rounded up to 256 B][count x (words - 1) x 16 B]: vs_attr_of() below.
 struct VsJob {
     const uint8_t* vb;
@@ -190,6 +195,8 @@ struct PassParams {
                                       // [3] busy tiles of the scope before it | 0x80000000
     unsigned long long* frag_stats;   // device counters of the statistics pass (never touched by geometry / raster kernels): [0] pixels that
                                       // ran a fragment program (winners of the depth resolve), [1] fragments covered before the depth test
+    uint32_t depth_only;              // 1: a depth-only scope (SHADOW draws; color == nullptr): raster_kernel_depth stores the depth image and nothing else
+    uint32_t shadowed;                // 1: some MODEL_PBR draw of the scope samples a shadow map (raster_kernel_shadow)
 };
 
 // Kernel arguments passed by value next to the PassParams pointer: what a wave needs before anything else, so that its

@@ -229,8 +229,10 @@ __device__ __forceinline__ uint32_t find_draw(ParamsRef P, uint32_t prim) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// a4: vertex-shader pre-pass for the MODEL / MODEL_FULL programs (vertex/model.hlsl:39-68)
+// a4: vertex-shader pre-pass for the MODEL / MODEL_FULL programs (vertex/model.hlsl:39-68) and SHADOW (vertex/shadow.hlsl:23-34)
 // ------------------------------------------------------------------------------------------------
+// SHADOW: the depth-only scopes' form (vertex_kernel_shadow), jobs of one word per vertex
+template <bool SHADOW = false>
 __device__ __forceinline__ void vertex_body(const PassParams* __restrict__ params) {
     if (MIRHI_GEOM_PRIO) __builtin_amdgcn_s_setprio(MIRHI_GEOM_PRIO);
     ParamsRef P = *(ParamsPtr)(uintptr_t)params;
@@ -248,7 +250,13 @@ __device__ __forceinline__ void vertex_body(const PassParams* __restrict__ param
     const uint8_t* v = J.vb + (size_t)vidx * J.stride;
     const CFloatPtr model = cf(J.object);
     const f4 p = {ldf(v, 0), ldf(v, 4), ldf(v, 8), 1.0f};
-    const f4 w = mat4_mul(model, p);                                         // vertex/model.hlsl:44
+    const f4 w = mat4_mul(model, p);                                         // vertex/model.hlsl:44 (vertex/shadow.hlsl:29)
+    if (SHADOW) {
+        // camera = ShadowConstants: lightSpaceMatrix @0 (vertex/shadow.hlsl:30); the clip stream only (a 12-byte vertex has nothing more to read)
+        const f4 c = mat4_mul(cf(J.camera), w);
+        reinterpret_cast<uint4*>(J.out)[vidx] = make_uint4(__float_as_uint(c.x), __float_as_uint(c.y), __float_as_uint(c.z), __float_as_uint(c.w));
+        return;
+    }
     const f4 c = mat4_mul(cf(J.camera) + 32, w);                             // :48
     const f3 n = {ldf(v, 12), ldf(v, 16), ldf(v, 20)};
     const f3 N = normalize3(mat3_mul(model + 16, n));                        // :51
@@ -270,6 +278,7 @@ __device__ __forceinline__ void vertex_body(const PassParams* __restrict__ param
 
 __global__ __launch_bounds__(GEOM_THREADS) void vertex_kernel(const PassParams* __restrict__ params) { vertex_body(params); }
 __global__ __launch_bounds__(GEOM_THREADS) void vertex_kernel_batch(const GeometryBatch B) { vertex_body(B.params[blockIdx.y]); }
+__global__ __launch_bounds__(GEOM_THREADS) void vertex_kernel_shadow(const PassParams* __restrict__ params) { vertex_body<true>(params); }
 
 __device__ __forceinline__ uint32_t pack_bgra8_srgb(f4 c);
 

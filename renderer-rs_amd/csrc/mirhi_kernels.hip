@@ -78,7 +78,8 @@ hipError_t launch_seq_store(NativeQueue* q, uint64_t* word, uint64_t value) {
 
 hipError_t launch_vertex(const PassParams& P, const PassParams* dev_params, hipStream_t stream, LaunchTiming t) {
     if (P.vs_total_slots == 0) return hipSuccess;
-    MIRHI_LAUNCH(vertex_kernel, dim3(P.vs_total_slots / GEOM_THREADS), dim3(GEOM_THREADS), stream, t, dev_params);
+    if (P.depth_only) MIRHI_LAUNCH(vertex_kernel_shadow, dim3(P.vs_total_slots / GEOM_THREADS), dim3(GEOM_THREADS), stream, t, dev_params);   // (clip stream only)
+    else MIRHI_LAUNCH(vertex_kernel, dim3(P.vs_total_slots / GEOM_THREADS), dim3(GEOM_THREADS), stream, t, dev_params);
     return launch_result();
 }
 
@@ -132,6 +133,19 @@ hipError_t launch_raster(const PassParams& P, const PassParams* dev_params, uint
     // the plain key (raw float bits) serves LESS / LESS_OR_EQUAL; everything else takes the generic key
     const bool plain = P.zflip == 0u && P.zmask == 0xFFFFFFFFu;
     const RasterHead H = {P.bin_count, P.bin_pool, big_count, P.tiles_x, P.tile_row_begin, P.bin_cap, P.big_cap, P.sub_cap, P.count_stride, P.fixed_recs, P.tile_row_step};
+    // depth-only scopes (programs 0) and scopes with a shadowed draw (bit 8) have variants of their own, whatever the selectors below would pick (the
+    // host keeps them on one team of four waves, single-list bins and the plain tile order; their key is an ordered one, never a predicate)
+    if (programs == 0u || (programs & 8u)) {
+        const dim3 block(RASTER_THREADS);
+        if (programs == 0u) {
+            if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_depth<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_depth<1, 1>), grid, block, stream, t, dev_params, H); }
+            else { if (plain) MIRHI_LAUNCH((raster_kernel_depth<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_depth<1, 0>), grid, block, stream, t, dev_params, H); }
+        } else {
+            if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_shadow<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_shadow<1, 1>), grid, block, stream, t, dev_params, H); }
+            else { if (plain) MIRHI_LAUNCH((raster_kernel_shadow<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_shadow<1, 0>), grid, block, stream, t, dev_params, H); }
+        }
+        return launch_result();
+    }
     if (P.raster_wide && allow_wide && !P.pred && P.tp_max_area && !P.alpha_scope && (programs == 2 || programs >= 4) && P.xcd_swizzle <= 1u) {
         // the wide mesh variants: eight or sixteen waves per tile (host-side choice, PassParams::raster_wide = waves per tile)
         const bool w16 = P.raster_wide >= 16u;
@@ -221,11 +235,11 @@ hipError_t launch_raster_batch(const PassParams* const* Ps, const PassParams* co
     (void)plain;
     return launch_result();
 }
-bool raster_batchable(const PassParams& P) { return !P.pred && P.zflip == 0u && P.zmask == 0xFFFFFFFFu && P.xcd_swizzle <= 1u && !P.ordered_recs && !P.alpha_scope && !P.raster_wide; }
+bool raster_batchable(const PassParams& P) { return !P.depth_only && !P.shadowed && !P.pred && P.zflip == 0u && P.zmask == 0xFFFFFFFFu && P.xcd_swizzle <= 1u && !P.ordered_recs && !P.alpha_scope && !P.raster_wide; }
 
 hipError_t launch_fragment_count(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, hipStream_t stream, LaunchTiming t) {
     const uint32_t rows = P.tile_row_end - P.tile_row_begin;
-    if (rows == 0 || P.tiles_x == 0 || P.ordered_recs) return hipSuccess;
+    if (rows == 0 || P.tiles_x == 0 || P.ordered_recs || P.depth_only) return hipSuccess;
     const RasterHead H = {P.bin_count, P.bin_pool, big_count, P.tiles_x, P.tile_row_begin, P.bin_cap, P.big_cap, P.sub_cap, P.count_stride, P.fixed_recs, P.tile_row_step};
     MIRHI_LAUNCH(fragment_count_kernel, dim3(P.tiles_x, rows), dim3(RASTER_THREADS), stream, t, dev_params, H);
     return launch_result();

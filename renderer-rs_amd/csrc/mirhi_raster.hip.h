@@ -621,7 +621,11 @@ __device__ __forceinline__ void raster_list(const uint4* __restrict__ list, uint
 // of a wave that has its SIMD to itself.  Splitting the tile's PIXELS over four times the waves needs no merge and no atomics (unlike the
 // two-team variant, which splits the records): same staging, same triangle-parallel walk, each wave visits the records that touch its
 // block and shades its 64 pixels.  Chosen by the host from the number of busy tiles the previous frame reported (PassParams::raster_wide).
-template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4>
+// PROGS = 0: a depth-only scope (SHADOW draws, PassParams::depth_only): coverage and depth as every variant, then the depth image is stored
+// and nothing else -- no colour, no shading, no primitive id (raster_kernel_depth).
+// SHADOWV (PROGS = 4, one team, four waves): the Cook-Torrance program with the directional light's shadow term for scopes with a shadowed
+// draw (PassParams::shadowed, raster_kernel_shadow) -- its own variant, so that the shadow map costs the other PROGS = 4 kernels nothing.
+template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4, bool SHADOWV = false>
 #ifndef MIRHI_PROGS2_WAVES
 #define MIRHI_PROGS2_WAVES 5
 #endif
@@ -724,7 +728,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
         // loaded, the clear depth if depth is stored and was not loaded (a loaded depth would be written back unchanged).
         // A fifth of the general path's instructions, and the workgroup's slots are free again a few microseconds sooner.
         if (TEAMS > 1 && team != 0u) return;
-        const bool write_color = !P.color_load, write_depth = P.depth && P.depth_store && !P.depth_load;
+        const bool write_color = PROGS != 0 && !P.color_load, write_depth = P.depth && P.depth_store && !P.depth_load;
         if (write_color || write_depth) {
             const uint32_t px0 = tx * TILE + (uint32_t)ix0, py0 = ty * TILE + (uint32_t)iy0;
 #pragma unroll
@@ -834,6 +838,35 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
             }
         }
     }
+    if constexpr (PROGS == 0) {
+        // depth-only resolve: the depth of each owned pixel (init_key / the key's depth, as the colour variants store it), the wave's two side-by-side
+        // blocks as one 8-byte store per lane (store_pair: 64-byte row segments) when every lane of both is inside the image
+        if (!(P.depth && P.depth_store)) return;
+        const uint32_t px0 = tx * TILE + (uint32_t)ix0, py0 = ty * TILE + (uint32_t)iy0;
+        uint32_t held = 0;
+        bool held_all = false;
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
+            const bool inb = px < P.width && py < P.height;
+            uint32_t izk, iidk, zorig;
+            init_key(P, px, py, inb, izk, iidk, zorig);
+            const uint32_t zkb = st.zk[b], idb = st.idk[b];
+            const bool none = !inb || ((zkb == izk) && (idb == iidk));
+            const uint32_t zb = (none || !P.zmask) ? zorig : (zkb ^ P.zflip);
+            uint32_t* const dimg = reinterpret_cast<uint32_t*>(P.depth);
+            const bool all = __ballot(inb) == ~0ull;
+            if (NB < 2) { if (inb) dimg[(size_t)py * P.width + px] = zb; continue; }
+            if ((b & 1) == 0) { held = zb; held_all = all; if (!all && inb) dimg[(size_t)py * P.width + px] = zb; }
+            else if (all && held_all) store_pair(dimg, py * P.width + (px - (uint32_t)BLOCK) - (lane & 7u), held, zb, lane);
+            else {
+                if (held_all) dimg[(size_t)py * P.width + px - BLOCK] = held;
+                if (inb) dimg[(size_t)py * P.width + px] = zb;
+            }
+        }
+        STAMP(4);
+        return;
+    }
     // The resolve reads its parameters through a laundered kernarg pointer: the scalar loads are issued here, not at
     // kernel entry, so their registers are not live across the raster loops (which otherwise spill SGPRs to VGPR lanes).
     const ParamsPtr R = launder_params((ParamsPtr)(uintptr_t)params);
@@ -921,7 +954,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
                 const float pxc = (float)px + 0.5f, pyc = (float)py + 0.5f;
                 if (PROGS == 1) col = shade_triangle_program(D, tri, pxc, pyc);
                 else if (PROGS == 2) col = shade_model_program<false>(D, tri, pxc, pyc);
-                else col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc) : shade_model_program<PROGS == 4>(D, tri, pxc, pyc);
+                else col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc) : shade_model_program<PROGS == 4, SHADOWV>(D, tri, pxc, pyc);
             }
             todo &= ~__ballot(mine);
         }
@@ -962,6 +995,16 @@ __global__ MIRHI_RASTER_BOUNDS void raster_kernel(const PassParams* __restrict__
 template <int PROGS, int KEYED, int WPT>
 __global__ __launch_bounds__(WPT * 64, (PROGS == 2 && WPT == 16 ? 6 : (PROGS == 2 ? 5 : 4))) void raster_kernel_wide(const PassParams* __restrict__ params, const RasterHead H) {
     raster_body<PROGS, KEYED, 1, 1, false, WPT>(params, H);
+}
+// a depth-only scope (shadow map): KEYED 0 (LESS / LESS_OR_EQUAL) or 1 (GREATER / GREATER_OR_EQUAL), with or without the triangle-parallel path
+template <int KEYED, int TP>
+__global__ __launch_bounds__(RASTER_THREADS, (TP ? 7 : 8)) void raster_kernel_depth(const PassParams* __restrict__ params, const RasterHead H) {
+    raster_body<0, KEYED, TP>(params, H);
+}
+// a scope with a shadowed MODEL_PBR draw (one team, four waves per tile; no predicate, ordered or alpha-masked segment carries one)
+template <int KEYED, int TP>
+__global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_shadow(const PassParams* __restrict__ params, const RasterHead H) {
+    raster_body<4, KEYED, TP, 1, false, 4, true>(params, H);
 }
 // up to MAX_BATCH independent rendering scopes of equal shape (the frames of one mirhi_queue_submit): grid (tiles_x, tile rows, scopes).
 // One launch instead of one per frame: the ramp-up and drain of a kernel (5 us of the 11 us an isolated 10k-triangle raster kernel

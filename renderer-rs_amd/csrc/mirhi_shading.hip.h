@@ -212,7 +212,7 @@ __device__ __forceinline__ f4 shade_triangle_program(DrawRef D, uint32_t tri, fl
     return shade_triangle_program(D, vin, pxc, pyc);
 }
 
-// a8: Cook-Torrance GGX, shaders/hlsl/pbr.hlsli (shadow pass not on the path: shadow = 1)
+// a8: Cook-Torrance GGX, shaders/hlsl/pbr.hlsli; the directional light's shadow term in its own raster variant (shade_pbr<true>)
 #define PBR_PI 3.14159265358979323846f
 #define PBR_EPSILON 0.0001f
 __device__ __forceinline__ float max0(float x) { return x > 0.0f ? x : 0.0f; }
@@ -281,7 +281,51 @@ __device__ __forceinline__ bool draw_needs_alpha_test(DrawRef D) {
     return !(hi < cutoff) && !(lo >= cutoff);
 }
 
+// CalculateShadow (shaders/hlsl/shadow.hlsli:49-121), line for line.  ShadowParams (shadow.hlsli:20-30) at D.shadow_data: LightSpaceMatrix @0,
+// ShadowBias @64, NormalBias @68, ShadowMapSize @72, ShadowStrength @80 -- wave-uniform, scalar loads once per draw.  The comparison sampler is
+// this build's (sampler.rs is empty, include/mirhi.h MIRHI_TEXTURE_SHADOW_MAP): LESS_OR_EQUAL against the reference depth clamped to [0, 1],
+// nearest texel, clamp-to-edge.
+__device__ __forceinline__ float shadow_tap(DrawRef D, float u, float v, float dref, float fw, float fh) {
+    const float fi = fminf(fmaxf(floorf(u * fw), 0.0f), fw - 1.0f);          // (fmaxf(NaN, 0) = 0)
+    const float fj = fminf(fmaxf(floorf(v * fh), 0.0f), fh - 1.0f);
+    const float texel = D.shadow_map[(size_t)(uint32_t)fj * D.shadow_w + (uint32_t)fi];
+    return dref <= texel ? 1.0f : 0.0f;
+}
+__device__ __forceinline__ float calculate_shadow(DrawRef D, f3 worldPos, f3 normal, f3 lightDir) {
+    const CBytePtr S = cb(D.shadow_data);
+    const CFloatPtr lsm = reinterpret_cast<CFloatPtr>(S);
+    const f4 ls = mat4_mul(lsm, {worldPos.x, worldPos.y, worldPos.z, 1.0f});                     // :58
+    float px = div_rn_nb(ls.x, ls.w), py = div_rn_nb(ls.y, ls.w);                               // :61
+    const float pz = div_rn_nb(ls.z, ls.w);
+    px = px * 0.5f + 0.5f; py = py * 0.5f + 0.5f;                                               // :65
+    py = 1.0f - py;                                                                             // :66
+    if (px < 0.0f || px > 1.0f || py < 0.0f || py > 1.0f || pz < 0.0f || pz > 1.0f) return 1.0f;   // :70-75
+    const float NdotL = dot3(normal, lightDir);                                                 // :79
+    const float b0 = ldcf(S, 64) * (1.0f - NdotL);                                              // :80
+    const float bias = b0 > 0.0005f ? b0 : 0.0005f;
+    const f3 offsetPos = add3(worldPos, scale3(normal, ldcf(S, 68)));                           // :84
+    const f4 ols = mat4_mul(lsm, {offsetPos.x, offsetPos.y, offsetPos.z, 1.0f});                // :85
+    float ox = div_rn_nb(ols.x, ols.w), oy = div_rn_nb(ols.y, ols.w);                           // :86
+    const float oz = div_rn_nb(ols.z, ols.w);
+    ox = ox * 0.5f + 0.5f; oy = oy * 0.5f + 0.5f;                                               // :87
+    oy = 1.0f - oy;                                                                             // :88
+    const float currentDepth = oz - bias;                                                       // :92
+    const float dref = fminf(fmaxf(currentDepth, 0.0f), 1.0f);                                  // (the sampler clamps D_ref)
+    const float tx = rcp_rn_nb(ldcf(S, 72)), ty = rcp_rn_nb(ldcf(S, 76));                       // :98
+    const float fw = (float)D.shadow_w, fh = (float)D.shadow_h;
+    float shadow = 0.0f;
+#pragma unroll
+    for (int x = -1; x <= 1; ++x)
+#pragma unroll
+        for (int y = -1; y <= 1; ++y)                                                           // :101-113
+            shadow += shadow_tap(D, ox + (float)x * tx, oy + (float)y * ty, dref, fw, fh);
+    shadow = div_rn_nb(shadow, 9.0f);                                                           // :116
+    return 1.0f + (shadow - 1.0f) * ldcf(S, 80);                                                // :120 lerp(1, shadow, ShadowStrength)
+}
+
 // pixel/model_pbr.hlsl:159-320 after the shared varying interpolation
+// SHADOW: the variant with the directional light's shadow term (model_pbr.hlsl:238-251) for draws with a shadow map bound
+template <bool SHADOW = false>
 __device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint32_t vi[3], float u, float v, f3 worldPos, f3 V, f3 N, const UvGrad& grad) {
     const CBytePtr M = cb(D.material);                                                  // MaterialData :36-59 (80 B)
     f4 baseColor = {ldcf(M, 0), ldcf(M, 4), ldcf(M, 8), ldcf(M, 12)};
@@ -321,7 +365,13 @@ __device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint3
         const f3 dir = {ldcf(cb(D.lights), 0), ldcf(cb(D.lights), 4), ldcf(cb(D.lights), 8)};
         const float intensity = ldcf(cb(D.lights), 12);
         const f3 color = {ldcf(cb(D.lights), 16), ldcf(cb(D.lights), 20), ldcf(cb(D.lights), 24)};
-        if (intensity != 0.0f) lighting = add3(lighting, pbr_direct(N, V, normalize3({-dir.x, -dir.y, -dir.z}), scale3(color, intensity), m));
+        if (!SHADOW || !D.shadow_map) {
+            if (intensity != 0.0f) lighting = add3(lighting, pbr_direct(N, V, normalize3({-dir.x, -dir.y, -dir.z}), scale3(color, intensity), m));
+        } else if (intensity != 0.0f) {                                                  // (intensity 0: exact zeros, shadow or not)
+            const f3 L = normalize3({-dir.x, -dir.y, -dir.z});
+            const float shadow = calculate_shadow(D, worldPos, N, L);                   // model_pbr.hlsl:238-245
+            lighting = add3(lighting, scale3(pbr_direct(N, V, L, scale3(color, intensity), m), shadow));   // :251
+        }
     }
     const uint32_t numPoint = D.point_lights ? ldcu(cb(D.lights), 32) : 0u;
     const uint32_t numSpot = D.spot_lights ? ldcu(cb(D.lights), 36) : 0u;
@@ -365,8 +415,8 @@ __device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint3
     return {col.x, col.y, col.z, baseColor.w};
 }
 
-// FULL: the variant that also carries the Cook-Torrance program and mip-mapped (trilinear) sampling
-template <bool FULL>
+// FULL: the variant that also carries the Cook-Torrance program and mip-mapped (trilinear) sampling; SHADOW: and the shadow term
+template <bool FULL, bool SHADOW = false>
 __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3], float pxc, float pyc) {
     f4 c[3];
     const bool full = D.program >= 2;
@@ -419,7 +469,7 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
         grad.dudy = ((by[0] * uvk[0][0] + by[1] * uvk[1][0]) + by[2] * uvk[2][0]) - u;
         grad.dvdy = ((by[0] * uvk[0][1] + by[1] * uvk[1][1]) + by[2] * uvk[2][1]) - v;
     }
-    if (FULL && D.program == 3) return shade_pbr(D, b, vi, u, v, worldPos, V, N, grad);
+    if (FULL && D.program == 3) return shade_pbr<SHADOW>(D, b, vi, u, v, worldPos, V, N, grad);
     // pixel/model_full.hlsl:85-150
     const f4 baseColor = {ldcf(cb(D.material), 0), ldcf(cb(D.material), 4), ldcf(cb(D.material), 8), ldcf(cb(D.material), 12)};
     const float roughness = ldcf(cb(D.material), 20), ao = ldcf(cb(D.material), 24);
@@ -490,11 +540,11 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
     return {col.x, col.y, col.z, albedoSample.w * baseColor.w};
 }
 
-template <bool FULL>
+template <bool FULL, bool SHADOW = false>
 __device__ __forceinline__ f4 shade_model_program(DrawRef D, uint32_t tri, float pxc, float pyc) {
     uint32_t vin[3];
     fetch_triangle_indices(D, tri, vin);
-    return shade_model_program<FULL>(D, vin, pxc, pyc);
+    return shade_model_program<FULL, SHADOW>(D, vin, pxc, pyc);
 }
 
 #pragma clang fp contract(fast)

@@ -10,7 +10,7 @@ from typing import Optional, Sequence
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libmirhost.so")
-SLOT_COUNT, TEXTURE_COUNT = 6, 5
+SLOT_COUNT, TEXTURE_COUNT = 7, 6
 
 
 class _Viewport(C.Structure):

@@ -15,7 +15,8 @@ from typing import List, Optional
 
 import numpy as np
 
-PROGRAM_TRIANGLE, PROGRAM_MODEL, PROGRAM_MODEL_FULL, PROGRAM_MODEL_PBR = 0, 1, 2, 3
+PROGRAM_TRIANGLE, PROGRAM_MODEL, PROGRAM_MODEL_FULL, PROGRAM_MODEL_PBR, PROGRAM_SHADOW = 0, 1, 2, 3, 4
+LOAD_OP_LOAD, LOAD_OP_CLEAR = 0, 1
 CULL_NONE, CULL_FRONT, CULL_BACK, CULL_FRONT_AND_BACK = 0, 1, 2, 3
 FRONT_CCW, FRONT_CW = 0, 1
 CMP_NEVER, CMP_LESS, CMP_EQUAL, CMP_LESS_OR_EQUAL, CMP_GREATER, CMP_NOT_EQUAL, CMP_GREATER_OR_EQUAL, CMP_ALWAYS = range(8)
@@ -137,6 +138,49 @@ def normal_matrix(model: np.ndarray) -> np.ndarray:
         return np.eye(4, dtype=f32)
     inv_t = np.linalg.inv(m64).T  # maths matrix (row-major) of inverse-transpose
     return inv_t.T.astype(f32)  # back to [col,row]
+
+
+def orthographic_rh(left, right, bottom, top, near, far) -> np.ndarray:
+    """glam Mat4::orthographic_rh (depth 0 at near, 1 at far), [col,row] like perspective_rh."""
+    rw, rh = f32(1.0 / (f32(right) - f32(left))), f32(1.0 / (f32(top) - f32(bottom)))
+    r = f32(1.0 / (f32(near) - f32(far)))
+    m = np.zeros((4, 4), dtype=f32)
+    m[0, 0], m[1, 1], m[2, 2] = rw + rw, rh + rh, r
+    m[3] = [-(f32(left) + f32(right)) * rw, -(f32(top) + f32(bottom)) * rh, r * f32(near), 1.0]
+    return m
+
+
+def light_space_matrix(direction, center=(0.0, 0.0, 0.0), half_extent: float = 6.0, near: float = 0.1, far: float = 25.0,
+                       distance: float = 10.0) -> np.ndarray:
+    """Orthographic light matrix of a directional light (projection * view, the convention of CameraData.viewProjection):
+    looks along `direction` at `center` from `distance` away, a square frustum of +-half_extent."""
+    d = _normalize(direction)
+    up = (0.0, 1.0, 0.0) if abs(float(d[1])) < 0.99 else (0.0, 0.0, -1.0)
+    eye = _v(center) - d * f32(distance)
+    view = look_at_rh(eye, center, up)
+    return mat_mul(orthographic_rh(-half_extent, half_extent, -half_extent, half_extent, near, far), view)
+
+
+def flip_clip_y(m: np.ndarray) -> np.ndarray:
+    """m with clip y negated (the Vulkan y flip projection_vulkan applies to a camera, camera.rs:135).  The shadow pass renders with
+    flip_clip_y(L) into a plain viewport, so that map row j holds v = (j + 0.5) / H of the lookup's v = 1 - (y * 0.5 + 0.5) with
+    ShadowParams.LightSpaceMatrix = L (shadow.hlsli:65-66)."""
+    out = m.astype(f32).copy()
+    out[:, 1] = -out[:, 1]
+    return out
+
+
+def shadow_constants_ubo(light_space: np.ndarray, model: np.ndarray) -> bytes:
+    """ShadowConstants 128 B of the SHADOW program (vertex/shadow.hlsl:7-11): lightSpaceMatrix@0 model@64."""
+    return light_space.astype(f32).tobytes() + model.astype(f32).tobytes()
+
+
+def shadow_ubo(light_space: np.ndarray, bias: float = 0.005, normal_bias: float = 0.02, size=(2048, 2048), strength: float = 1.0) -> bytes:
+    """ShadowParams 96 B (shaders/hlsl/shadow.hlsli:20-30): LightSpaceMatrix@0 ShadowBias@64 NormalBias@68 ShadowMapSize@72
+    ShadowStrength@80, padding to 96."""
+    out = (light_space.astype(f32).tobytes() + np.array([bias, normal_bias, size[0], size[1], strength, 0, 0, 0], dtype=f32).tobytes())
+    assert len(out) == 96
+    return out
 
 
 def camera_ubo(view: np.ndarray, proj: np.ndarray, eye) -> bytes:
@@ -269,6 +313,18 @@ class DrawSpec:
 
 
 @dataclass
+class ShadowSpec:
+    """A depth-only shadow scope ahead of a scene's main scope: the casters are PROGRAM_SHADOW draws (camera =
+    shadow_constants_ubo(flip_clip_y(L), model), viewport None = the map's extent), `params` the ShadowParams (LightSpaceMatrix L)
+    every MODEL_PBR draw of the scene samples the map with."""
+    casters: List[DrawSpec]
+    size: tuple = (2048, 2048)
+    params: bytes = b""
+    clear_depth: float = 1.0
+    load_op: int = LOAD_OP_CLEAR
+
+
+@dataclass
 class Scene:
     name: str
     width: int
@@ -276,6 +332,7 @@ class Scene:
     draws: List[DrawSpec] = field(default_factory=list)
     clear_color: tuple = (0.0, 0.0, 0.0, 1.0)  # rendering.rs:102-115 default
     clear_depth: float = 1.0                   # rendering.rs:356-370 default
+    shadow: Optional[ShadowSpec] = None        # None: no shadow scope (the oracle's PBR frame: shadow = 1)
 
     @property
     def num_triangles(self) -> int:
@@ -843,3 +900,65 @@ SMALL_CASES = {
     "random_small": lambda: random_triangles(300, 320, 200, seed=42, rmin=2, rmax=40),
     "sphere_small": lambda: displaced_sphere(24, 17, 256, 160, seed=3),
 }
+
+
+# ------------------------------------------------------------------------------------------------
+# shadow mapping (vertex/shadow.hlsl + pixel/shadow.hlsl, shadow.hlsli CalculateShadow in model_pbr.hlsl)
+# ------------------------------------------------------------------------------------------------
+SHADOWED_GROUND_LIGHT = (0.45, -1.0, 0.3)
+SHADOWED_GROUND_BOX = ((0.3, 1.1, 0.2), (0.7, 1.1, 0.7))        # centre, half extent
+SHADOWED_GROUND_EXTENT = 8.0                                      # the light frustum's half extent: covers the whole ground
+
+
+def _ground_quad(half: float, n: int) -> tuple:
+    """The y = 0 plane over [-half, half]^2, n x n quads, normal +y."""
+    uu, vv = np.meshgrid(np.linspace(0.0, 1.0, n + 1), np.linspace(0.0, 1.0, n + 1), indexing="xy")
+    uu, vv = uu.reshape(-1), vv.reshape(-1)
+    pos = np.stack([-half + 2 * half * uu, np.zeros_like(uu), half - 2 * half * vv], axis=1)
+    nrm = np.tile(np.array([0.0, 1.0, 0.0]), (pos.shape[0], 1))
+    tan = np.tile(np.array([1.0, 0.0, 0.0, 1.0]), (pos.shape[0], 1))
+    return _pack_vertex48(pos, nrm, np.stack([uu, vv], axis=1), tan), _grid_indices(n, n).astype(np.uint32)
+
+
+def shadowed_ground_case(width: int = 320, height: int = 240, map_size: int = 512, strength: float = 1.0,
+                         light_dir=SHADOWED_GROUND_LIGHT, intensity: float = 2.0) -> Scene:
+    """MODEL_PBR ground plane, a box that casts a shadow on it and a sphere, under one directional light; the box is the shadow
+    scope's only caster."""
+    view, proj, cam = default_camera(width, height, eye=(0.0, 4.5, 6.5))
+    light = light_ubo(direction=light_dir, intensity=intensity, color=(1.0, 0.97, 0.9))
+    ls = light_space_matrix(light_dir, half_extent=SHADOWED_GROUND_EXTENT)
+    gv, gi = _ground_quad(5.0, 8)
+    bv, bi = _box_mesh(*SHADOWED_GROUND_BOX)
+    sphere = displaced_sphere(24, 17, width, height, seed=3).draws[0]
+    eye4 = np.eye(4, dtype=f32)
+    draws = [
+        DrawSpec(vertices=gv, stride=48, count=gi.size, indices=gi, program=PROGRAM_MODEL_PBR, cull_mode=CULL_NONE, camera=cam,
+                 object=object_ubo(eye4), light=light, material=pbr_material_ubo((0.8, 0.8, 0.75, 1.0), 0.0, 0.7)),
+        DrawSpec(vertices=bv, stride=48, count=bi.size, indices=bi, program=PROGRAM_MODEL_PBR, cull_mode=CULL_BACK, front_face=FRONT_CCW,
+                 camera=cam, object=object_ubo(eye4), light=light, material=pbr_material_ubo((0.6, 0.3, 0.2, 1.0), 0.0, 0.5)),
+        DrawSpec(vertices=sphere.vertices, stride=48, count=sphere.count, indices=sphere.indices, program=PROGRAM_MODEL_PBR,
+                 cull_mode=CULL_BACK, front_face=sphere.front_face, camera=cam,
+                 object=object_ubo(trs((0.6, 0.6, 0.6), (0.0, 0.0, 0.0, 1.0), (-2.0, 0.8, 1.0))), light=light,
+                 material=pbr_material_ubo((0.2, 0.4, 0.8, 1.0), 0.3, 0.4)),
+    ]
+    caster = DrawSpec(vertices=bv, stride=48, count=bi.size, indices=bi, program=PROGRAM_SHADOW, cull_mode=CULL_NONE,
+                      camera=shadow_constants_ubo(flip_clip_y(ls), eye4))
+    shadow = ShadowSpec([caster], (map_size, map_size), shadow_ubo(ls, 0.005, 0.02, (map_size, map_size), strength))
+    return Scene("shadowed-ground", width, height, draws, clear_color=(0.02, 0.02, 0.03, 1.0), shadow=shadow)
+
+
+def pcf_factor(depth_map: np.ndarray, u: np.ndarray, v: np.ndarray, dref: np.ndarray, texel=None, strength: float = 1.0) -> np.ndarray:
+    """Numpy model of CalculateShadow's 3x3 comparison taps with this build's sampler (include/mirhi.h MIRHI_TEXTURE_SHADOW_MAP):
+    LESS_OR_EQUAL against clamp(dref, 0, 1), nearest texel, clamp-to-edge; tap offsets `texel` = 1 / ShadowMapSize (default the
+    map's extent).  Returns lerp(1, lit taps / 9, strength) per sample."""
+    h, w = depth_map.shape
+    tu, tv = (1.0 / w, 1.0 / h) if texel is None else texel
+    d = np.clip(dref, 0.0, 1.0)
+    lit = np.zeros(np.shape(u), dtype=np.float64)
+    for x in (-1, 0, 1):
+        for y in (-1, 0, 1):
+            i = np.clip(np.floor((u + x * tu) * w), 0, w - 1).astype(np.int64)
+            j = np.clip(np.floor((v + y * tv) * h), 0, h - 1).astype(np.int64)
+            lit += (d <= depth_map[j, i]).astype(np.float64)
+    s = lit / 9.0
+    return 1.0 + (s - 1.0) * strength
