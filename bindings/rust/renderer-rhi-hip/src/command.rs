@@ -98,6 +98,11 @@ impl CommandBuffer {
     pub fn bind_texture(&self, slot: TextureSlot, image: Option<&Image>) -> RhiResult<()> {
         check(unsafe { mirhi_sys::mirhi_cmd_bind_texture(self.raw, slot as i32, image.map_or(std::ptr::null_mut(), |i| i.raw)) })
     }
+    /// Set 2, bindings 3 / 4 of pixel/model_pbr_ibl_csm.hlsl:115-127: the four-layer D32 array and its `CSMParams` (336 B); `None` unbinds.
+    pub fn bind_shadow_cascades(&self, cascades: Option<(&Image, &Buffer)>, offset: u64, range: u64) -> RhiResult<()> {
+        let (array, params) = cascades.map_or((std::ptr::null_mut(), std::ptr::null_mut()), |(a, b)| (a.raw, b.raw));
+        check(unsafe { mirhi_sys::mirhi_cmd_bind_shadow_cascades(self.raw, array, params, offset, range) })
+    }
     pub fn set_viewport(&self, v: &Viewport) -> RhiResult<()> {                                                      // :522
         let raw = mirhi_sys::mirhi_viewport { x: v.x, y: v.y, width: v.width, height: v.height, min_depth: v.min_depth, max_depth: v.max_depth };
         check(unsafe { mirhi_sys::mirhi_cmd_set_viewport(self.raw, &raw) })

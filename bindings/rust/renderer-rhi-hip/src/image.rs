@@ -20,6 +20,20 @@ impl Image {
         check(unsafe { mirhi_sys::mirhi_image_create(device.raw, width, height, format as i32, &mut raw) })?;
         Ok(Self { device, raw })
     }
+    /// `layers` tightly packed width x height levels in one allocation (D32Sfloat only): the `Texture2DArray<float>` of shadow_csm.hlsli.
+    pub fn new_array(device: Arc<Device>, width: u32, height: u32, layers: u32, format: Format) -> RhiResult<Self> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { mirhi_sys::mirhi_image_create_array(device.raw, width, height, layers, format as i32, &mut raw) })?;
+        Ok(Self { device, raw })
+    }
+    /// A non-owning 2-D image of one layer (a `vk::ImageView` with `layer_count` 1, what `DepthAttachment` takes, rendering.rs:319-370).
+    /// Drop it before the array: the array refuses to be destroyed while a view is alive.
+    pub fn layer_view(&self, layer: u32) -> RhiResult<Self> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { mirhi_sys::mirhi_image_create_layer_view(self.raw, layer, &mut raw) })?;
+        Ok(Self { device: self.device.clone(), raw })
+    }
+    pub fn layers(&self) -> u32 { unsafe { mirhi_sys::mirhi_image_layers(self.raw) } }
     /// RGBA8 / float texels of level 0, row-major, top row first.
     pub fn upload(&self, texels: &[u8]) -> RhiResult<()> {
         check(unsafe { mirhi_sys::mirhi_image_upload(self.raw, texels.as_ptr().cast(), texels.len() as u64) })

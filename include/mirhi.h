@@ -30,7 +30,9 @@ extern "C" {
                                     mirhi_device_dispatch_path, mirhi_device_measure_roundtrip, mirhi_build_id, mirhi_device_set_tile_split_layout,
                                     mirhi_device_split_rows, mirhi_device_stats grew four words;
                                     still 5 (new enum values only): MIRHI_PROGRAM_SHADOW, MIRHI_SLOT_SHADOW_DATA, MIRHI_TEXTURE_SHADOW_MAP, depth-only
-                                    pipelines (colour format UNDEFINED) and depth-only rendering scopes (color_image NULL) */
+                                    pipelines (colour format UNDEFINED) and depth-only rendering scopes (color_image NULL);
+                                    still 5 (new functions only): mirhi_image_create_array, mirhi_image_create_layer_view, mirhi_image_layers,
+                                    mirhi_cmd_bind_shadow_cascades */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -138,6 +140,21 @@ typedef enum {
 } mirhi_format;
 mirhi_result mirhi_image_create(mirhi_device* dev, uint32_t width, uint32_t height, mirhi_format format, mirhi_image** out); /* DepthBuffer::new depth_buffer.rs:117-127 (0 size -> error) */
 mirhi_result mirhi_image_wrap_device_memory(mirhi_device* dev, uint32_t width, uint32_t height, mirhi_format format, void* device_ptr, mirhi_image** out);
+/* Layered images: the Texture2DArray<float> of pixel/model_pbr_ibl_csm.hlsl:115-116 (four shadow cascades, shadow_csm.hlsli:19).  ONE allocation of
+ * `layers` tightly packed width x height levels, layer k at byte offset k * width * height * bytes per texel.  D32_SFLOAT only (every other format:
+ * InvalidHandle); layers in [1, 2048] (Vulkan's guaranteed maxImageArrayLayers).  mirhi_image_width / _height report one layer's extent,
+ * mirhi_image_size_bytes the whole allocation, mirhi_image_upload / _read move the whole allocation (layers in order).  An array is no 2-D image: it is
+ * refused as an attachment and at MIRHI_TEXTURE_SHADOW_MAP; its layers are rendered and sampled one by one through layer views, and the whole of it is
+ * sampled through mirhi_cmd_bind_shadow_cascades. */
+mirhi_result mirhi_image_create_array(mirhi_device* dev, uint32_t width, uint32_t height, uint32_t layers, mirhi_format format, mirhi_image** out);
+/* A non-owning 2-D image of one layer: a VkImageView with baseArrayLayer = layer, layerCount = 1, which is what the reference's DepthAttachment takes
+ * (crates/rhi/src/rendering.rs:319-370).  Accepted wherever a D32_SFLOAT image is: as the depth_image of a depth-only scope, by mirhi_image_upload /
+ * _read (that layer only) and at MIRHI_TEXTURE_SHADOW_MAP (one layer as an ordinary shadow map).  layer >= layers: InvalidHandle.  Destroying a view
+ * frees nothing; destroying an array with live views fails as destroying a device with live children does.  Attachment ordering across queue lanes
+ * goes by the ARRAY: a scope that samples the array (or a view) waits for the scopes that wrote any of its layers on another lane, and the other way
+ * round; two scopes that write different layers of one array may be serialised. */
+mirhi_result mirhi_image_create_layer_view(mirhi_image* array, uint32_t layer, mirhi_image** out);
+uint32_t     mirhi_image_layers(const mirhi_image* img);   /* layers of an array; 1 for every other image (views included) */
 mirhi_result mirhi_image_upload(mirhi_image* img, const void* src, uint64_t len);
 mirhi_result mirhi_image_read(mirhi_image* img, void* dst, uint64_t len);   /* added: swapchain images have no readback (swapchain.rs:255) */
 /* Texture fidelity (image.rs / sampler.rs / texture.rs are stubs in the reference, the shaders assume
@@ -296,6 +313,18 @@ mirhi_result mirhi_cmd_bind_vertex_buffers(mirhi_cmd* cmd, uint32_t first_bindin
 mirhi_result mirhi_cmd_bind_index_buffer(mirhi_cmd* cmd, mirhi_buffer* buffer, uint64_t offset, mirhi_index_type type); /* :471 */
 mirhi_result mirhi_cmd_bind_uniform(mirhi_cmd* cmd, mirhi_uniform_slot slot, mirhi_buffer* buffer, uint64_t offset, uint64_t range); /* bind_descriptor_sets :493 + descriptor.rs:390-409 buffer_info */
 mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slot slot, mirhi_image* image);   /* descriptor.rs:411-420 image_info */
+/* Shadow cascades: set 2, bindings 3 and 4 of pixel/model_pbr_ibl_csm.hlsl:115-127 (Texture2DArray<float> shadowMap t10 / s8 and cbuffer ShadowData b3
+ * { CSMParams }).  `array`: a D32_SFLOAT array (not a view) of exactly CASCADE_COUNT = 4 layers (shadow_csm.hlsli:19), or NULL to unbind (the buffer is
+ * then ignored).  `params`: a uniform buffer holding CSMParams (shadow_csm.hlsli:23-39, 336 B, range >= 336; range 0 = to the end of the buffer):
+ * Cascades[k].ViewProjection @80k (the convention of ShadowParams.LightSpaceMatrix / CameraData.viewProjection), Cascades[k].SplitDepth @80k + 64,
+ * ShadowBias @320, NormalBias @324, ShadowMapSize @328.  The binding lives with the command buffer like the textures and is latched per draw.
+ * A MODEL_PBR draw recorded with cascades bound multiplies the directional light by CalculateShadowCSM (shadow_csm.hlsli:163-194,
+ * model_pbr_ibl_csm.hlsl:280-298) instead of by 1: SelectCascade on SV_Position.z (the depth the draw's scope resolves for the pixel), one
+ * 3 x 3 PCF in the selected layer with the comparison sampler of MIRHI_TEXTURE_SHADOW_MAP (taps are clamped to the edge WITHIN the layer), offsets of
+ * 1 / ShadowMapSize on both axes.  MODEL / MODEL_FULL / TRIANGLE ignore the binding.  A MODEL_PBR draw with a single shadow map AND cascades bound is
+ * refused (InvalidHandle), as are single-map and cascaded draws in one rendering scope; a cascaded draw's pipeline may not blend, discard fragments
+ * or use a predicate depth state, and needs the depth test (its depth key is where SV_Position.z comes from). */
+mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range);
 mirhi_result mirhi_cmd_set_viewport(mirhi_cmd* cmd, const mirhi_viewport* viewport);  /* set_viewport :522 */
 mirhi_result mirhi_cmd_set_scissor(mirhi_cmd* cmd, const mirhi_rect2d* scissor);      /* set_scissor :549 */
 /* instance_count > 1 (at most 4096): the path has no instance-rate input (binding 0 is per-vertex, vertex.rs:35-41,130-136; no program

@@ -201,6 +201,9 @@ _SIGNATURES = {
     "mirhi_buffer_destroy": (C.c_int32, [C.c_void_p]),
     "mirhi_image_create": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mirhi_image_wrap_device_memory": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mirhi_image_create_array": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mirhi_image_create_layer_view": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mirhi_image_layers": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_upload": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mirhi_image_read": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mirhi_image_generate_mips": (C.c_int32, [C.c_void_p]),
@@ -234,6 +237,7 @@ _SIGNATURES = {
     "mirhi_cmd_bind_index_buffer": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32]),
     "mirhi_cmd_bind_uniform": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64]),
     "mirhi_cmd_bind_texture": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mirhi_cmd_bind_shadow_cascades": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "mirhi_cmd_set_viewport": (C.c_int32, [C.c_void_p, C.POINTER(Viewport)]),
     "mirhi_cmd_set_scissor": (C.c_int32, [C.c_void_p, C.POINTER(Rect2D)]),
     "mirhi_cmd_draw": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -469,6 +473,29 @@ class Image:
             check(lib().mirhi_image_wrap_device_memory(device.handle, width, height, fmt, C.c_void_p(device_ptr), C.byref(h)))
         self.handle, self.device, self.width, self.height, self.format = h, device, width, height, fmt
 
+    @classmethod
+    def _adopt(cls, handle, device, width, height, fmt) -> "Image":
+        img = cls.__new__(cls)
+        img.handle, img.device, img.width, img.height, img.format = handle, device, width, height, fmt
+        return img
+
+    @classmethod
+    def array(cls, device: Device, width: int, height: int, layers: int, fmt: int) -> "Image":
+        """mirhi_image_create_array: `layers` tightly packed width x height levels in one allocation (D32_SFLOAT only)."""
+        h = C.c_void_p()
+        check(lib().mirhi_image_create_array(device.handle, width, height, layers, fmt, C.byref(h)))
+        return cls._adopt(h, device, width, height, fmt)
+
+    def layer_view(self, layer: int) -> "Image":
+        """mirhi_image_create_layer_view: a non-owning 2-D image of one layer (destroy it before the array)."""
+        h = C.c_void_p()
+        check(lib().mirhi_image_create_layer_view(self.handle, layer, C.byref(h)))
+        return Image._adopt(h, self.device, self.width, self.height, self.format)
+
+    @property
+    def layers(self) -> int:
+        return int(lib().mirhi_image_layers(self.handle))
+
     def upload(self, data):
         arr = _as_bytes(data)
         check(lib().mirhi_image_upload(self.handle, arr.ctypes.data, arr.size))
@@ -493,6 +520,9 @@ class Image:
         n = lib().mirhi_image_size_bytes(self.handle)
         raw = np.empty(n, dtype=np.uint8)
         check(lib().mirhi_image_read(self.handle, raw.ctypes.data, n))
+        layers = self.layers
+        if layers > 1:      # an array (D32_SFLOAT): the layers in order
+            return raw.view(np.float32).reshape(layers, self.height, self.width)
         if self.format == Format.R32G32B32A32_SFLOAT:
             return raw.view(np.float32).reshape(self.height, self.width, 4)
         if self.format == Format.D32_SFLOAT:
@@ -669,6 +699,10 @@ class CommandBuffer:
     def bind_texture(self, slot: int, image: Optional[Image]):
         check(lib().mirhi_cmd_bind_texture(self.handle, slot, image.handle if image else None))
 
+    def bind_shadow_cascades(self, array: Optional[Image], params: Optional[Buffer] = None, offset: int = 0, range_: int = 0):
+        """mirhi_cmd_bind_shadow_cascades: the four-layer D32 array and its CSMParams (scenes.csm_ubo); array=None unbinds."""
+        check(lib().mirhi_cmd_bind_shadow_cascades(self.handle, array.handle if array else None, params.handle if params else None, offset, range_))
+
     def set_viewport(self, x, y, width, height, min_depth=0.0, max_depth=1.0):
         vp = Viewport(x, y, width, height, min_depth, max_depth)
         check(lib().mirhi_cmd_set_viewport(self.handle, C.byref(vp)))
@@ -765,10 +799,14 @@ class SceneResources:
 
     def __init__(self, device: Device, scene, color_format: int = Format.R32G32B32A32_SFLOAT, want_prim: bool = False,
                  want_depth: bool = False, color_image: Optional[Image] = None, wrap_buffers=None,
-                 color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None):
+                 color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None,
+                 cascade_array: Optional[Image] = None):
         """scene.shadow (scenes.ShadowSpec) adds a depth-only shadow scope ahead of the main scope: recorded into the same command
         buffer, or with shadow_cmd=True into a command buffer of its own (self.shadow_cmd; render() submits both, the shadow one first --
-        put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames)."""
+        put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames).
+        scene.cascades (scenes.CascadeSpec): four depth-only scopes instead, one per layer view of a D32 array (self.cascade_array, or the
+        existing one passed as cascade_array=), in the same command buffer or with shadow_cmd=True in self.shadow_cmd; the MODEL_PBR draws
+        sample the array through bind_shadow_cascades."""
         self.device, self.scene = device, scene
         self.color_load_op = color_load_op
         self.owns_color = color_image is None
@@ -859,13 +897,45 @@ class SceneResources:
                                               camera=buf(BufferUsage.Uniform, c.camera, key=("u", c.camera)), draw=c))
             if shadow_cmd:
                 self.shadow_cmd = CommandBuffer(device)
+        self.cascades, self.cascade_array, self.cascade_views, self.cascade_state, self.owns_cascade_array = getattr(scene, "cascades", None), None, [], [], False
+        if self.cascades is not None:
+            assert self.shadow is None, "a scene has a single shadow map or cascades, not both"
+            cs = self.cascades
+            self.cascade_array = cascade_array
+            if self.cascade_array is None:
+                self.cascade_array, self.owns_cascade_array = Image.array(device, cs.size[0], cs.size[1], len(cs.casters), Format.D32_SFLOAT), True
+            self.cascade_views = [self.cascade_array.layer_view(k) for k in range(len(cs.casters))]
+            self.cascade_params = buf(BufferUsage.Uniform, cs.params, key=("u", cs.params))
+            for layer in cs.casters:
+                states = []
+                for c in layer:
+                    pkey = ("shadow-pipe", c.stride, c.cull_mode, c.front_face, c.depth_compare)
+                    if pkey not in cache:
+                        cache[pkey] = (GraphicsPipelineBuilder().vertex_shader(Program.SHADOW).fragment_shader(Program.SHADOW)
+                                       .vertex_binding(c.stride).vertex_attributes(SHADOW_VERTEX_OFFSETS)
+                                       .color_attachment_format(Format.UNDEFINED).depth_attachment_format(Format.D32_SFLOAT)
+                                       .cull_mode(c.cull_mode).front_face(c.front_face).depth_compare_op(c.depth_compare)).build(device)
+                        self.objs.append(cache[pkey])
+                    states.append(dict(pipe=cache[pkey], vb=buf(BufferUsage.Vertex, c.vertices),
+                                       ib=buf(BufferUsage.Index, c.indices) if c.indices is not None else None,
+                                       camera=buf(BufferUsage.Uniform, c.camera, key=("u", c.camera)), draw=c))
+                self.cascade_state.append(states)
+            if shadow_cmd:
+                self.shadow_cmd = CommandBuffer(device)
         self.record()
 
     def _record_shadow(self, cmd: "CommandBuffer"):
-        sh = self.shadow
+        if self.cascades is not None:
+            for view, states in zip(self.cascade_views, self.cascade_state):
+                self._record_depth_scope(cmd, self.cascades, view, states)
+        else:
+            self._record_depth_scope(cmd, self.shadow, self.shadow_map, self.shadow_state)
+
+    @staticmethod
+    def _record_depth_scope(cmd: "CommandBuffer", sh, target: Image, states):
         w, h = sh.size
-        cmd.begin_rendering(None, depth=self.shadow_map, clear_depth=sh.clear_depth, depth_load_op=sh.load_op, depth_store_op=StoreOp.STORE)
-        for st in self.shadow_state:
+        cmd.begin_rendering(None, depth=target, clear_depth=sh.clear_depth, depth_load_op=sh.load_op, depth_store_op=StoreOp.STORE)
+        for st in states:
             d = st["draw"]
             cmd.set_viewport(*(d.viewport or (0.0, 0.0, float(w), float(h), 0.0, 1.0)))
             cmd.set_scissor(*(d.scissor or (0, 0, w, h)))
@@ -886,7 +956,7 @@ class SceneResources:
             self._record_shadow(self.shadow_cmd)
             self.shadow_cmd.end()
         cmd.begin_reusable()
-        if self.shadow is not None and self.shadow_cmd is None:
+        if (self.shadow is not None or self.cascades is not None) and self.shadow_cmd is None:
             self._record_shadow(cmd)
         cmd.begin_rendering(self.color, clear_color=s.clear_color, color_load_op=self.color_load_op, depth=self.depth, clear_depth=s.clear_depth,
                             depth_store_op=StoreOp.STORE if self.depth else StoreOp.DONT_CARE, prim_id=self.prim)
@@ -910,6 +980,10 @@ class SceneResources:
                 cmd.bind_texture(TextureSlot.SHADOW_MAP, self.shadow_map)
             elif self.shadow is not None:
                 cmd.bind_texture(TextureSlot.SHADOW_MAP, None)
+            if self.cascades is not None and d.program == scenes.PROGRAM_MODEL_PBR:
+                cmd.bind_shadow_cascades(self.cascade_array, self.cascade_params)
+            elif self.cascades is not None:
+                cmd.bind_shadow_cascades(None)
             if st["ib"] is not None:
                 cmd.bind_index_buffer(st["ib"], 0, IndexType.UINT16 if d.index_type == 2 else IndexType.UINT32)
                 cmd.draw_indexed(d.count, getattr(d, "instances", 1), d.first, d.vertex_offset, 0)
@@ -937,6 +1011,10 @@ class SceneResources:
             self.shadow_cmd.destroy()
         if self.owns_shadow_map:
             self.shadow_map.destroy()
+        for v in self.cascade_views:
+            v.destroy()
+        if self.owns_cascade_array:
+            self.cascade_array.destroy()
         for o in self.objs:
             o.destroy()
         for o in (self.prim, self.depth, self.color):

@@ -480,6 +480,12 @@ struct mirhi_image {
     bool owned;
     uint32_t levels = 1;      // mip levels stored contiguously behind level 0 (mirhi_image_generate_mips)
     uint32_t max_anisotropy = 1;   // sampler state (mirhi_image_set_max_anisotropy): 1 = trilinear
+    // Layered images (mirhi_image_create_array): `layers` tightly packed width x height levels in one allocation; is_array marks the array object itself,
+    // which is no 2-D image (attachments and MIRHI_TEXTURE_SHADOW_MAP take a layer view).  A layer view (mirhi_image_create_layer_view) is a non-owning
+    // 2-D image of one layer: ptr points into the array, `parent` is the array -- what attachment ordering resolves a view to (for_each_attachment).
+    uint32_t layers = 1; bool is_array = false;
+    mirhi_image* parent = nullptr;
+    uint32_t views = 0;            // live layer views of an array (it cannot be destroyed before them)
     // Attachment ordering across queue lanes: the reference submits everything to one queue, so a scope that LOADs (or overwrites)
     // what an earlier submission rendered is behind it by construction; here two command buffers may sit on different lanes.  The
     // stream, command buffer and submission that used this image as an attachment last: a submit on ANOTHER stream waits for it
@@ -595,6 +601,8 @@ struct mirhi_cmd {
     mirhi_buffer* ib = nullptr; uint64_t ib_offset = 0; mirhi_index_type ib_type = MIRHI_INDEX_UINT32;
     struct { mirhi_buffer* buf; uint64_t offset, range; } uniforms[MIRHI_SLOT_COUNT] = {};
     mirhi_image* textures[MIRHI_TEXTURE_COUNT] = {};
+    mirhi_image* cascades = nullptr;       // mirhi_cmd_bind_shadow_cascades: the D32 array (t10) ...
+    struct { mirhi_buffer* buf; uint64_t offset, range; } cascade_params = {};      // ... and its CSMParams (b3 of set 2)
     bool has_viewport = false, has_scissor = false;
     uint8_t push_constants[128] = {0};     // vkCmdPushConstants: kept, read by no program on this path
     mirhi_viewport viewport{};
@@ -1008,7 +1016,46 @@ extern "C" mirhi_result mirhi_image_wrap_device_memory(mirhi_device* dev, uint32
 extern "C" uint32_t mirhi_image_width(const mirhi_image* img) { return img ? img->width : 0; }
 extern "C" uint32_t mirhi_image_height(const mirhi_image* img) { return img ? img->height : 0; }
 extern "C" int32_t mirhi_image_format(const mirhi_image* img) { return img ? (int32_t)img->format : 0; }
-extern "C" uint64_t mirhi_image_size_bytes(const mirhi_image* img) { return img ? (uint64_t)img->width * img->height * format_bpp(img->format) : 0; }
+extern "C" uint64_t mirhi_image_size_bytes(const mirhi_image* img) { return img ? (uint64_t)img->width * img->height * format_bpp(img->format) * img->layers : 0; }
+extern "C" uint32_t mirhi_image_layers(const mirhi_image* img) { return img ? img->layers : 0; }
+// Texture2DArray<float> (model_pbr_ibl_csm.hlsl:115-116): one allocation, layer k at byte offset k * width * height * bpp
+extern "C" mirhi_result mirhi_image_create_array(mirhi_device* dev, uint32_t w, uint32_t h, uint32_t layers, mirhi_format f, mirhi_image** out) {
+    NULL_CHECK(dev, "device"); NULL_CHECK(out, "out");
+    *out = nullptr;
+    if (w == 0 || h == 0) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: Image dimensions must be greater than 0 (got %ux%u)", w, h);
+    if (w > 16384 || h > 16384) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: Image dimensions exceed 16384 (got %ux%u)", w, h);
+    if (layers == 0 || layers > 2048u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: array layers must be in [1, 2048] (got %u)", layers);
+    if (f != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: array images of format %d (D32_SFLOAT only)", (int)f);
+    const uint64_t bytes = (uint64_t)w * h * format_bpp(f) * layers;
+    if (bytes > (1ull << 32)) return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: %ux%u x %u layers exceeds 4 GiB", w, h, layers);   // (texel offsets stay 32-bit in the kernels)
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, (size_t)bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: hipMalloc for %ux%u x %u image array: %s", w, h, layers, hipGetErrorString(e)); }
+    mirhi_image* img = new (std::nothrow) mirhi_image{dev, w, h, f, (uint8_t*)p, true};
+    if (!img) { (void)hipFree(p); return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: host allocation failed"); }
+    img->layers = layers; img->is_array = true;
+    { std::lock_guard<std::mutex> lock(dev->mu); dev->images.push_back(img); }
+    dev->children++;
+    *out = img;
+    return MIRHI_OK;
+}
+// VkImageView with baseArrayLayer = layer, layerCount = 1 (what DepthAttachment takes, rendering.rs:319-370)
+extern "C" mirhi_result mirhi_image_create_layer_view(mirhi_image* array, uint32_t layer, mirhi_image** out) {
+    NULL_CHECK(array, "image"); NULL_CHECK(out, "out");
+    *out = nullptr;
+    if (!array->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: layer views are made of array images (mirhi_image_create_array)");
+    if (layer >= array->layers) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: layer %u out of range (the array has %u layers)", layer, array->layers);
+    mirhi_device* dev = array->dev;
+    uint8_t* p = array->ptr + (size_t)layer * array->width * array->height * format_bpp(array->format);
+    mirhi_image* img = new (std::nothrow) mirhi_image{dev, array->width, array->height, array->format, p, false};
+    if (!img) return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: host allocation failed");
+    img->parent = array;
+    { std::lock_guard<std::mutex> lock(dev->mu); dev->images.push_back(img); array->views++; }
+    dev->children++;
+    *out = img;
+    return MIRHI_OK;
+}
 extern "C" void* mirhi_image_device_ptr(const mirhi_image* img) { return img ? img->ptr : nullptr; }
 extern "C" mirhi_result mirhi_image_upload(mirhi_image* img, const void* src, uint64_t len) {
     NULL_CHECK(img, "image"); NULL_CHECK(src, "src");
@@ -1087,9 +1134,11 @@ extern "C" mirhi_result mirhi_image_set_max_anisotropy(mirhi_image* img, uint32_
 }
 extern "C" mirhi_result mirhi_image_destroy(mirhi_image* img) {
     NULL_CHECK(img, "image");
+    if (img->views != 0) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: image array still has %u live layer views", img->views);
     (void)hipSetDevice(img->dev->ordinal);
     if (img->owned) { (void)sync_all_lanes(img->dev); (void)hipFree(img->ptr); }
-    { std::lock_guard<std::mutex> lock(img->dev->mu); auto& v = img->dev->images; v.erase(std::remove(v.begin(), v.end(), img), v.end()); }
+    { std::lock_guard<std::mutex> lock(img->dev->mu); auto& v = img->dev->images; v.erase(std::remove(v.begin(), v.end(), img), v.end());
+      if (img->parent) img->parent->views--; }      // (a view frees nothing)
     img->dev->children--;
     delete img;
     return MIRHI_OK;
@@ -1293,6 +1342,7 @@ static void reset_recording(mirhi_cmd* c) {
     c->pipeline = nullptr; c->vb = nullptr; c->ib = nullptr;
     for (auto& u : c->uniforms) u = {nullptr, 0, 0};
     for (auto& tx : c->textures) tx = nullptr;
+    c->cascades = nullptr; c->cascade_params = {nullptr, 0, 0};
     c->has_viewport = c->has_scissor = false;
 }
 static mirhi_result begin_common(mirhi_cmd* cmd, bool one_time) {
@@ -1326,6 +1376,7 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
         // depth-only scope (MIRHI_PROGRAM_SHADOW): the depth image's extent is the render area; only SHADOW draws are recorded here
         const mirhi_image* di = info->depth_image;
         if (di->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: depth attachment is not D32_SFLOAT");
+        if (di->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array is not an attachment: use a layer view (mirhi_image_create_layer_view)");
         if (info->prim_id_image) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: prim_id_image in a depth-only rendering scope");
         if (info->depth_store_op != MIRHI_STORE_OP_STORE)
             return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a depth-only rendering scope must store its depth (STORE)");
@@ -1344,6 +1395,8 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
     }
     NULL_CHECK(info->color_image, "color_image");
     const mirhi_image* ci = info->color_image;
+    if (ci->is_array || (info->depth_image && info->depth_image->is_array))
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array is not an attachment: use a layer view (mirhi_image_create_layer_view)");
     if (ci->format != MIRHI_FORMAT_B8G8R8A8_SRGB && ci->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: color attachment has non-colour format %d", (int)ci->format);
     if (info->depth_image) {
@@ -1412,12 +1465,32 @@ extern "C" mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slo
     if ((int)slot < 0 || (int)slot >= MIRHI_TEXTURE_COUNT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unknown texture slot %d", (int)slot);
     if (slot == MIRHI_TEXTURE_SHADOW_MAP) {       // t7 / s5 (model_pbr.hlsl:103-108): a depth image, sampled with the comparison sampler
         if (image && image->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow map must be D32_SFLOAT");
+        if (image && image->is_array)
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow map must be a 2-D image: bind a layer view, or the array with mirhi_cmd_bind_shadow_cascades");
         cmd->textures[slot] = image;
         return MIRHI_OK;
     }
     if (image && image->format != MIRHI_FORMAT_R8G8B8A8_UNORM && image->format != MIRHI_FORMAT_R8G8B8A8_SRGB)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: sampled images must be R8G8B8A8_UNORM or R8G8B8A8_SRGB");
     cmd->textures[slot] = image;
+    return MIRHI_OK;
+}
+// set 2, bindings 3 and 4 of pixel/model_pbr_ibl_csm.hlsl:115-127: Texture2DArray<float> shadowMap (t10 / s8) and cbuffer ShadowData { CSMParams } (b3)
+extern "C" mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range) {
+    REQUIRE_RECORDING(cmd);
+    if (!array) { cmd->cascades = nullptr; cmd->cascade_params = {nullptr, 0, 0}; return MIRHI_OK; }
+    if (array->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array, not a layer view");
+    if (!array->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array (mirhi_image_create_array)");
+    if (array->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow cascades must be D32_SFLOAT");
+    if (array->layers != 4u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow cascades must have CASCADE_COUNT = 4 layers (got %u)", array->layers);
+    NULL_CHECK(params, "buffer");
+    if (params->usage != MIRHI_BUFFER_UNIFORM) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: CSMParams must be in a uniform buffer (usage %d)", (int)params->usage);
+    if (range == 0 || range == UINT64_MAX) range = params->size > offset ? params->size - offset : 0;   // VK_WHOLE_SIZE
+    if (offset + range > params->size || range == 0 || (offset & 15))
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: uniform range offset %llu + range %llu exceeds buffer %llu or offset not 16-byte aligned",
+                    (unsigned long long)offset, (unsigned long long)range, (unsigned long long)params->size);
+    if (range < 336) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: CSMParams range %llu smaller than 336 bytes", (unsigned long long)range);
+    cmd->cascades = array; cmd->cascade_params = {params, offset, range};
     return MIRHI_OK;
 }
 extern "C" mirhi_result mirhi_cmd_set_viewport(mirhi_cmd* cmd, const mirhi_viewport* vp) {
@@ -1571,7 +1644,20 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                                                                                        op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL));
                 if (pd.blend_enable || pd.fragment_discard_enable || !keyed)
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a shadow map with blending, fragment discard or a predicate depth state");
+                if (cmd->cascades)
+                    return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: both a shadow map (MIRHI_TEXTURE_SHADOW_MAP) and shadow cascades (mirhi_cmd_bind_shadow_cascades) are bound");
                 d.shadow_map = (const float*)sm->ptr; d.shadow_w = sm->width; d.shadow_h = sm->height;
+            } else if (d.program == MIRHI_PROGRAM_MODEL_PBR && cmd->cascades) {
+                // CalculateShadowCSM (model_pbr_ibl_csm.hlsl:280-298): the array and its CSMParams.  SV_Position.z is the depth the key holds, so the
+                // draw needs an ordered depth key (depth test and write with an ordering compare op)
+                const mirhi_image* ca = cmd->cascades;
+                const uint32_t op = pd.depth_compare_op;
+                const bool keyed = pd.depth_test_enable && pd.depth_write_enable && (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL ||
+                                                                                     op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL);
+                if (pd.blend_enable || pd.fragment_discard_enable || !keyed)
+                    return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: shadow cascades with blending, fragment discard, a predicate depth state or no depth test");
+                d.shadow_map = (const float*)ca->ptr; d.shadow_w = ca->width; d.shadow_h = ca->height; d.shadow_layers = ca->layers;
+                d.shadow_data = cmd->cascade_params.buf->ptr + cmd->cascade_params.offset;
             }
         }
     }
@@ -1590,7 +1676,11 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     d.scissor_partial = (sx0 > 0 || sy0 > 0 || sx1 < (int64_t)ci.width - 1 || sy1 < (int64_t)ci.height - 1) ? 1u : 0u;
     if (sx0 > sx1 || sy0 > sy1) return MIRHI_OK;    // empty scissor: nothing can be covered
     if (d.shadow_map) {
-        mirhi_image* sm = cmd->textures[MIRHI_TEXTURE_SHADOW_MAP];
+        // one raster variant per scope: CalculateShadow (raster_kernel_shadow) or CalculateShadowCSM (raster_kernel_csm)
+        for (const DrawDesc& o : pass.draws)
+            if (o.shadow_map && (o.shadow_layers != 0u) != (d.shadow_layers != 0u))
+                return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: draws with a single shadow map and draws with shadow cascades in one rendering scope");
+        mirhi_image* sm = d.shadow_layers ? cmd->cascades : cmd->textures[MIRHI_TEXTURE_SHADOW_MAP];
         if (std::find(pass.sampled.begin(), pass.sampled.end(), sm) == pass.sampled.end()) pass.sampled.push_back(sm);
     }
     pass.draws.push_back(d);
@@ -2217,7 +2307,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         }
         P.xcd_swizzle = getenv("MIRHI_XCD_RUN") ? (uint32_t)atoi(getenv("MIRHI_XCD_RUN")) : 1u;
         P.depth_only = pass.depth_only ? 1u : 0u;
-        for (const DrawDesc& dd : draws) P.shadowed |= dd.shadow_map ? 1u : 0u;
+        for (const DrawDesc& dd : draws) P.shadowed |= dd.shadow_map ? (dd.shadow_layers ? 2u : 1u) : 0u;      // (never both in one scope: record_draw)
         if (P.depth_only || P.shadowed) { P.xcd_swizzle = 1u; P.raster_wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
         P.vs_jobs = dev_jobs + jobs_done;
         P.num_vs_jobs = (uint32_t)pass_jobs[pi].size();
@@ -2241,7 +2331,8 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         uint32_t progs = 0;
         for (const DrawDesc& dd : draws) progs |= dd.program == 0 ? 1u : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.tex_any_mips || dd.tex_srgb) ? 4u : 2u);
         // 8: a shadowed MODEL_PBR draw (raster_kernel_shadow, with the Cook-Torrance variant's programs); 0: a depth-only scope (raster_kernel_depth)
-        if (P.shadowed) progs = 4u | 8u;
+        // 16: ... whose shadow term is CalculateShadowCSM (raster_kernel_csm)
+        if (P.shadowed) progs = 4u | 8u | (P.shadowed == 2u ? 16u : 0u);
         cmd->plan_programs.push_back(P.depth_only ? 0u : (progs ? progs : 1u));
         cmd->plan_tris += pass.total_tris - pass.first_tri;
         // the kernels read their parameters from the block: copy 2*pi + parity of scope pi appends large triangles to counter
@@ -2314,12 +2405,13 @@ static mirhi_result timing_begin(mirhi_device* dev, uint32_t kernel, uint32_t la
 template <typename F>
 static void for_each_attachment(mirhi_device* dev, const mirhi_cmd* c, F&& f) {
     for (const RecordedPass& pass : c->planned) {
+        // a layer view stands for its array: scopes that write layers and scopes that sample the array meet on one object (a live view's array is alive)
         for (mirhi_image* img : {pass.info.color_image, pass.info.depth_image, pass.info.prim_id_image})
-            if (img && std::find(dev->images.begin(), dev->images.end(), img) != dev->images.end()) f(img);
+            if (img && std::find(dev->images.begin(), dev->images.end(), img) != dev->images.end()) f(img->parent ? img->parent : img);
         // the shadow maps the scope samples count as attachments: a read after another lane's write (the shadow scope) and a write after another lane's
         // read (the next frame's shadow scope behind this frame's lit one) are both ordered
         for (mirhi_image* img : pass.sampled)
-            if (img && std::find(dev->images.begin(), dev->images.end(), img) != dev->images.end()) f(img);
+            if (img && std::find(dev->images.begin(), dev->images.end(), img) != dev->images.end()) f(img->parent ? img->parent : img);
     }
 }
 // `c` is about to run on `stream` (or, natively, on `nq`): anything that used one of its attachments last somewhere else, and is not known

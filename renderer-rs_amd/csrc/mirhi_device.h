@@ -77,8 +77,10 @@ struct DrawDesc {
     const void* vs_out;           // shaded vertices, clip positions (16 B per vertex), indexed like the vertex buffer: see VsJob
     const float*   shadow_map;    // MODEL_PBR with MIRHI_TEXTURE_SHADOW_MAP bound: the D32 map (t7), else nullptr (shadow = 1)
     const uint8_t* shadow_data;   // ShadowParams (96 B, shadow.hlsli:20-30) when shadow_map is set
-    uint32_t shadow_w, shadow_h;  // the map's extent
-    uint32_t shadow_pad[2];
+    uint32_t shadow_w, shadow_h;  // the map's extent (with cascades: one layer's)
+    uint32_t shadow_layers;       // 0: a single map (CalculateShadow); 4: mirhi_cmd_bind_shadow_cascades -- shadow_map is the base of a D32 array of
+                                  // that many tightly packed layers, shadow_data its CSMParams (336 B, shadow_csm.hlsli:23-39): CalculateShadowCSM
+    uint32_t shadow_pad;
 };
 static_assert(sizeof(DrawDesc) % 16 == 0, "DrawDesc must stay 16-byte sized");
 
@@ -196,7 +198,7 @@ struct PassParams {
     unsigned long long* frag_stats;   // device counters of the statistics pass (never touched by geometry / raster kernels): [0] pixels that
                                       // ran a fragment program (winners of the depth resolve), [1] fragments covered before the depth test
     uint32_t depth_only;              // 1: a depth-only scope (SHADOW draws; color == nullptr): raster_kernel_depth stores the depth image and nothing else
-    uint32_t shadowed;                // 1: some MODEL_PBR draw of the scope samples a shadow map (raster_kernel_shadow)
+    uint32_t shadowed;                // 1: some MODEL_PBR draw of the scope samples a shadow map (raster_kernel_shadow); 2: a cascade array (raster_kernel_csm)
 };
 
 // Kernel arguments passed by value next to the PassParams pointer: what a wave needs before anything else, so that its

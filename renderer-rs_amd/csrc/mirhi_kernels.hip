@@ -140,6 +140,9 @@ hipError_t launch_raster(const PassParams& P, const PassParams* dev_params, uint
         if (programs == 0u) {
             if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_depth<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_depth<1, 1>), grid, block, stream, t, dev_params, H); }
             else { if (plain) MIRHI_LAUNCH((raster_kernel_depth<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_depth<1, 0>), grid, block, stream, t, dev_params, H); }
+        } else if (programs & 16u) {        // a cascaded draw (PassParams::shadowed = 2)
+            if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_csm<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_csm<1, 1>), grid, block, stream, t, dev_params, H); }
+            else { if (plain) MIRHI_LAUNCH((raster_kernel_csm<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_csm<1, 0>), grid, block, stream, t, dev_params, H); }
         } else {
             if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_shadow<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_shadow<1, 1>), grid, block, stream, t, dev_params, H); }
             else { if (plain) MIRHI_LAUNCH((raster_kernel_shadow<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_shadow<1, 0>), grid, block, stream, t, dev_params, H); }

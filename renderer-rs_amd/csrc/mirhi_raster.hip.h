@@ -625,7 +625,9 @@ __device__ __forceinline__ void raster_list(const uint4* __restrict__ list, uint
 // and nothing else -- no colour, no shading, no primitive id (raster_kernel_depth).
 // SHADOWV (PROGS = 4, one team, four waves): the Cook-Torrance program with the directional light's shadow term for scopes with a shadowed
 // draw (PassParams::shadowed, raster_kernel_shadow) -- its own variant, so that the shadow map costs the other PROGS = 4 kernels nothing.
-template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4, bool SHADOWV = false>
+// SHADOWV = 2: the same with CalculateShadowCSM for scopes with a cascaded draw (PassParams::shadowed = 2, raster_kernel_csm): the resolve hands
+// the winner's depth (SV_Position.z) to the fragment program; again a variant of its own, raster_kernel_shadow keeps its registers.
+template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4, int SHADOWV = 0>
 #ifndef MIRHI_PROGS2_WAVES
 #define MIRHI_PROGS2_WAVES 5
 #endif
@@ -954,6 +956,8 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
                 const float pxc = (float)px + 0.5f, pyc = (float)py + 0.5f;
                 if (PROGS == 1) col = shade_triangle_program(D, tri, pxc, pyc);
                 else if (PROGS == 2) col = shade_model_program<false>(D, tri, pxc, pyc);
+                else if (SHADOWV == 2) col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc)      // (a cascaded draw has a depth key: zmask != 0)
+                                                              : shade_model_program<PROGS == 4, SHADOWV>(D, tri, pxc, pyc, __uint_as_float(zkb ^ P.zflip));
                 else col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc) : shade_model_program<PROGS == 4, SHADOWV>(D, tri, pxc, pyc);
             }
             todo &= ~__ballot(mine);
@@ -1004,7 +1008,12 @@ __global__ __launch_bounds__(RASTER_THREADS, (TP ? 7 : 8)) void raster_kernel_de
 // a scope with a shadowed MODEL_PBR draw (one team, four waves per tile; no predicate, ordered or alpha-masked segment carries one)
 template <int KEYED, int TP>
 __global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_shadow(const PassParams* __restrict__ params, const RasterHead H) {
-    raster_body<4, KEYED, TP, 1, false, 4, true>(params, H);
+    raster_body<4, KEYED, TP, 1, false, 4, 1>(params, H);
+}
+// a scope with a cascaded MODEL_PBR draw (mirhi_cmd_bind_shadow_cascades): the same shape of kernel with CalculateShadowCSM
+template <int KEYED, int TP>
+__global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_csm(const PassParams* __restrict__ params, const RasterHead H) {
+    raster_body<4, KEYED, TP, 1, false, 4, 2>(params, H);
 }
 // up to MAX_BATCH independent rendering scopes of equal shape (the frames of one mirhi_queue_submit): grid (tiles_x, tile rows, scopes).
 // One launch instead of one per frame: the ramp-up and drain of a kernel (5 us of the 11 us an isolated 10k-triangle raster kernel

@@ -323,10 +323,57 @@ __device__ __forceinline__ float calculate_shadow(DrawRef D, f3 worldPos, f3 nor
     return 1.0f + (shadow - 1.0f) * ldcf(S, 80);                                                // :120 lerp(1, shadow, ShadowStrength)
 }
 
+// CalculateShadowCSM (shaders/hlsl/shadow_csm.hlsli:163-194) with SelectCascade (:55-71) and SampleCascadePCF (:90-146), line for line.  CSMParams
+// (:23-39, 336 B) at D.shadow_data: Cascades[k].ViewProjection @80k, Cascades[k].SplitDepth @80k + 64, ShadowBias @320, NormalBias @324,
+// ShadowMapSize @328.  D.shadow_map is the base of the four tightly packed layers of D.shadow_w x D.shadow_h texels; the sampler is the one of
+// MIRHI_TEXTURE_SHADOW_MAP, within the selected layer (clamp-to-edge never leaves it: the texel index is clamped before the layer offset is added).
+// clipSpaceDepth = SV_Position.z: the depth the raster kernel resolved for the pixel (the bits a D32 attachment stores).
+// The cascade index differs from lane to lane, so the selected matrix is fetched with per-lane vector loads (four 16-byte loads from a block
+// every wave of the scope keeps in cache); splits, biases and the map size stay wave-uniform scalar loads.
+__device__ __forceinline__ float calculate_shadow_csm(DrawRef D, f3 worldPos, f3 normal, f3 lightDir, float clipSpaceDepth) {
+    const CBytePtr S = cb(D.shadow_data);
+    uint32_t cascadeIndex = 0;                                                                  // :57
+#pragma unroll
+    for (uint32_t i = 0; i < 3u; ++i)                                                           // :62-68 (the last split passed, not the first)
+        if (clipSpaceDepth > ldcf(S, 80u * i + 64u)) cascadeIndex = i + 1u;
+    const float4* const mp = reinterpret_cast<const float4*>(D.shadow_data + 80u * cascadeIndex);   // :176 Cascades[cascadeIndex].ViewProjection
+    const float4 c0 = mp[0], c1 = mp[1], c2 = mp[2], c3 = mp[3];                                // (columns: the matrix convention of mat4_mul)
+    const float texelSize = rcp_rn_nb(ldcf(S, 328));                                            // :179
+    const f3 offsetPos = add3(worldPos, scale3(normal, ldcf(S, 324)));                          // :103
+    const float lx = ((c0.x * offsetPos.x + c1.x * offsetPos.y) + c2.x * offsetPos.z) + c3.x * 1.0f;   // :106 (mat4_mul's operation order)
+    const float ly = ((c0.y * offsetPos.x + c1.y * offsetPos.y) + c2.y * offsetPos.z) + c3.y * 1.0f;
+    const float lz = ((c0.z * offsetPos.x + c1.z * offsetPos.y) + c2.z * offsetPos.z) + c3.z * 1.0f;
+    const float lw = ((c0.w * offsetPos.x + c1.w * offsetPos.y) + c2.w * offsetPos.z) + c3.w * 1.0f;
+    float px = div_rn_nb(lx, lw), py = div_rn_nb(ly, lw);                                       // :107
+    const float pz = div_rn_nb(lz, lw);
+    px = px * 0.5f + 0.5f; py = py * 0.5f + 0.5f;                                               // :110
+    py = 1.0f - py;                                                                             // :111
+    if (px < 0.0f || px > 1.0f || py < 0.0f || py > 1.0f || pz < 0.0f || pz > 1.0f) return 1.0f;   // :114-119
+    const float NdotL = dot3(normal, lightDir);                                                 // :122
+    const float b0 = ldcf(S, 320) * (1.0f - NdotL);                                             // :123
+    const float adaptiveBias = b0 > 0.0005f ? b0 : 0.0005f;
+    const float currentDepth = pz - adaptiveBias;                                               // :124
+    const float dref = fminf(fmaxf(currentDepth, 0.0f), 1.0f);                                  // (the sampler clamps D_ref)
+    const float fw = (float)D.shadow_w, fh = (float)D.shadow_h;
+    const float* const layer = D.shadow_map + (size_t)cascadeIndex * D.shadow_w * D.shadow_h;   // :136 sampleUVW.z
+    float shadow = 0.0f;
+#pragma unroll
+    for (int x = -1; x <= 1; ++x)
+#pragma unroll
+        for (int y = -1; y <= 1; ++y) {                                                         // :130-143
+            const float u = px + (float)x * texelSize, v = py + (float)y * texelSize;
+            const float fi = fminf(fmaxf(floorf(u * fw), 0.0f), fw - 1.0f);                     // (shadow_tap's addressing, within the layer)
+            const float fj = fminf(fmaxf(floorf(v * fh), 0.0f), fh - 1.0f);
+            shadow += dref <= layer[(uint32_t)fj * D.shadow_w + (uint32_t)fi] ? 1.0f : 0.0f;
+        }
+    return div_rn_nb(shadow, 9.0f);                                                             // :145
+}
+
 // pixel/model_pbr.hlsl:159-320 after the shared varying interpolation
-// SHADOW: the variant with the directional light's shadow term (model_pbr.hlsl:238-251) for draws with a shadow map bound
-template <bool SHADOW = false>
-__device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint32_t vi[3], float u, float v, f3 worldPos, f3 V, f3 N, const UvGrad& grad) {
+// SHADOW 1: the variant with the directional light's shadow term (model_pbr.hlsl:238-251) for draws with a shadow map bound; 2: the variant with
+// CalculateShadowCSM instead (pixel/model_pbr_ibl_csm.hlsl:280-298) for draws with cascades bound, clipz = SV_Position.z
+template <int SHADOW = 0>
+__device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint32_t vi[3], float u, float v, f3 worldPos, f3 V, f3 N, const UvGrad& grad, float clipz = 0.0f) {
     const CBytePtr M = cb(D.material);                                                  // MaterialData :36-59 (80 B)
     f4 baseColor = {ldcf(M, 0), ldcf(M, 4), ldcf(M, 8), ldcf(M, 12)};
     float metallic = ldcf(M, 16), roughness = ldcf(M, 20), ao = ldcf(M, 24);
@@ -369,7 +416,8 @@ __device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint3
             if (intensity != 0.0f) lighting = add3(lighting, pbr_direct(N, V, normalize3({-dir.x, -dir.y, -dir.z}), scale3(color, intensity), m));
         } else if (intensity != 0.0f) {                                                  // (intensity 0: exact zeros, shadow or not)
             const f3 L = normalize3({-dir.x, -dir.y, -dir.z});
-            const float shadow = calculate_shadow(D, worldPos, N, L);                   // model_pbr.hlsl:238-245
+            const float shadow = SHADOW == 2 ? calculate_shadow_csm(D, worldPos, N, L, clipz)      // model_pbr_ibl_csm.hlsl:285-293
+                                             : calculate_shadow(D, worldPos, N, L);                // model_pbr.hlsl:238-245
             lighting = add3(lighting, scale3(pbr_direct(N, V, L, scale3(color, intensity), m), shadow));   // :251
         }
     }
@@ -415,9 +463,9 @@ __device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint3
     return {col.x, col.y, col.z, baseColor.w};
 }
 
-// FULL: the variant that also carries the Cook-Torrance program and mip-mapped (trilinear) sampling; SHADOW: and the shadow term
-template <bool FULL, bool SHADOW = false>
-__device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3], float pxc, float pyc) {
+// FULL: the variant that also carries the Cook-Torrance program and mip-mapped (trilinear) sampling; SHADOW: and the shadow term (shade_pbr)
+template <bool FULL, int SHADOW = 0>
+__device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3], float pxc, float pyc, float clipz = 0.0f) {
     f4 c[3];
     const bool full = D.program >= 2;
 #pragma unroll
@@ -469,7 +517,7 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
         grad.dudy = ((by[0] * uvk[0][0] + by[1] * uvk[1][0]) + by[2] * uvk[2][0]) - u;
         grad.dvdy = ((by[0] * uvk[0][1] + by[1] * uvk[1][1]) + by[2] * uvk[2][1]) - v;
     }
-    if (FULL && D.program == 3) return shade_pbr<SHADOW>(D, b, vi, u, v, worldPos, V, N, grad);
+    if (FULL && D.program == 3) return shade_pbr<SHADOW>(D, b, vi, u, v, worldPos, V, N, grad, clipz);
     // pixel/model_full.hlsl:85-150
     const f4 baseColor = {ldcf(cb(D.material), 0), ldcf(cb(D.material), 4), ldcf(cb(D.material), 8), ldcf(cb(D.material), 12)};
     const float roughness = ldcf(cb(D.material), 20), ao = ldcf(cb(D.material), 24);
@@ -540,11 +588,11 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
     return {col.x, col.y, col.z, albedoSample.w * baseColor.w};
 }
 
-template <bool FULL, bool SHADOW = false>
-__device__ __forceinline__ f4 shade_model_program(DrawRef D, uint32_t tri, float pxc, float pyc) {
+template <bool FULL, int SHADOW = 0>
+__device__ __forceinline__ f4 shade_model_program(DrawRef D, uint32_t tri, float pxc, float pyc, float clipz = 0.0f) {
     uint32_t vin[3];
     fetch_triangle_indices(D, tri, vin);
-    return shade_model_program<FULL, SHADOW>(D, vin, pxc, pyc);
+    return shade_model_program<FULL, SHADOW>(D, vin, pxc, pyc, clipz);
 }
 
 #pragma clang fp contract(fast)

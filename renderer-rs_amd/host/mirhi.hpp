@@ -251,6 +251,19 @@ public:
     Image(std::shared_ptr<Device> device, uint32_t w, uint32_t h, Format f) : device_(std::move(device)), w_(w), h_px_(h), f_(f) {
         check(mirhi_image_create(device_->handle(), w, h, (mirhi_format)f, &h_));
     }
+    // mirhi_image_create_array: `layers` tightly packed w x h levels in one allocation (D32_SFLOAT; the Texture2DArray of shadow_csm.hlsli)
+    static Image array(std::shared_ptr<Device> device, uint32_t w, uint32_t h, uint32_t layers, Format f) {
+        mirhi_image* raw = nullptr;
+        check(mirhi_image_create_array(device->handle(), w, h, layers, (mirhi_format)f, &raw));
+        return Image(std::move(device), raw, w, h, f);
+    }
+    // mirhi_image_create_layer_view: a non-owning 2-D image of one layer (rendering.rs:319-370 takes a view); destroy it before the array
+    Image layer_view(uint32_t layer) const {
+        mirhi_image* raw = nullptr;
+        check(mirhi_image_create_layer_view(h_, layer, &raw));
+        return Image(device_, raw, w_, h_px_, f_);
+    }
+    uint32_t layers() const { return mirhi_image_layers(h_); }
     Image(Image&& o) noexcept : device_(std::move(o.device_)), h_(o.h_), w_(o.w_), h_px_(o.h_px_), f_(o.f_) { o.h_ = nullptr; }
     Image(const Image&) = delete;
     ~Image() { if (h_) mirhi_image_destroy(h_); }
@@ -265,6 +278,7 @@ public:
     void set_max_anisotropy(uint32_t n) { check(mirhi_image_set_max_anisotropy(h_, n)); }          // sampler state (device.rs:161-165)
     uint32_t max_anisotropy() const { return mirhi_image_max_anisotropy(h_); }
 private:
+    Image(std::shared_ptr<Device> device, mirhi_image* raw, uint32_t w, uint32_t h, Format f) : device_(std::move(device)), h_(raw), w_(w), h_px_(h), f_(f) {}
     std::shared_ptr<Device> device_;
     mirhi_image* h_ = nullptr;
     uint32_t w_, h_px_;
@@ -442,6 +456,10 @@ public:
     void bind_index_buffer(const Buffer& b, uint64_t offset, IndexType t) const { check(mirhi_cmd_bind_index_buffer(h_, b.handle(), offset, (mirhi_index_type)t)); }
     void bind_uniform(mirhi_uniform_slot slot, const Buffer& b, uint64_t offset = 0, uint64_t range = 0) const { check(mirhi_cmd_bind_uniform(h_, slot, b.handle(), offset, range)); }
     void bind_texture(mirhi_texture_slot slot, const Image* img) const { check(mirhi_cmd_bind_texture(h_, slot, img ? img->handle() : nullptr)); }
+    // set 2, bindings 3 / 4 of pixel/model_pbr_ibl_csm.hlsl:115-127: the four-layer D32 array and its CSMParams (336 B); array nullptr unbinds
+    void bind_shadow_cascades(const Image* array, const Buffer* params, uint64_t offset = 0, uint64_t range = 0) const {
+        check(mirhi_cmd_bind_shadow_cascades(h_, array ? array->handle() : nullptr, params ? params->handle() : nullptr, offset, range));
+    }
     void set_viewport(const Viewport& v) const { mirhi_viewport vp{v.x, v.y, v.width, v.height, v.min_depth, v.max_depth}; check(mirhi_cmd_set_viewport(h_, &vp)); }
     void set_scissor(const Rect2D& r) const { mirhi_rect2d sc{r.x, r.y, r.width, r.height}; check(mirhi_cmd_set_scissor(h_, &sc)); }
     void draw(uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex, uint32_t first_instance) const { check(mirhi_cmd_draw(h_, vertex_count, instance_count, first_vertex, first_instance)); }

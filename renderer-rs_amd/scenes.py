@@ -325,6 +325,18 @@ class ShadowSpec:
 
 
 @dataclass
+class CascadeSpec:
+    """Four depth-only shadow scopes ahead of a scene's main scope, one per layer of a D32 array (shadow_csm.hlsli:19 CASCADE_COUNT):
+    casters[k] are the PROGRAM_SHADOW draws of layer k (camera = shadow_constants_ubo(flip_clip_y(M_k), model)), `params` the CSMParams
+    (csm_ubo) every MODEL_PBR draw of the scene samples the array with."""
+    casters: List[List[DrawSpec]]
+    size: tuple = (1024, 1024)            # one layer's extent
+    params: bytes = b""
+    clear_depth: float = 1.0
+    load_op: int = LOAD_OP_CLEAR
+
+
+@dataclass
 class Scene:
     name: str
     width: int
@@ -333,6 +345,7 @@ class Scene:
     clear_color: tuple = (0.0, 0.0, 0.0, 1.0)  # rendering.rs:102-115 default
     clear_depth: float = 1.0                   # rendering.rs:356-370 default
     shadow: Optional[ShadowSpec] = None        # None: no shadow scope (the oracle's PBR frame: shadow = 1)
+    cascades: Optional["CascadeSpec"] = None   # shadow cascades (shadow_csm.hlsli): four depth-only scopes ahead of the main scope; not with `shadow`
 
     @property
     def num_triangles(self) -> int:
@@ -962,3 +975,165 @@ def pcf_factor(depth_map: np.ndarray, u: np.ndarray, v: np.ndarray, dref: np.nda
             lit += (d <= depth_map[j, i]).astype(np.float64)
     s = lit / 9.0
     return 1.0 + (s - 1.0) * strength
+
+
+# ------------------------------------------------------------------------------------------------
+# cascaded shadow maps (shadow_csm.hlsli CalculateShadowCSM in pixel/model_pbr_ibl_csm.hlsl:280-298)
+# ------------------------------------------------------------------------------------------------
+CASCADE_COUNT = 4                                                   # shadow_csm.hlsli:19
+
+
+def csm_ubo(matrices, split_depths, bias: float = 0.005, normal_bias: float = 0.02, map_size: float = 2048.0) -> bytes:
+    """CSMParams 336 B (shaders/hlsl/shadow_csm.hlsli:23-39): Cascades[k].ViewProjection @80k, Cascades[k].SplitDepth @80k + 64 (padded to
+    80), ShadowBias @320, NormalBias @324, ShadowMapSize @328, padding @332.  split_depths: three (the shader reads no more) or four."""
+    assert len(matrices) == CASCADE_COUNT and len(split_depths) in (CASCADE_COUNT - 1, CASCADE_COUNT)
+    splits = list(split_depths) + [1.0] * (CASCADE_COUNT - len(split_depths))
+    out = b""
+    for m, sd in zip(matrices, splits):
+        out += np.asarray(m, dtype=f32).tobytes() + np.array([sd, 0, 0, 0], dtype=f32).tobytes()
+    out += np.array([bias, normal_bias, map_size, 0], dtype=f32).tobytes()
+    assert len(out) == 336
+    return out
+
+
+def csm_split_distances(near: float, far: float, count: int = CASCADE_COUNT, lam: float = 0.5) -> np.ndarray:
+    """The practical split scheme of "Parallel-Split Shadow Maps on Programmable GPUs" (Zhang et al., the paper shadow_csm.hlsli:12 cites):
+    far distance of slice i = lam * near * (far / near)^(i / count) + (1 - lam) * (near + (far - near) * i / count), i = 1 .. count
+    (lam = 1 logarithmic, lam = 0 uniform)."""
+    i = np.arange(1, count + 1, dtype=np.float64) / count
+    return lam * near * (far / near) ** i + (1.0 - lam) * (near + (far - near) * i)
+
+
+@dataclass
+class Cascades:
+    matrices: List[np.ndarray]            # per cascade: orthographic light matrix (projection * view), [col,row] float32
+    split_depths: np.ndarray              # per cascade: the camera's clip-space depth of the slice's far distance (float32)
+    distances: np.ndarray                 # count + 1 view distances: slice k is [distances[k], distances[k + 1]]
+    corners: List[np.ndarray]             # per cascade: the eight world-space corners of its slice of the camera frustum (float64)
+    half_extents: List[float]             # per cascade: half the side of its square light frustum (world units)
+
+
+def csm_cascades(view: np.ndarray, proj: np.ndarray, light_dir, near: float, far: float, count: int = CASCADE_COUNT, lam: float = 0.5,
+                 caster_margin: float = 8.0) -> Cascades:
+    """Splits the camera frustum between the view distances near and far into `count` slices (csm_split_distances) and gives each an
+    orthographic light matrix that encloses it: the light looks along light_dir at the slice's centre, its square frustum is the slice's
+    bounding box in light space (padded by 0.1 %), pulled back towards the light by caster_margin so that casters between the light and
+    the slice are kept.  The split depth is what the camera's projection gives the split distance, i.e. SV_Position.z of a fragment there
+    (viewport depth range 0..1).  The reference has no host code for cascades (no file under crates/ mentions one): this is this build's
+    own, as small as the containment test needs -- no texel snapping, no stabilisation."""
+    dist = np.concatenate([[float(near)], csm_split_distances(near, far, count, lam)])
+    p64, inv_view = proj.astype(np.float64), np.linalg.inv(view.astype(np.float64).T)      # maths (row-major) inverse view
+    tx, ty = 1.0 / abs(p64[0, 0]), 1.0 / abs(p64[1, 1])                                  # tan of the half angles
+    d = _normalize(light_dir).astype(np.float64)
+    up = np.array((0.0, 1.0, 0.0) if abs(d[1]) < 0.99 else (0.0, 0.0, -1.0))
+    mats, corners_all, halves = [], [], []
+    for k in range(count):
+        cs = []
+        for dd in (dist[k], dist[k + 1]):
+            for sx in (-1.0, 1.0):
+                for sy in (-1.0, 1.0):
+                    cs.append((inv_view @ np.array([sx * dd * tx, sy * dd * ty, -dd, 1.0]))[:3])
+        cs = np.array(cs)
+        centre = cs.mean(axis=0)
+        radius = float(np.linalg.norm(cs - centre, axis=1).max())
+        eye = centre - d * (radius + caster_margin)
+        lview = look_at_rh(eye, centre, up)
+        lc = np.concatenate([cs, np.ones((8, 1))], axis=1) @ lview.astype(np.float64)         # light-view space (p @ m for [col,row])
+        cx, cy = 0.5 * (lc[:, 0].min() + lc[:, 0].max()), 0.5 * (lc[:, 1].min() + lc[:, 1].max())
+        half = 1.001 * 0.5 * max(lc[:, 0].max() - lc[:, 0].min(), lc[:, 1].max() - lc[:, 1].min())
+        zn, zf = 0.1, float(-lc[:, 2].min()) * 1.001 + 0.01
+        mats.append(mat_mul(orthographic_rh(cx - half, cx + half, cy - half, cy + half, zn, zf), lview))
+        corners_all.append(cs)
+        halves.append(float(half))
+    sd = np.array([(p64[2, 2] * -dd + p64[3, 2]) / dd for dd in dist[1:]]).astype(f32)
+    return Cascades(mats, sd, dist, corners_all, halves)
+
+
+def csm_select(split_depths, clip_depth) -> np.ndarray:
+    """SelectCascade (shadow_csm.hlsli:55-71): the last i in 0..2 with clip_depth > SplitDepth[i], plus one (float32 comparison)."""
+    cd = np.asarray(clip_depth, dtype=f32)
+    idx = np.zeros(cd.shape, dtype=np.int64)
+    for i in range(CASCADE_COUNT - 1):
+        idx = np.where(cd > f32(split_depths[i]), i + 1, idx)
+    return idx
+
+
+def csm_factor(layers, matrices, split_depths, world_pos, normal, light_dir, clip_depth, bias: float, normal_bias: float,
+               map_size: float) -> np.ndarray:
+    """Numpy model of CalculateShadowCSM (shadow_csm.hlsli:163-194) with this build's sampler (pcf_factor): SelectCascade on clip_depth,
+    then SampleCascadePCF in the selected layer -- the normal offset first, ONE matrix product, the bounds test on the offset position
+    (outside: 1.0), adaptive bias max(bias * (1 - N.L), 0.0005), nine taps at uv + (x, y) / map_size, / 9.  Geometry in float64; the
+    texel decisions and the comparison as the sampler is specified.  layers: (4, H, W); world_pos (..., 3); normal (..., 3) or (3,);
+    light_dir: towards the light; clip_depth (...)."""
+    wp = np.asarray(world_pos, dtype=np.float64)
+    n = np.broadcast_to(np.asarray(normal, dtype=np.float64), wp.shape)
+    l = np.asarray(light_dir, dtype=np.float64)
+    idx = csm_select(split_depths, clip_depth)
+    off = wp + n * float(normal_bias)
+    p4 = np.concatenate([off, np.ones(off.shape[:-1] + (1,))], axis=-1)
+    ndotl = (n * l).sum(axis=-1)
+    ab = np.maximum(float(bias) * (1.0 - ndotl), 0.0005)
+    out = np.ones(idx.shape, dtype=np.float64)
+    for k in range(CASCADE_COUNT):
+        clip = p4 @ np.asarray(matrices[k], dtype=np.float64)
+        pc = clip[..., :3] / clip[..., 3:4]
+        u, v, z = pc[..., 0] * 0.5 + 0.5, 1.0 - (pc[..., 1] * 0.5 + 0.5), pc[..., 2]
+        inside = (u >= 0.0) & (u <= 1.0) & (v >= 0.0) & (v <= 1.0) & (z >= 0.0) & (z <= 1.0)
+        s = pcf_factor(np.asarray(layers[k]), u, v, z - ab, texel=(1.0 / map_size, 1.0 / map_size))
+        out = np.where(idx == k, np.where(inside, s, 1.0), out)
+    return out
+
+
+CASCADED_GROUND_LIGHT = (0.6, -1.0, 0.2)
+CASCADED_GROUND_EYE, CASCADED_GROUND_TARGET = (0.0, 3.0, 6.0), (0.0, 0.0, -14.0)
+CASCADED_GROUND_RANGE = (2.0, 60.0)                                # view distances the cascades cover
+CASCADED_GROUND_LAM = 0.6                                          # split scheme blend (csm_split_distances)
+CASCADED_GROUND_SPHERE = ((0.6, 0.6, 0.6), (-1.6, 0.8, 1.5))       # scale, translation of the displaced sphere
+
+
+def cascaded_ground_boxes(lam: float = CASCADED_GROUND_LAM):
+    """(centre, half extent) of one caster box per cascade of cascaded_ground_case: on the ground, at the middle view distance of the
+    cascade's slice, left of the view axis (the light throws the shadows to the right, into view), growing with the distance."""
+    dist = np.concatenate([[CASCADED_GROUND_RANGE[0]], csm_split_distances(*CASCADED_GROUND_RANGE, lam=lam)])
+    eye, tgt = np.array(CASCADED_GROUND_EYE), np.array(CASCADED_GROUND_TARGET)
+    fwd = (tgt - eye) / np.linalg.norm(tgt - eye)
+    boxes = []
+    for k in range(CASCADE_COUNT):
+        mid = 0.5 * (dist[k] + dist[k + 1])
+        t = eye[2] + (mid + eye[1] * fwd[1]) / fwd[2]              # z of the ground point (x ~ 0, y = 0) whose view distance (p - eye) . fwd is mid
+        size = 0.6 + 0.03 * mid + 0.0035 * mid * mid
+        boxes.append(((float(-(0.4 + 0.06 * mid) - 0.5 * size), float(size), float(t)), (float(size * 0.8), float(size), float(size * 0.8))))
+    return boxes
+
+
+def cascaded_ground_case(width: int = 480, height: int = 360, map_size: int = 2048, light_dir=CASCADED_GROUND_LIGHT,
+                         intensity: float = 2.0, lam: float = CASCADED_GROUND_LAM) -> Scene:
+    """A long MODEL_PBR ground strip receding from a perspective camera, a caster box in each cascade's depth range and the displaced
+    sphere, under one directional light; every box and the sphere are casters of all four cascade scopes."""
+    view, proj, cam = default_camera(width, height, eye=CASCADED_GROUND_EYE, target=CASCADED_GROUND_TARGET)
+    light = light_ubo(direction=light_dir, intensity=intensity, color=(1.0, 0.97, 0.9))
+    cas = csm_cascades(view, proj, light_dir, *CASCADED_GROUND_RANGE, lam=lam)
+    pos = np.array([[-40.0, 0.0, 8.0], [40.0, 0.0, 8.0], [40.0, 0.0, -90.0], [-40.0, 0.0, -90.0]])
+    gv = _pack_vertex48(pos, np.tile(np.array([0.0, 1.0, 0.0]), (4, 1)), np.array([[0, 0], [1, 0], [1, 1], [0, 1]], dtype=f32),
+                        np.tile(np.array([1.0, 0.0, 0.0, 1.0]), (4, 1)))
+    gi = np.array([0, 1, 2, 0, 2, 3], dtype=np.uint32)
+    eye4 = np.eye(4, dtype=f32)
+    sphere = displaced_sphere(24, 17, width, height, seed=3).draws[0]
+    sphere_model = trs(CASCADED_GROUND_SPHERE[0], (0.0, 0.0, 0.0, 1.0), CASCADED_GROUND_SPHERE[1])
+    draws = [DrawSpec(vertices=gv, stride=48, count=gi.size, indices=gi, program=PROGRAM_MODEL_PBR, cull_mode=CULL_NONE, camera=cam,
+                      object=object_ubo(eye4), light=light, material=pbr_material_ubo((0.8, 0.8, 0.75, 1.0), 0.0, 0.7))]
+    meshes = []
+    for centre, half in cascaded_ground_boxes(lam):
+        bv, bi = _box_mesh(centre, half)
+        meshes.append((bv, bi, eye4, CULL_NONE))
+        draws.append(DrawSpec(vertices=bv, stride=48, count=bi.size, indices=bi, program=PROGRAM_MODEL_PBR, cull_mode=CULL_BACK,
+                              front_face=FRONT_CCW, camera=cam, object=object_ubo(eye4), light=light,
+                              material=pbr_material_ubo((0.6, 0.3, 0.2, 1.0), 0.0, 0.5)))
+    meshes.append((sphere.vertices, sphere.indices, sphere_model, CULL_NONE))
+    draws.append(DrawSpec(vertices=sphere.vertices, stride=48, count=sphere.count, indices=sphere.indices, program=PROGRAM_MODEL_PBR,
+                          cull_mode=CULL_BACK, front_face=sphere.front_face, camera=cam, object=object_ubo(sphere_model), light=light,
+                          material=pbr_material_ubo((0.2, 0.4, 0.8, 1.0), 0.3, 0.4)))
+    casters = [[DrawSpec(vertices=v, stride=48, count=int(i.size), indices=i, program=PROGRAM_SHADOW, cull_mode=cull,
+                         camera=shadow_constants_ubo(flip_clip_y(m), model)) for v, i, model, cull in meshes] for m in cas.matrices]
+    spec = CascadeSpec(casters, (map_size, map_size), csm_ubo(cas.matrices, cas.split_depths, 0.005, 0.01, float(map_size)))
+    return Scene("cascaded-ground", width, height, draws, clear_color=(0.02, 0.02, 0.03, 1.0), cascades=spec)
