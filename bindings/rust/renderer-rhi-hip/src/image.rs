@@ -33,6 +33,27 @@ impl Image {
         check(unsafe { mirhi_sys::mirhi_image_create_layer_view(self.raw, layer, &mut raw) })?;
         Ok(Self { device: self.device.clone(), raw })
     }
+    /// Six faces (+X, -X, +Y, -Y, +Z, -Z) and `levels` mip levels in one allocation (R32G32B32A32Sfloat only): level-major, then face-major,
+    /// then row-major.  What the IBL precompute passes below read and write.
+    pub fn new_cube(device: Arc<Device>, size: u32, levels: u32, format: Format) -> RhiResult<Self> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { mirhi_sys::mirhi_image_create_cube(device.raw, size, levels, format as i32, &mut raw) })?;
+        Ok(Self { device, raw })
+    }
+    /// Sample count the prefilter pass uses when the caller has no reason for another.
+    pub const DEFAULT_PREFILTER_SAMPLES: u32 = 1024;
+    /// equirect_to_cubemap.hlsl: level 0 of this cube from a 2-D equirectangular image.
+    pub fn ibl_equirect_to_cube(&self, src2d: &Image) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_ibl_equirect_to_cube(src2d.raw, self.raw) }) }
+    /// Levels 1.. of this cube from its level 0 (2 x 2 box filter per face).
+    pub fn ibl_cube_generate_mips(&self) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_ibl_cube_generate_mips(self.raw) }) }
+    /// irradiance_map.hlsl: level 0 of this cube from the environment cube.
+    pub fn ibl_irradiance(&self, env: &Image) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_ibl_irradiance(env.raw, self.raw) }) }
+    /// prefilter_map.hlsl: every level of this cube from the environment cube's chain; `sample_count` in 1..=4096.
+    pub fn ibl_prefilter(&self, env: &Image, sample_count: u32) -> RhiResult<()> {
+        check(unsafe { mirhi_sys::mirhi_ibl_prefilter(env.raw, self.raw, sample_count) })
+    }
+    /// brdf_lut.hlsl: this square 2-D R32G32B32A32Sfloat image receives (A, B, 0, 1).
+    pub fn ibl_brdf_lut(&self) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_ibl_brdf_lut(self.raw) }) }
     pub fn layers(&self) -> u32 { unsafe { mirhi_sys::mirhi_image_layers(self.raw) } }
     /// RGBA8 / float texels of level 0, row-major, top row first.
     pub fn upload(&self, texels: &[u8]) -> RhiResult<()> {

@@ -32,7 +32,8 @@ extern "C" {
                                     still 5 (new enum values only): MIRHI_PROGRAM_SHADOW, MIRHI_SLOT_SHADOW_DATA, MIRHI_TEXTURE_SHADOW_MAP, depth-only
                                     pipelines (colour format UNDEFINED) and depth-only rendering scopes (color_image NULL);
                                     still 5 (new functions only): mirhi_image_create_array, mirhi_image_create_layer_view, mirhi_image_layers,
-                                    mirhi_cmd_bind_shadow_cascades */
+                                    mirhi_cmd_bind_shadow_cascades;
+                                    still 5 (new functions only): mirhi_image_create_cube and the five mirhi_ibl_ passes */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -175,6 +176,51 @@ int32_t      mirhi_image_format(const mirhi_image* img);
 uint64_t     mirhi_image_size_bytes(const mirhi_image* img);
 void*        mirhi_image_device_ptr(const mirhi_image* img);
 mirhi_result mirhi_image_destroy(mirhi_image* img);
+
+/* ---- IBL precompute: cube images and the reference's four compute shaders (shaders/hlsl/compute/) -------------------------------------
+ * What pixel/model_pbr_ibl_csm.hlsl samples as irradianceMap, prefilteredMap and brdfLUT, made on the device.  No Rust code of the reference runs
+ * these shaders, so the shaders are the specification.  Nothing here is recorded into a command buffer: each pass is an immediate operation
+ * like mirhi_image_generate_mips (it waits for every queue lane, runs on the device's stream and has finished when it returns).
+ *
+ * Cube images.  format R32G32B32A32_SFLOAT only (the environment is HDR, the shaders write float4); size a power of two in [1, 4096]; levels in
+ * [1, log2(size) + 1].  ONE allocation, level-major, then face-major, then row-major: level l holds six faces of (size >> l)^2 texels, faces
+ * 0..5 = +X, -X, +Y, -Y, +Z, -Z (GetCubemapDirection, equirect_to_cubemap.hlsl:22-56), rows top first; level l starts at texel
+ * 6 * sum over k < l of (size >> k)^2.  mirhi_image_width / _height report the size, mirhi_image_layers 6, mirhi_image_mip_levels `levels`,
+ * mirhi_image_size_bytes the whole chain, and mirhi_image_upload / _read move the whole chain.  A cube is no 2-D image and no array: it is refused
+ * (InvalidHandle, the message says "cube") as a colour, depth or prim-id attachment, at every mirhi_texture_slot, by mirhi_cmd_bind_shadow_cascades,
+ * mirhi_image_create_layer_view, mirhi_image_generate_mips and mirhi_image_set_max_anisotropy, and there is no wrapped cube.
+ *
+ * The sampler (the reference's sampler.rs is empty: this is the build's reading of `LinearSampler`).
+ *   Cube lookup, TextureCube.SampleLevel(LinearSampler, dir, lod): face and (s, t) by the Vulkan specification's cube-map face selection table --
+ *   major axis = the component of largest magnitude, ties prefer z, then y, then x; (sc, tc) = +X (-z, -y), -X (+z, -y), +Y (+x, +z), -Y (+x, -z),
+ *   +Z (+x, -y), -Z (-x, -y); s = sc / (2 |ma|) + 1/2, t likewise -- which is the inverse of GetCubemapDirection.  Bilinear inside the selected face
+ *   with clamp to edge, NOT seamless across faces: x = s n - 1/2, x0 = floor(x), fraction x - x0, the four texels at x0, x0 + 1 (and rows
+ *   likewise) each clamped to [0, n - 1].  lod is clamped to [0, levels - 1]; the levels floor(lod) and floor(lod) + 1 (clamped to the last)
+ *   are each filtered so and lerped by lod's fraction.
+ *   2-D lookup of the equirectangular source, Texture2D.SampleLevel(LinearSampler, uv, 0): bilinear at level 0, u repeats (longitude wraps),
+ *   v clamps to the edge.
+ * Numerics: float32 throughout, not bit-exact against anything: the kernels contract, use the hardware reciprocal / square root / logarithm and
+ * sum in parallel (tests bound the error against a float64 model).  Only mirhi_ibl_cube_generate_mips is exact.
+ * Refused with InvalidHandle: a non-cube where a cube is due (and the other way round), any format but R32G32B32A32_SFLOAT, source == destination,
+ * images of two devices. */
+mirhi_result mirhi_image_create_cube(mirhi_device* dev, uint32_t size, uint32_t levels, mirhi_format format, mirhi_image** out);
+/* equirect_to_cubemap.hlsl:78-105: level 0 of `cube`, all four channels, from the 2-D image `src2d` (DirectionToEquirectUV :59-75) */
+mirhi_result mirhi_ibl_equirect_to_cube(mirhi_image* src2d, mirhi_image* cube);
+/* Levels 1.. of a cube from its level 0, face by face with a 2 x 2 box filter in float, ((a + b) + (c + d)) * 0.25 (exact operations in this
+ * order).  The build's own definition: the reference never builds the chain that prefilter_map.hlsl:212 samples. */
+mirhi_result mirhi_ibl_cube_generate_mips(mirhi_image* cube);
+/* irradiance_map.hlsl:63-143: level 0 of `out` = (rgb, 1); IrradianceMapSize = out's size; sampleDelta 0.025 (:97), whose float32 loops (:101-103)
+ * make 252 phi x 63 theta steps; every lookup at level 0 of `env` */
+mirhi_result mirhi_ibl_irradiance(mirhi_image* env, mirhi_image* out);
+/* prefilter_map.hlsl:134-229 once per level of `out`, all levels in one launch: MipSize = size >> l, Roughness = l / (levels - 1) (0 when levels
+ * is 1); Roughness < 0.01 is the single lookup at R, level 0 (:168-173); resolution = 512.0 stays hard-coded (:204); the lookups use the whole
+ * chain of `env` (:212).  SourceMipLevel is read by nothing in the shader and is no parameter.  sample_count in [1, 4096] (the wrappers default
+ * to 1024). */
+mirhi_result mirhi_ibl_prefilter(mirhi_image* env, mirhi_image* out, uint32_t sample_count);
+/* brdf_lut.hlsl:116-206: the square 2-D R32G32B32A32_SFLOAT image `out2d` receives (A, B, 0, 1) -- the consumer declares Texture2D<float4> and
+ * reads .rg; 1024 samples (:133), NdotV = max(u, 0.001) (:198).  The reference stores rg16f (:18); that rounding is NOT reproduced (float
+ * storage, no new format). */
+mirhi_result mirhi_ibl_brdf_lut(mirhi_image* out2d);
 
 /* ---- pipeline: GraphicsPipelineBuilder (pipeline.rs:590-1059) -------------------------------------- */
 typedef enum {   /* replaces Shader::from_spirv_file (shader.rs:244-330): precompiled .hip programs */

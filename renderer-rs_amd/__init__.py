@@ -18,6 +18,7 @@ import numpy as np
 
 from . import build as _build
 from . import scenes  # noqa: F401  (re-export)
+from . import ibl  # noqa: F401  (re-export: the numpy model of the IBL precompute passes)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, os.environ.get("MIRHI_LIB_NAME", "libmirhi.so"))   # MIRHI_LIB_NAME: diagnostic builds only
@@ -204,6 +205,12 @@ _SIGNATURES = {
     "mirhi_image_create_array": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mirhi_image_create_layer_view": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mirhi_image_layers": (C.c_uint32, [C.c_void_p]),
+    "mirhi_image_create_cube": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mirhi_ibl_equirect_to_cube": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mirhi_ibl_cube_generate_mips": (C.c_int32, [C.c_void_p]),
+    "mirhi_ibl_irradiance": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mirhi_ibl_prefilter": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "mirhi_ibl_brdf_lut": (C.c_int32, [C.c_void_p]),
     "mirhi_image_upload": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mirhi_image_read": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mirhi_image_generate_mips": (C.c_int32, [C.c_void_p]),
@@ -464,6 +471,7 @@ class Buffer:
 
 class Image:
     """Colour target / DepthBuffer (crates/renderer/src/depth_buffer.rs:117-243) / sampled texture."""
+    is_cube = False     # True on what create_cube returns
 
     def __init__(self, device: Device, width: int, height: int, fmt: int, device_ptr: Optional[int] = None):
         h = C.c_void_p()
@@ -485,6 +493,44 @@ class Image:
         h = C.c_void_p()
         check(lib().mirhi_image_create_array(device.handle, width, height, layers, fmt, C.byref(h)))
         return cls._adopt(h, device, width, height, fmt)
+
+    @classmethod
+    def create_cube(cls, device: Device, size: int, levels: int = 1, fmt: int = Format.R32G32B32A32_SFLOAT) -> "Image":
+        """mirhi_image_create_cube: six faces and `levels` mip levels in one allocation (R32G32B32A32_SFLOAT only); level-major, then
+        face-major (+X, -X, +Y, -Y, +Z, -Z), then row-major."""
+        h = C.c_void_p()
+        check(lib().mirhi_image_create_cube(device.handle, size, levels, fmt, C.byref(h)))
+        img = cls._adopt(h, device, size, size, fmt)
+        img.is_cube = True
+        return img
+
+    def cube_levels(self, packed=None):
+        """The levels of a cube's packed chain (default: read it back) as views [6, n >> l, n >> l, 4] of that one array."""
+        packed = self.read() if packed is None else packed
+        return ibl.unpack_cube(packed, self.width, self.mip_levels)
+
+    def cube_face(self, level: int, face: int, packed=None) -> np.ndarray:
+        return self.cube_levels(packed)[level][face]
+
+    # the IBL precompute passes (include/mirhi.h "IBL precompute"): immediate, finished on return
+    def ibl_equirect_to_cube(self, src2d: "Image"):
+        """equirect_to_cubemap.hlsl: level 0 of this cube from the 2-D equirectangular image."""
+        check(lib().mirhi_ibl_equirect_to_cube(src2d.handle, self.handle))
+
+    def ibl_cube_generate_mips(self):
+        check(lib().mirhi_ibl_cube_generate_mips(self.handle))
+
+    def ibl_irradiance(self, env: "Image"):
+        """irradiance_map.hlsl: level 0 of this cube from the environment cube."""
+        check(lib().mirhi_ibl_irradiance(env.handle, self.handle))
+
+    def ibl_prefilter(self, env: "Image", sample_count: int = 1024):
+        """prefilter_map.hlsl: every level of this cube from the environment cube's chain."""
+        check(lib().mirhi_ibl_prefilter(env.handle, self.handle, int(sample_count)))
+
+    def ibl_brdf_lut(self):
+        """brdf_lut.hlsl: this square 2-D image receives (A, B, 0, 1)."""
+        check(lib().mirhi_ibl_brdf_lut(self.handle))
 
     def layer_view(self, layer: int) -> "Image":
         """mirhi_image_create_layer_view: a non-owning 2-D image of one layer (destroy it before the array)."""
@@ -520,6 +566,8 @@ class Image:
         n = lib().mirhi_image_size_bytes(self.handle)
         raw = np.empty(n, dtype=np.uint8)
         check(lib().mirhi_image_read(self.handle, raw.ctypes.data, n))
+        if self.is_cube:     # the packed chain, [texels, 4]: cube_levels() gives the level / face views
+            return raw.view(np.float32).reshape(-1, 4)
         layers = self.layers
         if layers > 1:      # an array (D32_SFLOAT): the layers in order
             return raw.view(np.float32).reshape(layers, self.height, self.width)

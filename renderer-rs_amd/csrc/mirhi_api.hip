@@ -484,6 +484,9 @@ struct mirhi_image {
     // which is no 2-D image (attachments and MIRHI_TEXTURE_SHADOW_MAP take a layer view).  A layer view (mirhi_image_create_layer_view) is a non-owning
     // 2-D image of one layer: ptr points into the array, `parent` is the array -- what attachment ordering resolves a view to (for_each_attachment).
     uint32_t layers = 1; bool is_array = false;
+    // Cube images (mirhi_image_create_cube): six faces and `levels` mip levels in one allocation, level-major, then face-major, then row-major; width =
+    // height = the edge of level 0, layers = 6.  A cube is neither a 2-D image nor an array: only the mirhi_ibl_* passes, upload and read take one.
+    bool is_cube = false;
     mirhi_image* parent = nullptr;
     uint32_t views = 0;            // live layer views of an array (it cannot be destroyed before them)
     // Attachment ordering across queue lanes: the reference submits everything to one queue, so a scope that LOADs (or overwrites)
@@ -986,6 +989,7 @@ extern "C" mirhi_result mirhi_buffer_destroy(mirhi_buffer* buf) {
 // ------------------------------------------------------------------------------------------------
 // images
 // ------------------------------------------------------------------------------------------------
+#include "mirhi_ibl.hip.h"   // cube layout (ibl_level_offset) and the IBL precompute kernels, launched further down beside mip_kernel
 static mirhi_result image_common(mirhi_device* dev, uint32_t w, uint32_t h, mirhi_format f, void* ext, mirhi_image** out) {
     NULL_CHECK(dev, "device"); NULL_CHECK(out, "out");
     *out = nullptr;
@@ -1016,7 +1020,11 @@ extern "C" mirhi_result mirhi_image_wrap_device_memory(mirhi_device* dev, uint32
 extern "C" uint32_t mirhi_image_width(const mirhi_image* img) { return img ? img->width : 0; }
 extern "C" uint32_t mirhi_image_height(const mirhi_image* img) { return img ? img->height : 0; }
 extern "C" int32_t mirhi_image_format(const mirhi_image* img) { return img ? (int32_t)img->format : 0; }
-extern "C" uint64_t mirhi_image_size_bytes(const mirhi_image* img) { return img ? (uint64_t)img->width * img->height * format_bpp(img->format) * img->layers : 0; }
+extern "C" uint64_t mirhi_image_size_bytes(const mirhi_image* img) {
+    if (!img) return 0;
+    if (img->is_cube) return (uint64_t)ibl_chain_texels(img->width, img->levels) * format_bpp(img->format);       // the whole chain
+    return (uint64_t)img->width * img->height * format_bpp(img->format) * img->layers;
+}
 extern "C" uint32_t mirhi_image_layers(const mirhi_image* img) { return img ? img->layers : 0; }
 // Texture2DArray<float> (model_pbr_ibl_csm.hlsl:115-116): one allocation, layer k at byte offset k * width * height * bpp
 extern "C" mirhi_result mirhi_image_create_array(mirhi_device* dev, uint32_t w, uint32_t h, uint32_t layers, mirhi_format f, mirhi_image** out) {
@@ -1044,6 +1052,7 @@ extern "C" mirhi_result mirhi_image_create_array(mirhi_device* dev, uint32_t w, 
 extern "C" mirhi_result mirhi_image_create_layer_view(mirhi_image* array, uint32_t layer, mirhi_image** out) {
     NULL_CHECK(array, "image"); NULL_CHECK(out, "out");
     *out = nullptr;
+    if (array->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image has no layer views");
     if (!array->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: layer views are made of array images (mirhi_image_create_array)");
     if (layer >= array->layers) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: layer %u out of range (the array has %u layers)", layer, array->layers);
     mirhi_device* dev = array->dev;
@@ -1091,6 +1100,7 @@ __global__ void mip_kernel(const uint32_t* __restrict__ src, uint32_t sw, uint32
 extern "C" uint32_t mirhi_image_mip_levels(const mirhi_image* img) { return img ? img->levels : 0; }
 extern "C" mirhi_result mirhi_image_generate_mips(mirhi_image* img) {
     NULL_CHECK(img, "image");
+    if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image's mip chain is built by mirhi_ibl_cube_generate_mips");
     if (img->format != MIRHI_FORMAT_R8G8B8A8_UNORM && img->format != MIRHI_FORMAT_R8G8B8A8_SRGB)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: mip chains are built for R8G8B8A8 textures only");
     if (!img->owned) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: cannot grow a wrapped image into a mip chain");
@@ -1122,9 +1132,128 @@ extern "C" mirhi_result mirhi_image_generate_mips(mirhi_image* img) {
     img->levels = levels;
     return MIRHI_OK;
 }
+// ------------------------------------------------------------------------------------------------
+// cube images and the IBL precompute passes (kernels: mirhi_ibl.hip.h; include/mirhi.h "IBL precompute")
+// ------------------------------------------------------------------------------------------------
+extern "C" mirhi_result mirhi_image_create_cube(mirhi_device* dev, uint32_t size, uint32_t levels, mirhi_format f, mirhi_image** out) {
+    NULL_CHECK(dev, "device"); NULL_CHECK(out, "out");
+    *out = nullptr;
+    if (f != MIRHI_FORMAT_R32G32B32A32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: cube images of format %d (R32G32B32A32_SFLOAT only)", (int)f);
+    if (size == 0 || size > 4096u || (size & (size - 1u))) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube's size must be a power of two in [1, 4096] (got %u)", size);
+    uint32_t full = 1; while ((size >> full) != 0u) full++;                       // log2(size) + 1
+    if (levels == 0 || levels > full) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a %u^2 cube has 1 to %u mip levels (got %u)", size, full, levels);
+    const uint64_t bytes = (uint64_t)ibl_chain_texels(size, levels) * 16u;         // (at most 8 * 4096^2 texels: texel offsets stay 32-bit in the kernels)
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, (size_t)bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: hipMalloc for a %u^2 cube of %u levels: %s", size, levels, hipGetErrorString(e)); }
+    mirhi_image* img = new (std::nothrow) mirhi_image{dev, size, size, f, (uint8_t*)p, true};
+    if (!img) { (void)hipFree(p); return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: host allocation failed"); }
+    img->layers = 6; img->levels = levels; img->is_cube = true;
+    { std::lock_guard<std::mutex> lock(dev->mu); dev->images.push_back(img); }
+    dev->children++;
+    *out = img;
+    return MIRHI_OK;
+}
+static mirhi_result ibl_cube_arg(const mirhi_image* img, const char* what) {
+    if (!img) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s is null", what);
+    if (!img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s must be a cube image (mirhi_image_create_cube)", what);
+    return MIRHI_OK;
+}
+static mirhi_result ibl_2d_arg(const mirhi_image* img, const char* what) {
+    if (!img) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s is null", what);
+    if (img->is_cube || img->is_array || img->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s must be a 2-D image", what);
+    if (img->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s must be R32G32B32A32_SFLOAT (format %d)", what, (int)img->format);
+    return MIRHI_OK;
+}
+static mirhi_result ibl_pair(const mirhi_image* a, const mirhi_image* b) {
+    if (a == b) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a pass cannot read and write the same image");
+    if (a->dev != b->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the two images belong to different devices");
+    return MIRHI_OK;
+}
+// the frame of every pass: lost device, all lanes idle, launch on the device stream, foreign write, wait (as mirhi_image_generate_mips)
+static mirhi_result ibl_begin(mirhi_device* dev) {
+    if (dev->native && dev->native->lost.load(std::memory_order_acquire)) return device_lost(dev);
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    { mirhi_result r0 = sync_all_lanes(dev); if (r0 != MIRHI_OK) return r0; }
+    dev->foreign_writes++;
+    return MIRHI_OK;
+}
+static mirhi_result ibl_end(mirhi_device* dev) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    return MIRHI_OK;
+}
+static IblCube ibl_cube_of(const mirhi_image* img) { return IblCube{(const float4*)img->ptr, img->width, img->levels}; }
+
+extern "C" mirhi_result mirhi_ibl_equirect_to_cube(mirhi_image* src2d, mirhi_image* cube) {
+    { mirhi_result r = ibl_2d_arg(src2d, "the equirectangular source"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_cube_arg(cube, "the destination"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_pair(src2d, cube); if (r != MIRHI_OK) return r; }
+    mirhi_device* dev = cube->dev;
+    { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
+    const uint32_t n = cube->width, texels = 6u * n * n;
+    hipLaunchKernelGGL(ibl_equirect_kernel, dim3((texels + 255u) / 256u), dim3(256), 0, dev->stream, (const float4*)src2d->ptr, src2d->width, src2d->height, (float4*)cube->ptr, n);
+    return ibl_end(dev);
+}
+extern "C" mirhi_result mirhi_ibl_cube_generate_mips(mirhi_image* cube) {
+    { mirhi_result r = ibl_cube_arg(cube, "the image"); if (r != MIRHI_OK) return r; }
+    mirhi_device* dev = cube->dev;
+    { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
+    for (uint32_t l = 1; l < cube->levels; l++) {
+        const uint32_t dn = cube->width >> l, texels = 6u * dn * dn;
+        hipLaunchKernelGGL(ibl_cube_mip_kernel, dim3((texels + 255u) / 256u), dim3(256), 0, dev->stream,
+                           (const float4*)cube->ptr + ibl_level_offset(cube->width, l - 1u), (float4*)cube->ptr + ibl_level_offset(cube->width, l), dn);
+        HIP_TRY(hipGetLastError());
+    }
+    return ibl_end(dev);
+}
+extern "C" mirhi_result mirhi_ibl_irradiance(mirhi_image* env, mirhi_image* out) {
+    { mirhi_result r = ibl_cube_arg(env, "the environment"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_cube_arg(out, "the destination"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_pair(env, out); if (r != MIRHI_OK) return r; }
+    mirhi_device* dev = out->dev;
+    { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
+    const uint32_t n = out->width;
+    hipLaunchKernelGGL(ibl_irradiance_kernel, dim3(6u * n * n), dim3(256), 0, dev->stream, ibl_cube_of(env), (float4*)out->ptr, n);
+    return ibl_end(dev);
+}
+extern "C" mirhi_result mirhi_ibl_prefilter(mirhi_image* env, mirhi_image* out, uint32_t sample_count) {
+    { mirhi_result r = ibl_cube_arg(env, "the environment"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_cube_arg(out, "the destination"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_pair(env, out); if (r != MIRHI_OK) return r; }
+    if (sample_count == 0 || sample_count > 4096u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: sample_count must be in [1, 4096] (got %u)", sample_count);
+    mirhi_device* dev = out->dev;
+    { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
+    IblPrefilterPlan plan{};
+    plan.levels = out->levels; plan.sample_count = sample_count; plan.size = out->width;     // (levels <= 13 = IBL_MAX_LEVELS: size <= 4096)
+    uint32_t blocks = 0;
+    for (uint32_t l = 0; l < out->levels; l++) {
+        const uint32_t m = out->width >> l, texels = 6u * m * m;
+        const bool mirror = out->levels == 1u || (float)l / (float)(out->levels - 1u) < 0.01f;
+        uint32_t lanes = 1;                         // split a texel's samples over 4, 16 or 64 lanes while the level has fewer than 128 Ki threads
+        while (!mirror && lanes < 64u && texels * lanes < 131072u) lanes *= 4u;
+        plan.first_block[l] = blocks; plan.lanes[l] = lanes;
+        blocks += (texels + 256u / lanes - 1u) / (256u / lanes);
+    }
+    plan.first_block[out->levels] = blocks;
+    hipLaunchKernelGGL(ibl_prefilter_kernel, dim3(blocks), dim3(256), (size_t)sample_count * sizeof(float4), dev->stream, ibl_cube_of(env), (float4*)out->ptr, plan);
+    return ibl_end(dev);
+}
+extern "C" mirhi_result mirhi_ibl_brdf_lut(mirhi_image* out2d) {
+    { mirhi_result r = ibl_2d_arg(out2d, "the destination"); if (r != MIRHI_OK) return r; }
+    if (out2d->width != out2d->height) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the BRDF LUT must be square (got %ux%u)", out2d->width, out2d->height);
+    if (out2d->levels != 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the BRDF LUT must have no mip chain");
+    mirhi_device* dev = out2d->dev;
+    { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
+    const uint32_t n = out2d->width;
+    hipLaunchKernelGGL(ibl_brdf_lut_kernel, dim3((n + 255u) / 256u, n), dim3(256), 0, dev->stream, (float4*)out2d->ptr, n);
+    return ibl_end(dev);
+}
 extern "C" uint32_t mirhi_image_max_anisotropy(const mirhi_image* img) { return img ? img->max_anisotropy : 0; }
 extern "C" mirhi_result mirhi_image_set_max_anisotropy(mirhi_image* img, uint32_t max_anisotropy) {
     NULL_CHECK(img, "image");
+    if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image has no anisotropic sampler (the cube sampler is fixed, include/mirhi.h)");
     if (img->format != MIRHI_FORMAT_R8G8B8A8_UNORM && img->format != MIRHI_FORMAT_R8G8B8A8_SRGB)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: anisotropic filtering applies to sampled R8G8B8A8 textures only");
     if (max_anisotropy < 1u || max_anisotropy > 16u)
@@ -1375,6 +1504,7 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
     if (!info->color_image && info->depth_image) {
         // depth-only scope (MIRHI_PROGRAM_SHADOW): the depth image's extent is the render area; only SHADOW draws are recorded here
         const mirhi_image* di = info->depth_image;
+        if (di->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image is not an attachment");
         if (di->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: depth attachment is not D32_SFLOAT");
         if (di->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array is not an attachment: use a layer view (mirhi_image_create_layer_view)");
         if (info->prim_id_image) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: prim_id_image in a depth-only rendering scope");
@@ -1395,6 +1525,8 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
     }
     NULL_CHECK(info->color_image, "color_image");
     const mirhi_image* ci = info->color_image;
+    if (ci->is_cube || (info->depth_image && info->depth_image->is_cube) || (info->prim_id_image && info->prim_id_image->is_cube))
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image is not an attachment");
     if (ci->is_array || (info->depth_image && info->depth_image->is_array))
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array is not an attachment: use a layer view (mirhi_image_create_layer_view)");
     if (ci->format != MIRHI_FORMAT_B8G8R8A8_SRGB && ci->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT)
@@ -1463,6 +1595,7 @@ extern "C" mirhi_result mirhi_cmd_bind_uniform(mirhi_cmd* cmd, mirhi_uniform_slo
 extern "C" mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slot slot, mirhi_image* image) {
     REQUIRE_RECORDING(cmd);
     if ((int)slot < 0 || (int)slot >= MIRHI_TEXTURE_COUNT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unknown texture slot %d", (int)slot);
+    if (image && image->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image cannot be bound at a texture slot (no program samples one yet)");
     if (slot == MIRHI_TEXTURE_SHADOW_MAP) {       // t7 / s5 (model_pbr.hlsl:103-108): a depth image, sampled with the comparison sampler
         if (image && image->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow map must be D32_SFLOAT");
         if (image && image->is_array)
@@ -1479,6 +1612,7 @@ extern "C" mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slo
 extern "C" mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range) {
     REQUIRE_RECORDING(cmd);
     if (!array) { cmd->cascades = nullptr; cmd->cascade_params = {nullptr, 0, 0}; return MIRHI_OK; }
+    if (array->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array, not a cube image");
     if (array->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array, not a layer view");
     if (!array->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array (mirhi_image_create_array)");
     if (array->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow cascades must be D32_SFLOAT");

@@ -264,6 +264,21 @@ public:
         return Image(device_, raw, w_, h_px_, f_);
     }
     uint32_t layers() const { return mirhi_image_layers(h_); }
+    // mirhi_image_create_cube: six faces and `levels` mip levels in one allocation (R32G32B32A32_SFLOAT), level-major, then face-major, then row-major
+    static Image cube(std::shared_ptr<Device> device, uint32_t size, uint32_t levels = 1, Format f = Format::R32G32B32A32_SFLOAT) {
+        mirhi_image* raw = nullptr;
+        check(mirhi_image_create_cube(device->handle(), size, levels, (mirhi_format)f, &raw));
+        return Image(std::move(device), raw, size, size, f);
+    }
+    uint64_t size_bytes() const { return mirhi_image_size_bytes(h_); }
+    // first texel of `level` in a cube's packed chain, and the texels of one of its faces
+    static uint64_t cube_level_offset(uint32_t size, uint32_t level) { uint64_t o = 0; for (uint32_t k = 0; k < level; k++) o += 6ull * (size >> k) * (size >> k); return o; }
+    // the IBL precompute passes (include/mirhi.h "IBL precompute"; shaders/hlsl/compute/): immediate, finished on return; `this` is the destination
+    void ibl_equirect_to_cube(const Image& src2d) const { check(mirhi_ibl_equirect_to_cube(src2d.h_, h_)); }
+    void ibl_cube_generate_mips() const { check(mirhi_ibl_cube_generate_mips(h_)); }
+    void ibl_irradiance(const Image& env) const { check(mirhi_ibl_irradiance(env.h_, h_)); }
+    void ibl_prefilter(const Image& env, uint32_t sample_count = 1024) const { check(mirhi_ibl_prefilter(env.h_, h_, sample_count)); }
+    void ibl_brdf_lut() const { check(mirhi_ibl_brdf_lut(h_)); }
     Image(Image&& o) noexcept : device_(std::move(o.device_)), h_(o.h_), w_(o.w_), h_px_(o.h_px_), f_(o.f_) { o.h_ = nullptr; }
     Image(const Image&) = delete;
     ~Image() { if (h_) mirhi_image_destroy(h_); }
