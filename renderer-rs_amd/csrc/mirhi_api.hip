@@ -30,6 +30,7 @@
 #include "../../include/mirhi.h"
 #include "mirhi_device.h"
 #include "mirhi_launch.h"
+#include "mirhi_variant.h"
 
 using namespace mirhi;
 
@@ -568,6 +569,7 @@ struct Workspace {
     uint32_t* prim_draw = nullptr; size_t prim_draw_bytes = 0;     // per primitive: its draw (scopes with several draws)
     uint32_t* status_host = nullptr;                             // pinned, device-mapped: [status bits, big-list length]
     uint32_t* status_dev = nullptr;                              // device view of status_host
+    void clear_status() { status_host[0] = 0; status_host[1] = 0; status_host[2] = 0; status_host[3] = 0; }      // re-arms the four words the kernels report in
     uint32_t* big_counts = nullptr;                              // two counters, used alternately (parity)
     uint32_t parity = 0;
     // statistics pass (MIRHI_PROFILE_FRAGMENTS), built on first use: a primitive-id image of the workspace's own and copies
@@ -2090,7 +2092,7 @@ extern "C" mirhi_result mirhi_cmd_end(mirhi_cmd* cmd) {
             HP(2);
             hand_over_status(cmd);
             HP(3);
-            cmd->ws.status_host[0] = 0; cmd->ws.status_host[1] = 0; cmd->ws.status_host[2] = 0; cmd->ws.status_host[3] = 0;
+            cmd->ws.clear_status();
             HP(4);
         }
         if (!(cmd->ws.dirty || cmd->ws.replan || cmd->ws.grow_pool)) {      // (the status just handed over may have asked for clears or another plan: rebuild below)
@@ -2105,7 +2107,7 @@ extern "C" mirhi_result mirhi_cmd_end(mirhi_cmd* cmd) {
         if (r != MIRHI_OK) return r;
         if (cmd->ws.status_host && (cmd->ws.status_host[0] | cmd->ws.status_host[1] | cmd->ws.status_host[2] | cmd->ws.status_host[3])) {
             hand_over_status(cmd);
-            cmd->ws.status_host[0] = 0; cmd->ws.status_host[1] = 0; cmd->ws.status_host[2] = 0; cmd->ws.status_host[3] = 0;
+            cmd->ws.clear_status();
         }
         if (cmd->ws.replan || cmd->ws.grow_pool || cmd->ws.dirty) goto rebuild;      // (the status just handed over asked for another plan)
         {
@@ -2192,7 +2194,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         if (cmd->ws.spread && (tris_now > 2 * cmd->ws.spread_tris || 2 * tris_now < cmd->ws.spread_tris)) cmd->ws.spread = false;
     }
     size_t total_draws = 0, max_tiles = 0, max_pages = 0, max_big = 0;
-    struct Geo { uint32_t tiles_x, tiles_y, r0, r1, rstep, bin_cap, sub_cap, big_cap, fixed_pages, fixed_per_tile; bool xcd_bins; };      // r0 / r1 / rstep: PassParams::tile_row_begin / _end / _step
+    struct Geo { uint32_t tiles_x, tiles_y, r0, r1, rstep, bin_cap, sub_cap, big_cap, fixed_pages, fixed_per_tile; bool xcd_bins, tri_prog; };      // r0 / r1 / rstep: PassParams::tile_row_begin / _end / _step
     std::vector<Geo> geo;
     for (auto& pass : cmd->passes) {
         const RecordedPass::Target& ci = pass.color_t;
@@ -2202,7 +2204,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         if (pass.depth_only) { g.r0 = 0; g.r1 = g.tiles_y; g.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
         const size_t tiles = (size_t)g.tiles_x * (g.r1 - g.r0);
         const RasterMode mode = raster_mode(pass, tiles, cmd->ws.spread, cmd->ws.wide);
-        g.xcd_bins = mode.xcd_bins;
+        g.xcd_bins = mode.xcd_bins; g.tri_prog = mode.tri_prog;      // tri_prog: some draw uses the TRIANGLE program
         // A tile's bin holds up to BIN_TABLE_ROW pages (4096 records; eight lists of 512 with per-XCD bins) before it spills into
         // the big list, which EVERY tile walks -- the limit costs nothing until it is used: pages come out of one pool, sized by
         // the scope's triangle count, not by tiles x capacity (round 1: 100 MB at 1080p, 400-510 MB at 4K per command buffer).
@@ -2270,7 +2272,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     w.stats_params_valid = false;
     hand_over_status(cmd);          // an earlier submission's status is not lost to the re-arm below (and may ask for a bigger pool: before the flags are cleared)
     w.grow_pool = false; w.replan = false;
-    w.status_host[0] = 0; w.status_host[1] = 0; w.status_host[2] = 0; w.status_host[3] = 0;
+    w.clear_status();
     w.big_counts = w.counters + CTR_BIG;
     if (!w.dirty && getenv("MIRHI_VERIFY_IDLE")) {
         // Test hook: what the plan relies on instead of clearing -- every kernel leaves the workspace re-armed -- is checked here, on the
@@ -2349,10 +2351,9 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         if (ord && (r = grow(&w.ordered, &w.ordered_bytes, ord)) != MIRHI_OK) return r;
     }
     size_t flat_tris = 0;
-    for (auto& pass : cmd->passes) {
-        bool tri_prog = false;
-        for (const DrawDesc& dd : pass.draws) tri_prog |= dd.program == MIRHI_PROGRAM_TRIANGLE;
-        if (tri_prog && pass.color_t.format == MIRHI_FORMAT_B8G8R8A8_SRGB && pass.total_tris > flat_tris) flat_tris = pass.total_tris;
+    for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
+        const RecordedPass& pass = cmd->passes[pi];
+        if (geo[pi].tri_prog && pass.color_t.format == MIRHI_FORMAT_B8G8R8A8_SRGB && pass.total_tris > flat_tris) flat_tris = pass.total_tris;
     }
     if (flat_tris && (r = grow(&w.flat_color, &w.flat_color_bytes, flat_tris * 4)) != MIRHI_OK) return r;
     {
@@ -2423,13 +2424,10 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         P.frag_stats = dev->frag_stats;
         P.first_prim = pass.first_tri;
         P.prim_draw = draws.size() > 1 ? w.prim_draw : nullptr;
+        P.flat_color = (g.tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB) ? w.flat_color : nullptr;
+        P.resolve_flat_only = (P.flat_color && !P.depth_load && P.color_format != 2u && !P.prim_out && !(P.depth && P.depth_store)) ? 1u : 0u;
         {
-            bool tri_prog = false;
-            for (const DrawDesc& dd : draws) tri_prog |= dd.program == MIRHI_PROGRAM_TRIANGLE;
-            P.flat_color = (tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB) ? w.flat_color : nullptr;
-            P.resolve_flat_only = (P.flat_color && !P.depth_load && P.color_format != 2u && !P.prim_out && !(P.depth && P.depth_store)) ? 1u : 0u;
-        }
-        {
+            // (evaluated again, not kept from the sizing loop above: hand_over_status in between may have changed w.spread / w.wide)
             const RasterMode mode = raster_mode(pass, (size_t)g.tiles_x * (g.r1 - g.r0), w.spread, w.wide);
             P.tp_max_area = mode.tp_max_area;
             P.alpha_scope = pass_is_masked_plain(pass) ? 1u : 0u;
@@ -2462,12 +2460,11 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         if (!draws.empty()) memcpy(w.pimage.data() + w.draws_off + draws_done * sizeof(DrawDesc), draws.data(), draws.size() * sizeof(DrawDesc));
         draws_done += draws.size();
         cmd->plan.push_back(P);
-        uint32_t progs = 0;
-        for (const DrawDesc& dd : draws) progs |= dd.program == 0 ? 1u : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.tex_any_mips || dd.tex_srgb) ? 4u : 2u);
-        // 8: a shadowed MODEL_PBR draw (raster_kernel_shadow, with the Cook-Torrance variant's programs); 0: a depth-only scope (raster_kernel_depth)
-        // 16: ... whose shadow term is CalculateShadowCSM (raster_kernel_csm)
-        if (P.shadowed) progs = 4u | 8u | (P.shadowed == 2u ? 16u : 0u);
-        cmd->plan_programs.push_back(P.depth_only ? 0u : (progs ? progs : 1u));
+        uint32_t progs = 0;         // the scope's program set (mirhi_variant.h)
+        for (const DrawDesc& dd : draws)
+            progs |= dd.program == MIRHI_PROGRAM_TRIANGLE ? PROGS_TRIANGLE : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.tex_any_mips || dd.tex_srgb) ? PROGS_PBR : PROGS_MODEL);
+        if (P.shadowed) progs = PROGS_PBR | PROGS_SHADOWED | (P.shadowed == 2u ? PROGS_CASCADED : 0u);
+        cmd->plan_programs.push_back(P.depth_only ? PROGS_DEPTH_ONLY : (progs ? progs : PROGS_TRIANGLE));
         cmd->plan_tris += pass.total_tris - pass.first_tri;
         // the kernels read their parameters from the block: copy 2*pi + parity of scope pi appends large triangles to counter
         // `parity` and re-arms the other one for the scope that follows on this workspace
@@ -2679,10 +2676,11 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
     // all command buffers sit on the first one's queue lane (so the batch keeps their order against earlier work of that lane).
     // Anything else runs command buffer by command buffer, in submission order on each lane.
     bool batched = cmd_count >= 2 && cmd_count <= (uint32_t)MAX_BATCH && dev->profiling == 0 && !native_env().no_batch;
+    // (a plan that names a wide variant is not batched, whether or not a submit would take it: the variant as with allow_wide)
+    auto variant_of = [](const mirhi_cmd* c) { return raster_variant(c->plan[0], c->plan_programs[0], true); };
     for (uint32_t i = 0; batched && i < cmd_count; i++) {
         const mirhi_cmd* c = cmds[i];
-        batched = c->plan.size() == 1 && raster_batchable(c->plan[0]) && c->lane == cmds[0]->lane &&
-                  raster_variant_key(c->plan[0], c->plan_programs[0]) == raster_variant_key(cmds[0]->plan[0], cmds[0]->plan_programs[0]) &&
+        batched = c->plan.size() == 1 && variant_of(c).batched_form && c->lane == cmds[0]->lane && variant_of(c) == variant_of(cmds[0]) &&
                   c->plan_programs[0] == cmds[0]->plan_programs[0] && !c->plan[0].color_load && !c->plan[0].depth_load;
         for (uint32_t j = 0; batched && j < i; j++) {
             const PassParams& A = cmds[j]->plan[0]; const PassParams& B = c->plan[0];
@@ -2845,11 +2843,6 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             hsa_signal_store_relaxed(fence->native_sig, 0);
         }
         fence->native_wait = true;
-        fence->pending = true; fence->signaled = false;
-        fence->cmds.assign(cmds, cmds + cmd_count);
-        fence->seqs.resize(cmd_count);
-        for (uint32_t i = 0; i < cmd_count; i++) fence->seqs[i] = cmds[i]->submit_seq;
-        fence->deferred = MIRHI_OK; fence->deferred_msg.clear();
     } else if (fence) {
         if (!fence_attached) {
             // the fence follows the last command buffer's lane and waits for the other lanes used by this submit
@@ -2864,6 +2857,8 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             }
             HIP_TRY(hipEventRecord(fence->event, fstream));
         }
+    }
+    if (fence) {
         fence->pending = true; fence->signaled = false;
         fence->cmds.assign(cmds, cmds + cmd_count);
         fence->seqs.resize(cmd_count);

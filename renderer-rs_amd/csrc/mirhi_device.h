@@ -10,6 +10,7 @@
 //                spilled from a full bin / an exhausted pool; every raster workgroup scans this list
 //   counters     bin_count[tiles], pool_next, big_count, status words
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace mirhi {

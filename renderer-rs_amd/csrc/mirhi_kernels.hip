@@ -19,11 +19,13 @@
 // compiled with -ffp-contract=off so results are bit-identical to the CPU oracle.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <cstdio>
 #include <cstdlib>
 #include <stdint.h>
 
 #include "mirhi_device.h"
 #include "mirhi_launch.h"
+#include "mirhi_variant.h"
 
 namespace mirhi {
 
@@ -97,88 +99,50 @@ hipError_t launch_geometry(const PassParams& P, const PassParams* dev_params, hi
     return launch_result();
 }
 
-template <int KEYED, int TP, int TEAMS = 1>
-static void launch_raster_k(const PassParams* P, const RasterHead& H, uint32_t programs, dim3 grid, hipStream_t stream, LaunchTiming t, bool masked = false) {
-    const dim3 block(RASTER_THREADS * TEAMS);
-    if constexpr (TP != 0) {    // alpha-masked scope (host: PassParams::alpha_scope, always with the triangle-parallel path and a PBR draw)
-        if (masked) {
-            MIRHI_LAUNCH((raster_kernel<4, KEYED, TP, TEAMS, true>), grid, block, stream, t, P, H);
-            return;
-        }
-    }
-    if (TEAMS > 1) {            // only the pure mesh variants exist with two teams (launch_raster checks)
-        if (programs == 2) MIRHI_LAUNCH((raster_kernel<2, KEYED, TP, TEAMS>), grid, block, stream, t, P, H);
-        else MIRHI_LAUNCH((raster_kernel<4, KEYED, TP, TEAMS>), grid, block, stream, t, P, H);
-        return;
-    }
-    if (programs == 2) MIRHI_LAUNCH((raster_kernel<2, KEYED, TP>), grid, block, stream, t, P, H);
-    else if (programs == 3) MIRHI_LAUNCH((raster_kernel<3, KEYED, TP>), grid, block, stream, t, P, H);
-    else if (programs >= 4) MIRHI_LAUNCH((raster_kernel<4, KEYED, TP>), grid, block, stream, t, P, H);
-    else MIRHI_LAUNCH((raster_kernel<1, KEYED, TP>), grid, block, stream, t, P, H);
+// ---- the raster launch: raster_variant (mirhi_variant.h) chooses, the two tables below turn the choice into a kernel entry --------
+// Each table names every instantiation of its kernels exactly once (nothing else in this file refers to them): the set of raster kernels in the code object
+// is the set of rows, and the code object holds them in the order of the rows.
+struct RasterEntry { uint32_t id; const char* name; void (*kernel)(const PassParams*, const RasterHead); };      // id: RasterVariant::kernel_id
+#define ORDERED(P) {raster_kernel_id(RASTER_ORDERED, P, 0, 0, 1, 0, 4), "ordered_kernel<" #P ">", ordered_kernel<P>}
+#define OWN(FAMILY, KERNEL, K, T) {raster_kernel_id(FAMILY, 0, K, T, 1, 0, 4), #KERNEL "<" #K ", " #T ">", KERNEL<K, T>}
+#define WIDE(P, K, W) {raster_kernel_id(RASTER_WIDE, P, K, 1, 1, 0, W), "raster_kernel_wide<" #P ", " #K ", " #W ">", raster_kernel_wide<P, K, W>}
+#define PLAIN(P, K, T, TEAMS, M) {raster_kernel_id(RASTER_PLAIN, P, K, T, TEAMS, M, 4 * TEAMS), "raster_kernel<" #P ", " #K ", " #T ", " #TEAMS ", " #M ">", raster_kernel<P, K, T, TEAMS, M>}
+static const RasterEntry k_raster_entries[] = {
+    ORDERED(2), ORDERED(3), ORDERED(4), ORDERED(1),
+    OWN(RASTER_DEPTH, raster_kernel_depth, 0, 1), OWN(RASTER_DEPTH, raster_kernel_depth, 1, 1), OWN(RASTER_DEPTH, raster_kernel_depth, 0, 0), OWN(RASTER_DEPTH, raster_kernel_depth, 1, 0),
+    OWN(RASTER_CSM, raster_kernel_csm, 0, 1), OWN(RASTER_CSM, raster_kernel_csm, 1, 1), OWN(RASTER_CSM, raster_kernel_csm, 0, 0), OWN(RASTER_CSM, raster_kernel_csm, 1, 0),
+    OWN(RASTER_SHADOW, raster_kernel_shadow, 0, 1), OWN(RASTER_SHADOW, raster_kernel_shadow, 1, 1), OWN(RASTER_SHADOW, raster_kernel_shadow, 0, 0), OWN(RASTER_SHADOW, raster_kernel_shadow, 1, 0),
+    WIDE(2, 0, 16), WIDE(2, 0, 8), WIDE(2, 1, 16), WIDE(2, 1, 8), WIDE(4, 0, 16), WIDE(4, 0, 8), WIDE(4, 1, 16), WIDE(4, 1, 8),
+    // predicate mode: pixel-parallel only
+    PLAIN(2, 2, 0, 1, false), PLAIN(4, 2, 0, 1, false), PLAIN(3, 2, 0, 1, false), PLAIN(1, 2, 0, 1, false),
+    // with the triangle-parallel path: two teams (alpha-masked, mesh), one team; per key
+    PLAIN(4, 0, 1, 2, true), PLAIN(2, 0, 1, 2, false), PLAIN(4, 0, 1, 2, false), PLAIN(2, 0, 1, 1, false), PLAIN(3, 0, 1, 1, false), PLAIN(4, 0, 1, 1, false), PLAIN(1, 0, 1, 1, false),
+    PLAIN(4, 1, 1, 2, true), PLAIN(2, 1, 1, 2, false), PLAIN(4, 1, 1, 2, false), PLAIN(2, 1, 1, 1, false), PLAIN(3, 1, 1, 1, false), PLAIN(4, 1, 1, 1, false), PLAIN(1, 1, 1, 1, false),
+    PLAIN(4, 0, 1, 1, true), PLAIN(4, 1, 1, 1, true),
+    // pixel-parallel only
+    PLAIN(2, 0, 0, 1, false), PLAIN(4, 0, 0, 1, false), PLAIN(3, 0, 0, 1, false), PLAIN(1, 0, 0, 1, false),
+    PLAIN(2, 1, 0, 1, false), PLAIN(4, 1, 0, 1, false), PLAIN(3, 1, 0, 1, false), PLAIN(1, 1, 0, 1, false),
+};
+#undef ORDERED
+#undef OWN
+#undef WIDE
+#undef PLAIN
+static const RasterEntry* raster_entry(const RasterVariant& v) {
+    for (const RasterEntry& e : k_raster_entries) if (e.id == v.kernel_id()) return &e;
+    return nullptr;
 }
 
 hipError_t launch_raster(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, uint32_t programs, hipStream_t stream, LaunchTiming t, bool allow_wide) {
-    const uint32_t rows = P.tile_row_end - P.tile_row_begin;
-    if (rows == 0 || P.tiles_x == 0) return hipSuccess;
-    if (P.ordered_recs) {           // ordered segment: fragments in primitive order (blending)
-        const RasterHead HO = {P.bin_count, P.bin_pool, big_count, P.tiles_x, P.tile_row_begin, P.bin_cap, P.big_cap, P.bin_cap, 0u, 0u, P.tile_row_step};
-        const dim3 og(P.tiles_x, rows), ob(ORDERED_THREADS);
-        if (programs == 2) MIRHI_LAUNCH(ordered_kernel<2>, og, ob, stream, t, dev_params, HO);
-        else if (programs == 3) MIRHI_LAUNCH(ordered_kernel<3>, og, ob, stream, t, dev_params, HO);
-        else if (programs >= 4) MIRHI_LAUNCH(ordered_kernel<4>, og, ob, stream, t, dev_params, HO);
-        else MIRHI_LAUNCH(ordered_kernel<1>, og, ob, stream, t, dev_params, HO);
-        return launch_result();
-    }
-    const dim3 grid = P.xcd_swizzle > 1u ? dim3(P.tiles_x * rows) : dim3(P.tiles_x, rows);
-    // the plain key (raw float bits) serves LESS / LESS_OR_EQUAL; everything else takes the generic key
-    const bool plain = P.zflip == 0u && P.zmask == 0xFFFFFFFFu;
-    const RasterHead H = {P.bin_count, P.bin_pool, big_count, P.tiles_x, P.tile_row_begin, P.bin_cap, P.big_cap, P.sub_cap, P.count_stride, P.fixed_recs, P.tile_row_step};
-    // depth-only scopes (programs 0) and scopes with a shadowed draw (bit 8) have variants of their own, whatever the selectors below would pick (the
-    // host keeps them on one team of four waves, single-list bins and the plain tile order; their key is an ordered one, never a predicate)
-    if (programs == 0u || (programs & 8u)) {
-        const dim3 block(RASTER_THREADS);
-        if (programs == 0u) {
-            if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_depth<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_depth<1, 1>), grid, block, stream, t, dev_params, H); }
-            else { if (plain) MIRHI_LAUNCH((raster_kernel_depth<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_depth<1, 0>), grid, block, stream, t, dev_params, H); }
-        } else if (programs & 16u) {        // a cascaded draw (PassParams::shadowed = 2)
-            if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_csm<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_csm<1, 1>), grid, block, stream, t, dev_params, H); }
-            else { if (plain) MIRHI_LAUNCH((raster_kernel_csm<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_csm<1, 0>), grid, block, stream, t, dev_params, H); }
-        } else {
-            if (P.tp_max_area) { if (plain) MIRHI_LAUNCH((raster_kernel_shadow<0, 1>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_shadow<1, 1>), grid, block, stream, t, dev_params, H); }
-            else { if (plain) MIRHI_LAUNCH((raster_kernel_shadow<0, 0>), grid, block, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_shadow<1, 0>), grid, block, stream, t, dev_params, H); }
-        }
-        return launch_result();
-    }
-    if (P.raster_wide && allow_wide && !P.pred && P.tp_max_area && !P.alpha_scope && (programs == 2 || programs >= 4) && P.xcd_swizzle <= 1u) {
-        // the wide mesh variants: eight or sixteen waves per tile (host-side choice, PassParams::raster_wide = waves per tile)
-        const bool w16 = P.raster_wide >= 16u;
-        const dim3 wb(w16 ? 1024 : 512);
-#define MIRHI_WIDE(PR, KE) do { if (w16) MIRHI_LAUNCH((raster_kernel_wide<PR, KE, 16>), grid, wb, stream, t, dev_params, H); else MIRHI_LAUNCH((raster_kernel_wide<PR, KE, 8>), grid, wb, stream, t, dev_params, H); } while (0)
-        if (programs == 2) { if (plain) MIRHI_WIDE(2, 0); else MIRHI_WIDE(2, 1); }
-        else { if (plain) MIRHI_WIDE(4, 0); else MIRHI_WIDE(4, 1); }
-#undef MIRHI_WIDE
-    }
-    else if (P.pred) launch_raster_k<2, 0>(dev_params, H, programs, grid, stream, t);          // (the host keeps tp_max_area = 0 for predicate scopes)
-    else if (P.tp_max_area && P.raster_teams == 2u && (programs == 2 || programs >= 4)) {
-        if (plain) launch_raster_k<0, 1, 2>(dev_params, H, programs, grid, stream, t, P.alpha_scope != 0u); else launch_raster_k<1, 1, 2>(dev_params, H, programs, grid, stream, t, P.alpha_scope != 0u);
-    }
-    else if (P.tp_max_area) { if (plain) launch_raster_k<0, 1>(dev_params, H, programs, grid, stream, t, P.alpha_scope != 0u); else launch_raster_k<1, 1>(dev_params, H, programs, grid, stream, t, P.alpha_scope != 0u); }
-    else { if (plain) launch_raster_k<0, 0>(dev_params, H, programs, grid, stream, t); else launch_raster_k<1, 0>(dev_params, H, programs, grid, stream, t); }
+    if (P.tile_row_end == P.tile_row_begin || P.tiles_x == 0) return hipSuccess;
+    const RasterVariant v = raster_variant(P, programs, allow_wide);
+    const RasterHead H = v.family == RASTER_ORDERED ? ordered_head(P, big_count) : raster_head(P, big_count);
+    const RasterEntry* e = raster_entry(v);
+    if (!e) return hipErrorInvalidDeviceFunction;       // (a variant without a kernel: the selector and the table disagree)
+    MIRHI_LAUNCH(e->kernel, dim3(v.grid[0], v.grid[1], v.grid[2]), dim3(v.block), stream, t, dev_params, H);
     return launch_result();
 }
 
 // ---- batched launches --------------------------------------------------------------------------------------------
-uint64_t raster_variant_key(const PassParams& P, uint32_t programs) {
-    const bool plain = P.zflip == 0u && P.zmask == 0xFFFFFFFFu;
-    const uint32_t keyed = P.pred ? 2u : (plain ? 0u : 1u);
-    const uint32_t tp = (!P.pred && P.tp_max_area) ? 1u : 0u;
-    const uint32_t teams = (tp && P.raster_teams == 2u && (programs == 2 || programs >= 4)) ? 2u : 1u;
-    const uint32_t prog = programs >= 4 ? 4u : programs;
-    return (uint64_t)prog | ((uint64_t)keyed << 4) | ((uint64_t)tp << 8) | ((uint64_t)teams << 12) | ((uint64_t)(P.xcd_swizzle > 1u ? 1u : 0u) << 16) |
-           ((uint64_t)P.tiles_x << 20) | ((uint64_t)(P.tile_row_end - P.tile_row_begin) << 36) | ((uint64_t)(P.ordered_recs ? 1u : 0u) << 52) |
-           ((uint64_t)(P.raster_wide >> 3) << 53);
-}
-
 hipError_t launch_vertex_batch(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream) {
     GeometryBatch B{};
     uint32_t most = 0;
@@ -203,48 +167,38 @@ hipError_t launch_geometry_batch(const PassParams* const* P, const PassParams* c
     return launch_result();
 }
 
-template <int KEYED, int TP, int TEAMS = 1>
-static void launch_raster_batch_k(const RasterBatch& B, uint32_t programs, dim3 grid, hipStream_t stream, LaunchTiming t) {
-    const dim3 block(RASTER_THREADS * TEAMS);
-    if (TEAMS > 1) {
-        if (programs == 2) MIRHI_LAUNCH((raster_kernel_batch<2, KEYED, TP, TEAMS>), grid, block, stream, t, B);
-        else MIRHI_LAUNCH((raster_kernel_batch<4, KEYED, TP, TEAMS>), grid, block, stream, t, B);
-        return;
-    }
-    if (programs == 2) MIRHI_LAUNCH((raster_kernel_batch<2, KEYED, TP>), grid, block, stream, t, B);
-    else if (programs == 3) MIRHI_LAUNCH((raster_kernel_batch<3, KEYED, TP>), grid, block, stream, t, B);
-    else if (programs >= 4) MIRHI_LAUNCH((raster_kernel_batch<4, KEYED, TP>), grid, block, stream, t, B);
-    else MIRHI_LAUNCH((raster_kernel_batch<1, KEYED, TP>), grid, block, stream, t, B);
+// only the variants a frame loop meets are instantiated in batched form (RasterVariant::batched_form); all of them take the plain key
+struct RasterBatchEntry { uint32_t id; const char* name; void (*kernel)(const RasterBatch); };
+#define BATCH(P, T, TEAMS) {raster_kernel_id(RASTER_PLAIN, P, 0, T, TEAMS, 0, 4 * TEAMS), "raster_kernel_batch<" #P ", 0, " #T ", " #TEAMS ">", raster_kernel_batch<P, 0, T, TEAMS>}
+static const RasterBatchEntry k_raster_batch_entries[] = {
+    BATCH(2, 1, 2), BATCH(4, 1, 2), BATCH(2, 1, 1), BATCH(3, 1, 1), BATCH(4, 1, 1), BATCH(1, 1, 1), BATCH(2, 0, 1), BATCH(4, 0, 1), BATCH(3, 0, 1), BATCH(1, 0, 1),
+};
+#undef BATCH
+// the batched instantiation of a variant, or nullptr where none exists
+static const RasterBatchEntry* raster_batch_entry(const RasterVariant& v) {
+    if (!v.batched_form) return nullptr;
+    for (const RasterBatchEntry& e : k_raster_batch_entries) if (e.id == v.kernel_id()) return &e;
+    return nullptr;
 }
 
+// the scopes are of one variant (mirhi_queue_submit checks): the first one's
 hipError_t launch_raster_batch(const PassParams* const* Ps, const PassParams* const* dev_params, uint32_t* const* big_count, uint32_t n, uint32_t programs, hipStream_t stream, hipEvent_t stop) {
     LaunchTiming t{}; t.stop = stop;
     const PassParams& P = *Ps[0];
-    const uint32_t rows = P.tile_row_end - P.tile_row_begin;
-    if (rows == 0 || P.tiles_x == 0) return hipSuccess;
+    if (P.tile_row_end == P.tile_row_begin || P.tiles_x == 0) return hipSuccess;
+    const RasterVariant v = raster_variant(P, programs, true);
+    const RasterBatchEntry* e = raster_batch_entry(v);
+    if (!e) return hipErrorInvalidDeviceFunction;
     RasterBatch B{};
-    for (uint32_t i = 0; i < n; i++) {
-        const PassParams& Q = *Ps[i];
-        B.params[i] = dev_params[i];
-        B.head[i] = RasterHead{Q.bin_count, Q.bin_pool, big_count[i], Q.tiles_x, Q.tile_row_begin, Q.bin_cap, Q.big_cap, Q.sub_cap, Q.count_stride, Q.fixed_recs, Q.tile_row_step};
-    }
-    const dim3 grid(P.tiles_x, rows, n);           // (the XCD run-length order of a 1-D grid is a measurement knob: such scopes are not batched)
-    const bool plain = P.zflip == 0u && P.zmask == 0xFFFFFFFFu;
-    // only the variants a frame loop meets are instantiated in batched form: LESS / LESS_OR_EQUAL keys, with and without the
-    // triangle-parallel path and the two-team mesh mode; everything else goes scope by scope (mirhi_queue_submit checks)
-    if (P.tp_max_area && P.raster_teams == 2u && (programs == 2 || programs >= 4)) launch_raster_batch_k<0, 1, 2>(B, programs, grid, stream, t);
-    else if (P.tp_max_area) launch_raster_batch_k<0, 1>(B, programs, grid, stream, t);
-    else launch_raster_batch_k<0, 0>(B, programs, grid, stream, t);
-    (void)plain;
+    for (uint32_t i = 0; i < n; i++) { B.params[i] = dev_params[i]; B.head[i] = raster_head(*Ps[i], big_count[i]); }
+    MIRHI_LAUNCH(e->kernel, dim3(v.grid[0], v.grid[1], n), dim3(v.block), stream, t, B);
     return launch_result();
 }
-bool raster_batchable(const PassParams& P) { return !P.depth_only && !P.shadowed && !P.pred && P.zflip == 0u && P.zmask == 0xFFFFFFFFu && P.xcd_swizzle <= 1u && !P.ordered_recs && !P.alpha_scope && !P.raster_wide; }
 
 hipError_t launch_fragment_count(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, hipStream_t stream, LaunchTiming t) {
     const uint32_t rows = P.tile_row_end - P.tile_row_begin;
     if (rows == 0 || P.tiles_x == 0 || P.ordered_recs || P.depth_only) return hipSuccess;
-    const RasterHead H = {P.bin_count, P.bin_pool, big_count, P.tiles_x, P.tile_row_begin, P.bin_cap, P.big_cap, P.sub_cap, P.count_stride, P.fixed_recs, P.tile_row_step};
-    MIRHI_LAUNCH(fragment_count_kernel, dim3(P.tiles_x, rows), dim3(RASTER_THREADS), stream, t, dev_params, H);
+    MIRHI_LAUNCH(fragment_count_kernel, dim3(P.tiles_x, rows), dim3(RASTER_THREADS), stream, t, dev_params, raster_head(P, big_count));
     return launch_result();
 }
 
@@ -253,6 +207,24 @@ hipError_t launch_winner_count(const uint32_t* prim, uint32_t pixels, unsigned l
     const uint32_t blocks = (pixels + RASTER_THREADS * 16u - 1u) / (RASTER_THREADS * 16u);
     hipLaunchKernelGGL(winner_count_kernel, dim3(blocks), dim3(RASTER_THREADS), 0, stream, prim, pixels, stats);
     return launch_result();
+}
+
+// Outside the C ABI (not in include/mirhi.h) and without a HIP call: the kernel, grid and block that launch_raster -- with n_batch >= 2: launch_raster_batch
+// of that many scopes -- chooses for a scope of 5 x 4 tiles.  in: programs, allow_wide, then PassParams::pred, zflip, zmask, tp_max_area, raster_teams,
+// raster_wide, alpha_scope, xcd_swizzle, "ordered_recs is set", n_batch (0 = single launch).  Returns 1 where no batched form exists.
+extern "C" int mirhi_debug_raster_choice(const uint32_t in[12], char* name, uint32_t name_len, uint32_t grid_block[4]) {
+    static TriRec some_recs;
+    PassParams P{};
+    P.tiles_x = 5u; P.tile_row_begin = 0u; P.tile_row_end = 4u; P.tile_row_step = 1u;
+    P.pred = in[2]; P.zflip = in[3]; P.zmask = in[4]; P.tp_max_area = in[5]; P.raster_teams = in[6]; P.raster_wide = in[7]; P.alpha_scope = in[8]; P.xcd_swizzle = in[9];
+    P.ordered_recs = in[10] ? &some_recs : nullptr;
+    const uint32_t n = in[11];
+    const RasterVariant v = raster_variant(P, in[0], n >= 2u || in[1] != 0u);
+    const RasterBatchEntry* b = n >= 2u ? raster_batch_entry(v) : nullptr;
+    if (n >= 2u && !b) return 1;
+    snprintf(name, name_len, "%s", b ? b->name : raster_entry(v)->name);
+    grid_block[0] = v.grid[0]; grid_block[1] = v.grid[1]; grid_block[2] = b ? n : v.grid[2]; grid_block[3] = v.block;
+    return 0;
 }
 
 #ifdef MIRHI_STAMPS

@@ -19,13 +19,11 @@ struct LaunchTiming { hipEvent_t start = nullptr, stop = nullptr; NativeQueue* n
 hipError_t launch_vertex(const PassParams& P, const PassParams* dev_params, hipStream_t stream, LaunchTiming t = {});      // no-op unless the scope uses MODEL programs
 hipError_t launch_geometry(const PassParams& P, const PassParams* dev_params, hipStream_t stream, LaunchTiming t = {});
 // big_count: the large-triangle counter of this submit's parity (dev_params carries the same pointer)
-// programs: bit0 TRIANGLE, bit1 MODEL / MODEL_FULL, bit2 MODEL_PBR
+// programs: the scope's program set, PROGS_* of mirhi_variant.h
 // allow_wide: false = the scope's plain / two-team variant even if its plan names a wide one (PassParams::raster_wide): the submit's choice
 hipError_t launch_raster(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, uint32_t programs, hipStream_t stream, LaunchTiming t = {}, bool allow_wide = true);
-// Batched forms: n (2 .. MAX_BATCH) independent scopes of equal target shape and equal kernel variants (raster_variant_key) in one
-// launch each; P[i] / dev_params[i] / big_count[i] as above, per scope.  Ordered (blended) scopes are never batched.
-bool raster_batchable(const PassParams& P);                                 // a variant that exists in batched form
-uint64_t raster_variant_key(const PassParams& P, uint32_t programs);        // equal keys <=> the same raster_kernel instantiation and grid
+// Batched forms: n (2 .. MAX_BATCH) independent scopes of equal target shape and equal kernel variants (raster_variant of mirhi_variant.h: equal
+// values with batched_form set) in one launch each; P[i] / dev_params[i] / big_count[i] as above, per scope.  Ordered (blended) scopes are never batched.
 hipError_t launch_vertex_batch(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream);
 hipError_t launch_geometry_batch(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream);
 hipError_t launch_raster_batch(const PassParams* const* P, const PassParams* const* dev_params, uint32_t* const* big_count, uint32_t n, uint32_t programs, hipStream_t stream,
