@@ -103,6 +103,12 @@ impl CommandBuffer {
         let (array, params) = cascades.map_or((std::ptr::null_mut(), std::ptr::null_mut()), |(a, b)| (a.raw, b.raw));
         check(unsafe { mirhi_sys::mirhi_cmd_bind_shadow_cascades(self.raw, array, params, offset, range) })
     }
+    /// Set 3 of pixel/model_pbr_ibl.hlsl:133-155: irradiance cube, prefiltered cube and BRDF LUT of `ShaderProgram::ModelPbrIbl` draws; `None` unbinds.
+    pub fn bind_ibl(&self, set: Option<(&Image, &Image, &Image)>) -> RhiResult<()> {
+        let n = std::ptr::null_mut();
+        let (irradiance, prefiltered, brdf_lut) = set.map_or((n, n, n), |(a, b, c)| (a.raw, b.raw, c.raw));
+        check(unsafe { mirhi_sys::mirhi_cmd_bind_ibl(self.raw, irradiance, prefiltered, brdf_lut) })
+    }
     pub fn set_viewport(&self, v: &Viewport) -> RhiResult<()> {                                                      // :522
         let raw = mirhi_sys::mirhi_viewport { x: v.x, y: v.y, width: v.width, height: v.height, min_depth: v.min_depth, max_depth: v.max_depth };
         check(unsafe { mirhi_sys::mirhi_cmd_set_viewport(self.raw, &raw) })

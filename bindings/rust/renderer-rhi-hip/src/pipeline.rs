@@ -23,7 +23,7 @@ pub enum BlendOp { Add = 0, Subtract = 1, ReverseSubtract = 2, Min = 3, Max = 4 
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ShaderStage { Vertex, Fragment }
 #[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)]
-pub enum ShaderProgram { Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4 }
+pub enum ShaderProgram { Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4, ModelPbrIbl = 5 }
 
 /// pipeline.rs:499-529
 #[derive(Clone, Copy, Debug)]
@@ -55,6 +55,7 @@ impl Shader {
         }
         let name = path.as_ref().file_name().and_then(|s| s.to_str()).unwrap_or("").to_ascii_lowercase();
         let program = if name.starts_with("triangle") { ShaderProgram::Triangle }
+                      else if name.starts_with("model_pbr_ibl") { ShaderProgram::ModelPbrIbl }
                       else if name.starts_with("model_pbr") { ShaderProgram::ModelPbr }
                       else if name.starts_with("shadow") { ShaderProgram::Shadow }
                       else if name.starts_with("model_full") { ShaderProgram::ModelFull }

@@ -33,7 +33,8 @@ extern "C" {
                                     pipelines (colour format UNDEFINED) and depth-only rendering scopes (color_image NULL);
                                     still 5 (new functions only): mirhi_image_create_array, mirhi_image_create_layer_view, mirhi_image_layers,
                                     mirhi_cmd_bind_shadow_cascades;
-                                    still 5 (new functions only): mirhi_image_create_cube and the five mirhi_ibl_ passes */
+                                    still 5 (new functions only): mirhi_image_create_cube and the five mirhi_ibl_ passes;
+                                    still 5 (one new enum value, one new function): MIRHI_PROGRAM_MODEL_PBR_IBL, mirhi_cmd_bind_ibl */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -188,7 +189,8 @@ mirhi_result mirhi_image_destroy(mirhi_image* img);
  * 6 * sum over k < l of (size >> k)^2.  mirhi_image_width / _height report the size, mirhi_image_layers 6, mirhi_image_mip_levels `levels`,
  * mirhi_image_size_bytes the whole chain, and mirhi_image_upload / _read move the whole chain.  A cube is no 2-D image and no array: it is refused
  * (InvalidHandle, the message says "cube") as a colour, depth or prim-id attachment, at every mirhi_texture_slot, by mirhi_cmd_bind_shadow_cascades,
- * mirhi_image_create_layer_view, mirhi_image_generate_mips and mirhi_image_set_max_anisotropy, and there is no wrapped cube.
+ * mirhi_image_create_layer_view, mirhi_image_generate_mips and mirhi_image_set_max_anisotropy, and there is no wrapped cube.  A frame samples cubes
+ * through mirhi_cmd_bind_ibl (MIRHI_PROGRAM_MODEL_PBR_IBL) and nowhere else.
  *
  * The sampler (the reference's sampler.rs is empty: this is the build's reading of `LinearSampler`).
  *   Cube lookup, TextureCube.SampleLevel(LinearSampler, dir, lod): face and (s, t) by the Vulkan specification's cube-map face selection table --
@@ -230,7 +232,7 @@ typedef enum {   /* replaces Shader::from_spirv_file (shader.rs:244-330): precom
     MIRHI_PROGRAM_MODEL_FULL = 2,   /* vertex/model.hlsl + pixel/model_full.hlsl + lights.hlsli */
     MIRHI_PROGRAM_MODEL_PBR = 3,    /* vertex/model.hlsl + pixel/model_pbr.hlsl + pbr.hlsli (Cook-Torrance GGX); the directional light is multiplied
                                        by CalculateShadow (shadow.hlsli:49-121, model_pbr.hlsl:238-251) when MIRHI_TEXTURE_SHADOW_MAP is bound, else shadow = 1 */
-    MIRHI_PROGRAM_SHADOW = 4        /* vertex/shadow.hlsl + pixel/shadow.hlsl: depth-only pass in light space.  Reads ShadowConstants (vertex/shadow.hlsl:7-11:
+    MIRHI_PROGRAM_SHADOW = 4,       /* vertex/shadow.hlsl + pixel/shadow.hlsl: depth-only pass in light space.  Reads ShadowConstants (vertex/shadow.hlsl:7-11:
                                        lightSpaceMatrix @0, model @64, 128 B) from the b0 slot MIRHI_SLOT_CAMERA; position only, attribute_offsets[0] = 0 of
                                        attribute_count 1, any vertex_stride >= 12 that is a multiple of 4 (a packed position stream or the 48-byte Vertex).
                                        Clip = lightSpaceMatrix * (model * p), in the MODEL vertex path's operation order (vertex/model.hlsl:44-48): a SHADOW
@@ -239,6 +241,10 @@ typedef enum {   /* replaces Shader::from_spirv_file (shader.rs:244-330): precom
                                        "no attachment at this location"), depth D32_SFLOAT with test and write on and LESS / LESS_OR_EQUAL / GREATER /
                                        GREATER_OR_EQUAL; no blending, no fragment discard.  SHADOW draws are recorded only in depth-only scopes
                                        (mirhi_rendering_info.color_image NULL) and only SHADOW draws there. */
+    MIRHI_PROGRAM_MODEL_PBR_IBL = 5 /* vertex/model.hlsl + pixel/model_pbr_ibl.hlsl: MODEL_PBR's vertex layout, uniform slots, five material textures and 80-byte
+                                       MaterialData, with the image-based ambient term of mirhi_cmd_bind_ibl (below) in place of the hemisphere ambient.  The
+                                       directional light's shadow term comes from what is bound, exactly as for MODEL_PBR: nothing = 1, MIRHI_TEXTURE_SHADOW_MAP =
+                                       CalculateShadow, mirhi_cmd_bind_shadow_cascades = CalculateShadowCSM (which is pixel/model_pbr_ibl_csm.hlsl). */
 } mirhi_program;
 typedef enum { MIRHI_TOPOLOGY_POINT_LIST = 0, MIRHI_TOPOLOGY_LINE_LIST = 1, MIRHI_TOPOLOGY_LINE_STRIP = 2,
                MIRHI_TOPOLOGY_TRIANGLE_LIST = 3, MIRHI_TOPOLOGY_TRIANGLE_STRIP = 4, MIRHI_TOPOLOGY_TRIANGLE_FAN = 5 } mirhi_topology;   /* pipeline.rs:274-300 */
@@ -371,6 +377,37 @@ mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slot slot, mir
  * refused (InvalidHandle), as are single-map and cascaded draws in one rendering scope; a cascaded draw's pipeline may not blend, discard fragments
  * or use a predicate depth state, and needs the depth test (its depth key is where SV_Position.z comes from). */
 mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range);
+/* The IBL set: descriptor set 3 of pixel/model_pbr_ibl.hlsl:133-155 (= model_pbr_ibl_csm.hlsl) -- TextureCube irradianceMap (t7), TextureCube prefilteredMap
+ * (t8), Texture2D<float4> brdfLUT (t9): what mirhi_ibl_irradiance, mirhi_ibl_prefilter and mirhi_ibl_brdf_lut make (or any upload of the same shape).  All three
+ * NULL unbinds the set; mirhi_cmd_begin* and mirhi_cmd_reset clear it, as they clear the cascades.  The set lives with the command buffer and is latched by
+ * MIRHI_PROGRAM_MODEL_PBR_IBL draws; draws of every other program ignore it (their frames keep their bits).  There is no texture slot for these images:
+ * MIRHI_TEXTURE_COUNT stays 6 and a cube stays refused at every mirhi_texture_slot.
+ *
+ * What a MODEL_PBR_IBL fragment computes -- the build's reading of the shader, with the sampler stated above ("IBL precompute", "The sampler"):
+ *   Front half, the three light loops and the shadow term: model_pbr_ibl.hlsl:205-346, line for line those of model_pbr.hlsl (same device code).
+ *   Ambient (:355-384).  ambient = (kD * irradiance * albedo + prefiltered * (F0 * brdf.x + brdf.y)) * ao with F0 = lerp(0.04, albedo, metallic) (:356),
+ *     NdotV = max(dot(N, V), 0) (:359), F = FresnelSchlickRoughness(NdotV, F0, roughness) = F0 + (max(1 - roughness, F0) - F0) * (1 - saturate(NdotV))^5
+ *     (:362, pbr.hlsli:147-152), kD = (1 - F) * (1 - metallic) (:365-366), R = reflect(-V, N) = 2 dot(N, V) N - V (:259), N = GetWorldNormal's result,
+ *     roughness taken after ClampRoughness (:262: max(roughness, 0.04)).
+ *   Final colour (:393-395).  color = ambient + Lo + emissive, alpha = baseColor.a.  There is no hemisphere ambient, and Lo is NOT multiplied by
+ *     lerp(1, ao, 0.5): that factor is model_pbr.hlsl's alone (model_pbr.hlsl:311).
+ *   irradianceMap.Sample(N) (:369) is the cube lookup at lod 0 (level 0 of `irradiance`; further levels are never read); .rgb is used.
+ *   prefilteredMap.SampleLevel(R, roughness * MAX_REFLECTION_LOD) (:373-377) is the cube lookup at lod = roughness * 7.0: MAX_REFLECTION_LOD = 7.0 stays
+ *     hard-coded (pbr.hlsli:373) whatever the cube's chain; the sampler clamps the lod to [0, levels - 1] as stated, so a 5-level cube saturates at
+ *     roughness 4/7 and an 8-level one uses its whole chain.
+ *   brdfLUT.Sample(float2(NdotV, roughness)) (:380) is bilinear at level 0 with clamp to edge on both axes -- the filter of one cube face applied to
+ *     the n x n image: x = NdotV n - 1/2 along a row, y = roughness n - 1/2 down the rows; only .rg is read.
+ *   Numerics: float32, not bit-exact -- the ambient term contracts and is bounded against the float64 model of renderer-rs_amd/ibl.py; Lo
+ *   keeps MODEL_PBR's exact sequences.  Where the two largest |components| of N or R tie, float32 may select another face than exact arithmetic, and the
+ *   stated sampler is not seamless there.
+ * Refused with InvalidHandle: `irradiance` or `prefiltered` that is no cube; a `brdf_lut` that is a cube, an array (or layer view), not square or not
+ * R32G32B32A32_SFLOAT; some arguments NULL but not all; images of two devices or of another device than `cmd`.  At the draw: a MODEL_PBR_IBL draw with no
+ * IBL set bound; with blending, fragment discard or a predicate depth state (the rule of the shadowed variants); a rendering scope whose MODEL_PBR_IBL
+ * draws were recorded under two different sets (unsupported: the set is per scope); the single-map / cascades rules of MODEL_PBR apply unchanged.
+ * `discard` below alphaCutoff (:216-220) is decided per draw as for MODEL_PBR; a draw that would need it per fragment is reported at the fence ("alpha cutoff").
+ * The images are ordered across queue lanes like shadow maps a scope samples; the mirhi_ibl_ passes wait for every lane, so a pass on a bound image never
+ * overlaps a frame that samples it. */
+mirhi_result mirhi_cmd_bind_ibl(mirhi_cmd* cmd, mirhi_image* irradiance, mirhi_image* prefiltered, mirhi_image* brdf_lut);
 mirhi_result mirhi_cmd_set_viewport(mirhi_cmd* cmd, const mirhi_viewport* viewport);  /* set_viewport :522 */
 mirhi_result mirhi_cmd_set_scissor(mirhi_cmd* cmd, const mirhi_rect2d* scissor);      /* set_scissor :549 */
 /* instance_count > 1 (at most 4096): the path has no instance-rate input (binding 0 is per-vertex, vertex.rs:35-41,130-136; no program

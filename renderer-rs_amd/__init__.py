@@ -38,7 +38,7 @@ class Format:
 
 
 class Program:
-    NONE, TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR, SHADOW = -1, 0, 1, 2, 3, 4
+    NONE, TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR, SHADOW, MODEL_PBR_IBL = -1, 0, 1, 2, 3, 4, 5
 
 
 class PrimitiveTopology:  # pipeline.rs:274-282
@@ -245,6 +245,7 @@ _SIGNATURES = {
     "mirhi_cmd_bind_uniform": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64]),
     "mirhi_cmd_bind_texture": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mirhi_cmd_bind_shadow_cascades": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mirhi_cmd_bind_ibl": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mirhi_cmd_set_viewport": (C.c_int32, [C.c_void_p, C.POINTER(Viewport)]),
     "mirhi_cmd_set_scissor": (C.c_int32, [C.c_void_p, C.POINTER(Rect2D)]),
     "mirhi_cmd_draw": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -751,6 +752,10 @@ class CommandBuffer:
         """mirhi_cmd_bind_shadow_cascades: the four-layer D32 array and its CSMParams (scenes.csm_ubo); array=None unbinds."""
         check(lib().mirhi_cmd_bind_shadow_cascades(self.handle, array.handle if array else None, params.handle if params else None, offset, range_))
 
+    def bind_ibl(self, irradiance: Optional[Image], prefiltered: Optional[Image] = None, brdf_lut: Optional[Image] = None):
+        """mirhi_cmd_bind_ibl: the irradiance cube, the prefiltered cube and the BRDF LUT Program.MODEL_PBR_IBL draws sample; all None unbinds."""
+        check(lib().mirhi_cmd_bind_ibl(self.handle, *(i.handle if i is not None else None for i in (irradiance, prefiltered, brdf_lut))))
+
     def set_viewport(self, x, y, width, height, min_depth=0.0, max_depth=1.0):
         vp = Viewport(x, y, width, height, min_depth, max_depth)
         check(lib().mirhi_cmd_set_viewport(self.handle, C.byref(vp)))
@@ -848,13 +853,16 @@ class SceneResources:
     def __init__(self, device: Device, scene, color_format: int = Format.R32G32B32A32_SFLOAT, want_prim: bool = False,
                  want_depth: bool = False, color_image: Optional[Image] = None, wrap_buffers=None,
                  color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None,
-                 cascade_array: Optional[Image] = None):
+                 cascade_array: Optional[Image] = None, ibl_images: Optional[Sequence[Image]] = None):
         """scene.shadow (scenes.ShadowSpec) adds a depth-only shadow scope ahead of the main scope: recorded into the same command
         buffer, or with shadow_cmd=True into a command buffer of its own (self.shadow_cmd; render() submits both, the shadow one first --
         put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames).
         scene.cascades (scenes.CascadeSpec): four depth-only scopes instead, one per layer view of a D32 array (self.cascade_array, or the
         existing one passed as cascade_array=), in the same command buffer or with shadow_cmd=True in self.shadow_cmd; the MODEL_PBR draws
-        sample the array through bind_shadow_cascades."""
+        sample the array through bind_shadow_cascades.
+        scene.ibl (scenes.IblSpec): the IBL set bound for the scene's MODEL_PBR_IBL draws -- the spec's own images, images created here from its
+        arrays and uploaded (self.ibl_images, destroyed with the resources), or the existing three passed as ibl_images= (irradiance cube,
+        prefiltered cube, BRDF LUT; shared between frames, the caller's to destroy)."""
         self.device, self.scene = device, scene
         self.color_load_op = color_load_op
         self.owns_color = color_image is None
@@ -970,6 +978,13 @@ class SceneResources:
                 self.cascade_state.append(states)
             if shadow_cmd:
                 self.shadow_cmd = CommandBuffer(device)
+        self.ibl, self.ibl_images, self.owns_ibl = getattr(scene, "ibl", None), None, False
+        if ibl_images is not None:
+            self.ibl_images = tuple(ibl_images)
+        elif self.ibl is not None and self.ibl.images is not None:
+            self.ibl_images = tuple(self.ibl.images)
+        elif self.ibl is not None:
+            self.ibl_images, self.owns_ibl = self.ibl.create_images(device, Image, Format.R32G32B32A32_SFLOAT), True
         self.record()
 
     def _record_shadow(self, cmd: "CommandBuffer"):
@@ -1023,12 +1038,16 @@ class SceneResources:
             for slot, img in enumerate(st["textures"]):
                 if img is not None or slot < 2:
                     cmd.bind_texture(slot, img)
-            if self.shadow is not None and d.program == scenes.PROGRAM_MODEL_PBR:
+            pbr = d.program in (scenes.PROGRAM_MODEL_PBR, scenes.PROGRAM_MODEL_PBR_IBL)     # the Cook-Torrance programs take the same shadow bindings
+            if d.program == scenes.PROGRAM_MODEL_PBR_IBL:
+                assert self.ibl_images is not None, "a MODEL_PBR_IBL draw needs scene.ibl or ibl_images="
+                cmd.bind_ibl(*self.ibl_images)
+            if self.shadow is not None and pbr:
                 cmd.bind_uniform(Slot.SHADOW_DATA, self.shadow_data)
                 cmd.bind_texture(TextureSlot.SHADOW_MAP, self.shadow_map)
             elif self.shadow is not None:
                 cmd.bind_texture(TextureSlot.SHADOW_MAP, None)
-            if self.cascades is not None and d.program == scenes.PROGRAM_MODEL_PBR:
+            if self.cascades is not None and pbr:
                 cmd.bind_shadow_cascades(self.cascade_array, self.cascade_params)
             elif self.cascades is not None:
                 cmd.bind_shadow_cascades(None)
@@ -1063,6 +1082,9 @@ class SceneResources:
             v.destroy()
         if self.owns_cascade_array:
             self.cascade_array.destroy()
+        if self.owns_ibl:
+            for img in self.ibl_images:
+                img.destroy()
         for o in self.objs:
             o.destroy()
         for o in (self.prim, self.depth, self.color):

@@ -522,6 +522,15 @@ struct RecordedPass {
     int32_t area[4] = {0, 0, 0, 0};
     bool depth_only = false;               // color_image NULL: SHADOW draws into the depth image (raster_kernel_depth)
     std::vector<mirhi_image*> sampled;     // shadow maps the scope's draws sample (MIRHI_TEXTURE_SHADOW_MAP): ordered like attachments
+    // the IBL set the scope's MODEL_PBR_IBL draws were recorded under (mirhi_cmd_bind_ibl; one per scope, all its segments): resolved like the targets
+    struct IblSet {
+        const uint8_t* irradiance = nullptr; const uint8_t* prefiltered = nullptr; const uint8_t* lut = nullptr;
+        uint32_t irr_size = 0, pre_size = 0, pre_levels = 0, lut_size = 0;
+        bool operator==(const IblSet& o) const {
+            return irradiance == o.irradiance && prefiltered == o.prefiltered && lut == o.lut && irr_size == o.irr_size && pre_size == o.pre_size &&
+                   pre_levels == o.pre_levels && lut_size == o.lut_size;
+        }
+    } ibl;
 };
 
 // Words of the counter block that never move (a re-recorded frame of another shape finds them where the last frame's kernels
@@ -608,6 +617,7 @@ struct mirhi_cmd {
     mirhi_image* textures[MIRHI_TEXTURE_COUNT] = {};
     mirhi_image* cascades = nullptr;       // mirhi_cmd_bind_shadow_cascades: the D32 array (t10) ...
     struct { mirhi_buffer* buf; uint64_t offset, range; } cascade_params = {};      // ... and its CSMParams (b3 of set 2)
+    mirhi_image* ibl[3] = {};              // mirhi_cmd_bind_ibl: irradiance cube, prefiltered cube, BRDF LUT (set 3); all three or none
     bool has_viewport = false, has_scissor = false;
     uint8_t push_constants[128] = {0};     // vkCmdPushConstants: kept, read by no program on this path
     mirhi_viewport viewport{};
@@ -1310,7 +1320,7 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
     if (d->blend_attachment_count != 0 && d->blend_attachment_count != d->color_attachment_count)
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: Blend attachment count (%u) must match color attachment count (%u)", d->blend_attachment_count, d->color_attachment_count);
     // --- program selection replaces SPIR-V module creation (shader.rs:244-330) ---
-    if (d->vertex_program < 0 || d->vertex_program > MIRHI_PROGRAM_SHADOW || d->fragment_program < 0 || d->fragment_program > MIRHI_PROGRAM_SHADOW)
+    if (d->vertex_program < 0 || d->vertex_program > MIRHI_PROGRAM_MODEL_PBR_IBL || d->fragment_program < 0 || d->fragment_program > MIRHI_PROGRAM_MODEL_PBR_IBL)
         return fail(MIRHI_ERR_SHADER, "Shader error: unknown program id (vertex %d, fragment %d)", d->vertex_program, d->fragment_program);
     const bool vs_shadow = d->vertex_program == MIRHI_PROGRAM_SHADOW, fs_shadow = d->fragment_program == MIRHI_PROGRAM_SHADOW;
     const bool vs_model = d->vertex_program != MIRHI_PROGRAM_TRIANGLE, fs_model = d->fragment_program != MIRHI_PROGRAM_TRIANGLE;
@@ -1474,6 +1484,7 @@ static void reset_recording(mirhi_cmd* c) {
     for (auto& u : c->uniforms) u = {nullptr, 0, 0};
     for (auto& tx : c->textures) tx = nullptr;
     c->cascades = nullptr; c->cascade_params = {nullptr, 0, 0};
+    for (auto& im : c->ibl) im = nullptr;
     c->has_viewport = c->has_scissor = false;
 }
 static mirhi_result begin_common(mirhi_cmd* cmd, bool one_time) {
@@ -1597,7 +1608,7 @@ extern "C" mirhi_result mirhi_cmd_bind_uniform(mirhi_cmd* cmd, mirhi_uniform_slo
 extern "C" mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slot slot, mirhi_image* image) {
     REQUIRE_RECORDING(cmd);
     if ((int)slot < 0 || (int)slot >= MIRHI_TEXTURE_COUNT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unknown texture slot %d", (int)slot);
-    if (image && image->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image cannot be bound at a texture slot (no program samples one yet)");
+    if (image && image->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image cannot be bound at a texture slot (the IBL cubes are bound with mirhi_cmd_bind_ibl)");
     if (slot == MIRHI_TEXTURE_SHADOW_MAP) {       // t7 / s5 (model_pbr.hlsl:103-108): a depth image, sampled with the comparison sampler
         if (image && image->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow map must be D32_SFLOAT");
         if (image && image->is_array)
@@ -1627,6 +1638,24 @@ extern "C" mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_ima
                     (unsigned long long)offset, (unsigned long long)range, (unsigned long long)params->size);
     if (range < 336) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: CSMParams range %llu smaller than 336 bytes", (unsigned long long)range);
     cmd->cascades = array; cmd->cascade_params = {params, offset, range};
+    return MIRHI_OK;
+}
+// set 3 of pixel/model_pbr_ibl.hlsl:133-155: TextureCube irradianceMap (t7 / s5), TextureCube prefilteredMap (t8 / s6), Texture2D<float4> brdfLUT (t9 / s7)
+extern "C" mirhi_result mirhi_cmd_bind_ibl(mirhi_cmd* cmd, mirhi_image* irradiance, mirhi_image* prefiltered, mirhi_image* brdf_lut) {
+    REQUIRE_RECORDING(cmd);
+    if (!irradiance && !prefiltered && !brdf_lut) { for (auto& im : cmd->ibl) im = nullptr; return MIRHI_OK; }
+    if (!irradiance || !prefiltered || !brdf_lut)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the IBL set is three images (irradiance, prefiltered, BRDF LUT): all of them, or all NULL to unbind");
+    if (irradiance->dev != prefiltered->dev || irradiance->dev != brdf_lut->dev)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the IBL images belong to two devices");
+    if (irradiance->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the IBL images belong to another device than the command buffer");
+    if (!irradiance->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the irradiance map must be a cube image (mirhi_image_create_cube)");
+    if (!prefiltered->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the prefiltered map must be a cube image (mirhi_image_create_cube)");
+    if (brdf_lut->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the BRDF LUT must be a 2-D image, not a cube image");
+    if (brdf_lut->is_array || brdf_lut->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the BRDF LUT must be a 2-D image, not an image array or a layer view");
+    if (brdf_lut->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the BRDF LUT must be R32G32B32A32_SFLOAT");
+    if (brdf_lut->width != brdf_lut->height) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the BRDF LUT must be square (got %u x %u)", brdf_lut->width, brdf_lut->height);
+    cmd->ibl[0] = irradiance; cmd->ibl[1] = prefiltered; cmd->ibl[2] = brdf_lut;
     return MIRHI_OK;
 }
 extern "C" mirhi_result mirhi_cmd_set_viewport(mirhi_cmd* cmd, const mirhi_viewport* vp) {
@@ -1700,7 +1729,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
             prev.carry_out = true;
             next.info = prev.info;
             next.color_t = prev.color_t; next.depth_t = prev.depth_t; next.prim_t = prev.prim_t;
-            next.depth_only = prev.depth_only;
+            next.depth_only = prev.depth_only; next.ibl = prev.ibl;
             memcpy(next.area, prev.area, sizeof next.area);
             next.info.color_load_op = MIRHI_LOAD_OP_LOAD;
             next.carry_in = true;
@@ -1758,12 +1787,13 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         d.camera = (const float*)p;
         if ((r = uptr(MIRHI_SLOT_OBJECT, 128, &p, "ObjectData (b1)")) != MIRHI_OK) return r;
         d.object = (const float*)p;
-        if (d.program == MIRHI_PROGRAM_MODEL_FULL || d.program == MIRHI_PROGRAM_MODEL_PBR) {
+        const bool pbr = d.program == MIRHI_PROGRAM_MODEL_PBR || d.program == MIRHI_PROGRAM_MODEL_PBR_IBL;      // the Cook-Torrance programs: same slots, textures, shadow terms
+        if (d.program == MIRHI_PROGRAM_MODEL_FULL || pbr) {
             if ((r = uptr(MIRHI_SLOT_LIGHTS, 48, &d.lights, "LightUBO (b2)")) != MIRHI_OK) return r;
-            if ((r = uptr(MIRHI_SLOT_MATERIAL, d.program == MIRHI_PROGRAM_MODEL_PBR ? 80 : 32, &d.material, "MaterialData (b3)")) != MIRHI_OK) return r;
+            if ((r = uptr(MIRHI_SLOT_MATERIAL, pbr ? 80 : 32, &d.material, "MaterialData (b3)")) != MIRHI_OK) return r;
             if (cmd->uniforms[MIRHI_SLOT_POINT_LIGHTS].buf) d.point_lights = cmd->uniforms[MIRHI_SLOT_POINT_LIGHTS].buf->ptr + cmd->uniforms[MIRHI_SLOT_POINT_LIGHTS].offset;
             if (cmd->uniforms[MIRHI_SLOT_SPOT_LIGHTS].buf) d.spot_lights = cmd->uniforms[MIRHI_SLOT_SPOT_LIGHTS].buf->ptr + cmd->uniforms[MIRHI_SLOT_SPOT_LIGHTS].offset;
-            for (int t = 0; t < (d.program == MIRHI_PROGRAM_MODEL_PBR ? 5 : 2); t++)
+            for (int t = 0; t < (pbr ? 5 : 2); t++)
                 if (cmd->textures[t]) {
                     const mirhi_image* ti = cmd->textures[t];
                     d.tex[t] = ti->ptr; d.tex_w[t] = ti->width; d.tex_h[t] = ti->height; d.tex_levels[t] = ti->levels;
@@ -1771,7 +1801,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                     if (ti->levels > 1) d.tex_any_mips = 1;
                     if (ti->levels > 1) d.tex_aniso |= (ti->max_anisotropy - 1u) << (4 * t);
                 }
-            if (d.program == MIRHI_PROGRAM_MODEL_PBR && cmd->textures[MIRHI_TEXTURE_SHADOW_MAP]) {
+            if (pbr && cmd->textures[MIRHI_TEXTURE_SHADOW_MAP]) {
                 // CalculateShadow (model_pbr.hlsl:238-251): the map and its ShadowParams; the shadowed raster variant resolves ordered depth keys only
                 const mirhi_image* sm = cmd->textures[MIRHI_TEXTURE_SHADOW_MAP];
                 if ((r = uptr(MIRHI_SLOT_SHADOW_DATA, 96, &d.shadow_data, "ShadowParams (SHADOW_DATA)")) != MIRHI_OK) return r;
@@ -1783,7 +1813,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                 if (cmd->cascades)
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: both a shadow map (MIRHI_TEXTURE_SHADOW_MAP) and shadow cascades (mirhi_cmd_bind_shadow_cascades) are bound");
                 d.shadow_map = (const float*)sm->ptr; d.shadow_w = sm->width; d.shadow_h = sm->height;
-            } else if (d.program == MIRHI_PROGRAM_MODEL_PBR && cmd->cascades) {
+            } else if (pbr && cmd->cascades) {
                 // CalculateShadowCSM (model_pbr_ibl_csm.hlsl:280-298): the array and its CSMParams.  SV_Position.z is the depth the key holds, so the
                 // draw needs an ordered depth key (depth test and write with an ordering compare op)
                 const mirhi_image* ca = cmd->cascades;
@@ -1794,6 +1824,15 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: shadow cascades with blending, fragment discard, a predicate depth state or no depth test");
                 d.shadow_map = (const float*)ca->ptr; d.shadow_w = ca->width; d.shadow_h = ca->height; d.shadow_layers = ca->layers;
                 d.shadow_data = cmd->cascade_params.buf->ptr + cmd->cascade_params.offset;
+            }
+            if (d.program == MIRHI_PROGRAM_MODEL_PBR_IBL) {
+                // set 3 (mirhi_cmd_bind_ibl).  raster_kernel_ibl resolves ordered depth keys only, like the shadowed variants
+                if (!cmd->ibl[0]) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: program %d (MODEL_PBR_IBL) needs an IBL set bound (mirhi_cmd_bind_ibl)", pd.fragment_program);
+                const uint32_t op = pd.depth_compare_op;
+                const bool keyed = !pd.depth_test_enable || (pd.depth_write_enable && (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL ||
+                                                                                       op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL));
+                if (pd.blend_enable || pd.fragment_discard_enable || !keyed)
+                    return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: MODEL_PBR_IBL with blending, fragment discard or a predicate depth state");
             }
         }
     }
@@ -1811,6 +1850,17 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     d.sx0 = (int32_t)sx0; d.sy0 = (int32_t)sy0; d.sx1 = (int32_t)sx1; d.sy1 = (int32_t)sy1;
     d.scissor_partial = (sx0 > 0 || sy0 > 0 || sx1 < (int64_t)ci.width - 1 || sy1 < (int64_t)ci.height - 1) ? 1u : 0u;
     if (sx0 > sx1 || sy0 > sy1) return MIRHI_OK;    // empty scissor: nothing can be covered
+    if (d.program == MIRHI_PROGRAM_MODEL_PBR_IBL) {
+        // the set is per scope (PassParams): every MODEL_PBR_IBL draw of the scope, in all its segments, is recorded under the same three images
+        RecordedPass::IblSet set;
+        set.irradiance = cmd->ibl[0]->ptr; set.prefiltered = cmd->ibl[1]->ptr; set.lut = cmd->ibl[2]->ptr;
+        set.irr_size = cmd->ibl[0]->width; set.pre_size = cmd->ibl[1]->width; set.pre_levels = cmd->ibl[1]->levels; set.lut_size = cmd->ibl[2]->width;
+        if (pass.ibl.irradiance && !(pass.ibl == set))
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: MODEL_PBR_IBL draws recorded under two different IBL sets in one rendering scope");
+        pass.ibl = set;
+        for (mirhi_image* im : cmd->ibl)
+            if (std::find(pass.sampled.begin(), pass.sampled.end(), im) == pass.sampled.end()) pass.sampled.push_back(im);
+    }
     if (d.shadow_map) {
         // one raster variant per scope: CalculateShadow (raster_kernel_shadow) or CalculateShadowCSM (raster_kernel_csm)
         for (const DrawDesc& o : pass.draws)
@@ -1960,7 +2010,7 @@ struct RasterMode { uint32_t tp_max_area, teams; bool tri_prog; bool wide_eligib
 // waves per tile, single-list bins -- the team and wide selectors below leave them alone.
 static bool pass_is_depth_or_shadowed(const RecordedPass& pass) {
     if (pass.depth_only) return true;
-    for (const DrawDesc& dd : pass.draws) if (dd.shadow_map) return true;
+    for (const DrawDesc& dd : pass.draws) if (dd.shadow_map || dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL) return true;      // (raster_kernel_ibl: the same shape)
     return false;
 }
 // wide: what the command buffer's busy-tile feedback asks for (Workspace::wide: 0 / 8 / 16 waves per tile)
@@ -2021,7 +2071,7 @@ static bool same_recording(const std::vector<RecordedPass>& a, const std::vector
         if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || x.key_set != y.key_set || x.depth_test != y.depth_test || x.depth_compare != y.depth_compare ||
             x.depth_write != y.depth_write || x.frag_discard != y.frag_discard || memcmp(x.blend, y.blend, sizeof x.blend) != 0 ||
             x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
-        if (x.depth_only != y.depth_only || x.sampled != y.sampled) return false;
+        if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl)) return false;
         if (x.draws.size() != y.draws.size() || x.draw_vb_bytes != y.draw_vb_bytes) return false;
         if (!x.draws.empty() && memcmp(x.draws.data(), y.draws.data(), x.draws.size() * sizeof(DrawDesc)) != 0) return false;
     }
@@ -2440,7 +2490,12 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         P.xcd_swizzle = getenv("MIRHI_XCD_RUN") ? (uint32_t)atoi(getenv("MIRHI_XCD_RUN")) : 1u;
         P.depth_only = pass.depth_only ? 1u : 0u;
         for (const DrawDesc& dd : draws) P.shadowed |= dd.shadow_map ? (dd.shadow_layers ? 2u : 1u) : 0u;      // (never both in one scope: record_draw)
-        if (P.depth_only || P.shadowed) { P.xcd_swizzle = 1u; P.raster_wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
+        for (const DrawDesc& dd : draws) P.ibl |= dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL ? 1u : 0u;
+        if (P.ibl) {
+            P.ibl_irradiance = (const float*)pass.ibl.irradiance; P.ibl_prefiltered = (const float*)pass.ibl.prefiltered; P.ibl_lut = (const float*)pass.ibl.lut;
+            P.ibl_irr_size = pass.ibl.irr_size; P.ibl_pre_size = pass.ibl.pre_size; P.ibl_pre_levels = pass.ibl.pre_levels; P.ibl_lut_size = pass.ibl.lut_size;
+        }
+        if (P.depth_only || P.shadowed || P.ibl) { P.xcd_swizzle = 1u; P.raster_wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
         P.vs_jobs = dev_jobs + jobs_done;
         P.num_vs_jobs = (uint32_t)pass_jobs[pi].size();
         P.vs_total_slots = 0;
@@ -2462,8 +2517,9 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         cmd->plan.push_back(P);
         uint32_t progs = 0;         // the scope's program set (mirhi_variant.h)
         for (const DrawDesc& dd : draws)
-            progs |= dd.program == MIRHI_PROGRAM_TRIANGLE ? PROGS_TRIANGLE : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.tex_any_mips || dd.tex_srgb) ? PROGS_PBR : PROGS_MODEL);
+            progs |= dd.program == MIRHI_PROGRAM_TRIANGLE ? PROGS_TRIANGLE : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL || dd.tex_any_mips || dd.tex_srgb) ? PROGS_PBR : PROGS_MODEL);
         if (P.shadowed) progs = PROGS_PBR | PROGS_SHADOWED | (P.shadowed == 2u ? PROGS_CASCADED : 0u);
+        if (P.ibl) progs = PROGS_PBR | PROGS_IBL | (P.shadowed ? PROGS_SHADOWED : 0u) | (P.shadowed == 2u ? PROGS_CASCADED : 0u);
         cmd->plan_programs.push_back(P.depth_only ? PROGS_DEPTH_ONLY : (progs ? progs : PROGS_TRIANGLE));
         cmd->plan_tris += pass.total_tris - pass.first_tri;
         // the kernels read their parameters from the block: copy 2*pi + parity of scope pi appends large triangles to counter

@@ -200,6 +200,12 @@ struct PassParams {
                                       // ran a fragment program (winners of the depth resolve), [1] fragments covered before the depth test
     uint32_t depth_only;              // 1: a depth-only scope (SHADOW draws; color == nullptr): raster_kernel_depth stores the depth image and nothing else
     uint32_t shadowed;                // 1: some MODEL_PBR draw of the scope samples a shadow map (raster_kernel_shadow); 2: a cascade array (raster_kernel_csm)
+    // The IBL set of a scope with MODEL_PBR_IBL draws (mirhi_cmd_bind_ibl: set 3 of pixel/model_pbr_ibl.hlsl; one set per scope; raster_kernel_ibl alone
+    // reads these words): base of the irradiance cube (level 0 is sampled), of the prefiltered cube's chain and of the square BRDF LUT -- float4
+    // texels in the layouts of include/mirhi.h "IBL precompute" -- with their edge lengths and the prefiltered chain's level count.  0 / nullptr otherwise.
+    uint32_t ibl;                     // 1: some draw of the scope is MODEL_PBR_IBL
+    uint32_t ibl_irr_size, ibl_pre_size, ibl_pre_levels, ibl_lut_size, ibl_pad;
+    const float* ibl_irradiance; const float* ibl_prefiltered; const float* ibl_lut;
 };
 
 // Kernel arguments passed by value next to the PassParams pointer: what a wave needs before anything else, so that its

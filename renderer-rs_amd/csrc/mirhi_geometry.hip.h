@@ -566,7 +566,8 @@ __device__ __forceinline__ void geometry_body(const PassParams* __restrict__ par
     bool is_flat = true;
     const bool want_flat = EARLY_COLOUR && P.flat_color != nullptr && D.program == 0;      // (evaluated where it is used in the other allocation)
     bool dropped = false;
-    if (D.program == 3) {
+    if (D.program == 3 || D.program == 5) {
+        // (model_pbr_ibl.hlsl:216-220 has the same lines)
         // pixel/model_pbr.hlsl:174-178 `if (baseColor.a < alphaCutoff) discard;` decided per draw where one decision covers it: alpha is
         // baseColorFactor.a, or a texel alpha in [0,1] times it.  A draw whose texels could fall on both sides of the cutoff needs the
         // discard per fragment, before the depth write: fragment_discard_enable routes the draw to a scope that does that (alpha_scope:

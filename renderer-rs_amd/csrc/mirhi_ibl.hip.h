@@ -15,60 +15,8 @@
 
 #define IBL_PI 3.14159265359f          // the shaders' #define PI
 
-struct IblCube { const float4* texels; uint32_t size, levels; };
+#include "mirhi_ibl_sample.hip.h"      // IblCube, ibl_level_offset, ibl_select_face, ibl_bilinear, ibl_sample_cube
 
-__host__ __device__ inline uint32_t ibl_level_offset(uint32_t size, uint32_t level) {      // 6 * sum_{k < level} (size >> k)^2; size a power of two, size >> level >= 1
-    const uint32_t m = size >> level;
-    return 8u * (size * size - m * m);
-}
-__host__ __device__ inline uint32_t ibl_chain_texels(uint32_t size, uint32_t levels) {     // texels of a chain of `levels` >= 1 levels
-    const uint32_t m = size >> (levels - 1u);
-    return ibl_level_offset(size, levels - 1u) + 6u * m * m;
-}
-
-struct IblFaceUV { uint32_t face; float s, t; };
-// the Vulkan specification's cube-map face selection (major axis = largest magnitude, ties prefer z, then y, then x): the inverse of GetCubemapDirection
-__device__ inline IblFaceUV ibl_select_face(float x, float y, float z) {
-    #pragma clang fp contract(fast)
-    const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
-    IblFaceUV r; float sc, tc, ma;
-    if (az >= ax && az >= ay) { r.face = z < 0.0f ? 5u : 4u; sc = z < 0.0f ? -x : x; tc = -y; ma = az; }
-    else if (ay >= ax)        { r.face = y < 0.0f ? 3u : 2u; sc = x; tc = y < 0.0f ? -z : z; ma = ay; }
-    else                      { r.face = x < 0.0f ? 1u : 0u; sc = x < 0.0f ? z : -z; tc = -y; ma = ax; }
-    const float h = 0.5f * __builtin_amdgcn_rcpf(ma);
-    r.s = sc * h + 0.5f; r.t = tc * h + 0.5f;
-    return r;
-}
-__device__ inline float4 ibl_lerp4(float4 a, float4 b, float f) {
-    #pragma clang fp contract(fast)
-    return make_float4(a.x + (b.x - a.x) * f, a.y + (b.y - a.y) * f, a.z + (b.z - a.z) * f, a.w + (b.w - a.w) * f);
-}
-// bilinear inside one face of n x n texels, clamp to edge: x = s n - 1/2, floor, fraction, four clamped texels
-__device__ inline float4 ibl_bilinear(const float4* __restrict__ face, uint32_t n, float s, float t) {
-    #pragma clang fp contract(fast)
-    const float x = s * (float)n - 0.5f, y = t * (float)n - 0.5f;
-    const float x0 = floorf(x), y0 = floorf(y);
-    const int hi = (int)n - 1;
-    const int i0 = min(max((int)x0, 0), hi), i1 = min(max((int)x0 + 1, 0), hi);
-    const int j0 = min(max((int)y0, 0), hi), j1 = min(max((int)y0 + 1, 0), hi);
-    const float4 a = face[(uint32_t)j0 * n + (uint32_t)i0], b = face[(uint32_t)j0 * n + (uint32_t)i1];
-    const float4 c = face[(uint32_t)j1 * n + (uint32_t)i0], d = face[(uint32_t)j1 * n + (uint32_t)i1];
-    return ibl_lerp4(ibl_lerp4(a, b, x - x0), ibl_lerp4(c, d, x - x0), y - y0);
-}
-__device__ inline float4 ibl_sample_cube_level(const IblCube& c, uint32_t level, const IblFaceUV& f) {
-    const uint32_t n = c.size >> level;
-    return ibl_bilinear(c.texels + ibl_level_offset(c.size, level) + f.face * n * n, n, f.s, f.t);
-}
-// TextureCube.SampleLevel(LinearSampler, dir, lod): lod clamped to [0, levels - 1], levels floor(lod) and floor(lod) + 1 (clamped) lerped by the fraction
-__device__ inline float4 ibl_sample_cube(const IblCube& c, float x, float y, float z, float lod) {
-    const IblFaceUV f = ibl_select_face(x, y, z);
-    lod = fminf(fmaxf(lod, 0.0f), (float)(c.levels - 1u));
-    const float l0f = floorf(lod), frac = lod - l0f;
-    const uint32_t l0 = min((uint32_t)(int)l0f, c.levels - 1u);
-    float4 r = ibl_sample_cube_level(c, l0, f);
-    if (frac > 0.0f) r = ibl_lerp4(r, ibl_sample_cube_level(c, min(l0 + 1u, c.levels - 1u), f), frac);
-    return r;
-}
 // GetCubemapDirection (equirect_to_cubemap.hlsl:22-56) at the centre of texel (px, py) of an n x n face
 __device__ inline float3 ibl_texel_direction(uint32_t face, uint32_t px, uint32_t py, uint32_t n) {
     #pragma clang fp contract(fast)

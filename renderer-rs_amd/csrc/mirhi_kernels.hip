@@ -32,6 +32,7 @@ namespace mirhi {
 #include "mirhi_exact.hip.h"
 #include "mirhi_common.hip.h"
 #include "mirhi_geometry.hip.h"
+#include "mirhi_ibl_sample.hip.h"
 #include "mirhi_shading.hip.h"
 #include "mirhi_raster.hip.h"
 #include "mirhi_stats.hip.h"
@@ -105,6 +106,7 @@ hipError_t launch_geometry(const PassParams& P, const PassParams* dev_params, hi
 struct RasterEntry { uint32_t id; const char* name; void (*kernel)(const PassParams*, const RasterHead); };      // id: RasterVariant::kernel_id
 #define ORDERED(P) {raster_kernel_id(RASTER_ORDERED, P, 0, 0, 1, 0, 4), "ordered_kernel<" #P ">", ordered_kernel<P>}
 #define OWN(FAMILY, KERNEL, K, T) {raster_kernel_id(FAMILY, 0, K, T, 1, 0, 4), #KERNEL "<" #K ", " #T ">", KERNEL<K, T>}
+#define IBL(K, T, S) {raster_kernel_id(RASTER_IBL, S, K, T, 1, 0, 4), "raster_kernel_ibl<" #K ", " #T ", " #S ">", raster_kernel_ibl<K, T, S>}
 #define WIDE(P, K, W) {raster_kernel_id(RASTER_WIDE, P, K, 1, 1, 0, W), "raster_kernel_wide<" #P ", " #K ", " #W ">", raster_kernel_wide<P, K, W>}
 #define PLAIN(P, K, T, TEAMS, M) {raster_kernel_id(RASTER_PLAIN, P, K, T, TEAMS, M, 4 * TEAMS), "raster_kernel<" #P ", " #K ", " #T ", " #TEAMS ", " #M ">", raster_kernel<P, K, T, TEAMS, M>}
 static const RasterEntry k_raster_entries[] = {
@@ -122,7 +124,10 @@ static const RasterEntry k_raster_entries[] = {
     // pixel-parallel only
     PLAIN(2, 0, 0, 1, false), PLAIN(4, 0, 0, 1, false), PLAIN(3, 0, 0, 1, false), PLAIN(1, 0, 0, 1, false),
     PLAIN(2, 1, 0, 1, false), PLAIN(4, 1, 0, 1, false), PLAIN(3, 1, 0, 1, false), PLAIN(1, 1, 0, 1, false),
+    // MODEL_PBR_IBL scopes: per key, with and without the triangle-parallel path, per shadow term (none, single map, cascades)
+    IBL(0, 1, 0), IBL(1, 1, 0), IBL(0, 0, 0), IBL(1, 0, 0), IBL(0, 1, 1), IBL(1, 1, 1), IBL(0, 0, 1), IBL(1, 0, 1), IBL(0, 1, 2), IBL(1, 1, 2), IBL(0, 0, 2), IBL(1, 0, 2),
 };
+#undef IBL
 #undef ORDERED
 #undef OWN
 #undef WIDE

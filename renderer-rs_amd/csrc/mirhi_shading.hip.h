@@ -1,4 +1,4 @@
-// mirhi_shading.hip.h -- fragment programs: TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR; texture sampling; sRGB pack (rows a8, a9)
+// mirhi_shading.hip.h -- fragment programs: TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR, MODEL_PBR_IBL; texture sampling; sRGB pack (rows a8, a9)
 // Part of the single device translation unit mirhi_kernels.hip (included inside namespace mirhi).
 #ifndef MIRHI_SHADING_HIP_H
 #define MIRHI_SHADING_HIP_H
@@ -273,7 +273,8 @@ __device__ __forceinline__ float pbr_base_alpha(DrawRef D, const f4 c[3], const 
 // true if the draw's fragments have to be alpha-tested one by one: MODEL_PBR with a base colour texture whose texel alpha (in [0, 1]
 // times baseColorFactor.a) can fall on both sides of alphaCutoff -- the decision geometry_body takes per draw otherwise
 __device__ __forceinline__ bool draw_needs_alpha_test(DrawRef D) {
-    if (D.program != 3u) return false;
+    if (D.program != 3u) return false;      // (MODEL_PBR_IBL, program 5, has the same discard but its pipelines refuse fragment_discard_enable: no masked
+                                            // scope holds one.  A masked IBL form would have to be let through here, as geometry_body's per-draw decision is.)
     const CBytePtr M = cb(D.material);
     const float fa = ldcf(M, 12), cutoff = ldcf(M, 44);
     if (ldcu(M, 48) == 0u) return false;
@@ -369,11 +370,13 @@ __device__ __forceinline__ float calculate_shadow_csm(DrawRef D, f3 worldPos, f3
     return div_rn_nb(shadow, 9.0f);                                                             // :145
 }
 
-// pixel/model_pbr.hlsl:159-320 after the shared varying interpolation
-// SHADOW 1: the variant with the directional light's shadow term (model_pbr.hlsl:238-251) for draws with a shadow map bound; 2: the variant with
-// CalculateShadowCSM instead (pixel/model_pbr_ibl_csm.hlsl:280-298) for draws with cascades bound, clipz = SV_Position.z
-template <int SHADOW = 0>
-__device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint32_t vi[3], float u, float v, f3 worldPos, f3 V, f3 N, const UvGrad& grad, float clipz = 0.0f) {
+// The Cook-Torrance programs, pixel/model_pbr.hlsl:159-320 and pixel/model_pbr_ibl.hlsl:199-396 / model_pbr_ibl_csm.hlsl, after the shared varying
+// interpolation.  The two files share their front half (material factors and the five textures, GetWorldNormal, ClampRoughness: pbr_surface) and
+// the three light loops with the directional light's shadow term (pbr_direct_lighting); they differ in the ambient term and the final sum
+// (shade_pbr / shade_pbr_ibl).
+struct PbrSurface { PbrMaterial m; f3 N, emissive; float ao, alpha; };
+// model_pbr.hlsl:159-236 = model_pbr_ibl.hlsl:205-262: N comes in as the normalised vertex normal and leaves as GetWorldNormal's
+__device__ __forceinline__ PbrSurface pbr_surface(DrawRef D, const float b[3], const uint32_t vi[3], float u, float v, f3 N, const UvGrad& grad) {
     const CBytePtr M = cb(D.material);                                                  // MaterialData :36-59 (80 B)
     f4 baseColor = {ldcf(M, 0), ldcf(M, 4), ldcf(M, 8), ldcf(M, 12)};
     float metallic = ldcf(M, 16), roughness = ldcf(M, 20), ao = ldcf(M, 24);
@@ -403,10 +406,18 @@ __device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint3
             N = normalize3(add3(add3(scale3(T, ns.x), scale3(Bt, ns.y)), scale3(N, ns.z)));
         }
     }
-    PbrMaterial m;
-    m.albedo = {baseColor.x, baseColor.y, baseColor.z};
-    m.metallic = metallic;
-    m.roughness = roughness > 0.04f ? roughness : 0.04f;                                // ClampRoughness :476-479
+    PbrSurface s;
+    s.m.albedo = {baseColor.x, baseColor.y, baseColor.z};
+    s.m.metallic = metallic;
+    s.m.roughness = roughness > 0.04f ? roughness : 0.04f;                              // ClampRoughness :476-479
+    s.N = N; s.emissive = emissive; s.ao = ao; s.alpha = baseColor.w;
+    return s;
+}
+// Lo of model_pbr.hlsl:229-305 = model_pbr_ibl.hlsl:275-346 (model_pbr_ibl_csm.hlsl:275-347).  SHADOW 1: the directional light's shadow term
+// (model_pbr.hlsl:238-251) for draws with a shadow map bound; 2: CalculateShadowCSM instead (pixel/model_pbr_ibl_csm.hlsl:280-298) for draws with
+// cascades bound, clipz = SV_Position.z
+template <int SHADOW>
+__device__ __forceinline__ f3 pbr_direct_lighting(DrawRef D, f3 worldPos, f3 V, f3 N, const PbrMaterial& m, float clipz) {
     f3 lighting = {0.0f, 0.0f, 0.0f};
     {
         const f3 dir = {ldcf(cb(D.lights), 0), ldcf(cb(D.lights), 4), ldcf(cb(D.lights), 8)};
@@ -454,18 +465,86 @@ __device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint3
         if (__ballot(datt * satt > 0.0f) == 0ull) continue;
         lighting = add3(lighting, pbr_direct(N, V, L, scale3(scale3(scale3(color, intensity), datt), satt), m));
     }
+    return lighting;
+}
+template <int SHADOW = 0>
+__device__ __forceinline__ f4 shade_pbr(DrawRef D, const float b[3], const uint32_t vi[3], float u, float v, f3 worldPos, f3 V, f3 N, const UvGrad& grad, float clipz = 0.0f) {
+    const PbrSurface s = pbr_surface(D, b, vi, u, v, N, grad);
+    const PbrMaterial& m = s.m;
+    N = s.N;
+    const float ao = s.ao;
+    f3 lighting = pbr_direct_lighting<SHADOW>(D, worldPos, V, N, m, clipz);
     const float up = N.y * 0.5f + 0.5f;                                                 // CalculateHemisphereAmbient pbr.hlsli:483-492
     const f3 amb = {0.08f + (0.15f - 0.08f) * up, 0.06f + (0.18f - 0.06f) * up, 0.04f + (0.25f - 0.04f) * up};
     const float om = 1.0f - m.metallic;
     const f3 ambient = scale3(scale3(mul3(amb, m.albedo), ao), om);
     lighting = scale3(lighting, 1.0f + (ao - 1.0f) * 0.5f);                             // lerp(1, ao, 0.5) :311
-    const f3 col = add3(add3(ambient, lighting), emissive);
-    return {col.x, col.y, col.z, baseColor.w};
+    const f3 col = add3(add3(ambient, lighting), s.emissive);
+    return {col.x, col.y, col.z, s.alpha};
 }
 
-// FULL: the variant that also carries the Cook-Torrance program and mip-mapped (trilinear) sampling; SHADOW: and the shadow term (shade_pbr)
-template <bool FULL, int SHADOW = 0>
-__device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3], float pxc, float pyc, float clipz = 0.0f) {
+// The ambient term of pixel/model_pbr_ibl.hlsl:355-384 (include/mirhi.h, "MODEL_PBR_IBL"): irradianceMap.Sample(N), prefilteredMap.SampleLevel(R,
+// roughness * MAX_REFLECTION_LOD) and brdfLUT.Sample((NdotV, roughness)) with the sampler of mirhi_ibl_sample.hip.h -- the lookups are the precompute
+// kernels' own functions.  The set is per scope: base pointers, sizes and the level count come from the parameter block through scalar loads.
+// Sixteen 16-byte gathers per pixel (4 irradiance, 2 x 4 prefiltered, 4 LUT): every address is computed and every load issued before the first
+// texel is used, so the sixteen are in flight together; both prefiltered levels are always fetched (floor(lod) and the next, clamped to the last:
+// a fraction of 0 returns the first one unchanged), which keeps the sequence free of branches.  Tolerance-checked against the float64 model of
+// renderer-rs_amd/ibl.py like the precompute passes, not on the oracle's bit-exact path: this function contracts.
+__device__ __forceinline__ f3 ibl_ambient(ParamsPtr R, f3 N, f3 V, const PbrMaterial& m, float ao) {
+    #pragma clang fp contract(fast)
+    const float4* const irr = reinterpret_cast<const float4*>(R->ibl_irradiance);
+    const float4* const pre = reinterpret_cast<const float4*>(R->ibl_prefiltered);
+    const float4* const lut = reinterpret_cast<const float4*>(R->ibl_lut);
+    const uint32_t irr_n = R->ibl_irr_size, pre_n = R->ibl_pre_size, pre_levels = R->ibl_pre_levels, lut_n = R->ibl_lut_size;
+    const float ndv_raw = dot3(N, V);
+    const float NdotV = max0(ndv_raw);                                                  // :359
+    const f3 Rv = {2.0f * ndv_raw * N.x - V.x, 2.0f * ndv_raw * N.y - V.y, 2.0f * ndv_raw * N.z - V.z};      // :259 reflect(-V, N)
+    // addresses
+    const IblFaceUV fn = ibl_select_face(N.x, N.y, N.z);                               // :369 (lod 0: the one level)
+    const IblTaps ki = ibl_bilinear_taps(irr_n, fn.s, fn.t);
+    const float4* const pi = irr + fn.face * irr_n * irr_n;
+    const IblFaceUV fr = ibl_select_face(Rv.x, Rv.y, Rv.z);                            // :373-377
+    const float lod = fminf(fmaxf(m.roughness * 7.0f, 0.0f), (float)(pre_levels - 1u));    // MAX_REFLECTION_LOD pbr.hlsli:373; the sampler's clamp
+    const float l0f = floorf(lod), frac = lod - l0f;
+    const uint32_t l0 = min((uint32_t)(int)l0f, pre_levels - 1u), l1 = min(l0 + 1u, pre_levels - 1u);
+    const uint32_t n0 = pre_n >> l0, n1 = pre_n >> l1;
+    const IblTaps k0 = ibl_bilinear_taps(n0, fr.s, fr.t), k1 = ibl_bilinear_taps(n1, fr.s, fr.t);
+    const float4* const p0 = pre + ibl_level_offset(pre_n, l0) + fr.face * n0 * n0;
+    const float4* const p1 = pre + ibl_level_offset(pre_n, l1) + fr.face * n1 * n1;
+    const IblTaps kl = ibl_bilinear_taps(lut_n, NdotV, m.roughness);                   // :380 (u = NdotV: column, v = roughness: row)
+    // the sixteen loads
+    const float4 ia = pi[ki.o00], ib = pi[ki.o10], ic = pi[ki.o01], id = pi[ki.o11];
+    const float4 pa = p0[k0.o00], pb = p0[k0.o10], pc = p0[k0.o01], pd = p0[k0.o11];
+    const float4 qa = p1[k1.o00], qb = p1[k1.o10], qc = p1[k1.o01], qd = p1[k1.o11];
+    const float4 la = lut[kl.o00], lb = lut[kl.o10], lc = lut[kl.o01], ld = lut[kl.o11];
+    // filters
+    const float4 irradiance = ibl_bilinear_filter(ki, ia, ib, ic, id);
+    const float4 prefiltered = ibl_lerp4(ibl_bilinear_filter(k0, pa, pb, pc, pd), ibl_bilinear_filter(k1, qa, qb, qc, qd), frac);
+    const float4 brdf = ibl_bilinear_filter(kl, la, lb, lc, ld);
+    const f3 F0 = {0.04f + (m.albedo.x - 0.04f) * m.metallic, 0.04f + (m.albedo.y - 0.04f) * m.metallic, 0.04f + (m.albedo.z - 0.04f) * m.metallic};   // :356
+    const float o = 1.0f - saturatef(NdotV), o2 = o * o, p5 = o2 * o2 * o;              // FresnelSchlickRoughness pbr.hlsli:147-152
+    const float r1 = 1.0f - m.roughness, om = 1.0f - m.metallic;
+    const f3 F = {F0.x + (fmaxf(r1, F0.x) - F0.x) * p5, F0.y + (fmaxf(r1, F0.y) - F0.y) * p5, F0.z + (fmaxf(r1, F0.z) - F0.z) * p5};
+    const f3 kD = {(1.0f - F.x) * om, (1.0f - F.y) * om, (1.0f - F.z) * om};           // :365-366
+    return {(kD.x * (irradiance.x * m.albedo.x) + prefiltered.x * (F0.x * brdf.x + brdf.y)) * ao,      // :370, :381, :384
+            (kD.y * (irradiance.y * m.albedo.y) + prefiltered.y * (F0.y * brdf.x + brdf.y)) * ao,
+            (kD.z * (irradiance.z * m.albedo.z) + prefiltered.z * (F0.z * brdf.x + brdf.y)) * ao};
+}
+// pixel/model_pbr_ibl.hlsl:199-396 (SHADOW 0 / 1) and pixel/model_pbr_ibl_csm.hlsl (SHADOW 2): color = ambient + Lo + emissive (:393) -- no hemisphere
+// ambient, and Lo is NOT scaled by lerp(1, ao, 0.5), which is model_pbr.hlsl's alone
+template <int SHADOW>
+__device__ __forceinline__ f4 shade_pbr_ibl(DrawRef D, ParamsPtr R, const float b[3], const uint32_t vi[3], float u, float v, f3 worldPos, f3 V, f3 N, const UvGrad& grad, float clipz) {
+    const PbrSurface s = pbr_surface(D, b, vi, u, v, N, grad);
+    const f3 Lo = pbr_direct_lighting<SHADOW>(D, worldPos, V, s.N, s.m, clipz);
+    const f3 ambient = ibl_ambient(R, s.N, V, s.m, s.ao);
+    const f3 col = add3(add3(ambient, Lo), s.emissive);
+    return {col.x, col.y, col.z, s.alpha};
+}
+
+// FULL: the variant that also carries the Cook-Torrance program and mip-mapped (trilinear) sampling; SHADOW: and the shadow term (shade_pbr); IBL: and MODEL_PBR_IBL (shade_pbr_ibl,
+// R = the scope's parameter block, where the IBL set lives)
+template <bool FULL, int SHADOW = 0, bool IBL = false>
+__device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3], float pxc, float pyc, float clipz = 0.0f, ParamsPtr R = nullptr) {
     f4 c[3];
     const bool full = D.program >= 2;
 #pragma unroll
@@ -517,6 +596,7 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
         grad.dudy = ((by[0] * uvk[0][0] + by[1] * uvk[1][0]) + by[2] * uvk[2][0]) - u;
         grad.dvdy = ((by[0] * uvk[0][1] + by[1] * uvk[1][1]) + by[2] * uvk[2][1]) - v;
     }
+    if constexpr (IBL) { if (D.program == 5) return shade_pbr_ibl<SHADOW>(D, R, b, vi, u, v, worldPos, V, N, grad, clipz); }
     if (FULL && D.program == 3) return shade_pbr<SHADOW>(D, b, vi, u, v, worldPos, V, N, grad, clipz);
     // pixel/model_full.hlsl:85-150
     const f4 baseColor = {ldcf(cb(D.material), 0), ldcf(cb(D.material), 4), ldcf(cb(D.material), 8), ldcf(cb(D.material), 12)};
@@ -588,11 +668,11 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
     return {col.x, col.y, col.z, albedoSample.w * baseColor.w};
 }
 
-template <bool FULL, int SHADOW = 0>
-__device__ __forceinline__ f4 shade_model_program(DrawRef D, uint32_t tri, float pxc, float pyc, float clipz = 0.0f) {
+template <bool FULL, int SHADOW = 0, bool IBL = false>
+__device__ __forceinline__ f4 shade_model_program(DrawRef D, uint32_t tri, float pxc, float pyc, float clipz = 0.0f, ParamsPtr R = nullptr) {
     uint32_t vin[3];
     fetch_triangle_indices(D, tri, vin);
-    return shade_model_program<FULL, SHADOW>(D, vin, pxc, pyc, clipz);
+    return shade_model_program<FULL, SHADOW, IBL>(D, vin, pxc, pyc, clipz, R);
 }
 
 #pragma clang fp contract(fast)

@@ -14,9 +14,11 @@ enum : uint32_t {
     PROGS_PBR = 4u,           // MODEL_PBR, or a MODEL draw with a mip chain or an sRGB texture (the Cook-Torrance variant's programs)
     PROGS_SHADOWED = 8u,      // a MODEL_PBR draw that samples a shadow map (always together with PROGS_PBR): raster_kernel_shadow
     PROGS_CASCADED = 16u,     // ... whose shadow term is CalculateShadowCSM (always together with PROGS_SHADOWED): raster_kernel_csm
+    PROGS_IBL = 32u,          // a MODEL_PBR_IBL draw (always together with PROGS_PBR; with PROGS_SHADOWED / PROGS_CASCADED when its draws are shadowed): raster_kernel_ibl
 };
 
-enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED };
+// (RASTER_IBL behind RASTER_ORDERED: the values of the families before it are recorded in tests/golden/raster_variants.json)
+enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL };
 
 // the kernel instantiation alone (no launch shape) as one word
 constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves) {
@@ -27,7 +29,7 @@ constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t ke
 // instantiation with the same launch shape.
 struct RasterVariant {
     RasterFamily family;
-    uint32_t progs;           // PROGS of raster_kernel / raster_kernel_wide / ordered_kernel: 1 .. 4 (0: the family takes none)
+    uint32_t progs;           // PROGS of raster_kernel / raster_kernel_wide / ordered_kernel: 1 .. 4 (0: the family takes none); RASTER_IBL: its SHADOWV, 0 .. 2
     uint32_t keyed;           // KEYED: 0 the plain key (raw float bits: LESS / LESS_OR_EQUAL), 1 the generic key, 2 predicate mode
     uint32_t tp;              // TP: 1 = with the triangle-parallel path
     uint32_t teams;           // TEAMS: 1, or 2 (the two-team mesh variants)
@@ -56,7 +58,12 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
         return v;
     }
     if (P.xcd_swizzle > 1u) { v.grid[0] = P.tiles_x * rows; v.grid[1] = 1u; }
-    if (programs == PROGS_DEPTH_ONLY || (programs & PROGS_SHADOWED)) {
+    if (programs & PROGS_IBL) {
+        // a scope with a MODEL_PBR_IBL draw: a family of its own like the shadowed ones (one team of four waves, single-list bins, plain tile order, an
+        // ordered key), one kernel per shadow term of its draws
+        v.family = RASTER_IBL;
+        v.progs = (programs & PROGS_CASCADED) ? 2u : ((programs & PROGS_SHADOWED) ? 1u : 0u);
+    } else if (programs == PROGS_DEPTH_ONLY || (programs & PROGS_SHADOWED)) {
         // depth-only scopes and scopes with a shadowed draw have variants of their own, whatever the selectors below would pick (the host keeps
         // them on one team of four waves, single-list bins and the plain tile order; their key is an ordered one, never a predicate)
         v.family = programs == PROGS_DEPTH_ONLY ? RASTER_DEPTH : ((programs & PROGS_CASCADED) ? RASTER_CSM : RASTER_SHADOW);

@@ -316,7 +316,7 @@ private:
 // ------------------------------------------------------------------------------------------------
 // crates/rhi/src/pipeline.rs
 // ------------------------------------------------------------------------------------------------
-enum class ShaderProgram { None = -1, Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4 };   // replaces Shader::from_spirv_file
+enum class ShaderProgram { None = -1, Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4, ModelPbrIbl = 5 };   // replaces Shader::from_spirv_file
 enum class PrimitiveTopology { PointList = 0, LineList, LineStrip, TriangleList, TriangleStrip, TriangleFan };
 enum class PolygonMode { Fill = 0, Line, Point };
 enum class CullMode { None = 0, Front, Back, FrontAndBack };
@@ -474,6 +474,10 @@ public:
     // set 2, bindings 3 / 4 of pixel/model_pbr_ibl_csm.hlsl:115-127: the four-layer D32 array and its CSMParams (336 B); array nullptr unbinds
     void bind_shadow_cascades(const Image* array, const Buffer* params, uint64_t offset = 0, uint64_t range = 0) const {
         check(mirhi_cmd_bind_shadow_cascades(h_, array ? array->handle() : nullptr, params ? params->handle() : nullptr, offset, range));
+    }
+    // set 3 of pixel/model_pbr_ibl.hlsl:133-155: irradiance cube, prefiltered cube, BRDF LUT of ShaderProgram::ModelPbrIbl draws; three nullptr unbind
+    void bind_ibl(const Image* irradiance, const Image* prefiltered, const Image* brdf_lut) const {
+        check(mirhi_cmd_bind_ibl(h_, irradiance ? irradiance->handle() : nullptr, prefiltered ? prefiltered->handle() : nullptr, brdf_lut ? brdf_lut->handle() : nullptr));
     }
     void set_viewport(const Viewport& v) const { mirhi_viewport vp{v.x, v.y, v.width, v.height, v.min_depth, v.max_depth}; check(mirhi_cmd_set_viewport(h_, &vp)); }
     void set_scissor(const Rect2D& r) const { mirhi_rect2d sc{r.x, r.y, r.width, r.height}; check(mirhi_cmd_set_scissor(h_, &sc)); }

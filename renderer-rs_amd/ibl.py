@@ -2,7 +2,8 @@
 (shaders/hlsl/compute/{equirect_to_cubemap,irradiance_map,prefilter_map,brdf_lut}.hlsl) restated operation by operation, with
 the cube and equirect samplers this build states in the header.  There is no oracle for these passes: this model, run in float64,
 is the yardstick the GPU kernels are measured against; run in float32 (`dtype=np.float32`, same operation order, serial sums) it
-gives the error a float32 evaluation of the same formulas has, which is what the GPU tolerance is derived from.
+gives the error a float32 evaluation of the same formulas has, which is what the GPU tolerance is derived from.  The last section is the
+consumer of those images: the ambient term of pixel/model_pbr_ibl.hlsl (MODEL_PBR_IBL, mirhi_cmd_bind_ibl) over the same samplers.
 
 A cube is a list of levels, level l an array [6, n >> l, n >> l, C] (faces +X, -X, +Y, -Y, +Z, -Z; rows top first).  pack_cube /
 unpack_cube convert to and from the one-allocation layout of mirhi_image_create_cube (level-major, face-major, row-major)."""
@@ -106,7 +107,7 @@ def _bilinear_face(level, face, s, t, dtype):
     """Bilinear inside the selected face, clamp to edge (not seamless): x = s n - 1/2, floor, fraction, four clamped texels."""
     T = np.dtype(dtype).type
     n = level.shape[1]
-    flat = level.reshape(6 * n * n, level.shape[-1])
+    flat = level.reshape(-1, level.shape[-1])          # (six faces of a cube level, or the one "face" of a 2-D image: sample_lut)
     x = s * T(n) - T(0.5)
     y = t * T(n) - T(0.5)
     x0 = np.floor(x)
@@ -376,6 +377,61 @@ def brdf_lut(size: int, dtype=np.float64):
     out[:, 1] = B / T(LUT_SAMPLES)
     out[:, 3] = T(1.0)
     return out.reshape(size, size, 4)
+
+
+# ---- the consumer: the ambient term of pixel/model_pbr_ibl.hlsl:355-384 (MIRHI_PROGRAM_MODEL_PBR_IBL, include/mirhi.h mirhi_cmd_bind_ibl) --------
+MAX_REFLECTION_LOD = 7.0    # pbr.hlsli:373, hard-coded there
+MIN_ROUGHNESS = 0.04        # ClampRoughness, pbr.hlsli:476-479
+
+
+def sample_lut(lut, u, v, dtype=np.float64):
+    """brdfLUT.Sample(LinearSampler, float2(u, v)) on the square image [n, n, C]: bilinear at level 0, clamp to edge on both axes -- the
+    filter of one cube face (u along a row, v down the rows)."""
+    lut = np.asarray(lut, dtype=dtype)
+    u = np.asarray(u, dtype=dtype)
+    v = np.broadcast_to(np.asarray(v, dtype=dtype), u.shape)
+    return _bilinear_face(lut[None], np.zeros(u.shape, dtype=np.int64), u, v, dtype)
+
+
+def fresnel_schlick_roughness(cos_theta, F0, roughness, dtype=np.float64):
+    """FresnelSchlickRoughness (pbr.hlsli:147-152): cos_theta [...], F0 [..., 3], roughness [...] -> [..., 3]."""
+    T = np.dtype(dtype).type
+    ct = np.clip(np.asarray(cos_theta, dtype=dtype), T(0.0), T(1.0))
+    F0 = np.asarray(F0, dtype=dtype)
+    F90 = np.maximum((T(1.0) - np.asarray(roughness, dtype=dtype))[..., None], F0)
+    o = T(1.0) - ct
+    return F0 + (F90 - F0) * (o * o * o * o * o)[..., None]
+
+
+def reflect(V, N):
+    """reflect(-V, N) = 2 dot(N, V) N - V (model_pbr_ibl.hlsl:259)."""
+    return np.asarray(2.0, dtype=N.dtype) * _dot(N, V)[..., None] * N - V
+
+
+def ambient(irradiance_levels, prefiltered_levels, lut, N, V, albedo, metallic, roughness, ao, dtype=np.float64):
+    """model_pbr_ibl.hlsl:355-384: (kD * irradiance * albedo + prefiltered * (F0 * brdf.x + brdf.y)) * ao for unit vectors N, V [..., 3],
+    albedo [..., 3] and metallic, roughness, ao [...]; `roughness` is the material's, ClampRoughness (:262) is applied here.  The cubes
+    are lists of levels [6, n, n, C >= 3] (level 0 of the irradiance cube is the one sampled), lut [n, n, C >= 2]."""
+    T = np.dtype(dtype).type
+    N, V, albedo = (np.asarray(a, dtype=dtype) for a in (N, V, albedo))
+    metallic, ao = (np.broadcast_to(np.asarray(a, dtype=dtype), N.shape[:-1]) for a in (metallic, ao))
+    rough = np.maximum(np.broadcast_to(np.asarray(roughness, dtype=dtype), N.shape[:-1]), T(MIN_ROUGHNESS))
+    F0 = T(0.04) + (albedo - T(0.04)) * metallic[..., None]                                    # :356
+    ndv = np.maximum(_dot(N, V), T(0.0))                                                        # :359
+    F = fresnel_schlick_roughness(ndv, F0, rough, dtype)                                        # :362
+    kD = (T(1.0) - F) * (T(1.0) - metallic)[..., None]                                          # :365-366
+    irr = sample_cube([np.asarray(irradiance_levels[0], dtype=dtype)[..., :3]], N, 0.0, dtype)  # :369
+    pre = sample_cube([np.asarray(l, dtype=dtype)[..., :3] for l in prefiltered_levels], reflect(V, N), rough * T(MAX_REFLECTION_LOD), dtype)   # :373-377
+    brdf = sample_lut(np.asarray(lut, dtype=dtype)[..., :2], ndv, rough, dtype)                 # :380
+    spec = pre * (F0 * brdf[..., 0:1] + brdf[..., 1:2])                                         # :381
+    return (kD * (irr * albedo) + spec) * ao[..., None]                                         # :370, :384
+
+
+def tie_mask(d, rel=1e-4):
+    """True where the two largest |components| of d [..., 3] are within `rel` of each other (relative to the largest): the cube lookup may
+    select either face there, and the stated sampler is not seamless."""
+    a = np.sort(np.abs(np.asarray(d, dtype=np.float64)), axis=-1)
+    return (a[..., 2] - a[..., 1]) <= rel * a[..., 2]
 
 
 # ---- test environment ---------------------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ from typing import List, Optional
 
 import numpy as np
 
-PROGRAM_TRIANGLE, PROGRAM_MODEL, PROGRAM_MODEL_FULL, PROGRAM_MODEL_PBR, PROGRAM_SHADOW = 0, 1, 2, 3, 4
+PROGRAM_TRIANGLE, PROGRAM_MODEL, PROGRAM_MODEL_FULL, PROGRAM_MODEL_PBR, PROGRAM_SHADOW, PROGRAM_MODEL_PBR_IBL = 0, 1, 2, 3, 4, 5
 LOAD_OP_LOAD, LOAD_OP_CLEAR = 0, 1
 CULL_NONE, CULL_FRONT, CULL_BACK, CULL_FRONT_AND_BACK = 0, 1, 2, 3
 FRONT_CCW, FRONT_CW = 0, 1
@@ -337,6 +337,29 @@ class CascadeSpec:
 
 
 @dataclass
+class IblSpec:
+    """The IBL set of a scene's MODEL_PBR_IBL draws (mirhi_cmd_bind_ibl): either three existing images (`images`: irradiance cube, prefiltered
+    cube, BRDF LUT -- the caller's) or the arrays to upload: `irradiance` one level [6, n, n, 4], `prefiltered` a list of levels [6, m >> l, m >> l, 4],
+    `lut` [k, k, 4] (float32; the layouts of renderer-rs_amd/ibl.py)."""
+    irradiance: Optional[np.ndarray] = None
+    prefiltered: Optional[list] = None
+    lut: Optional[np.ndarray] = None
+    images: Optional[tuple] = None
+
+    def create_images(self, device, image_cls, lut_format: int = 2):
+        """Three new images holding the arrays (the caller destroys them): (irradiance cube, prefiltered cube, LUT).  lut_format: the caller's
+        R32G32B32A32_SFLOAT (mirhi_format; this module knows no Format class)."""
+        from . import ibl as _ibl
+        irr = image_cls.create_cube(device, int(self.irradiance.shape[1]), 1)
+        irr.upload(_ibl.pack_cube([self.irradiance]))
+        pre = image_cls.create_cube(device, int(self.prefiltered[0].shape[1]), len(self.prefiltered))
+        pre.upload(_ibl.pack_cube(self.prefiltered))
+        lut = image_cls(device, int(self.lut.shape[1]), int(self.lut.shape[0]), lut_format)
+        lut.upload(np.ascontiguousarray(self.lut, dtype=np.float32))
+        return irr, pre, lut
+
+
+@dataclass
 class Scene:
     name: str
     width: int
@@ -346,6 +369,7 @@ class Scene:
     clear_depth: float = 1.0                   # rendering.rs:356-370 default
     shadow: Optional[ShadowSpec] = None        # None: no shadow scope (the oracle's PBR frame: shadow = 1)
     cascades: Optional["CascadeSpec"] = None   # shadow cascades (shadow_csm.hlsli): four depth-only scopes ahead of the main scope; not with `shadow`
+    ibl: Optional["IblSpec"] = None            # the IBL set of the scene's MODEL_PBR_IBL draws (mirhi_cmd_bind_ibl)
 
     @property
     def num_triangles(self) -> int:
@@ -913,6 +937,70 @@ SMALL_CASES = {
     "random_small": lambda: random_triangles(300, 320, 200, seed=42, rmin=2, rmax=40),
     "sphere_small": lambda: displaced_sphere(24, 17, 256, 160, seed=3),
 }
+
+
+# ------------------------------------------------------------------------------------------------
+# image-based ambient lighting (pixel/model_pbr_ibl.hlsl, MIRHI_PROGRAM_MODEL_PBR_IBL)
+# ------------------------------------------------------------------------------------------------
+# (normal, roughness, metallic, ao, emissive) per facet: the normals' major axes are +X -X +Y -Y +Z -Z twice over, no two largest |components|
+# closer than 0.2; every roughness of {0, 0.3, 4/7, 0.8, 1} and metallic of {0, 0.5, 1} occurs
+IBL_FACETS = (
+    ((0.9, 0.3, 0.25), 0.0, 0.0, 1.0, (0.0, 0.0, 0.0)), ((-0.8, 0.2, 0.5), 0.3, 0.5, 0.7, (0.0, 0.0, 0.0)),
+    ((0.3, 0.85, 0.4), 4.0 / 7.0, 1.0, 1.0, (0.0, 0.0, 0.0)), ((0.2, -0.9, 0.35), 0.8, 0.0, 0.4, (0.0, 0.0, 0.0)),
+    ((0.25, 0.3, 0.9), 1.0, 0.5, 1.0, (0.0, 0.0, 0.0)), ((-0.3, 0.2, -0.85), 0.3, 1.0, 0.6, (0.0, 0.0, 0.0)),
+    ((0.8, -0.45, -0.3), 0.8, 0.5, 1.0, (0.3, 0.1, 0.05)), ((-0.9, -0.35, 0.2), 1.0, 0.0, 0.8, (0.0, 0.0, 0.0)),
+    ((-0.35, 0.8, -0.4), 0.0, 1.0, 1.0, (0.0, 0.0, 0.0)), ((-0.4, -0.85, -0.2), 4.0 / 7.0, 0.0, 0.5, (0.0, 0.0, 0.0)),
+    ((-0.2, -0.45, 0.85), 0.3, 0.0, 1.0, (0.0, 0.0, 0.0)), ((0.45, 0.15, -0.9), 4.0 / 7.0, 0.5, 0.9, (0.0, 0.0, 0.0)),
+)
+IBL_FACETS_EYE = (0.35, 0.25, 6.0)
+
+
+def ibl_test_images(pre_size: int = 16, pre_levels: int = 5, irr_size: int = 8, lut_size: int = 16, zero: bool = False):
+    """Uploadable contents for an IBL set (float32): ibl.analytic_environment scaled differently per cube and per level -- a wrong level or face
+    shows -- and a smooth LUT that is not symmetric in its axes.  zero: all three images zero."""
+    from . import ibl as _ibl
+    irr = (0.5 * _ibl.analytic_environment(irr_size)).astype(f32)
+    pre = [((1.0 + 0.25 * l) * _ibl.analytic_environment(pre_size >> l)).astype(f32) for l in range(pre_levels)]
+    c = (np.arange(lut_size) + 0.5) / lut_size
+    ndv, rough = np.meshgrid(c, c, indexing="xy")           # column = NdotV, row = roughness
+    lut = np.stack([0.9 * (1.0 - rough) + 0.1 * ndv, 0.3 * ndv * rough + 0.05, np.zeros_like(ndv), np.ones_like(ndv)], axis=-1).astype(f32)
+    if zero:
+        irr, pre, lut = np.zeros_like(irr), [np.zeros_like(l) for l in pre], np.zeros_like(lut)
+    return IblSpec(irradiance=irr, prefiltered=pre, lut=lut)
+
+
+def ibl_facets_case(width: int = 128, height: int = 96, lit: bool = False, ao=None, program: int = PROGRAM_MODEL_PBR_IBL,
+                    pre_size: int = 16, pre_levels: int = 5) -> Scene:
+    """Twelve flat quads in a 4 x 3 grid, each in its own plane z = const facing the camera, every vertex of a quad carrying the quad's
+    (made-up) normal of IBL_FACETS, so N is constant per primitive and known; materials without textures.  lit=False: no light reaches
+    anything (Lo is exact zero); lit=True: a directional, a point and a spot light.  ao: overrides every facet's occlusion factor.
+    scene.facets lists, per quad (= draw d, primitives 2 d and 2 d + 1): normal, plane z, base colour, roughness, metallic, ao, emissive."""
+    view, proj, cam = default_camera(width, height, eye=IBL_FACETS_EYE)
+    if lit:
+        light = light_ubo(direction=(0.3, -0.5, -0.8), intensity=1.5, color=(1.0, 0.95, 0.9), num_point=1, num_spot=1)
+        points = point_light((1.0, 1.0, 2.5), 9.0, (0.9, 0.6, 0.4), 6.0)
+        spots = spot_light((-1.5, 0.5, 4.0), math.cos(0.3), (0.3, -0.1, -1.0), math.cos(0.6), (0.4, 0.7, 1.0), 12.0)
+    else:
+        light, points, spots = light_ubo(intensity=0.0), b"", b""
+    obj = object_ubo(np.eye(4, dtype=f32))
+    idx = np.array([0, 1, 2, 0, 2, 3], dtype=np.uint32)
+    draws, facets = [], []
+    for k, (nrm, rough, metal, fao, emis) in enumerate(IBL_FACETS):
+        gx, gy = k % 4, k // 4
+        x0, y0, z = -2.0 + gx * 1.0 + 0.06, -1.5 + gy * 1.0 + 0.06, -0.6 + 0.1 * k
+        pos = np.array([[x0, y0, z], [x0 + 0.88, y0, z], [x0 + 0.88, y0 + 0.88, z], [x0, y0 + 0.88, z]])
+        n = np.asarray(nrm, dtype=np.float64)
+        n = n / np.linalg.norm(n)
+        verts = _pack_vertex48(pos, np.tile(n, (4, 1)), np.array([[0, 0], [1, 0], [1, 1], [0, 1]], dtype=np.float64), np.tile(np.array([1.0, 0.0, 0.0, 1.0]), (4, 1)))
+        base = (0.35 + 0.05 * k, 0.9 - 0.06 * k, 0.5 + 0.03 * ((k * 5) % 12), 1.0)
+        fao = fao if ao is None else ao
+        draws.append(DrawSpec(vertices=verts, stride=48, count=6, indices=idx, program=program, cull_mode=CULL_NONE, camera=cam, object=obj, light=light,
+                              material=pbr_material_ubo(base, metal, rough, fao, emissive=emis), point_lights=points, spot_lights=spots))
+        facets.append(dict(normal=verts[0, 3:6].copy(), z=float(f32(z)), base=np.asarray(base, dtype=f32), roughness=float(f32(rough)), metallic=float(f32(metal)),
+                           ao=float(f32(fao)), emissive=np.asarray(emis, dtype=f32)))
+    scene = Scene("ibl-facets", width, height, draws, clear_color=(0.01, 0.02, 0.03, 1.0), ibl=ibl_test_images(pre_size, pre_levels))
+    scene.facets, scene.view, scene.proj, scene.eye = facets, view, proj, _v(IBL_FACETS_EYE)
+    return scene
 
 
 # ------------------------------------------------------------------------------------------------

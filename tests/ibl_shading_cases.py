@@ -1,0 +1,117 @@
+"""Shared by tests/test_ibl_shading_cpu.py and tests/test_gpu_ibl_shading.py: the expected MODEL_PBR_IBL frame of scenes.ibl_facets_case in numpy
+alone -- the primitive of a pixel comes from a prim-id image (or from the facets' screen rectangles), the world position from the pixel centre's
+ray and the facet's plane, then renderer_rs_amd.ibl.ambient -- and the error measure of DESIGN.md 8d / 8e."""
+import dataclasses
+
+import numpy as np
+
+NO_PRIM = 0xFFFFFFFF
+RGB_TOL = 1e-4
+
+
+def assert_close(out_rgba, ref_rgba, name, mask=None):
+    """The project's colour comparison (tests/test_gpu_shadow.py): |dRGB| / max(1, |ref|) < 1e-4."""
+    a, b = out_rgba[..., :3].astype(np.float64), ref_rgba[..., :3].astype(np.float64)
+    err = np.abs(a - b) / np.maximum(1.0, np.abs(b))
+    if mask is not None:
+        err = err[mask]
+    worst = float(err.max()) if err.size else 0.0
+    assert worst < RGB_TOL, f"{name}: max |dRGB| = {worst}"
+
+
+def rel_err(x, m64):
+    """err(X) = max |X - M64| / max(|M64|, 1e-3 max |M64|)."""
+    m64 = np.asarray(m64, dtype=np.float64)
+    if m64.size == 0:
+        return 0.0
+    floor = 1e-3 * float(np.max(np.abs(m64)))
+    return float(np.max(np.abs(np.asarray(x, dtype=np.float64) - m64) / np.maximum(np.abs(m64), max(floor, 1e-300))))
+
+
+def bound_for(e32):
+    return max(8.0 * e32, 1e-4)
+
+
+def facet_pixels(scene, prim):
+    """(py, px, facet) of the covered pixels of a prim-id image: quad d is primitives 2 d and 2 d + 1."""
+    py, px = np.nonzero(prim != NO_PRIM)
+    return py, px, (prim[py, px] // 2).astype(np.int64)
+
+
+def world_positions(scene, py, px, facet, dtype=np.float64):
+    """Where the ray through the centre of pixel (px, py) meets the plane z = facets[facet].z, with the float32 viewProjection the GPU reads."""
+    T = np.dtype(dtype).type
+    from renderer_rs_amd import scenes as S
+    M = S.mat_mul(scene.proj, scene.view).astype(dtype).T            # maths matrix, rows
+    xd = (px.astype(dtype) + T(0.5)) / T(scene.width) * T(2.0) - T(1.0)
+    yd = (py.astype(dtype) + T(0.5)) / T(scene.height) * T(2.0) - T(1.0)
+    z = np.array([f["z"] for f in scene.facets], dtype=dtype)[facet]
+    a = M[0][None, :] - xd[:, None] * M[3][None, :]
+    b = M[1][None, :] - yd[:, None] * M[3][None, :]
+    ra, rb = -(a[:, 2] * z + a[:, 3]), -(b[:, 2] * z + b[:, 3])
+    det = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+    x = (ra * b[:, 1] - a[:, 1] * rb) / det
+    y = (a[:, 0] * rb - ra * b[:, 0]) / det
+    return np.stack([x, y, z], axis=-1)
+
+
+def surface(scene, py, px, facet, dtype=np.float64):
+    """N, V and the material of every listed pixel."""
+    from renderer_rs_amd import ibl
+    P = world_positions(scene, py, px, facet, dtype)
+    F = scene.facets
+    N = ibl._normalize(np.array([f["normal"] for f in F], dtype=dtype)[facet])
+    V = ibl._normalize(scene.eye.astype(dtype)[None, :] - P)
+    g = lambda key: np.array([f[key] for f in F], dtype=dtype)[facet]
+    return dict(P=P, N=N, V=V, albedo=g("base")[:, :3], alpha=g("base")[:, 3], metallic=g("metallic"), roughness=g("roughness"), ao=g("ao"), emissive=g("emissive"))
+
+
+def expected_ambient(scene, images, py, px, facet, dtype=np.float64, ao=None):
+    """ambient of every listed pixel; images = (irradiance levels, prefiltered levels, lut) as arrays."""
+    from renderer_rs_amd import ibl
+    s = surface(scene, py, px, facet, dtype)
+    irr, pre, lut = images
+    return ibl.ambient(irr, pre, lut, s["N"], s["V"], s["albedo"], s["metallic"], s["roughness"], s["ao"] if ao is None else ao, dtype), s
+
+
+def scene_images(scene):
+    sp = scene.ibl
+    return [sp.irradiance], sp.prefiltered, sp.lut
+
+
+def keep_mask(scene, py, px, facet):
+    """Pixels whose R is not within 1e-4 (relative) of a face tie, decided by the float64 model alone."""
+    from renderer_rs_amd import ibl
+    s = surface(scene, py, px, facet, np.float64)
+    return ~ibl.tie_mask(ibl.reflect(s["V"], s["N"]), 1e-4)
+
+
+def hemisphere_ambient(N, albedo, metallic, ao):
+    """CalculateHemisphereAmbient (pbr.hlsli:483-492) as model_pbr.hlsl applies it: lerp(ground, sky, N.y / 2 + 1 / 2) * albedo * ao * (1 - metallic)."""
+    up = N[:, 1:2] * 0.5 + 0.5
+    ground, sky = np.array([0.08, 0.06, 0.04]), np.array([0.15, 0.18, 0.25])
+    return (ground + (sky - ground) * up) * albedo * np.asarray(ao)[..., None] * (1.0 - metallic)[:, None]
+
+
+def with_program(scene, program, **material_overrides):
+    """The scene with every draw's program replaced (the oracle knows MODEL_PBR, not MODEL_PBR_IBL)."""
+    out = dataclasses.replace(scene, draws=[dataclasses.replace(d, program=program) for d in scene.draws])
+    for k in ("facets", "view", "proj", "eye"):
+        if hasattr(scene, k):
+            setattr(out, k, getattr(scene, k))
+    return out
+
+
+def software_prim(scene):
+    """The prim-id image of ibl_facets_case without a GPU: the quads are axis-aligned rectangles in their planes, so a pixel belongs to quad d when
+    its ray meets plane d inside the rectangle (the quads do not overlap on screen)."""
+    H, W = scene.height, scene.width
+    prim = np.full((H, W), NO_PRIM, dtype=np.uint32)
+    py, px = np.mgrid[0:H, 0:W]
+    py, px = py.reshape(-1), px.reshape(-1)
+    for d, draw in enumerate(scene.draws):
+        v = np.asarray(draw.vertices, dtype=np.float64)
+        P = world_positions(scene, py, px, np.full(py.shape, d), np.float64)
+        inside = (P[:, 0] > v[0, 0]) & (P[:, 0] < v[2, 0]) & (P[:, 1] > v[0, 1]) & (P[:, 1] < v[2, 1])
+        prim[py[inside], px[inside]] = 2 * d       # (which of the two triangles does not matter to facet_pixels)
+    return prim
