@@ -31,6 +31,7 @@
 #include "mirhi_device.h"
 #include "mirhi_launch.h"
 #include "mirhi_variant.h"
+#include "mirhi_scope.h"
 
 using namespace mirhi;
 
@@ -512,9 +513,7 @@ struct RecordedPass {
     std::vector<DrawDesc> draws;
     std::vector<uint64_t> draw_vb_bytes;   // bytes of the bound vertex buffer range per draw (vertex pre-pass extent)
     uint32_t total_tris = 0;
-    bool key_set = false;
-    uint32_t depth_test = 0, depth_compare = 0, depth_write = 0, frag_discard = 0;
-    uint32_t blend[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // enable, src colour, dst colour, colour op, src alpha, dst alpha, alpha op, write mask
+    DepthState state;                      // depth / blend state of the segment's draws (mirhi_scope.h)
     // a scope whose pipelines change the depth state is continued in a new segment: colour is kept (LOAD), depth is
     // carried through the depth attachment or, without one, a transient buffer of the workspace
     uint32_t first_tri = 0;                // primitive ids continue across the segments of a scope
@@ -1338,7 +1337,7 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported color attachment format %d", cf);
     if (vs_shadow) {
         const int32_t op = d->depth_compare_op;
-        if (!d->depth_test_enable || !d->depth_write_enable || !(op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL || op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL))
+        if (!d->depth_test_enable || !d->depth_write_enable || !ordering_compare((uint32_t)op))
             return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth-only pipelines need depth test and write with LESS, LESS_OR_EQUAL, GREATER or GREATER_OR_EQUAL");
         if (d->blend_enable || d->fragment_discard_enable)
             return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: blending or fragment discard in a depth-only pipeline");
@@ -1701,26 +1700,24 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     if (pd.color_attachment_formats[0] != (int32_t)ci.format)
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)ci.format);
     // depth state must be uniform within a rendering scope (DESIGN.md "Depth key")
-    const uint32_t dtest = pd.depth_test_enable ? 1u : 0u;
-    const uint32_t dcmp = dtest ? (uint32_t)pd.depth_compare_op : (uint32_t)MIRHI_COMPARE_ALWAYS;
-    const uint32_t dwrite = dtest && pd.depth_write_enable ? 1u : 0u;       // Vulkan: no depth write without the depth test
+    DepthState ds;
+    ds.key_set = true;
+    ds.test = pd.depth_test_enable ? 1u : 0u;
+    ds.compare = ds.test ? (uint32_t)pd.depth_compare_op : (uint32_t)MIRHI_COMPARE_ALWAYS;
+    ds.write = ds.test && pd.depth_write_enable ? 1u : 0u;       // Vulkan: no depth write without the depth test
     const bool never = pd.depth_test_enable && pd.depth_compare_op == MIRHI_COMPARE_NEVER;
     const uint32_t tri_count = count / 3u;
     if (instance_count == 0 || tri_count == 0) return MIRHI_OK;
     if (never) { cmd->passes.back().total_tris += tri_count; return MIRHI_OK; }     // draws nothing, but its primitives keep their ids
-    uint32_t blend[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (pd.blend_enable) {
+        uint32_t* blend = ds.blend;
         blend[0] = 1; blend[1] = (uint32_t)pd.src_color_blend_factor; blend[2] = (uint32_t)pd.dst_color_blend_factor; blend[3] = (uint32_t)pd.color_blend_op;
         blend[4] = (uint32_t)pd.src_alpha_blend_factor; blend[5] = (uint32_t)pd.dst_alpha_blend_factor; blend[6] = (uint32_t)pd.alpha_blend_op;
         blend[7] = pd.color_write_mask & 0xFu;
     }
-    const uint32_t discard = pd.fragment_discard_enable ? 1u : 0u;
-    if (!cmd->passes.back().key_set) {
-        RecordedPass& p0 = cmd->passes.back();
-        p0.key_set = true; p0.depth_test = dtest; p0.depth_compare = dcmp; p0.depth_write = dwrite; p0.frag_discard = discard;
-        memcpy(p0.blend, blend, sizeof blend);
-    } else if (cmd->passes.back().depth_test != dtest || cmd->passes.back().depth_compare != dcmp || cmd->passes.back().depth_write != dwrite ||
-               cmd->passes.back().frag_discard != discard || memcmp(cmd->passes.back().blend, blend, sizeof blend) != 0) {
+    ds.discard = pd.fragment_discard_enable ? 1u : 0u;
+    if (!cmd->passes.back().state.key_set) cmd->passes.back().state = ds;
+    else if (!(cmd->passes.back().state == ds)) {
         // One raster launch resolves one depth state (DESIGN.md "Depth key"): the scope continues in a new segment that
         // loads what the previous one stored -- fragments keep their submission order across the cut.
         RecordedPass next;
@@ -1735,8 +1732,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
             next.carry_in = true;
             next.first_tri = next.total_tris = prev.total_tris;
         }
-        next.key_set = true; next.depth_test = dtest; next.depth_compare = dcmp; next.depth_write = dwrite; next.frag_discard = discard;
-        memcpy(next.blend, blend, sizeof blend);
+        next.state = ds;
         cmd->passes.push_back(std::move(next));
     }
     RecordedPass& pass = cmd->passes.back();
@@ -1805,10 +1801,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                 // CalculateShadow (model_pbr.hlsl:238-251): the map and its ShadowParams; the shadowed raster variant resolves ordered depth keys only
                 const mirhi_image* sm = cmd->textures[MIRHI_TEXTURE_SHADOW_MAP];
                 if ((r = uptr(MIRHI_SLOT_SHADOW_DATA, 96, &d.shadow_data, "ShadowParams (SHADOW_DATA)")) != MIRHI_OK) return r;
-                const uint32_t op = pd.depth_compare_op;
-                const bool keyed = !pd.depth_test_enable || (pd.depth_write_enable && (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL ||
-                                                                                       op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL));
-                if (pd.blend_enable || pd.fragment_discard_enable || !keyed)
+                if (!ordered_key_only(ds, false))
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a shadow map with blending, fragment discard or a predicate depth state");
                 if (cmd->cascades)
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: both a shadow map (MIRHI_TEXTURE_SHADOW_MAP) and shadow cascades (mirhi_cmd_bind_shadow_cascades) are bound");
@@ -1817,10 +1810,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                 // CalculateShadowCSM (model_pbr_ibl_csm.hlsl:280-298): the array and its CSMParams.  SV_Position.z is the depth the key holds, so the
                 // draw needs an ordered depth key (depth test and write with an ordering compare op)
                 const mirhi_image* ca = cmd->cascades;
-                const uint32_t op = pd.depth_compare_op;
-                const bool keyed = pd.depth_test_enable && pd.depth_write_enable && (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL ||
-                                                                                     op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL);
-                if (pd.blend_enable || pd.fragment_discard_enable || !keyed)
+                if (!ordered_key_only(ds, true))
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: shadow cascades with blending, fragment discard, a predicate depth state or no depth test");
                 d.shadow_map = (const float*)ca->ptr; d.shadow_w = ca->width; d.shadow_h = ca->height; d.shadow_layers = ca->layers;
                 d.shadow_data = cmd->cascade_params.buf->ptr + cmd->cascade_params.offset;
@@ -1828,10 +1818,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
             if (d.program == MIRHI_PROGRAM_MODEL_PBR_IBL) {
                 // set 3 (mirhi_cmd_bind_ibl).  raster_kernel_ibl resolves ordered depth keys only, like the shadowed variants
                 if (!cmd->ibl[0]) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: program %d (MODEL_PBR_IBL) needs an IBL set bound (mirhi_cmd_bind_ibl)", pd.fragment_program);
-                const uint32_t op = pd.depth_compare_op;
-                const bool keyed = !pd.depth_test_enable || (pd.depth_write_enable && (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL ||
-                                                                                       op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL));
-                if (pd.blend_enable || pd.fragment_discard_enable || !keyed)
+                if (!ordered_key_only(ds, false))
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: MODEL_PBR_IBL with blending, fragment discard or a predicate depth state");
             }
         }
@@ -1937,113 +1924,6 @@ static mirhi_result grow(T** ptr, size_t* have, size_t want_bytes) {
     return MIRHI_OK;
 }
 
-// A segment is resolved fragment by fragment in primitive order (ordered_kernel) when its colour is blended, when its
-// depth state makes the stored depth depend on the order of all fragments (NotEqual with depth write), or when its fragment
-// program may discard single fragments (mirhi_pipeline_desc::fragment_discard_enable: visibility then needs the program's result).
-static void depth_key_setup(PassParams& P, const RecordedPass& pass);
-// fragment_discard_enable without blending under a depth state the depth key resolves by minimum (not a predicate state): visibility stays
-// order-independent -- a kept fragment competes by its key -- so the segment keeps bins and the raster kernel, and alpha is tested per
-// covered pixel in front of the key minimum (PassParams::alpha_scope, raster_small_masked).  MIRHI_MASKED_ORDERED=1 (A/B runs): the
-// ordered resolve instead.
-static bool pass_is_masked_plain(const RecordedPass& pass) {
-    if (!pass.key_set || !pass.frag_discard || pass.blend[0] != 0) return false;
-    if (pass.depth_test && pass.depth_write && pass.depth_compare == MIRHI_COMPARE_NOT_EQUAL) return false;
-    if (getenv("MIRHI_MASKED_ORDERED") && atoi(getenv("MIRHI_MASKED_ORDERED")) != 0) return false;
-    PassParams key{};
-    depth_key_setup(key, pass);
-    return key.pred == 0u;
-}
-static bool pass_is_ordered(const RecordedPass& pass) {
-    return pass.key_set && (pass.blend[0] != 0 || (pass.frag_discard != 0 && !pass_is_masked_plain(pass)) ||
-                            (pass.depth_test && pass.depth_write && pass.depth_compare == MIRHI_COMPARE_NOT_EQUAL));
-}
-
-static void depth_key_setup(PassParams& P, const RecordedPass& pass) {
-    const uint32_t cbits = [&] { float f = pass.info.clear_depth; f = f > 0.0f ? (f < 1.0f ? f : 1.0f) : 0.0f; uint32_t u; memcpy(&u, &f, 4); return u; }();
-    P.clear_depth_bits = cbits;
-    P.pred = 0;
-    const uint32_t op = pass.key_set ? pass.depth_compare : (uint32_t)MIRHI_COMPARE_ALWAYS;
-    const bool test = pass.key_set && pass.depth_test;
-    const bool write = test && pass.depth_write;
-    if (!test || (op == MIRHI_COMPARE_ALWAYS && !write)) {      // every fragment passes, nothing is written: later primitive wins
-        P.zflip = 0; P.zmask = 0; P.idflip = 1; P.strict = 0; P.init_zk = 0; P.init_idk = NO_PRIM; return;
-    }
-    const bool ordered = write && (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_LESS_OR_EQUAL || op == MIRHI_COMPARE_GREATER ||
-                                   op == MIRHI_COMPARE_GREATER_OR_EQUAL);
-    if (!ordered) {
-        // Predicate mode.  Without depth write (or with Equal, which can only rewrite the same value) the stored depth
-        // never changes inside the scope: every fragment is tested against the depth the scope started with and the latest
-        // passing primitive owns the pixel.  Always with write: everything passes, the latest primitive's depth is stored.
-        static const uint32_t bits[8] = {0u, 1u, 2u, 3u, 4u, 5u, 6u, 7u};     // Never, Less, Equal, LessOrEqual, Greater, NotEqual, GreaterOrEqual, Always
-        P.pred = bits[op & 7u] | (op == MIRHI_COMPARE_ALWAYS ? 8u : 0u);
-        if (P.pred == 0) P.pred = 16u;                                           // (Never is dropped at record time; keep the mode bit set)
-        P.zflip = 0; P.zmask = 0xFFFFFFFFu; P.idflip = 1; P.strict = 0;
-        P.init_zk = cbits; P.init_idk = NO_PRIM;
-        return;
-    }
-    const bool greater = (op == MIRHI_COMPARE_GREATER || op == MIRHI_COMPARE_GREATER_OR_EQUAL);
-    P.strict = (op == MIRHI_COMPARE_LESS || op == MIRHI_COMPARE_GREATER) ? 1u : 0u;
-    P.zflip = greater ? 0xFFFFFFFFu : 0u;
-    P.zmask = 0xFFFFFFFFu;
-    P.idflip = P.strict ? 0u : 1u;            // strict: earlier primitive keeps ties; or-equal: later primitive wins
-    const uint32_t t = cbits ^ P.zflip;
-    if (!P.strict) { P.init_zk = t; P.init_idk = NO_PRIM; }
-    else if (t == 0u) { P.init_zk = 0u; P.init_idk = 0u; }   // nothing can pass
-    else { P.init_zk = t - 1u; P.init_idk = NO_PRIM; }
-}
-
-// How a scope is rastered (decided once per recorded scope, used for sizing the workspace and for the launch):
-//  tp_max_area  triangle-parallel resolve of small records pays when tiles hold many triangles (meshes); sparse scopes keep
-//               the leaner pixel-parallel-only kernel.  Scopes of TRIANGLE-program draws switch at 16 triangles per tile on
-//               average (their variant gives up one wave of occupancy for the LDS key array); mesh-program scopes lose nothing
-//               and a mesh covers a fraction of the frame (the dancer asset: 8 per tile on average, 124 per tile it touches),
-//               so they switch at 4.  Box limit 64 pixels: measured against 96 / 128 on the dancer (74 / 81 / 89 us), C3
-//               (38.6 / 36.8 / 37.1), C4 (112.9 / 112.4 / 112.4) and C5 (202 / 206 / 211).
-//  teams        two teams per tile + per-XCD bins when a mesh scope is dense enough for the triangle-parallel variant yet
-//               averages under 16 triangles per tile: then its triangles sit in a small part of the frame (the dancer: 919 in
-//               the fullest tile), the chip is far from full, the raster kernel lasts as long as the fullest tile's serial
-//               chain -- which two teams cut (dancer raster 62.6 -> 44.0 us; four teams: 47.4) -- and the geometry kernel as
-//               long as the queue of atomics on the hottest bin counter, which per-XCD counters cut (see reserve_bin_slots).
-//  MIRHI_TP_MAX_AREA (0 = off), MIRHI_TP_DENSITY, MIRHI_RASTER_TEAMS (1 / 2) override for A/B measurements.
-struct RasterMode { uint32_t tp_max_area, teams; bool tri_prog; bool wide_eligible; bool xcd_bins; uint32_t wide; };
-// Depth-only scopes and scopes with a shadowed draw have raster variants of their own (raster_kernel_depth / raster_kernel_shadow): one team of four
-// waves per tile, single-list bins -- the team and wide selectors below leave them alone.
-static bool pass_is_depth_or_shadowed(const RecordedPass& pass) {
-    if (pass.depth_only) return true;
-    for (const DrawDesc& dd : pass.draws) if (dd.shadow_map || dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL) return true;      // (raster_kernel_ibl: the same shape)
-    return false;
-}
-// wide: what the command buffer's busy-tile feedback asks for (Workspace::wide: 0 / 8 / 16 waves per tile)
-static RasterMode raster_mode(const RecordedPass& pass, size_t tiles, bool spread = false, uint32_t wide = 0) {
-    RasterMode m{0u, 1u, false, false, false, 0u};
-    for (const DrawDesc& dd : pass.draws) m.tri_prog |= dd.program == MIRHI_PROGRAM_TRIANGLE;
-    PassParams key{};
-    depth_key_setup(key, pass);
-    const size_t avg = tiles ? (pass.total_tris - pass.first_tri) / tiles : 0;
-    const size_t density = getenv("MIRHI_TP_DENSITY") ? (size_t)atoi(getenv("MIRHI_TP_DENSITY")) : (m.tri_prog ? 16 : 4);
-    const bool dense = tiles && avg >= density;
-    m.tp_max_area = getenv("MIRHI_TP_MAX_AREA") ? (uint32_t)atoi(getenv("MIRHI_TP_MAX_AREA")) : (dense ? 64u : 0u);
-    if (key.pred) m.tp_max_area = 0;      // predicate scopes resolve pixel-parallel only (the LDS key array holds ordered keys)
-    else if (pass_is_masked_plain(pass) && m.tp_max_area == 0u) m.tp_max_area = 1u;    // alpha-masked scope: its records need the triangle-parallel path (LDS key array)
-    const bool mesh_only = !m.tri_prog && !pass.draws.empty() && !pass_is_depth_or_shadowed(pass);      // (their variants: one team of four waves)
-    m.teams = getenv("MIRHI_RASTER_TEAMS") ? (uint32_t)atoi(getenv("MIRHI_RASTER_TEAMS")) : (avg < 16 ? 2u : 1u);
-    if (!(m.tp_max_area && mesh_only && !pass_is_ordered(pass)) || m.teams != 2u) m.teams = 1u;
-    if (spread && !getenv("MIRHI_RASTER_TEAMS")) m.teams = 1u;      // measured on an earlier submission of this command buffer (Workspace::spread)
-    // per-XCD bins go with the concentrated-mesh mode (the geometry kernel's counter contention), whichever raster variant then reads them
-    m.xcd_bins = m.teams == 2u && !(getenv("MIRHI_XCD_BINS") && atoi(getenv("MIRHI_XCD_BINS")) == 0);
-    // The wide variants (eight / sixteen waves per tile, raster_body WPT) take over from both the plain and the two-team variant once the
-    // busy-tile count says the mesh sits in few tiles.  MIRHI_RASTER_WIDE = 0 / 8 / 16 forces it (tests, A/B runs); a forced
-    // MIRHI_RASTER_TEAMS = 2 keeps the two teams.
-    m.wide_eligible = m.tp_max_area && mesh_only && !pass_is_ordered(pass) && !pass_is_masked_plain(pass) && !key.pred &&
-                      !(getenv("MIRHI_RASTER_TEAMS") && atoi(getenv("MIRHI_RASTER_TEAMS")) == 2 && !getenv("MIRHI_RASTER_WIDE"));
-    if (m.wide_eligible) {
-        const uint32_t forced = getenv("MIRHI_RASTER_WIDE") ? (uint32_t)atoi(getenv("MIRHI_RASTER_WIDE")) : 0xFFFFFFFFu;
-        m.wide = forced == 0xFFFFFFFFu ? wide : (forced == 0u ? 0u : (forced == 8u ? 8u : 16u));
-        // (teams stays what the scope gets when a submit decides against the wide variant: see mirhi_queue_submit, "frames in flight")
-    }
-    return m;
-}
-
 // Sizes the workspace of a recorded command buffer and builds its launch plan.  Runs at end() -- unless the recording is the one the
 // current plan was built from -- and again in front of a submit when an earlier submission exhausted the bin pool
 // (Workspace::grow_pool) or showed a spread-out mesh (Workspace::replan).
@@ -2068,8 +1948,7 @@ static bool same_recording(const std::vector<RecordedPass>& a, const std::vector
         if (x.info.color_load_op != y.info.color_load_op || x.info.color_store_op != y.info.color_store_op || x.info.depth_load_op != y.info.depth_load_op ||
             x.info.depth_store_op != y.info.depth_store_op || memcmp(x.info.clear_color, y.info.clear_color, sizeof x.info.clear_color) != 0 ||
             memcmp(&x.info.clear_depth, &y.info.clear_depth, sizeof(float)) != 0) return false;
-        if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || x.key_set != y.key_set || x.depth_test != y.depth_test || x.depth_compare != y.depth_compare ||
-            x.depth_write != y.depth_write || x.frag_discard != y.frag_discard || memcmp(x.blend, y.blend, sizeof x.blend) != 0 ||
+        if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || !(x.state == y.state) ||
             x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
         if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl)) return false;
         if (x.draws.size() != y.draws.size() || x.draw_vb_bytes != y.draw_vb_bytes) return false;
@@ -2231,82 +2110,47 @@ static mirhi_result pblock_commit(Workspace& w, hipStream_t stream) {
     return MIRHI_OK;
 }
 
-static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
-    mirhi_device* dev = cmd->dev;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    if (cmd->lane >= dev->lanes.size()) cmd->lane = 0;
-    hipStream_t stream = dev->lanes[cmd->lane];
-    cmd->plan_valid = false;
-    { mirhi_result rs = settle_pending(cmd, in_submit); if (rs != MIRHI_OK) return rs; }
-    {
-        uint64_t tris_now = 0;
-        for (auto& pass : cmd->passes) tris_now += pass.total_tris - pass.first_tri;
-        if (cmd->ws.spread && (tris_now > 2 * cmd->ws.spread_tris || 2 * tris_now < cmd->ws.spread_tris)) cmd->ws.spread = false;
-    }
-    size_t total_draws = 0, max_tiles = 0, max_pages = 0, max_big = 0;
-    struct Geo { uint32_t tiles_x, tiles_y, r0, r1, rstep, bin_cap, sub_cap, big_cap, fixed_pages, fixed_per_tile; bool xcd_bins, tri_prog; };      // r0 / r1 / rstep: PassParams::tile_row_begin / _end / _step
-    std::vector<Geo> geo;
-    for (auto& pass : cmd->passes) {
-        const RecordedPass::Target& ci = pass.color_t;
-        Geo g;
-        g.tiles_x = (ci.width + TILE - 1) / TILE; g.tiles_y = (ci.height + TILE - 1) / TILE;
-        { uint32_t count; split_rows(dev->split_layout, dev->split_rank, dev->split_world, g.tiles_y, &g.r0, &g.rstep, &count); g.r1 = g.r0 + count; }
-        if (pass.depth_only) { g.r0 = 0; g.r1 = g.tiles_y; g.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
-        const size_t tiles = (size_t)g.tiles_x * (g.r1 - g.r0);
-        const RasterMode mode = raster_mode(pass, tiles, cmd->ws.spread, cmd->ws.wide);
-        g.xcd_bins = mode.xcd_bins; g.tri_prog = mode.tri_prog;      // tri_prog: some draw uses the TRIANGLE program
-        // A tile's bin holds up to BIN_TABLE_ROW pages (4096 records; eight lists of 512 with per-XCD bins) before it spills into
-        // the big list, which EVERY tile walks -- the limit costs nothing until it is used: pages come out of one pool, sized by
-        // the scope's triangle count, not by tiles x capacity (round 1: 100 MB at 1080p, 400-510 MB at 4K per command buffer).
-        // MIRHI_BIN_CAP (records per list, A/B runs and the spill tests) lowers it.
-        uint32_t cap = (uint32_t)BIN_TABLE_ROW * BIN_PAGE_RECS;
-        if (getenv("MIRHI_BIN_CAP")) cap = std::min<uint32_t>(cap, std::max<uint32_t>(8u * BIN_PAGE_RECS, ((uint32_t)atoi(getenv("MIRHI_BIN_CAP")) + 511u) & ~511u));
-        g.bin_cap = cap; g.sub_cap = g.xcd_bins ? cap / 8u : cap;
-        // Pool: the first page of every single-list bin has a fixed place (page = tile); the dynamic part is sized for the
-        // (triangle, tile) pairs the scope is likely to produce -- 8 per triangle for small scopes (scattered 50-pixel triangles
-        // make 5), towards 1.5 for big meshes (1.2 measured on the 1M-triangle grid) -- plus one partly filled page per list.  A scope
-        // that needs more spills into the big list (correct, slower) and the pool is doubled for the next submit.
-        const size_t tris = pass.total_tris - pass.first_tri;
-        size_t pairs = std::max(std::max(std::min<size_t>(8 * tris, 262144), std::min<size_t>(3 * tris, 786432)), 3 * tris / 2);
-        if (pairs > 16 * tris) pairs = 16 * tris;                        // (a binned triangle spans at most 4 x 4 tiles)
-        // fixed pages per tile: what the average density fills (x 1.3 for triangles that straddle tiles), at least one, at most eight --
-        // a uniform mesh (the 1M-triangle grid: 123 per tile) then bins without a single allocation, a concentrated one (the
-        // dancer asset) opens pages where its triangles are
-        g.fixed_per_tile = g.xcd_bins ? 0u : (uint32_t)std::min<size_t>(8, std::max<size_t>(1, tiles ? (13 * tris / (10 * tiles) + BIN_PAGE_RECS - 1) / BIN_PAGE_RECS : 1));
-        if (getenv("MIRHI_FIXED_PAGES") && !g.xcd_bins) g.fixed_per_tile = (uint32_t)std::min(8, std::max(1, atoi(getenv("MIRHI_FIXED_PAGES"))));   // (tests, A/B runs)
-        g.fixed_pages = g.fixed_per_tile * (uint32_t)tiles;
-        // dynamic part: the estimated pairs that the fixed pages will not take (they take at most half of it when the triangles sit
-        // in a part of the frame), never less than a quarter of the estimate, plus a partly filled page for one tile in four
-        const size_t fixed_capacity = (size_t)g.fixed_pages * BIN_PAGE_RECS;
-        const size_t dyn_records = std::max(pairs > fixed_capacity / 2 ? pairs - fixed_capacity / 2 : 0, pairs / 4) * cmd->ws.pool_scale;
-        size_t pages = g.fixed_pages + ((dyn_records / BIN_PAGE_RECS + tiles * (g.xcd_bins ? 8 : 1) / 4 + 64 + 7) & ~(size_t)7);
-        if (getenv("MIRHI_POOL_PAGES")) pages = g.fixed_pages + 8 * (((size_t)atoi(getenv("MIRHI_POOL_PAGES")) + 7) / 8);      // (pool-exhaustion test)
-        g.big_cap = pass.total_tris + pass.total_tris / 4 + 1024;
-        geo.push_back(g);
-        total_draws += pass.draws.size();
-        if (tiles > max_tiles) max_tiles = tiles;
-        if (pages > max_pages) max_pages = pages;
-        if (g.big_cap > max_big) max_big = g.big_cap;
-    }
+// ---- build_plan, step by step ----------------------------------------------------------------------
+// 1. what a scope is and how it is rastered and binned (mirhi_scope.h), on its share of the tile rows
+struct ScopePlan {
+    uint32_t tiles_x, tiles_y, r0, r1, rstep;      // r0 / r1 / rstep: PassParams::tile_row_begin / _end / _step
+    size_t tris;                                   // the segment's own triangles
+    ScopeClass cls; RasterMode mode; BinGeometry bins;
+    size_t tiles() const { return (size_t)tiles_x * (r1 - r0); }
+};
+static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, const Workspace& w, const PlanKnobs& knobs) {
+    ScopePlan s;
+    s.tiles_x = (pass.color_t.width + TILE - 1) / TILE; s.tiles_y = (pass.color_t.height + TILE - 1) / TILE;
+    { uint32_t count; split_rows(dev->split_layout, dev->split_rank, dev->split_world, s.tiles_y, &s.r0, &s.rstep, &count); s.r1 = s.r0 + count; }
+    if (pass.depth_only) { s.r0 = 0; s.r1 = s.tiles_y; s.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
+    s.tris = pass.total_tris - pass.first_tri;
+    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs);
+    s.mode = raster_mode(s.cls, s.tiles(), s.tris, w.spread, w.wide, knobs);
+    s.bins = bin_geometry(s.tiles(), s.tris, pass.total_tris, s.mode.xcd_bins, w.pool_scale, knobs);
+    return s;
+}
+
+// 2. bins, page table, big list and counters for the largest scope; the previous submission's status handed over; everything re-armed.
+// Buffers only ever grow, and a frame loop's do not: the steady state allocates nothing.  Counters and page table are cleared
+// when they are new (or after a frame that went wrong on the device: Workspace::dirty) -- never otherwise: every kernel leaves
+// them re-armed (raster_body: bin counters, table rows, pool counters, the other parity's big-list counter), and the fixed
+// words of the counter block do not move when the tile count changes (CTR_*).
+static mirhi_result rearm_workspace(mirhi_cmd* cmd, const std::vector<ScopePlan>& scopes, size_t max_tiles, hipStream_t stream, const PlanKnobs& knobs) {
     Workspace& w = cmd->ws;
     mirhi_result r;
-    // Buffers only ever grow, and a frame loop's do not: the steady state allocates nothing.  Counters and page table are cleared
-    // when they are new (or after a frame that went wrong on the device: Workspace::dirty) -- never otherwise: every kernel leaves
-    // them re-armed (raster_body: bin counters, table rows, pool counters, the other parity's big-list counter), and the fixed
-    // words of the counter block do not move when the tile count changes (CTR_*).
+    size_t max_pages = 0, max_big = 0;
+    bool any_xcd_bins = false;
+    for (const ScopePlan& s : scopes) { max_pages = std::max(max_pages, s.bins.pages); max_big = std::max<size_t>(max_big, s.bins.big_cap); any_xcd_bins |= s.mode.xcd_bins; }
     if ((r = grow(&w.bin_pool, &w.bin_pool_bytes, (max_pages ? max_pages : 1) * BIN_PAGE_RECS * sizeof(BinRec))) != MIRHI_OK) return r;
     {
         const bool had = w.bin_table != nullptr && w.bin_table_bytes >= (max_tiles ? max_tiles : 1) * BIN_TABLE_ROW * sizeof(uint32_t);
         if ((r = grow(&w.bin_table, &w.bin_table_bytes, (max_tiles ? max_tiles : 1) * BIN_TABLE_ROW * sizeof(uint32_t))) != MIRHI_OK) return r;
         if (!had) w.dirty = true;
     }
-    const size_t pool_pages = w.bin_pool_bytes / (BIN_PAGE_RECS * sizeof(BinRec));
-    w.xcd_tiles_last = (!geo.empty() && geo.back().xcd_bins) ? geo.back().tiles_x * (geo.back().r1 - geo.back().r0) : 0u;
+    w.xcd_tiles_last = (!scopes.empty() && scopes.back().mode.xcd_bins) ? (uint32_t)scopes.back().tiles() : 0u;
     if ((r = grow(&w.big_recs, &w.big_recs_bytes, (max_big ? max_big : 1) * sizeof(BigRec))) != MIRHI_OK) return r;
     {
         size_t counter_bytes = w.counters_words * 4;
-        bool any_xcd_bins = false;
-        for (const Geo& g : geo) any_xcd_bins |= g.xcd_bins;
         // fixed words (big-list and pool counters), then the bin counters: one per tile -- per tile and XCD in scopes with per-XCD bins -- 64 bytes apart
         const size_t want_words = CTR_BINS + (any_xcd_bins ? 8 : 1) * max_tiles * (size_t)BIN_COUNT_STRIDE;
         const bool had = w.counters && counter_bytes >= want_words * 4;
@@ -2314,7 +2158,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         w.counters_words = counter_bytes / 4;
         if (!had) w.dirty = true;
     }
-    if (getenv("MIRHI_ALWAYS_CLEAR")) w.dirty = true;             // (A/B runs: the round-2 behaviour, two memsets per recording)
+    if (knobs.always_clear.set) w.dirty = true;             // (A/B runs: the round-2 behaviour, two memsets per recording)
     if (!w.status_host) {
         HIP_TRY(hipHostMalloc((void**)&w.status_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(hipHostGetDevicePointer((void**)&w.status_dev, w.status_host, 0));
@@ -2324,7 +2168,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     w.grow_pool = false; w.replan = false;
     w.clear_status();
     w.big_counts = w.counters + CTR_BIG;
-    if (!w.dirty && getenv("MIRHI_VERIFY_IDLE")) {
+    if (!w.dirty && knobs.verify_idle.set) {
         // Test hook: what the plan relies on instead of clearing -- every kernel leaves the workspace re-armed -- is checked here, on the
         // host: all bin and pool counters zero, the big-list counter of the next parity zero, every page-table entry PAGE_EMPTY.
         HIP_TRY(hipStreamSynchronize(stream));
@@ -2340,80 +2184,151 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     if (w.dirty) {
         HIP_TRY(hipMemsetAsync(w.bin_table, 0xFF, w.bin_table_bytes, stream));          // PAGE_EMPTY
         HIP_TRY(hipMemsetAsync(w.counters, 0, w.counters_words * 4, stream));
-        dev->foreign_writes++;
+        cmd->dev->foreign_writes++;
         w.parity = 0;
         w.dirty = false;
         cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true;      // (a submit on another stream or queue waits for the clears)
     }
+    return MIRHI_OK;
+}
 
-    // vertex pre-pass jobs: one per distinct (vertex range, camera, object, program class) of each scope
-    struct HostJob { VsJob j; size_t out_off; };
-    std::vector<std::vector<HostJob>> pass_jobs(cmd->passes.size());
-    std::vector<std::vector<DrawDesc>> pass_draws(cmd->passes.size());      // the recorded descriptors stay as recorded (plan cache); these get the plan's fields
-    size_t vs_bytes_max = 0, jobs_total = 0;
-    for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
-        RecordedPass& pass = cmd->passes[pi];
-        pass_draws[pi] = pass.draws;
-        size_t off = 0; uint32_t slots = 0;
-        for (size_t di = 0; di < pass.draws.size(); di++) {
-            DrawDesc& dd = pass_draws[pi][di];
-            dd.vs_words = 0; dd.vs_out = nullptr; dd.vs_attr = nullptr;
-            if (dd.program == MIRHI_PROGRAM_TRIANGLE) continue;
-            const uint32_t words = dd.program == MIRHI_PROGRAM_SHADOW ? 1u : (dd.program == MIRHI_PROGRAM_MODEL ? 3u : 5u);   // (SHADOW: the clip stream only)
-            const uint64_t vbb = pass.draw_vb_bytes[di];
-            const uint64_t vsz = dd.program == MIRHI_PROGRAM_SHADOW ? 12u : 48u;
-            const uint32_t count = vbb >= vsz ? (uint32_t)((vbb - vsz) / dd.stride + 1) : 0u;
-            size_t found = SIZE_MAX;
-            for (size_t j = 0; j < pass_jobs[pi].size(); j++) {
-                const VsJob& J = pass_jobs[pi][j].j;
-                if (J.vb == dd.vb && J.camera == dd.camera && J.object == dd.object && J.stride == dd.stride && J.words >= words && (J.words == 1u) == (words == 1u) && J.count >= count) { found = j; break; }
-            }
-            if (found == SIZE_MAX) {
-                HostJob hj{};
-                hj.j.vb = dd.vb; hj.j.camera = dd.camera; hj.j.object = dd.object; hj.j.stride = dd.stride; hj.j.count = count;
-                hj.j.words = words; hj.j.slot_base = slots; hj.out_off = off;
-                slots += (count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
-                off += vs_attr_offset(count) + (((size_t)count * (words - 1u) * 16 + 255) & ~(size_t)255);      // clip stream, then the attribute stream
-                pass_jobs[pi].push_back(hj);
-                found = pass_jobs[pi].size() - 1;
-            }
-            dd.vs_words = pass_jobs[pi][found].j.words;
-            dd.vs_out = (const void*)(uintptr_t)(pass_jobs[pi][found].out_off + 1);   // offset + 1, patched to a pointer below
-            dd.vs_attr = (const void*)(uintptr_t)(pass_jobs[pi][found].out_off + vs_attr_offset(pass_jobs[pi][found].j.count) + 1);
+// 3. vertex pre-pass jobs of one scope: one per distinct (vertex range, camera, object, program class).  The recorded descriptors stay as recorded
+// (plan cache); `draws` are copies with the plan's fields, vs_out / vs_attr as offset + 1 into the scope's output (patched to pointers in step 4)
+struct VertexPlan { std::vector<VsJob> jobs; std::vector<size_t> out_off; std::vector<DrawDesc> draws; size_t out_bytes = 0; };
+static VertexPlan vertex_jobs(const RecordedPass& pass) {
+    VertexPlan v;
+    v.draws = pass.draws;
+    uint32_t slots = 0;
+    for (size_t di = 0; di < pass.draws.size(); di++) {
+        DrawDesc& dd = v.draws[di];
+        dd.vs_words = 0; dd.vs_out = nullptr; dd.vs_attr = nullptr;
+        if (dd.program == MIRHI_PROGRAM_TRIANGLE) continue;
+        const uint32_t words = dd.program == MIRHI_PROGRAM_SHADOW ? 1u : (dd.program == MIRHI_PROGRAM_MODEL ? 3u : 5u);   // (SHADOW: the clip stream only)
+        const uint64_t vbb = pass.draw_vb_bytes[di];
+        const uint64_t vsz = dd.program == MIRHI_PROGRAM_SHADOW ? 12u : 48u;
+        const uint32_t count = vbb >= vsz ? (uint32_t)((vbb - vsz) / dd.stride + 1) : 0u;
+        size_t found = SIZE_MAX;
+        for (size_t j = 0; j < v.jobs.size(); j++) {
+            const VsJob& J = v.jobs[j];
+            if (J.vb == dd.vb && J.camera == dd.camera && J.object == dd.object && J.stride == dd.stride && J.words >= words && (J.words == 1u) == (words == 1u) && J.count >= count) { found = j; break; }
         }
-        if (off > vs_bytes_max) vs_bytes_max = off;
-        jobs_total += pass_jobs[pi].size();
+        if (found == SIZE_MAX) {
+            VsJob j{};
+            j.vb = dd.vb; j.camera = dd.camera; j.object = dd.object; j.stride = dd.stride; j.count = count;
+            j.words = words; j.slot_base = slots;
+            slots += (count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
+            v.jobs.push_back(j); v.out_off.push_back(v.out_bytes);
+            v.out_bytes += vs_attr_offset(count) + (((size_t)count * (words - 1u) * 16 + 255) & ~(size_t)255);      // clip stream, then the attribute stream
+            found = v.jobs.size() - 1;
+        }
+        dd.vs_words = v.jobs[found].words;
+        dd.vs_out = (const void*)(uintptr_t)(v.out_off[found] + 1);
+        dd.vs_attr = (const void*)(uintptr_t)(v.out_off[found] + vs_attr_offset(v.jobs[found].count) + 1);
     }
-    if ((r = grow(&w.vs_out, &w.vs_out_bytes, vs_bytes_max ? vs_bytes_max : 256)) != MIRHI_OK) return r;
-    {
-        size_t carry = 0;
-        for (auto& pass : cmd->passes)
-            if ((pass.carry_in || pass.carry_out) && !pass.depth_t.ptr) {
-                const size_t need = (size_t)pass.color_t.width * pass.color_t.height * 4;
-                if (need > carry) carry = need;
-            }
-        if (carry && (r = grow(&w.carry_depth, &w.carry_depth_bytes, carry)) != MIRHI_OK) return r;
+    return v;
+}
+
+// ... and the buffers whose size the scopes' contents decide: vertex output, depth hand-over, ordered records, flat colours, primitive -> draw
+static mirhi_result grow_scope_buffers(Workspace& w, const std::vector<RecordedPass>& passes, const std::vector<ScopePlan>& scopes, const std::vector<VertexPlan>& vertex) {
+    mirhi_result r;
+    size_t vs_bytes = 0, carry = 0, ord = 0, flat_tris = 0, pd = 0;
+    for (size_t pi = 0; pi < passes.size(); pi++) {
+        const RecordedPass& pass = passes[pi];
+        vs_bytes = std::max(vs_bytes, vertex[pi].out_bytes);
+        if ((pass.carry_in || pass.carry_out) && !pass.depth_t.ptr) carry = std::max(carry, (size_t)pass.color_t.width * pass.color_t.height * 4);
+        if (scopes[pi].cls.ordered) ord = std::max(ord, scopes[pi].tris * sizeof(TriRec));
+        if (scopes[pi].cls.tri_prog && pass.color_t.format == MIRHI_FORMAT_B8G8R8A8_SRGB) flat_tris = std::max<size_t>(flat_tris, pass.total_tris);
+        if (pass.draws.size() > 1) pd = std::max(pd, scopes[pi].tris);
     }
-    {
-        size_t ord = 0;
-        for (auto& pass : cmd->passes)
-            if (pass_is_ordered(pass)) { const size_t need = (size_t)(pass.total_tris - pass.first_tri) * sizeof(TriRec); if (need > ord) ord = need; }
-        if (ord && (r = grow(&w.ordered, &w.ordered_bytes, ord)) != MIRHI_OK) return r;
-    }
-    size_t flat_tris = 0;
-    for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
-        const RecordedPass& pass = cmd->passes[pi];
-        if (geo[pi].tri_prog && pass.color_t.format == MIRHI_FORMAT_B8G8R8A8_SRGB && pass.total_tris > flat_tris) flat_tris = pass.total_tris;
-    }
+    if ((r = grow(&w.vs_out, &w.vs_out_bytes, vs_bytes ? vs_bytes : 256)) != MIRHI_OK) return r;
+    if (carry && (r = grow(&w.carry_depth, &w.carry_depth_bytes, carry)) != MIRHI_OK) return r;
+    if (ord && (r = grow(&w.ordered, &w.ordered_bytes, ord)) != MIRHI_OK) return r;
     if (flat_tris && (r = grow(&w.flat_color, &w.flat_color_bytes, flat_tris * 4)) != MIRHI_OK) return r;
-    {
-        size_t pd = 0;
-        for (auto& pass : cmd->passes)
-            if (pass.draws.size() > 1 && (size_t)(pass.total_tris - pass.first_tri) > pd) pd = pass.total_tris - pass.first_tri;
-        if (pd && (r = grow(&w.prim_draw, &w.prim_draw_bytes, pd * 4)) != MIRHI_OK) return r;
+    if (pd && (r = grow(&w.prim_draw, &w.prim_draw_bytes, pd * 4)) != MIRHI_OK) return r;
+    return MIRHI_OK;
+}
+
+// 4. one scope's parameters from its class, mode, bins and the workspace (the draws and vertex jobs are placed by build_plan)
+static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, const RasterMode& mode, const Workspace& w, size_t max_tiles, unsigned long long* frag_stats) {
+    const RecordedPass::Target& ci = pass.color_t;
+    const size_t pool_pages = w.bin_pool_bytes / (BIN_PAGE_RECS * sizeof(BinRec));
+    PassParams P;
+    memset(&P, 0, sizeof P);
+    P.width = ci.width; P.height = ci.height;
+    P.tiles_x = s.tiles_x; P.tiles_y = s.tiles_y; P.tile_row_begin = s.r0; P.tile_row_end = s.r1; P.tile_row_step = s.rstep;
+    P.num_draws = (uint32_t)pass.draws.size(); P.total_tris = pass.total_tris;
+    set_raster_choice(P, s.cls, mode, pass.state, w.ordered, pass.first_tri, pass.total_tris);
+    memcpy(P.clear_color, pass.info.clear_color, sizeof P.clear_color);
+    {   // sRGB OETF + UNORM8 of the clear colour, BGRA byte order (swapchain.rs:561-570)
+        auto sat = [](float c) { return c > 0.0f ? (c < 1.0f ? c : 1.0f) : 0.0f; };
+        auto enc = [&](float c) { c = sat(c); float e = c <= 0.0031308f ? 12.92f * c : 1.055f * std::pow(c, 1.0f / 2.4f) - 0.055f; return (uint32_t)std::nearbyint(sat(e) * 255.0f); };
+        P.clear_packed = enc(P.clear_color[2]) | (enc(P.clear_color[1]) << 8) | (enc(P.clear_color[0]) << 16) |
+                         ((uint32_t)std::nearbyint(sat(P.clear_color[3]) * 255.0f) << 24);
     }
+    P.color_load = pass.info.color_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
+    P.color_format = ci.format;
+    P.color = const_cast<uint8_t*>(ci.ptr);
+    if (pass.depth_t.ptr) {
+        P.depth = (float*)const_cast<uint8_t*>(pass.depth_t.ptr);
+        P.depth_load = pass.info.depth_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
+        P.depth_store = pass.info.depth_store_op == MIRHI_STORE_OP_STORE ? 1u : 0u;
+    } else if (pass.carry_in || pass.carry_out) {
+        P.depth = w.carry_depth;               // no depth attachment: the segments of the scope hand depth over here
+    }
+    if (pass.carry_in) P.depth_load = 1u;
+    if (pass.carry_out) P.depth_store = 1u;
+    P.prim_out = (uint32_t*)const_cast<uint8_t*>(pass.prim_t.ptr);
+    P.bin_pool = w.bin_pool; P.bin_count = w.counters + CTR_BINS; P.bin_cap = s.bins.bin_cap;
+    P.bin_table = w.bin_table; P.pool_next = w.counters + CTR_POOL;
+    P.pool_dyn_base = s.bins.fixed_pages; P.pool_dyn_pages = (uint32_t)((pool_pages - s.bins.fixed_pages) / 8);      // per XCD
+    P.fixed_recs = s.bins.fixed_per_tile * BIN_PAGE_RECS;
+    P.big_recs = w.big_recs; P.big_count = w.big_counts; P.big_count_next = w.big_counts + 1; P.big_cap = s.bins.big_cap;
+    P.status = w.status_dev;
+    P.frag_stats = frag_stats;
+    P.first_prim = pass.first_tri;
+    P.prim_draw = pass.draws.size() > 1 ? w.prim_draw : nullptr;
+    P.flat_color = (s.cls.tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB) ? w.flat_color : nullptr;
+    P.resolve_flat_only = (P.flat_color && !P.depth_load && P.color_format != 2u && !P.prim_out && !(P.depth && P.depth_store)) ? 1u : 0u;
+    P.sub_cap = s.bins.sub_cap;                                       // (the bins are those the workspace was sized for: s.mode, not `mode`)
+    P.count_stride = s.mode.xcd_bins ? (uint32_t)max_tiles : 0u;
+    P.depth_only = pass.depth_only ? 1u : 0u;
+    if (P.ibl) {
+        P.ibl_irradiance = (const float*)pass.ibl.irradiance; P.ibl_prefiltered = (const float*)pass.ibl.prefiltered; P.ibl_lut = (const float*)pass.ibl.lut;
+        P.ibl_irr_size = pass.ibl.irr_size; P.ibl_pre_size = pass.ibl.pre_size; P.ibl_pre_levels = pass.ibl.pre_levels; P.ibl_lut_size = pass.ibl.lut_size;
+    }
+    return P;
+}
+
+static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
+    const PlanKnobs knobs = PlanKnobs::read();
+    mirhi_device* dev = cmd->dev;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    if (cmd->lane >= dev->lanes.size()) cmd->lane = 0;
+    hipStream_t stream = dev->lanes[cmd->lane];
+    cmd->plan_valid = false;
+    { mirhi_result rs = settle_pending(cmd, in_submit); if (rs != MIRHI_OK) return rs; }
+    Workspace& w = cmd->ws;
+    const size_t n = cmd->passes.size();
+    {
+        uint64_t tris_now = 0;
+        for (auto& pass : cmd->passes) tris_now += pass.total_tris - pass.first_tri;
+        if (w.spread && (tris_now > 2 * w.spread_tris || 2 * tris_now < w.spread_tris)) w.spread = false;
+    }
+    mirhi_result r;
+    std::vector<ScopePlan> scopes;
+    size_t total_draws = 0, max_tiles = 0;
+    for (const RecordedPass& pass : cmd->passes) {
+        scopes.push_back(plan_scope(dev, pass, w, knobs));
+        total_draws += pass.draws.size();
+        max_tiles = std::max(max_tiles, scopes.back().tiles());
+    }
+    if ((r = rearm_workspace(cmd, scopes, max_tiles, stream, knobs)) != MIRHI_OK) return r;
+    std::vector<VertexPlan> vertex;
+    size_t jobs_total = 0;
+    for (const RecordedPass& pass : cmd->passes) { vertex.push_back(vertex_jobs(pass)); jobs_total += vertex.back().jobs.size(); }
+    if ((r = grow_scope_buffers(w, cmd->passes, scopes, vertex)) != MIRHI_OK) return r;
     // the parameter block: [2 x PassParams per scope][draw descriptors][vertex jobs]
-    const size_t params_bytes = cmd->passes.size() * 2 * sizeof(PassParams);
+    const size_t params_bytes = n * 2 * sizeof(PassParams);
     w.draws_off = (params_bytes + 255) & ~(size_t)255;
     w.jobs_off = (w.draws_off + total_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
     const size_t block_bytes = w.jobs_off + jobs_total * sizeof(VsJob);
@@ -2425,103 +2340,36 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     w.draws_count = total_draws;
 
     size_t draws_done = 0, jobs_done = 0;
-    bool any_wide_eligible = false;
+    w.wide_eligible = false;
     cmd->plan.clear(); cmd->plan_programs.clear(); cmd->plan_tris = 0;
-    for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
-        RecordedPass& pass = cmd->passes[pi];
-        std::vector<DrawDesc>& draws = pass_draws[pi];
-        const Geo& g = geo[pi];
-        const RecordedPass::Target& ci = pass.color_t;
-        PassParams P;
-        memset(&P, 0, sizeof P);
-        P.width = ci.width; P.height = ci.height;
-        P.tiles_x = g.tiles_x; P.tiles_y = g.tiles_y; P.tile_row_begin = g.r0; P.tile_row_end = g.r1; P.tile_row_step = g.rstep;
-        P.num_draws = (uint32_t)draws.size(); P.total_tris = pass.total_tris;
+    for (size_t pi = 0; pi < n; pi++) {
+        const ScopePlan& s = scopes[pi];
+        VertexPlan& v = vertex[pi];
+        // (the mode is evaluated again, not kept from step 1: hand_over_status in between may have changed w.spread / w.wide)
+        const RasterMode mode = raster_mode(s.cls, s.tiles(), s.tris, w.spread, w.wide, knobs);
+        w.wide_eligible |= mode.wide_eligible;
+        PassParams P = fill_params(cmd->passes[pi], s, mode, w, max_tiles, dev->frag_stats);
         P.draws = dev_draws + draws_done;
-        depth_key_setup(P, pass);
-        if (pass_is_ordered(pass)) {
-            P.ordered_recs = w.ordered; P.ordered_first = pass.first_tri; P.ordered_count = pass.total_tris - pass.first_tri;
-            P.ord_depth_test = pass.depth_test; P.ord_depth_write = pass.depth_write; P.ord_depth_op = pass.depth_compare;
-            memcpy(P.blend, pass.blend, sizeof P.blend);
-            P.idflip = 0; P.pred = 0;               // records carry the plain primitive id; the kernel applies the depth state itself
-        }
-        memcpy(P.clear_color, pass.info.clear_color, sizeof P.clear_color);
-        {   // sRGB OETF + UNORM8 of the clear colour, BGRA byte order (swapchain.rs:561-570)
-            auto sat = [](float c) { return c > 0.0f ? (c < 1.0f ? c : 1.0f) : 0.0f; };
-            auto enc = [&](float c) { c = sat(c); float e = c <= 0.0031308f ? 12.92f * c : 1.055f * std::pow(c, 1.0f / 2.4f) - 0.055f; return (uint32_t)std::nearbyint(sat(e) * 255.0f); };
-            P.clear_packed = enc(P.clear_color[2]) | (enc(P.clear_color[1]) << 8) | (enc(P.clear_color[0]) << 16) |
-                             ((uint32_t)std::nearbyint(sat(P.clear_color[3]) * 255.0f) << 24);
-        }
-        P.color_load = pass.info.color_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
-        P.color_format = ci.format;
-        P.color = const_cast<uint8_t*>(ci.ptr);
-        if (pass.depth_t.ptr) {
-            P.depth = (float*)const_cast<uint8_t*>(pass.depth_t.ptr);
-            P.depth_load = pass.info.depth_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
-            P.depth_store = pass.info.depth_store_op == MIRHI_STORE_OP_STORE ? 1u : 0u;
-        } else if (pass.carry_in || pass.carry_out) {
-            P.depth = w.carry_depth;               // no depth attachment: the segments of the scope hand depth over here
-        }
-        if (pass.carry_in) P.depth_load = 1u;
-        if (pass.carry_out) P.depth_store = 1u;
-        P.prim_out = (uint32_t*)const_cast<uint8_t*>(pass.prim_t.ptr);
-        P.bin_pool = w.bin_pool; P.bin_count = w.counters + CTR_BINS; P.bin_cap = g.bin_cap;
-        P.bin_table = w.bin_table; P.pool_next = w.counters + CTR_POOL;
-        P.pool_dyn_base = g.fixed_pages; P.pool_dyn_pages = (uint32_t)((pool_pages - g.fixed_pages) / 8);      // per XCD
-        P.fixed_recs = g.fixed_per_tile * BIN_PAGE_RECS;
-        P.big_recs = w.big_recs; P.big_count = w.big_counts; P.big_count_next = w.big_counts + 1; P.big_cap = g.big_cap;
-        P.status = w.status_dev;
-        P.frag_stats = dev->frag_stats;
-        P.first_prim = pass.first_tri;
-        P.prim_draw = draws.size() > 1 ? w.prim_draw : nullptr;
-        P.flat_color = (g.tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB) ? w.flat_color : nullptr;
-        P.resolve_flat_only = (P.flat_color && !P.depth_load && P.color_format != 2u && !P.prim_out && !(P.depth && P.depth_store)) ? 1u : 0u;
-        {
-            // (evaluated again, not kept from the sizing loop above: hand_over_status in between may have changed w.spread / w.wide)
-            const RasterMode mode = raster_mode(pass, (size_t)g.tiles_x * (g.r1 - g.r0), w.spread, w.wide);
-            P.tp_max_area = mode.tp_max_area;
-            P.alpha_scope = pass_is_masked_plain(pass) ? 1u : 0u;
-            P.raster_teams = mode.teams;
-            P.raster_wide = mode.wide;          // waves per tile of the wide variants: 0 (four waves), 8 or 16
-            any_wide_eligible |= mode.wide_eligible;
-            P.sub_cap = g.sub_cap;
-            P.count_stride = g.xcd_bins ? (uint32_t)max_tiles : 0u;
-        }
-        P.xcd_swizzle = getenv("MIRHI_XCD_RUN") ? (uint32_t)atoi(getenv("MIRHI_XCD_RUN")) : 1u;
-        P.depth_only = pass.depth_only ? 1u : 0u;
-        for (const DrawDesc& dd : draws) P.shadowed |= dd.shadow_map ? (dd.shadow_layers ? 2u : 1u) : 0u;      // (never both in one scope: record_draw)
-        for (const DrawDesc& dd : draws) P.ibl |= dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL ? 1u : 0u;
-        if (P.ibl) {
-            P.ibl_irradiance = (const float*)pass.ibl.irradiance; P.ibl_prefiltered = (const float*)pass.ibl.prefiltered; P.ibl_lut = (const float*)pass.ibl.lut;
-            P.ibl_irr_size = pass.ibl.irr_size; P.ibl_pre_size = pass.ibl.pre_size; P.ibl_pre_levels = pass.ibl.pre_levels; P.ibl_lut_size = pass.ibl.lut_size;
-        }
-        if (P.depth_only || P.shadowed || P.ibl) { P.xcd_swizzle = 1u; P.raster_wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
         P.vs_jobs = dev_jobs + jobs_done;
-        P.num_vs_jobs = (uint32_t)pass_jobs[pi].size();
-        P.vs_total_slots = 0;
+        P.num_vs_jobs = (uint32_t)v.jobs.size();
         VsJob* const img_jobs = reinterpret_cast<VsJob*>(w.pimage.data() + w.jobs_off) + jobs_done;
-        for (size_t j = 0; j < pass_jobs[pi].size(); j++) {
-            HostJob& hj = pass_jobs[pi][j];
-            hj.j.out = w.vs_out + hj.out_off;
-            P.vs_total_slots = hj.j.slot_base + (hj.j.count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
-            img_jobs[j] = hj.j;
+        for (size_t j = 0; j < v.jobs.size(); j++) {
+            v.jobs[j].out = w.vs_out + v.out_off[j];
+            P.vs_total_slots = v.jobs[j].slot_base + (v.jobs[j].count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
+            img_jobs[j] = v.jobs[j];
         }
-        jobs_done += pass_jobs[pi].size();
-        for (DrawDesc& dd : draws)
-            if (dd.vs_words) { dd.vs_out = w.vs_out + ((size_t)(uintptr_t)dd.vs_out - 1); dd.vs_attr = w.vs_out + ((size_t)(uintptr_t)dd.vs_attr - 1); }
+        jobs_done += v.jobs.size();
         uint32_t slots = 0;
-        for (DrawDesc& dd : draws) { dd.slot_base = slots; slots += (dd.tri_count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS; }
+        for (DrawDesc& dd : v.draws) {
+            if (dd.vs_words) { dd.vs_out = w.vs_out + ((size_t)(uintptr_t)dd.vs_out - 1); dd.vs_attr = w.vs_out + ((size_t)(uintptr_t)dd.vs_attr - 1); }
+            dd.slot_base = slots; slots += (dd.tri_count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
+        }
         P.total_slots = slots;
-        if (!draws.empty()) memcpy(w.pimage.data() + w.draws_off + draws_done * sizeof(DrawDesc), draws.data(), draws.size() * sizeof(DrawDesc));
-        draws_done += draws.size();
+        if (!v.draws.empty()) memcpy(w.pimage.data() + w.draws_off + draws_done * sizeof(DrawDesc), v.draws.data(), v.draws.size() * sizeof(DrawDesc));
+        draws_done += v.draws.size();
         cmd->plan.push_back(P);
-        uint32_t progs = 0;         // the scope's program set (mirhi_variant.h)
-        for (const DrawDesc& dd : draws)
-            progs |= dd.program == MIRHI_PROGRAM_TRIANGLE ? PROGS_TRIANGLE : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL || dd.tex_any_mips || dd.tex_srgb) ? PROGS_PBR : PROGS_MODEL);
-        if (P.shadowed) progs = PROGS_PBR | PROGS_SHADOWED | (P.shadowed == 2u ? PROGS_CASCADED : 0u);
-        if (P.ibl) progs = PROGS_PBR | PROGS_IBL | (P.shadowed ? PROGS_SHADOWED : 0u) | (P.shadowed == 2u ? PROGS_CASCADED : 0u);
-        cmd->plan_programs.push_back(P.depth_only ? PROGS_DEPTH_ONLY : (progs ? progs : PROGS_TRIANGLE));
-        cmd->plan_tris += pass.total_tris - pass.first_tri;
+        cmd->plan_programs.push_back(s.cls.programs);
+        cmd->plan_tris += s.tris;
         // the kernels read their parameters from the block: copy 2*pi + parity of scope pi appends large triangles to counter
         // `parity` and re-arms the other one for the scope that follows on this workspace
         for (uint32_t parity = 0; parity < 2; parity++) {
@@ -2533,7 +2381,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
             memcpy(w.pimage.data() + (2 * pi + parity) * sizeof(PassParams), &Q, sizeof Q);
         }
     }
-    w.wide_eligible = any_wide_eligible;
+    // 5. commit
     if ((r = pblock_commit(w, stream)) != MIRHI_OK) return r;
     if (!w.pblock_direct) { cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true; }     // (the copy is in the lane's stream)
     { std::lock_guard<std::mutex> lk(dev->mu); cmd->planned = cmd->passes; }      // (settle_readers scans `planned` of pending command buffers under this lock)
@@ -2541,6 +2389,42 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     cmd->plan_valid = true;
     dev->stats.workspace_bytes = w.bytes();
     return MIRHI_OK;
+}
+
+// Outside the C ABI (not in include/mirhi.h) and without a HIP call: what build_plan decides for one scope -- class, raster mode (one evaluation),
+// bins -- and the kernel, grid and block that raster_variant then gives at 5 x 4 tiles.  The environment is read as build_plan reads it.
+// in: DepthState key_set, test, compare, write, discard, blend enable; clear-depth float bits; depth_only; tiles; triangles; spread; wide; pool_scale;
+// allow_wide; number of draws (at most 4); per draw: program, shadow kind 0 / 1 / 2, "has a mip chain or an sRGB texture".
+// out: the key's eight words; ordered, masked_plain, tri_prog, shadowed, ibl, own_family, programs; tp_max_area, teams, wide_eligible, xcd_bins, wide,
+// xcd_swizzle; bin_cap, sub_cap, fixed_per_tile, fixed_pages, pool pages (low, high word), big_cap; grid x, y, z, block.
+extern "C" int mirhi_debug_raster_choice(const uint32_t in[12], char* name, uint32_t name_len, uint32_t grid_block[4]);
+extern "C" int mirhi_debug_scope_plan(const uint32_t* in, uint32_t* out, char* name, uint32_t name_len) {
+    static float some_map; static TriRec some_recs;
+    const PlanKnobs knobs = PlanKnobs::read();
+    DepthState s;
+    s.key_set = in[0] != 0u; s.test = in[1]; s.compare = in[2]; s.write = in[3]; s.discard = in[4]; s.blend[0] = in[5];
+    float clear_depth; memcpy(&clear_depth, &in[6], 4);
+    const uint32_t n = in[14];
+    if (n > 4u) return -1;
+    DrawDesc draws[4];
+    memset(draws, 0, sizeof draws);
+    for (uint32_t i = 0; i < n; i++) {
+        draws[i].program = in[15 + 3 * i];
+        if (in[16 + 3 * i]) { draws[i].shadow_map = &some_map; draws[i].shadow_layers = in[16 + 3 * i] == 2u ? 4u : 0u; }
+        draws[i].tex_any_mips = in[17 + 3 * i];
+    }
+    const ScopeClass c = classify_scope(s, clear_depth, draws, n, in[7] != 0u, knobs);
+    const RasterMode m = raster_mode(c, in[8], in[9], in[10] != 0u, in[11], knobs);
+    const BinGeometry g = bin_geometry(in[8], in[9], in[9], m.xcd_bins, in[12], knobs);
+    const uint32_t words[28] = {c.key.clear_depth_bits, c.key.pred, c.key.zflip, c.key.zmask, c.key.idflip, c.key.strict, c.key.init_zk, c.key.init_idk,
+                                c.ordered, c.masked_plain, c.tri_prog, c.shadowed, c.ibl, c.own_family, c.programs,
+                                m.tp_max_area, m.teams, m.wide_eligible, m.xcd_bins, m.wide, m.xcd_swizzle,
+                                g.bin_cap, g.sub_cap, g.fixed_per_tile, g.fixed_pages, (uint32_t)g.pages, (uint32_t)((uint64_t)g.pages >> 32), g.big_cap};
+    memcpy(out, words, sizeof words);
+    PassParams P{};
+    set_raster_choice(P, c, m, s, &some_recs, 0u, in[9]);
+    const uint32_t choice[12] = {c.programs, in[13], P.pred, P.zflip, P.zmask, P.tp_max_area, P.raster_teams, P.raster_wide, P.alpha_scope, P.xcd_swizzle, P.ordered_recs ? 1u : 0u, 0u};
+    return mirhi_debug_raster_choice(choice, name, name_len, out + 28);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2715,8 +2599,9 @@ extern "C" mirhi_result mirhi_queue_submit(mirhi_device* dev, uint32_t cmd_count
 
 static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd* const* cmds, mirhi_fence* fence) {
     HIP_TRY(hipSetDevice(dev->ordinal));
+    const PlanKnobs knobs = PlanKnobs::read();
     for (uint32_t i = 0; i < cmd_count; i++)
-        if ((cmds[i]->ws.grow_pool && !getenv("MIRHI_POOL_PAGES")) || cmds[i]->ws.replan) {   // an earlier submission ran out of bin pages (a bigger pool, the same plan) or showed a spread-out mesh (one team)
+        if ((cmds[i]->ws.grow_pool && !knobs.pool_pages.set) || cmds[i]->ws.replan) {   // an earlier submission ran out of bin pages (a bigger pool, the same plan) or showed a spread-out mesh (one team)
             const mirhi_result rp = build_plan(cmds[i], true);
             if (rp != MIRHI_OK) return rp;
         }
@@ -2816,7 +2701,7 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
         // MAX_FRAMES_IN_FLIGHT = 2 loop does, a loop that keeps four frames queued gets the plain / two-team variants.
         int in_flight = 1;
         for (const mirhi_cmd* o : dev->cmds) in_flight += (o != c && o->pending) ? 1 : 0;
-        const bool allow_wide = in_flight <= 2 || getenv("MIRHI_RASTER_WIDE") != nullptr;
+        const bool allow_wide = in_flight <= 2 || knobs.raster_wide.set;
         c->last_stream = use_native ? nullptr : stream; c->last_native = use_native ? nq : nullptr; c->pending = true; c->submit_seq++;
         { const mirhi_result ro = order_attachments(dev, c, stream, use_native ? nq : nullptr); if (ro != MIRHI_OK) return ro; }
         if (std::find(dev->unchecked.begin(), dev->unchecked.end(), c) == dev->unchecked.end()) dev->unchecked.push_back(c);
@@ -2961,7 +2846,7 @@ static mirhi_result status_of(mirhi_device* dev, mirhi_cmd* c) {
             else if (b <= (cur == 16u ? 300u : 240u)) want = 16u;
             else if (b <= (cur == 8u ? 640u : 512u)) want = 8u;
             else want = 0u;
-            if (want != cur && c->ws.wide_eligible && !getenv("MIRHI_RASTER_WIDE")) { c->ws.wide = want; c->ws.replan = true; }
+            if (want != cur && c->ws.wide_eligible && !PlanKnobs::read().raster_wide.set) { c->ws.wide = want; c->ws.replan = true; }
         }
         if (feedback && !c->ws.spread && c->ws.xcd_tiles_last && c->ws.status_host[2] > 2u * c->ws.xcd_tiles_last) { c->ws.spread = true; c->ws.replan = true; c->ws.spread_tris = c->plan_tris; }
         if (c->ws.status_host[0] & (STATUS_PAGE_TIMEOUT | STATUS_BIG_OVERFLOW)) c->ws.dirty = true;     // counters / page table are cleared before the next frame
