@@ -109,6 +109,11 @@ impl CommandBuffer {
         let (irradiance, prefiltered, brdf_lut) = set.map_or((n, n, n), |(a, b, c)| (a.raw, b.raw, c.raw));
         check(unsafe { mirhi_sys::mirhi_cmd_bind_ibl(self.raw, irradiance, prefiltered, brdf_lut) })
     }
+    /// Set 0 of pixel/skybox.hlsl: the environment cube of `ShaderProgram::Skybox` draws (`draw(3, 1, 0, 0)`; the first 64 bytes of
+    /// the push constants are inverseViewProjection); `None` unbinds.
+    pub fn bind_skybox(&self, environment: Option<&Image>) -> RhiResult<()> {
+        check(unsafe { mirhi_sys::mirhi_cmd_bind_skybox(self.raw, environment.map_or(std::ptr::null_mut(), |i| i.raw)) })
+    }
     pub fn set_viewport(&self, v: &Viewport) -> RhiResult<()> {                                                      // :522
         let raw = mirhi_sys::mirhi_viewport { x: v.x, y: v.y, width: v.width, height: v.height, min_depth: v.min_depth, max_depth: v.max_depth };
         check(unsafe { mirhi_sys::mirhi_cmd_set_viewport(self.raw, &raw) })

@@ -23,7 +23,7 @@ pub enum BlendOp { Add = 0, Subtract = 1, ReverseSubtract = 2, Min = 3, Max = 4 
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum ShaderStage { Vertex, Fragment }
 #[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)]
-pub enum ShaderProgram { Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4, ModelPbrIbl = 5 }
+pub enum ShaderProgram { Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4, ModelPbrIbl = 5, Skybox = 6 }
 
 /// pipeline.rs:499-529
 #[derive(Clone, Copy, Debug)]
@@ -58,6 +58,7 @@ impl Shader {
                       else if name.starts_with("model_pbr_ibl") { ShaderProgram::ModelPbrIbl }
                       else if name.starts_with("model_pbr") { ShaderProgram::ModelPbr }
                       else if name.starts_with("shadow") { ShaderProgram::Shadow }
+                      else if name.starts_with("skybox") { ShaderProgram::Skybox }
                       else if name.starts_with("model_full") { ShaderProgram::ModelFull }
                       else if name.starts_with("model") { ShaderProgram::Model }
                       else { return Err(RhiError::ShaderError(format!("Shader error: no precompiled program for '{name}'"))); };

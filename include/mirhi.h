@@ -34,7 +34,8 @@ extern "C" {
                                     still 5 (new functions only): mirhi_image_create_array, mirhi_image_create_layer_view, mirhi_image_layers,
                                     mirhi_cmd_bind_shadow_cascades;
                                     still 5 (new functions only): mirhi_image_create_cube and the five mirhi_ibl_ passes;
-                                    still 5 (one new enum value, one new function): MIRHI_PROGRAM_MODEL_PBR_IBL, mirhi_cmd_bind_ibl */
+                                    still 5 (one new enum value, one new function): MIRHI_PROGRAM_MODEL_PBR_IBL, mirhi_cmd_bind_ibl;
+                                    still 5 (one new enum value, one new function): MIRHI_PROGRAM_SKYBOX, mirhi_cmd_bind_skybox */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -190,7 +191,7 @@ mirhi_result mirhi_image_destroy(mirhi_image* img);
  * mirhi_image_size_bytes the whole chain, and mirhi_image_upload / _read move the whole chain.  A cube is no 2-D image and no array: it is refused
  * (InvalidHandle, the message says "cube") as a colour, depth or prim-id attachment, at every mirhi_texture_slot, by mirhi_cmd_bind_shadow_cascades,
  * mirhi_image_create_layer_view, mirhi_image_generate_mips and mirhi_image_set_max_anisotropy, and there is no wrapped cube.  A frame samples cubes
- * through mirhi_cmd_bind_ibl (MIRHI_PROGRAM_MODEL_PBR_IBL) and nowhere else.
+ * through mirhi_cmd_bind_ibl (MIRHI_PROGRAM_MODEL_PBR_IBL) and mirhi_cmd_bind_skybox (MIRHI_PROGRAM_SKYBOX) and nowhere else.
  *
  * The sampler (the reference's sampler.rs is empty: this is the build's reading of `LinearSampler`).
  *   Cube lookup, TextureCube.SampleLevel(LinearSampler, dir, lod): face and (s, t) by the Vulkan specification's cube-map face selection table --
@@ -241,10 +242,12 @@ typedef enum {   /* replaces Shader::from_spirv_file (shader.rs:244-330): precom
                                        "no attachment at this location"), depth D32_SFLOAT with test and write on and LESS / LESS_OR_EQUAL / GREATER /
                                        GREATER_OR_EQUAL; no blending, no fragment discard.  SHADOW draws are recorded only in depth-only scopes
                                        (mirhi_rendering_info.color_image NULL) and only SHADOW draws there. */
-    MIRHI_PROGRAM_MODEL_PBR_IBL = 5 /* vertex/model.hlsl + pixel/model_pbr_ibl.hlsl: MODEL_PBR's vertex layout, uniform slots, five material textures and 80-byte
+    MIRHI_PROGRAM_MODEL_PBR_IBL = 5,/* vertex/model.hlsl + pixel/model_pbr_ibl.hlsl: MODEL_PBR's vertex layout, uniform slots, five material textures and 80-byte
                                        MaterialData, with the image-based ambient term of mirhi_cmd_bind_ibl (below) in place of the hemisphere ambient.  The
                                        directional light's shadow term comes from what is bound, exactly as for MODEL_PBR: nothing = 1, MIRHI_TEXTURE_SHADOW_MAP =
                                        CalculateShadow, mirhi_cmd_bind_shadow_cascades = CalculateShadowCSM (which is pixel/model_pbr_ibl_csm.hlsl). */
+    MIRHI_PROGRAM_SKYBOX = 6        /* vertex/skybox.hlsl + pixel/skybox.hlsl: the environment cube behind the scene (mirhi_cmd_bind_skybox, below).  Valid only as
+                                       the pair SKYBOX / SKYBOX; no vertex input: vertex_stride and attribute_count 0, no vertex buffer at the draw. */
 } mirhi_program;
 typedef enum { MIRHI_TOPOLOGY_POINT_LIST = 0, MIRHI_TOPOLOGY_LINE_LIST = 1, MIRHI_TOPOLOGY_LINE_STRIP = 2,
                MIRHI_TOPOLOGY_TRIANGLE_LIST = 3, MIRHI_TOPOLOGY_TRIANGLE_STRIP = 4, MIRHI_TOPOLOGY_TRIANGLE_FAN = 5 } mirhi_topology;   /* pipeline.rs:274-300 */
@@ -408,6 +411,33 @@ mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, 
  * The images are ordered across queue lanes like shadow maps a scope samples; the mirhi_ibl_ passes wait for every lane, so a pass on a bound image never
  * overlaps a frame that samples it. */
 mirhi_result mirhi_cmd_bind_ibl(mirhi_cmd* cmd, mirhi_image* irradiance, mirhi_image* prefiltered, mirhi_image* brdf_lut);
+/* SKYBOX: set 0, bindings 0 / 1 of pixel/skybox.hlsl (TextureCube environmentMap + sampler).  `environment`: an R32G32B32A32_SFLOAT cube of the command
+ * buffer's device with any number of levels; NULL unbinds; mirhi_cmd_begin* and mirhi_cmd_reset clear it.  There is no texture slot for it either.
+ *
+ * What a MIRHI_PROGRAM_SKYBOX draw is -- the build's reading of the two shaders:
+ *   The draw is mirhi_cmd_draw(cmd, 3, 1, 0, 0): no vertex buffer, no index buffer.  One primitive, the triangle with clip positions (-1, -1, 1, 1),
+ *     (3, -1, 1, 1), (-1, 3, 1, 1) from SV_VertexID (vertex/skybox.hlsl:20-35).  It goes through the draw's viewport and scissor like any triangle (snapped
+ *     to 1 / 256 pixel, top-left rule; the part outside the viewport rectangle is covered too and is the scissor's to cut), is kept or culled by
+ *     cull_mode / front_face under the geometry kernel's winding rule (a negative-height viewport flips it), and takes one primitive id, which the
+ *     prim-id attachment holds wherever the sky is visible.  Its depth is the viewport's max_depth (z = w = 1).
+ *   Push constants (vertex/skybox.hlsl:5-9): bytes [0, 64) at the time of the draw are inverseViewProjection, in the memory convention of
+ *     CameraData.viewProjection.  They are latched when the draw is recorded; a later mirhi_cmd_push_constants does not change a recorded draw.
+ *   Direction (vertex/skybox.hlsl:40-42, pixel/skybox.hlsl:24).  At each vertex w = M (x, -y, 1, 1), LocalPos = w.xyz / w.w, computed on the host in
+ *     double from the float32 matrix (no less exact than the shader's float32); per pixel LocalPos is the AFFINE interpolation of the three vertex values at the pixel centre (all clip w are 1: perspective-correct and
+ *     linear interpolation coincide) -- not M clip / w per pixel, which differs when M's last row has x or y in it; then normalize.
+ *   Colour (pixel/skybox.hlsl:25-30): the cube lookup of "IBL precompute" at lod 0, all four channels, written through the colour store and encoding of a
+ *     raster resolve for both colour formats.  Lod 0 is a stated deviation like irradianceMap.Sample's above: `Sample` takes an implicit lod, the path has
+ *     no derivatives.  Numerics as for MODEL_PBR_IBL: float32, not bit-exact, bounded against the float64 model.
+ *   Depth state: every compare op, with or without the depth test and depth write, under CLEAR or LOAD of colour and depth.  A fragment passes when
+ *     compare(max_depth, stored) holds (always, with the test off); with depth write the stored depth becomes max_depth; NEVER keeps the id and draws
+ *     nothing.  The reference draws it after the models with LESS_OR_EQUAL and no write; drawn first into cleared attachments it fills the frame.
+ *     In a scope without a depth_image `stored` is what the scope's earlier segments resolved (depth stays on chip / in the library's own buffer, as
+ *     for every depth-testing draw), or clear_depth when nothing was drawn before the sky.
+ *   A SKYBOX draw is always a segment of its rendering scope of its own.  The environment is ordered across queue lanes like the IBL set.
+ * Refused with InvalidHandle: a non-cube, another format or another device's image here; at the draw: no environment bound; vertex_count != 3,
+ * first_vertex != 0 or instance_count > 1; mirhi_cmd_draw_indexed or an indirect draw with a SKYBOX pipeline; a pipeline with blend_enable or
+ * fragment_discard_enable; a depth-only rendering scope.  A pipeline that pairs SKYBOX with another program is refused at creation (ShaderError). */
+mirhi_result mirhi_cmd_bind_skybox(mirhi_cmd* cmd, mirhi_image* environment);
 mirhi_result mirhi_cmd_set_viewport(mirhi_cmd* cmd, const mirhi_viewport* viewport);  /* set_viewport :522 */
 mirhi_result mirhi_cmd_set_scissor(mirhi_cmd* cmd, const mirhi_rect2d* scissor);      /* set_scissor :549 */
 /* instance_count > 1 (at most 4096): the path has no instance-rate input (binding 0 is per-vertex, vertex.rs:35-41,130-136; no program
@@ -422,7 +452,8 @@ mirhi_result mirhi_cmd_draw_indexed(mirhi_cmd* cmd, uint32_t index_count, uint32
 mirhi_result mirhi_cmd_draw_indirect(mirhi_cmd* cmd, mirhi_buffer* buffer, uint64_t offset, uint32_t draw_count, uint32_t stride);
 mirhi_result mirhi_cmd_draw_indexed_indirect(mirhi_cmd* cmd, mirhi_buffer* buffer, uint64_t offset, uint32_t draw_count, uint32_t stride);
 /* push_constants / push_constants_bytes :732-769.  Validated as Vulkan does (offset and length multiples of 4, offset + length <= 128) and kept
- * with the command buffer; the programs on this path read none (no HLSL file of the reference declares a push-constant block). */
+ * with the command buffer (mirhi_cmd_begin* and mirhi_cmd_reset zero them); MIRHI_PROGRAM_SKYBOX reads bytes [0, 64) when its draw is recorded,
+ * no other program reads any. */
 mirhi_result mirhi_cmd_push_constants(mirhi_cmd* cmd, uint32_t stage_flags, uint32_t offset, const void* data, uint32_t len);
 
 /* ---- submit + sync: vkQueueSubmit (renderer.rs:407-424, frame_manager.rs:439-462), Fence (sync.rs:168-298) */

@@ -38,7 +38,7 @@ class Format:
 
 
 class Program:
-    NONE, TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR, SHADOW, MODEL_PBR_IBL = -1, 0, 1, 2, 3, 4, 5
+    NONE, TRIANGLE, MODEL, MODEL_FULL, MODEL_PBR, SHADOW, MODEL_PBR_IBL, SKYBOX = -1, 0, 1, 2, 3, 4, 5, 6
 
 
 class PrimitiveTopology:  # pipeline.rs:274-282
@@ -246,6 +246,7 @@ _SIGNATURES = {
     "mirhi_cmd_bind_texture": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mirhi_cmd_bind_shadow_cascades": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "mirhi_cmd_bind_ibl": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mirhi_cmd_bind_skybox": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_cmd_set_viewport": (C.c_int32, [C.c_void_p, C.POINTER(Viewport)]),
     "mirhi_cmd_set_scissor": (C.c_int32, [C.c_void_p, C.POINTER(Rect2D)]),
     "mirhi_cmd_draw": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -756,6 +757,10 @@ class CommandBuffer:
         """mirhi_cmd_bind_ibl: the irradiance cube, the prefiltered cube and the BRDF LUT Program.MODEL_PBR_IBL draws sample; all None unbinds."""
         check(lib().mirhi_cmd_bind_ibl(self.handle, *(i.handle if i is not None else None for i in (irradiance, prefiltered, brdf_lut))))
 
+    def bind_skybox(self, environment: Optional[Image]):
+        """mirhi_cmd_bind_skybox: the environment cube Program.SKYBOX draws sample; None unbinds."""
+        check(lib().mirhi_cmd_bind_skybox(self.handle, environment.handle if environment is not None else None))
+
     def set_viewport(self, x, y, width, height, min_depth=0.0, max_depth=1.0):
         vp = Viewport(x, y, width, height, min_depth, max_depth)
         check(lib().mirhi_cmd_set_viewport(self.handle, C.byref(vp)))
@@ -853,7 +858,7 @@ class SceneResources:
     def __init__(self, device: Device, scene, color_format: int = Format.R32G32B32A32_SFLOAT, want_prim: bool = False,
                  want_depth: bool = False, color_image: Optional[Image] = None, wrap_buffers=None,
                  color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None,
-                 cascade_array: Optional[Image] = None, ibl_images: Optional[Sequence[Image]] = None):
+                 cascade_array: Optional[Image] = None, ibl_images: Optional[Sequence[Image]] = None, sky_image: Optional[Image] = None):
         """scene.shadow (scenes.ShadowSpec) adds a depth-only shadow scope ahead of the main scope: recorded into the same command
         buffer, or with shadow_cmd=True into a command buffer of its own (self.shadow_cmd; render() submits both, the shadow one first --
         put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames).
@@ -862,7 +867,9 @@ class SceneResources:
         sample the array through bind_shadow_cascades.
         scene.ibl (scenes.IblSpec): the IBL set bound for the scene's MODEL_PBR_IBL draws -- the spec's own images, images created here from its
         arrays and uploaded (self.ibl_images, destroyed with the resources), or the existing three passed as ibl_images= (irradiance cube,
-        prefiltered cube, BRDF LUT; shared between frames, the caller's to destroy)."""
+        prefiltered cube, BRDF LUT; shared between frames, the caller's to destroy).
+        scene.sky (scenes.SkySpec): a Program.SKYBOX draw behind (or with first=True ahead of) the scene's draws; its environment cube is the spec's
+        image, one created here from its levels (self.sky_image, destroyed with the resources) or the existing one passed as sky_image=."""
         self.device, self.scene = device, scene
         self.color_load_op = color_load_op
         self.owns_color = color_image is None
@@ -985,7 +992,30 @@ class SceneResources:
             self.ibl_images = tuple(self.ibl.images)
         elif self.ibl is not None:
             self.ibl_images, self.owns_ibl = self.ibl.create_images(device, Image, Format.R32G32B32A32_SFLOAT), True
+        self.sky, self.sky_image, self.owns_sky, self.sky_pipe = getattr(scene, "sky", None), sky_image, False, None
+        if self.sky is not None:
+            if self.sky_image is None and self.sky.image is not None:
+                self.sky_image = self.sky.image
+            elif self.sky_image is None:
+                self.sky_image, self.owns_sky = self.sky.create_image(device, Image), True
+            k = self.sky
+            b = (GraphicsPipelineBuilder().vertex_shader(Program.SKYBOX).fragment_shader(Program.SKYBOX).vertex_binding(0).vertex_attributes(())
+                 .color_attachment_format(self.color_format).cull_mode(k.cull_mode).front_face(k.front_face)
+                 .depth_test_enable(k.depth_test).depth_write_enable(k.depth_write).depth_compare_op(k.depth_compare))
+            if k.depth_test or k.depth_write:
+                b.depth_attachment_format(Format.D32_SFLOAT)
+            self.sky_pipe = b.build(device)
+            self.objs.append(self.sky_pipe)
         self.record()
+
+    def _record_sky(self, cmd: "CommandBuffer"):
+        s, k = self.scene, self.sky
+        cmd.set_viewport(*(k.viewport or (0.0, 0.0, float(s.width), float(s.height), 0.0, 1.0)))
+        cmd.set_scissor(*(k.scissor or (0, 0, s.width, s.height)))
+        cmd.bind_pipeline(self.sky_pipe)
+        cmd.bind_skybox(self.sky_image)
+        cmd.push_constants(0, 0, np.ascontiguousarray(k.inv_view_proj, dtype=np.float32).tobytes())
+        cmd.draw(3, 1, 0, 0)
 
     def _record_shadow(self, cmd: "CommandBuffer"):
         if self.cascades is not None:
@@ -1023,6 +1053,8 @@ class SceneResources:
             self._record_shadow(cmd)
         cmd.begin_rendering(self.color, clear_color=s.clear_color, color_load_op=self.color_load_op, depth=self.depth, clear_depth=s.clear_depth,
                             depth_store_op=StoreOp.STORE if self.depth else StoreOp.DONT_CARE, prim_id=self.prim)
+        if self.sky is not None and self.sky.first:
+            self._record_sky(cmd)
         for st in self.draw_state:
             d = st["draw"]
             vp = d.viewport or (0.0, 0.0, float(s.width), float(s.height), 0.0, 1.0)
@@ -1056,6 +1088,8 @@ class SceneResources:
                 cmd.draw_indexed(d.count, getattr(d, "instances", 1), d.first, d.vertex_offset, 0)
             else:
                 cmd.draw(d.count, getattr(d, "instances", 1), d.first, 0)
+        if self.sky is not None and not self.sky.first:
+            self._record_sky(cmd)
         cmd.end_rendering()
         cmd.end()
 
@@ -1085,6 +1119,8 @@ class SceneResources:
         if self.owns_ibl:
             for img in self.ibl_images:
                 img.destroy()
+        if self.owns_sky:
+            self.sky_image.destroy()
         for o in self.objs:
             o.destroy()
         for o in (self.prim, self.depth, self.color):

@@ -530,6 +530,18 @@ struct RecordedPass {
                    pre_levels == o.pre_levels && lut_size == o.lut_size;
         }
     } ibl;
+    // A SKYBOX segment: the one SKYBOX draw it consists of, as PassParams takes it (the sky_ words), fixed when the draw was recorded -- push
+    // constants, viewport, scissor and the environment are latched per draw.  All bytes defined (memcmp compares two recordings).
+    struct SkyDraw {
+        uint32_t on, visible, size, levels;
+        const uint8_t* env;
+        int32_t a[3], b[3], scissor[4];
+        long long e0[3];
+        float pos0[3], posx[3], posy[3];
+        uint32_t depth_bits, compare, write, prim;
+        SkyDraw() { memset(this, 0, sizeof *this); }
+        bool operator==(const SkyDraw& o) const { return memcmp(this, &o, sizeof *this) == 0; }
+    } sky;
 };
 
 // Words of the counter block that never move (a re-recorded frame of another shape finds them where the last frame's kernels
@@ -617,8 +629,9 @@ struct mirhi_cmd {
     mirhi_image* cascades = nullptr;       // mirhi_cmd_bind_shadow_cascades: the D32 array (t10) ...
     struct { mirhi_buffer* buf; uint64_t offset, range; } cascade_params = {};      // ... and its CSMParams (b3 of set 2)
     mirhi_image* ibl[3] = {};              // mirhi_cmd_bind_ibl: irradiance cube, prefiltered cube, BRDF LUT (set 3); all three or none
+    mirhi_image* skybox = nullptr;         // mirhi_cmd_bind_skybox: the environment cube of SKYBOX draws (set 0 of pixel/skybox.hlsl)
     bool has_viewport = false, has_scissor = false;
-    uint8_t push_constants[128] = {0};     // vkCmdPushConstants: kept, read by no program on this path
+    uint8_t push_constants[128] = {0};     // vkCmdPushConstants: bytes [0, 64) are a SKYBOX draw's inverseViewProjection, latched when it is recorded
     mirhi_viewport viewport{};
     mirhi_rect2d scissor{};
     // device-side plan, built at end()
@@ -1319,11 +1332,12 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
     if (d->blend_attachment_count != 0 && d->blend_attachment_count != d->color_attachment_count)
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: Blend attachment count (%u) must match color attachment count (%u)", d->blend_attachment_count, d->color_attachment_count);
     // --- program selection replaces SPIR-V module creation (shader.rs:244-330) ---
-    if (d->vertex_program < 0 || d->vertex_program > MIRHI_PROGRAM_MODEL_PBR_IBL || d->fragment_program < 0 || d->fragment_program > MIRHI_PROGRAM_MODEL_PBR_IBL)
+    if (d->vertex_program < 0 || d->vertex_program > MIRHI_PROGRAM_SKYBOX || d->fragment_program < 0 || d->fragment_program > MIRHI_PROGRAM_SKYBOX)
         return fail(MIRHI_ERR_SHADER, "Shader error: unknown program id (vertex %d, fragment %d)", d->vertex_program, d->fragment_program);
     const bool vs_shadow = d->vertex_program == MIRHI_PROGRAM_SHADOW, fs_shadow = d->fragment_program == MIRHI_PROGRAM_SHADOW;
     const bool vs_model = d->vertex_program != MIRHI_PROGRAM_TRIANGLE, fs_model = d->fragment_program != MIRHI_PROGRAM_TRIANGLE;
-    if (vs_model != fs_model || vs_shadow != fs_shadow)
+    const bool vs_sky = d->vertex_program == MIRHI_PROGRAM_SKYBOX, fs_sky = d->fragment_program == MIRHI_PROGRAM_SKYBOX;
+    if (vs_model != fs_model || vs_shadow != fs_shadow || vs_sky != fs_sky)
         return fail(MIRHI_ERR_SHADER, "Shader error: vertex program %d does not produce the inputs of fragment program %d", d->vertex_program, d->fragment_program);
     // --- what this rasterizer does not implement fails loudly instead of rendering something else ---
     if (d->color_attachment_count != 1) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: %u color attachments (exactly 1 supported)", d->color_attachment_count);
@@ -1360,6 +1374,15 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
             return fail(MIRHI_ERR_PIPELINE, "Pipeline error: invalid blend op");
     }
     if (d->depth_clamp_enable || d->depth_bias_enable) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth clamp / depth bias");
+    if (vs_sky) {
+        // vertex/skybox.hlsl has no vertex input (SV_VertexID alone): no binding, no attributes (a blending or discarding one is refused at the draw)
+        if (d->attribute_count != 0) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: program %d (SKYBOX) has no vertex input, got %u vertex attributes", d->vertex_program, d->attribute_count);
+        mirhi_pipeline* p = new (std::nothrow) mirhi_pipeline{dev, *d};
+        if (!p) return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: host allocation failed");
+        dev->children++;
+        *out = p;
+        return MIRHI_OK;
+    }
     const uint32_t want_stride = vs_shadow ? 12u : (vs_model ? 48u : 24u);      // vertex.rs:35-41 / :130-136; vertex/shadow.hlsl:13-16 (position only)
     if (d->vertex_stride < want_stride || (d->vertex_stride & 3u))
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: vertex stride %u too small for program %d (needs >= %u, multiple of 4)", d->vertex_stride, d->vertex_program, want_stride);
@@ -1484,6 +1507,8 @@ static void reset_recording(mirhi_cmd* c) {
     for (auto& tx : c->textures) tx = nullptr;
     c->cascades = nullptr; c->cascade_params = {nullptr, 0, 0};
     for (auto& im : c->ibl) im = nullptr;
+    c->skybox = nullptr;
+    memset(c->push_constants, 0, sizeof c->push_constants);
     c->has_viewport = c->has_scissor = false;
 }
 static mirhi_result begin_common(mirhi_cmd* cmd, bool one_time) {
@@ -1657,6 +1682,16 @@ extern "C" mirhi_result mirhi_cmd_bind_ibl(mirhi_cmd* cmd, mirhi_image* irradian
     cmd->ibl[0] = irradiance; cmd->ibl[1] = prefiltered; cmd->ibl[2] = brdf_lut;
     return MIRHI_OK;
 }
+// set 0, bindings 0 / 1 of pixel/skybox.hlsl: TextureCube environmentMap + its sampler
+extern "C" mirhi_result mirhi_cmd_bind_skybox(mirhi_cmd* cmd, mirhi_image* environment) {
+    REQUIRE_RECORDING(cmd);
+    if (!environment) { cmd->skybox = nullptr; return MIRHI_OK; }
+    if (!environment->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the skybox environment must be a cube image (mirhi_image_create_cube)");
+    if (environment->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the skybox environment must be R32G32B32A32_SFLOAT");
+    if (environment->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the skybox environment belongs to another device than the command buffer");
+    cmd->skybox = environment;
+    return MIRHI_OK;
+}
 extern "C" mirhi_result mirhi_cmd_set_viewport(mirhi_cmd* cmd, const mirhi_viewport* vp) {
     REQUIRE_RECORDING(cmd); NULL_CHECK(vp, "viewport");
     if (!(vp->width > 0.0f) || !(vp->height != 0.0f) || !(vp->min_depth >= 0.0f && vp->min_depth <= 1.0f) || !(vp->max_depth >= 0.0f && vp->max_depth <= 1.0f))
@@ -1673,10 +1708,117 @@ extern "C" mirhi_result mirhi_cmd_set_scissor(mirhi_cmd* cmd, const mirhi_rect2d
     return MIRHI_OK;
 }
 
+// The scope continues in a new segment that loads what the previous one stored (carry_out / carry_in): fragments keep their submission order
+// across the cut, primitive ids continue.
+static void cut_segment(mirhi_cmd* cmd) {
+    RecordedPass next;
+    {
+        RecordedPass& prev = cmd->passes.back();
+        prev.carry_out = true;
+        next.info = prev.info;
+        next.color_t = prev.color_t; next.depth_t = prev.depth_t; next.prim_t = prev.prim_t;
+        next.depth_only = prev.depth_only; next.ibl = prev.ibl;
+        memcpy(next.area, prev.area, sizeof next.area);
+        next.info.color_load_op = MIRHI_LOAD_OP_LOAD;
+        next.carry_in = true;
+        next.first_tri = next.total_tris = prev.total_tris;
+    }
+    cmd->passes.push_back(std::move(next));
+}
+
+// A SKYBOX draw (include/mirhi.h "SKYBOX"): always a segment of its own, set up here -- the triangle's edge functions, the three vertex values of
+// LocalPos (divided on the host, in double) as an affine function of the pixel centre, scissor, depth state -- from the push constants, viewport and
+// scissor of this moment.
+static mirhi_result record_sky_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, uint32_t instance_count, uint32_t first) {
+    const mirhi_pipeline_desc& pd = cmd->pipeline->desc;
+    if (indexed) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX pipeline draws with mirhi_cmd_draw(cmd, 3, 1, 0, 0): draw_indexed has nothing to index");
+    if (cmd->passes.back().depth_only) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX draw in a depth-only rendering scope (pixel/skybox.hlsl writes colour)");
+    if (pd.blend_enable || pd.fragment_discard_enable) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a SKYBOX draw with blending or fragment discard");
+    if (count != 3u || first != 0u || instance_count > 1u)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX draw is vertex_count 3, first_vertex 0, instance_count 1 (got %u, %u, %u)", count, first, instance_count);
+    if (!cmd->skybox) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: program %d (SKYBOX) needs an environment cube bound (mirhi_cmd_bind_skybox)", pd.fragment_program);
+    if (!cmd->has_viewport || !cmd->has_scissor) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: viewport and scissor are dynamic state and must be set before drawing (pipeline.rs:697)");
+    const RecordedPass::Target ci = cmd->passes.back().color_t;
+    if (pd.color_attachment_formats[0] != (int32_t)ci.format)
+        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)ci.format);
+    if (instance_count == 0) return MIRHI_OK;
+    if ((uint64_t)cmd->passes.back().total_tris + 1u > (uint64_t)MAX_PRIM_ID) return fail(MIRHI_ERR_DEVICE, "Vulkan error: too many primitives in one rendering scope");
+    if (pd.depth_test_enable && pd.depth_compare_op == MIRHI_COMPARE_NEVER) { cmd->passes.back().total_tris += 1u; return MIRHI_OK; }     // draws nothing, keeps its id
+    DepthState ds;
+    ds.key_set = true;
+    ds.test = pd.depth_test_enable ? 1u : 0u;
+    ds.compare = ds.test ? (uint32_t)pd.depth_compare_op : (uint32_t)MIRHI_COMPARE_ALWAYS;
+    ds.write = ds.test && pd.depth_write_enable ? 1u : 0u;
+    // a segment of its own, even when its depth state equals its neighbour's; a segment that holds no draw yet (nothing recorded, or only draws that
+    // kept their ids and drew nothing: NEVER, an empty scissor) becomes the sky segment
+    {
+        const RecordedPass& back = cmd->passes.back();
+        if (back.sky.on || !back.draws.empty()) cut_segment(cmd);
+    }
+    RecordedPass& pass = cmd->passes.back();
+    pass.state = ds;
+    RecordedPass::SkyDraw& k = pass.sky;
+    k.on = 1u;
+    k.env = cmd->skybox->ptr; k.size = cmd->skybox->width; k.levels = cmd->skybox->levels;
+    k.compare = ds.compare; k.write = ds.write; k.prim = pass.total_tris;
+    const mirhi_viewport& vp = cmd->viewport;
+    { float f = vp.max_depth; f = f > 0.0f ? (f < 1.0f ? f : 1.0f) : 0.0f; memcpy(&k.depth_bits, &f, 4); }
+    // viewport transform and snap of the three vertices, as setup_triangle has them (clip w = 1)
+    const float hw = 0.5f * vp.width, hh = 0.5f * vp.height, cx = vp.x + hw, cy = vp.y + hh;
+    static const float clip[3][2] = {{-1.0f, -1.0f}, {3.0f, -1.0f}, {-1.0f, 3.0f}};      // vertex/skybox.hlsl: SV_VertexID 0, 1, 2
+    int32_t X[3], Y[3];
+    bool in_range = true;
+    for (int i = 0; i < 3; i++) {
+        const float xs = clip[i][0] * hw + cx, ys = clip[i][1] * hh + cy;
+        in_range = in_range && std::fabs(xs) <= 32768.0f && std::fabs(ys) <= 32768.0f;      // (mirhi_cmd_set_viewport keeps |x| + |width| <= 8192: always)
+        X[i] = (int32_t)std::rint(xs * 256.0f); Y[i] = (int32_t)std::rint(ys * 256.0f);
+    }
+    const int64_t S = (int64_t)(X[1] - X[0]) * (int64_t)(Y[2] - Y[0]) - (int64_t)(X[2] - X[0]) * (int64_t)(Y[1] - Y[0]);
+    const bool front = pd.front_face == 0 ? S < 0 : S > 0;                                  // the geometry kernel's winding rule (Vulkan: a = -S / 2)
+    bool visible = in_range && S != 0 && pd.cull_mode != 3 && !(pd.cull_mode == 2 && !front) && !(pd.cull_mode == 1 && front);
+    if (S < 0) { std::swap(X[1], X[2]); std::swap(Y[1], Y[2]); }
+    for (int i = 0; i < 3; i++) {
+        const int a = i, b = (i + 1) % 3;
+        const int32_t dx = X[b] - X[a], dy = Y[b] - Y[a];
+        const bool topleft = dy < 0 || (dy == 0 && dx > 0);
+        k.a[i] = -dy; k.b[i] = dx;
+        k.e0[i] = (int64_t)k.a[i] * (128 - X[a]) + (int64_t)k.b[i] * (128 - Y[a]) + (topleft ? 0 : -1);      // E_i + bias at the centre of pixel (0, 0)
+    }
+    int64_t sx0 = cmd->scissor.x, sy0 = cmd->scissor.y;
+    int64_t sx1 = sx0 + (int64_t)cmd->scissor.width - 1, sy1 = sy0 + (int64_t)cmd->scissor.height - 1;
+    if (sx1 > (int64_t)ci.width - 1) sx1 = (int64_t)ci.width - 1;
+    if (sy1 > (int64_t)ci.height - 1) sy1 = (int64_t)ci.height - 1;
+    if (sx0 > sx1 || sy0 > sy1) { visible = false; sx0 = sy0 = 0; sx1 = sy1 = -1; }
+    k.scissor[0] = (int32_t)sx0; k.scissor[1] = (int32_t)sy0; k.scissor[2] = (int32_t)sx1; k.scissor[3] = (int32_t)sy1;
+    k.visible = visible ? 1u : 0u;
+    // LocalPos = (M (x, -y, 1, 1)).xyz / .w per vertex (vertex/skybox.hlsl:40-42), M = push constants [0, 64) in CameraData.viewProjection's convention
+    float M[16];
+    memcpy(M, cmd->push_constants, sizeof M);
+    double L[3][3];
+    for (int i = 0; i < 3; i++) {
+        // (in double from the float32 matrix: w.w is the difference of the two far-plane terms, -9.99 + 10 for near 0.1 / far 100, and a float32 sum
+        // leaves 1e-6 of it per vertex -- measured as 2e-5 of the frame against the float64 model, 1e-6 so)
+        const double v[4] = {(double)clip[i][0], -(double)clip[i][1], 1.0, 1.0};
+        double w[4];
+        for (int r = 0; r < 4; r++) w[r] = (((double)M[r] * v[0] + (double)M[4 + r] * v[1]) + (double)M[8 + r] * v[2]) + (double)M[12 + r] * v[3];
+        for (int r = 0; r < 3; r++) L[i][r] = w[r] / w[3];
+    }
+    // ... interpolated affinely: L(xn, yn) = L0 + (L1 - L0) (xn + 1) / 4 + (L2 - L0) (yn + 1) / 4 with xn = (x - cx) / hw, yn = (y - cy) / hh
+    for (int r = 0; r < 3; r++) {
+        const double dx = (L[1][r] - L[0][r]) / (4.0 * (double)hw), dy = (L[2][r] - L[0][r]) / (4.0 * (double)hh);
+        k.posx[r] = (float)dx; k.posy[r] = (float)dy;
+        k.pos0[r] = (float)(L[0][r] + dx * ((double)hw - (double)cx) + dy * ((double)hh - (double)cy));
+    }
+    if (std::find(pass.sampled.begin(), pass.sampled.end(), cmd->skybox) == pass.sampled.end()) pass.sampled.push_back(cmd->skybox);
+    pass.total_tris += 1u;
+    return MIRHI_OK;
+}
+
 static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, uint32_t instance_count, uint32_t first, int32_t vertex_offset) {
     REQUIRE_RECORDING(cmd);
     if (!cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: draw outside a rendering scope");
     if (!cmd->pipeline) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: no pipeline bound");
+    if (cmd->pipeline->desc.vertex_program == MIRHI_PROGRAM_SKYBOX) return record_sky_draw(cmd, indexed, count, instance_count, first);
     if (!cmd->vb) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: no vertex buffer bound to binding 0");
     if (indexed && !cmd->ib) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: no index buffer bound");
     if (!cmd->has_viewport || !cmd->has_scissor) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: viewport and scissor are dynamic state and must be set before drawing (pipeline.rs:697)");
@@ -1717,23 +1859,11 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     }
     ds.discard = pd.fragment_discard_enable ? 1u : 0u;
     if (!cmd->passes.back().state.key_set) cmd->passes.back().state = ds;
-    else if (!(cmd->passes.back().state == ds)) {
+    else if (!(cmd->passes.back().state == ds) || cmd->passes.back().sky.on) {
         // One raster launch resolves one depth state (DESIGN.md "Depth key"): the scope continues in a new segment that
-        // loads what the previous one stored -- fragments keep their submission order across the cut.
-        RecordedPass next;
-        {
-            RecordedPass& prev = cmd->passes.back();
-            prev.carry_out = true;
-            next.info = prev.info;
-            next.color_t = prev.color_t; next.depth_t = prev.depth_t; next.prim_t = prev.prim_t;
-            next.depth_only = prev.depth_only; next.ibl = prev.ibl;
-            memcpy(next.area, prev.area, sizeof next.area);
-            next.info.color_load_op = MIRHI_LOAD_OP_LOAD;
-            next.carry_in = true;
-            next.first_tri = next.total_tris = prev.total_tris;
-        }
-        next.state = ds;
-        cmd->passes.push_back(std::move(next));
+        // loads what the previous one stored -- fragments keep their submission order across the cut.  (Behind a SKYBOX draw: always.)
+        cut_segment(cmd);
+        cmd->passes.back().state = ds;
     }
     RecordedPass& pass = cmd->passes.back();
 
@@ -1874,6 +2004,8 @@ extern "C" mirhi_result mirhi_cmd_draw_indexed(mirhi_cmd* cmd, uint32_t index_co
 static mirhi_result record_indirect(mirhi_cmd* cmd, bool indexed, mirhi_buffer* buffer, uint64_t offset, uint32_t draw_count, uint32_t stride) {
     REQUIRE_RECORDING(cmd); NULL_CHECK(buffer, "buffer");
     if (buffer->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: indirect buffer belongs to another device");
+    if (cmd->pipeline && cmd->pipeline->desc.vertex_program == MIRHI_PROGRAM_SKYBOX)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX pipeline draws with mirhi_cmd_draw(cmd, 3, 1, 0, 0): no indirect draws");
     const uint32_t words = indexed ? 5u : 4u;
     if (draw_count == 0) return MIRHI_OK;
     if ((offset & 3u) || (draw_count > 1 && (stride < words * 4u || (stride & 3u))))
@@ -1950,7 +2082,7 @@ static bool same_recording(const std::vector<RecordedPass>& a, const std::vector
             memcmp(&x.info.clear_depth, &y.info.clear_depth, sizeof(float)) != 0) return false;
         if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || !(x.state == y.state) ||
             x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
-        if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl)) return false;
+        if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl) || !(x.sky == y.sky)) return false;
         if (x.draws.size() != y.draws.size() || x.draw_vb_bytes != y.draw_vb_bytes) return false;
         if (!x.draws.empty() && memcmp(x.draws.data(), y.draws.data(), x.draws.size() * sizeof(DrawDesc)) != 0) return false;
     }
@@ -2124,7 +2256,7 @@ static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, c
     { uint32_t count; split_rows(dev->split_layout, dev->split_rank, dev->split_world, s.tiles_y, &s.r0, &s.rstep, &count); s.r1 = s.r0 + count; }
     if (pass.depth_only) { s.r0 = 0; s.r1 = s.tiles_y; s.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
     s.tris = pass.total_tris - pass.first_tri;
-    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs);
+    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs, pass.sky.on != 0u);
     s.mode = raster_mode(s.cls, s.tiles(), s.tris, w.spread, w.wide, knobs);
     s.bins = bin_geometry(s.tiles(), s.tris, pass.total_tris, s.mode.xcd_bins, w.pool_scale, knobs);
     return s;
@@ -2296,6 +2428,14 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
         P.ibl_irradiance = (const float*)pass.ibl.irradiance; P.ibl_prefiltered = (const float*)pass.ibl.prefiltered; P.ibl_lut = (const float*)pass.ibl.lut;
         P.ibl_irr_size = pass.ibl.irr_size; P.ibl_pre_size = pass.ibl.pre_size; P.ibl_pre_levels = pass.ibl.pre_levels; P.ibl_lut_size = pass.ibl.lut_size;
     }
+    if (P.sky) {
+        const RecordedPass::SkyDraw& k = pass.sky;
+        P.sky_visible = k.visible; P.sky_size = k.size; P.sky_levels = k.levels; P.sky_env = (const float*)k.env;
+        memcpy(P.sky_a, k.a, sizeof P.sky_a); memcpy(P.sky_b, k.b, sizeof P.sky_b); memcpy(P.sky_scissor, k.scissor, sizeof P.sky_scissor);
+        for (int i = 0; i < 3; i++) P.sky_e0[i] = k.e0[i];
+        memcpy(P.sky_pos0, k.pos0, sizeof P.sky_pos0); memcpy(P.sky_posx, k.posx, sizeof P.sky_posx); memcpy(P.sky_posy, k.posy, sizeof P.sky_posy);
+        P.sky_depth_bits = k.depth_bits; P.sky_compare = k.compare; P.sky_write = k.write; P.sky_prim = k.prim;
+    }
     return P;
 }
 
@@ -2413,7 +2553,7 @@ extern "C" int mirhi_debug_scope_plan(const uint32_t* in, uint32_t* out, char* n
         if (in[16 + 3 * i]) { draws[i].shadow_map = &some_map; draws[i].shadow_layers = in[16 + 3 * i] == 2u ? 4u : 0u; }
         draws[i].tex_any_mips = in[17 + 3 * i];
     }
-    const ScopeClass c = classify_scope(s, clear_depth, draws, n, in[7] != 0u, knobs);
+    const ScopeClass c = classify_scope(s, clear_depth, draws, n, in[7] != 0u, knobs, n == 1u && draws[0].program == (uint32_t)MIRHI_PROGRAM_SKYBOX);      // (a SKYBOX draw is a segment of its own)
     const RasterMode m = raster_mode(c, in[8], in[9], in[10] != 0u, in[11], knobs);
     const BinGeometry g = bin_geometry(in[8], in[9], in[9], m.xcd_bins, in[12], knobs);
     const uint32_t words[28] = {c.key.clear_depth_bits, c.key.pred, c.key.zflip, c.key.zmask, c.key.idflip, c.key.strict, c.key.init_zk, c.key.init_idk,
@@ -2710,7 +2850,9 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             // alternate the big-list counter: the raster kernel zeroes the other one for the next scope
             const PassParams* dp = c->ws.params + 2 * pi + c->ws.parity;
             uint32_t* big_count = c->ws.big_counts + c->ws.parity;
-            c->ws.parity ^= 1u;
+            // (a SKYBOX segment takes no bins and touches no counter: it re-arms nothing and parity stays where it is -- the raster kernel that
+            // follows finds the counters as the one before the sky left them)
+            if (!P.sky) c->ws.parity ^= 1u;
             // ordered segment: slots of primitives that no draw of the segment covers (a Never draw keeps its ids) must read
             // as "no coverage" -- an all-zero record is a degenerate triangle whose edge functions are negative everywhere
             if (P.ordered_recs && P.ordered_count) HIP_TRY(hipMemsetAsync(P.ordered_recs, 0, (size_t)P.ordered_count * sizeof(TriRec), stream));
@@ -2727,6 +2869,7 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
                 tv.native_flags = (head_sys ? NATIVE_ACQUIRE_SYSTEM : 0u) | (sys ? NATIVE_RELEASE_SYSTEM : 0u);
                 tg.native_flags = (((P.vs_total_slots == 0u && head_sys) || sys) ? NATIVE_ACQUIRE_SYSTEM : 0u) | (sys ? NATIVE_RELEASE_SYSTEM : 0u);      // (behind a vertex kernel: that one took the acquire)
                 tr.native_flags = NATIVE_RELEASE_SYSTEM | (sys ? NATIVE_ACQUIRE_SYSTEM : 0u);
+                if (P.sky && head_sys) tr.native_flags |= NATIVE_ACQUIRE_SYSTEM;      // (a SKYBOX segment has no vertex or geometry packet: its only one takes the head's acquire)
             }
             {   // small scopes: fewer triangles per geometry wave (GeometryHead::tris_per_wave) -- the chip is mostly idle, a shorter wave is a shorter frame
                 const uint32_t geo_waves = P.total_slots / (uint32_t)GEOM_THREADS;
@@ -2750,7 +2893,7 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             HIP_TRY(le);
             const bool has_tiles = P.tile_row_end > P.tile_row_begin && P.tiles_x;
             const uint32_t* winners = nullptr;
-            if (counted && has_tiles && !P.ordered_recs && !P.depth_only) {      // (ordered -- blended -- segments and depth-only scopes are not counted)
+            if (counted && has_tiles && !P.ordered_recs && !P.depth_only && !P.sky) {      // (ordered -- blended -- segments, depth-only scopes and SKYBOX segments are not counted)
                 mirhi_result r;
                 if (timed && (r = timing_begin(dev, MIRHI_KERNEL_FRAGMENT_COUNT, c->lane, &tc)) != MIRHI_OK) return r;
                 HIP_TRY(launch_fragment_count(P, dp, big_count, stream, tc));

@@ -206,7 +206,22 @@ struct PassParams {
     uint32_t ibl;                     // 1: some draw of the scope is MODEL_PBR_IBL
     uint32_t ibl_irr_size, ibl_pre_size, ibl_pre_levels, ibl_lut_size, ibl_pad;
     const float* ibl_irradiance; const float* ibl_prefiltered; const float* ibl_lut;
+    // A SKYBOX segment (vertex/skybox.hlsl + pixel/skybox.hlsl: one draw, a segment of its own; sky_kernel alone reads these words).
+    // The triangle is set up on the host: oriented integer edge functions with the top-left bias, E_i(px, py) = sky_e0[i] + 256 (sky_a[i] px +
+    // sky_b[i] py) >= 0 for all i <=> pixel (px, py) is covered; LocalPos at a pixel centre = sky_pos0 + sky_posx (px + 1/2) + sky_posy (py + 1/2).
+    uint32_t sky;                     // 1: the segment is a SKYBOX draw (no DrawDesc, no bins)
+    uint32_t sky_visible;             // 0: culled, degenerate or cut away by an empty scissor: only the load / clear / store ops happen
+    uint32_t sky_size, sky_levels;    // the environment cube's edge and level count (level 0 is sampled)
+    const float* sky_env;             // its base (float4 texels, the layout of include/mirhi.h "IBL precompute")
+    int32_t  sky_a[3], sky_b[3];
+    int32_t  sky_scissor[4];          // inclusive x0, y0, x1, y1
+    long long sky_e0[3];
+    float    sky_pos0[3], sky_posx[3], sky_posy[3];
+    uint32_t sky_depth_bits;          // the viewport's max_depth: the fragment's depth
+    uint32_t sky_compare, sky_write;  // mirhi_compare_op (ALWAYS when the depth test is off), 1: passing fragments store sky_depth_bits
+    uint32_t sky_prim;                // the draw's primitive id
 };
+static_assert(sizeof(PassParams) % 8 == 0, "PassParams holds pointers");
 
 // Kernel arguments passed by value next to the PassParams pointer: what a wave needs before anything else, so that its
 // first dependent loads (draw table, bin counter -> bin records) hang off the kernarg load, not off a second memory hop.

@@ -1,6 +1,6 @@
 // mirhi_kernels.hip -- gfx950 (CDNA4) kernels of the compute rasterizer.
 //
-// Two kernels per rendering scope (DESIGN.md "Kernels"):
+// Two kernels per rendering scope (DESIGN.md "Kernels"; a SKYBOX segment runs sky_kernel alone, mirhi_sky.hip.h):
 //   geometry_kernel  one lane per input triangle: index + vertex fetch, vertex-shader position,
 //                    clip / divide / viewport / snap / cull / depth-plane setup, then tile binning.
 //                    Restates SURVEY 8a rows a1, a2, a4, a5 (crates/rhi/src/vertex.rs:20-61,88-170;
@@ -35,6 +35,7 @@ namespace mirhi {
 #include "mirhi_ibl_sample.hip.h"
 #include "mirhi_shading.hip.h"
 #include "mirhi_raster.hip.h"
+#include "mirhi_sky.hip.h"
 #include "mirhi_stats.hip.h"
 #include "mirhi_ordered.hip.h"
 
@@ -126,6 +127,8 @@ static const RasterEntry k_raster_entries[] = {
     PLAIN(2, 1, 0, 1, false), PLAIN(4, 1, 0, 1, false), PLAIN(3, 1, 0, 1, false), PLAIN(1, 1, 0, 1, false),
     // MODEL_PBR_IBL scopes: per key, with and without the triangle-parallel path, per shadow term (none, single map, cascades)
     IBL(0, 1, 0), IBL(1, 1, 0), IBL(0, 0, 0), IBL(1, 0, 0), IBL(0, 1, 1), IBL(1, 1, 1), IBL(0, 0, 1), IBL(1, 0, 1), IBL(0, 1, 2), IBL(1, 1, 2), IBL(0, 0, 2), IBL(1, 0, 2),
+    // a SKYBOX segment (no key, no bins: one kernel)
+    {raster_kernel_id(RASTER_SKY, 0, 0, 0, 1, 0, 4), "sky_kernel", sky_kernel},
 };
 #undef IBL
 #undef ORDERED
@@ -202,7 +205,7 @@ hipError_t launch_raster_batch(const PassParams* const* Ps, const PassParams* co
 
 hipError_t launch_fragment_count(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, hipStream_t stream, LaunchTiming t) {
     const uint32_t rows = P.tile_row_end - P.tile_row_begin;
-    if (rows == 0 || P.tiles_x == 0 || P.ordered_recs || P.depth_only) return hipSuccess;
+    if (rows == 0 || P.tiles_x == 0 || P.ordered_recs || P.depth_only || P.sky) return hipSuccess;
     MIRHI_LAUNCH(fragment_count_kernel, dim3(P.tiles_x, rows), dim3(RASTER_THREADS), stream, t, dev_params, raster_head(P, big_count));
     return launch_result();
 }

@@ -138,11 +138,18 @@ struct ScopeClass {
     // _shadow / _csm / _ibl): one team of four waves per tile, single-list bins, plain tile order -- the team and wide selectors leave them alone.
     bool own_family;
     uint32_t programs;        // the scope's program set (mirhi_variant.h: PROGS_*)
+    // A SKYBOX segment (one SKYBOX draw, always a segment of its own: record_draw): no triangles, vertex jobs or bins; its raster launch is sky_kernel.
+    // A family of its own: plain tile order, no wide or two-team variant, no triangle-parallel path.
+    bool sky;
 };
 
-inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const DrawDesc* draws, size_t n, bool depth_only, const PlanKnobs& knobs) {
+inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const DrawDesc* draws, size_t n, bool depth_only, const PlanKnobs& knobs, bool sky = false) {
     ScopeClass c{};
     c.key = depth_key_setup(s, clear_depth);
+    if (sky) {      // (the depth state is the sky kernel's own business: PassParams::sky_compare / sky_write; nothing of the segment is ordered or masked)
+        c.sky = true; c.has_draws = true; c.own_family = true; c.programs = PROGS_SKY;
+        return c;
+    }
     c.masked_plain = s.key_set && s.discard && s.blend[0] == 0 && !s.order_dependent_depth() && !(knobs.masked_ordered.set && knobs.masked_ordered.value != 0) &&
                      c.key.pred == 0u;
     c.ordered = s.key_set && (s.blend[0] != 0 || (s.discard != 0 && !c.masked_plain) || s.order_dependent_depth());
@@ -203,6 +210,7 @@ inline RasterMode raster_mode(const ScopeClass& c, size_t tiles, size_t tris, bo
     }
     m.xcd_swizzle = knobs.xcd_run.set ? (uint32_t)knobs.xcd_run.value : 1u;
     if (c.own_family) { m.xcd_swizzle = 1u; m.wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
+    if (c.sky) { m.tp_max_area = 0u; m.teams = 1u; m.wide_eligible = false; m.xcd_bins = false; }
     return m;
 }
 
@@ -223,6 +231,7 @@ inline void set_raster_choice(PassParams& P, const ScopeClass& c, const RasterMo
     P.xcd_swizzle = m.xcd_swizzle;
     P.shadowed = c.shadowed;
     P.ibl = c.ibl;
+    P.sky = c.sky ? 1u : 0u;
 }
 
 // Bins and page pool of one scope.  tris: the segment's own triangles, total_tris: with those of the scope's earlier segments (primitive ids continue)

@@ -316,7 +316,7 @@ private:
 // ------------------------------------------------------------------------------------------------
 // crates/rhi/src/pipeline.rs
 // ------------------------------------------------------------------------------------------------
-enum class ShaderProgram { None = -1, Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4, ModelPbrIbl = 5 };   // replaces Shader::from_spirv_file
+enum class ShaderProgram { None = -1, Triangle = 0, Model = 1, ModelFull = 2, ModelPbr = 3, Shadow = 4, ModelPbrIbl = 5, Skybox = 6 };   // replaces Shader::from_spirv_file
 enum class PrimitiveTopology { PointList = 0, LineList, LineStrip, TriangleList, TriangleStrip, TriangleFan };
 enum class PolygonMode { Fill = 0, Line, Point };
 enum class CullMode { None = 0, Front, Back, FrontAndBack };
@@ -479,6 +479,8 @@ public:
     void bind_ibl(const Image* irradiance, const Image* prefiltered, const Image* brdf_lut) const {
         check(mirhi_cmd_bind_ibl(h_, irradiance ? irradiance->handle() : nullptr, prefiltered ? prefiltered->handle() : nullptr, brdf_lut ? brdf_lut->handle() : nullptr));
     }
+    // set 0 of pixel/skybox.hlsl: the environment cube of ShaderProgram::Skybox draws (draw(3, 1, 0, 0), push constants [0, 64) = inverseViewProjection); nullptr unbinds
+    void bind_skybox(const Image* environment) const { check(mirhi_cmd_bind_skybox(h_, environment ? environment->handle() : nullptr)); }
     void set_viewport(const Viewport& v) const { mirhi_viewport vp{v.x, v.y, v.width, v.height, v.min_depth, v.max_depth}; check(mirhi_cmd_set_viewport(h_, &vp)); }
     void set_scissor(const Rect2D& r) const { mirhi_rect2d sc{r.x, r.y, r.width, r.height}; check(mirhi_cmd_set_scissor(h_, &sc)); }
     void draw(uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex, uint32_t first_instance) const { check(mirhi_cmd_draw(h_, vertex_count, instance_count, first_vertex, first_instance)); }

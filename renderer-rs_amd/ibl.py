@@ -434,6 +434,74 @@ def tie_mask(d, rel=1e-4):
     return (a[..., 2] - a[..., 1]) <= rel * a[..., 2]
 
 
+
+# ---- SKYBOX (vertex/skybox.hlsl + pixel/skybox.hlsl; include/mirhi.h "SKYBOX") -----------------------------------------------------
+SKY_CLIP = ((-1.0, -1.0), (3.0, -1.0), (-1.0, 3.0))      # vertex/skybox.hlsl:20-24, SV_VertexID 0, 1, 2
+
+
+def skybox_local_pos(inv_view_proj, viewport, width: int, height: int, dtype=np.float64):
+    """LocalPos at every pixel centre, [height, width, 3], as the shaders compute it: at each of the three vertices w = M (x, -y, 1, 1) and
+    LocalPos = w.xyz / w.w (vertex/skybox.hlsl:40-42), then the affine interpolation of the three vertex values over the viewport
+    (x, y, width, height, ...): all clip w are 1.  inv_view_proj: [col, row] (4, 4) or the 16 floats in memory order (the convention of
+    CameraData.viewProjection)."""
+    T = np.dtype(dtype).type
+    M = np.asarray(inv_view_proj, dtype=dtype).reshape(4, 4).T        # maths matrix
+    L = []
+    for x, y in SKY_CLIP:
+        w = M @ np.array([x, -y, 1.0, 1.0], dtype=dtype)
+        L.append(w[:3] / w[3])
+    vx, vy, vw, vh = (T(v) for v in viewport[:4])
+    hw, hh = vw * T(0.5), vh * T(0.5)
+    xn = ((np.arange(width, dtype=dtype) + T(0.5)) - (vx + hw)) / hw
+    yn = ((np.arange(height, dtype=dtype) + T(0.5)) - (vy + hh)) / hh
+    a = ((xn + T(1.0)) * T(0.25))[None, :, None]
+    b = ((yn + T(1.0)) * T(0.25))[:, None, None]
+    return (L[0] + (L[1] - L[0]) * a + (L[2] - L[0]) * b).astype(dtype)
+
+
+def skybox_directions(inv_view_proj, viewport, width: int, height: int, dtype=np.float64):
+    """normalize(LocalPos) per pixel (pixel/skybox.hlsl:24): [height, width, 3]."""
+    return _normalize(skybox_local_pos(inv_view_proj, viewport, width, height, dtype)).astype(dtype)
+
+
+def skybox(levels, inv_view_proj, viewport, width: int, height: int, dtype=np.float64):
+    """The sky frame [height, width, 4]: the cube lookup at lod 0 along skybox_directions (the stated deviation: `Sample` without derivatives)."""
+    return sample_cube(levels[:1], skybox_directions(inv_view_proj, viewport, width, height, dtype), 0.0, dtype)
+
+
+def skybox_coverage(viewport, scissor, width: int, height: int, cull_mode: int = 0, front_face: int = 0):
+    """Pixels the sky triangle covers, bool [height, width]: the three vertices through the viewport in float32, snapped to 1 / 256 pixel,
+    culled under the geometry kernel's winding rule (front_face 0 = counter-clockwise: front <=> S < 0), integer edge functions at the pixel
+    centres with the top-left rule, cut by the scissor (x, y, width, height; None = the frame)."""
+    f = np.float32
+    vx, vy, vw, vh = (f(v) for v in viewport[:4])
+    hw, hh = f(0.5) * vw, f(0.5) * vh
+    cx, cy = vx + hw, vy + hh
+    X = [int(np.rint(f(f(f(x) * hw + cx) * f(256.0)))) for x, _ in SKY_CLIP]
+    Y = [int(np.rint(f(f(f(y) * hh + cy) * f(256.0)))) for _, y in SKY_CLIP]
+    S = (X[1] - X[0]) * (Y[2] - Y[0]) - (X[2] - X[0]) * (Y[1] - Y[0])
+    front = S < 0 if front_face == 0 else S > 0
+    out = np.zeros((height, width), dtype=bool)
+    if S == 0 or cull_mode == 3 or (cull_mode == 2 and not front) or (cull_mode == 1 and front):
+        return out
+    if S < 0:
+        X[1], X[2], Y[1], Y[2] = X[2], X[1], Y[2], Y[1]
+    px = 256 * np.arange(width, dtype=np.int64)[None, :] + 128
+    py = 256 * np.arange(height, dtype=np.int64)[:, None] + 128
+    inside = np.ones((height, width), dtype=bool)
+    for i in range(3):
+        j = (i + 1) % 3
+        dx, dy = X[j] - X[i], Y[j] - Y[i]
+        bias = 0 if (dy < 0 or (dy == 0 and dx > 0)) else -1
+        inside &= (-dy * (px - X[i]) + dx * (py - Y[i]) + bias) >= 0
+    if scissor is not None:
+        sx, sy, sw, sh = scissor
+        cut = np.zeros_like(inside)
+        cut[max(sy, 0):max(sy + sh, 0), max(sx, 0):max(sx + sw, 0)] = True
+        inside &= cut
+    return inside
+
+
 # ---- test environment ---------------------------------------------------------------------------------------------------------
 LOBE_AXIS = (0.48, 0.64, 0.6)      # unit vector
 LOBE_PEAK = 20.0

@@ -15,7 +15,7 @@ from typing import List, Optional
 
 import numpy as np
 
-PROGRAM_TRIANGLE, PROGRAM_MODEL, PROGRAM_MODEL_FULL, PROGRAM_MODEL_PBR, PROGRAM_SHADOW, PROGRAM_MODEL_PBR_IBL = 0, 1, 2, 3, 4, 5
+PROGRAM_TRIANGLE, PROGRAM_MODEL, PROGRAM_MODEL_FULL, PROGRAM_MODEL_PBR, PROGRAM_SHADOW, PROGRAM_MODEL_PBR_IBL, PROGRAM_SKYBOX = 0, 1, 2, 3, 4, 5, 6
 LOAD_OP_LOAD, LOAD_OP_CLEAR = 0, 1
 CULL_NONE, CULL_FRONT, CULL_BACK, CULL_FRONT_AND_BACK = 0, 1, 2, 3
 FRONT_CCW, FRONT_CW = 0, 1
@@ -360,6 +360,30 @@ class IblSpec:
 
 
 @dataclass
+class SkySpec:
+    """The sky of a scene (PROGRAM_SKYBOX, mirhi_cmd_bind_skybox): the environment cube -- `levels`, a list of [6, n >> l, n >> l, 4] float32
+    arrays to upload, or `image`, an existing cube (the caller's) -- and inverseViewProjection ([col, row] float32, the push constants).
+    Drawn after the scene's draws with LESS_OR_EQUAL and no depth write, as the reference intends; first=True: ahead of them."""
+    inv_view_proj: np.ndarray
+    levels: Optional[list] = None
+    image: Optional[object] = None
+    depth_test: bool = True
+    depth_write: bool = False
+    depth_compare: int = CMP_LESS_OR_EQUAL
+    cull_mode: int = CULL_NONE
+    front_face: int = FRONT_CCW
+    viewport: Optional[tuple] = None      # (x, y, w, h, min_depth, max_depth); None = full extent, 0..1
+    scissor: Optional[tuple] = None
+    first: bool = False
+
+    def create_image(self, device, image_cls):
+        from . import ibl as _ibl
+        img = image_cls.create_cube(device, int(self.levels[0].shape[1]), len(self.levels))
+        img.upload(_ibl.pack_cube([np.asarray(l, dtype=np.float32) for l in self.levels]))
+        return img
+
+
+@dataclass
 class Scene:
     name: str
     width: int
@@ -370,6 +394,7 @@ class Scene:
     shadow: Optional[ShadowSpec] = None        # None: no shadow scope (the oracle's PBR frame: shadow = 1)
     cascades: Optional["CascadeSpec"] = None   # shadow cascades (shadow_csm.hlsli): four depth-only scopes ahead of the main scope; not with `shadow`
     ibl: Optional["IblSpec"] = None            # the IBL set of the scene's MODEL_PBR_IBL draws (mirhi_cmd_bind_ibl)
+    sky: Optional["SkySpec"] = None            # the environment drawn behind the scene (PROGRAM_SKYBOX, mirhi_cmd_bind_skybox)
 
     @property
     def num_triangles(self) -> int:
@@ -1000,6 +1025,44 @@ def ibl_facets_case(width: int = 128, height: int = 96, lit: bool = False, ao=No
                            ao=float(f32(fao)), emissive=np.asarray(emis, dtype=f32)))
     scene = Scene("ibl-facets", width, height, draws, clear_color=(0.01, 0.02, 0.03, 1.0), ibl=ibl_test_images(pre_size, pre_levels))
     scene.facets, scene.view, scene.proj, scene.eye = facets, view, proj, _v(IBL_FACETS_EYE)
+    return scene
+
+
+# ------------------------------------------------------------------------------------------------
+# the sky (vertex/skybox.hlsl + pixel/skybox.hlsl, MIRHI_PROGRAM_SKYBOX)
+# ------------------------------------------------------------------------------------------------
+SKYBOX_CAMERAS = ((0.6, 0.3), (math.pi / 4.0, 0.6155))      # (yaw, pitch); the second looks at a cube corner: both see three faces
+
+
+def sky_rotation(yaw: float, pitch: float) -> np.ndarray:
+    """Rotation-only view matrix ([col, row] float32) of a camera turned by `yaw` about +Y, then pitched up by `pitch`."""
+    cy, sy, cp, sp = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch)
+    fwd = np.array([-sy * cp, sp, -cy * cp])
+    right = np.array([cy, 0.0, -sy])
+    up = np.cross(right, fwd)
+    m = np.eye(4)
+    m[0, :3], m[1, :3], m[2, :3] = right, up, -fwd      # maths rows
+    return m.T.astype(f32)                              # -> [col, row]
+
+
+def inverse_view_projection(view: np.ndarray, proj: np.ndarray) -> np.ndarray:
+    """inverse(proj * view) as [col, row] float32 (inverted in float64)."""
+    vp = mat_mul(proj, view).astype(np.float64).T      # maths matrix
+    return np.linalg.inv(vp).T.astype(f32)
+
+
+def skybox_case(width: int = 128, height: int = 96, camera: int = 0, size: int = 16, levels: int = 5, fov_deg: float = 60.0) -> Scene:
+    """The sky alone: ibl.analytic_environment of size^2 (further levels: cube_mips scaled by 1 + l / 4, which a lod-0 lookup must never
+    show) behind nothing, camera SKYBOX_CAMERAS[camera] with a vertical field of view of 60 degrees.  scene.sky.inv_view_proj is the matrix."""
+    from . import ibl as _ibl
+    yaw, pitch = SKYBOX_CAMERAS[camera]
+    view = sky_rotation(yaw, pitch)
+    proj = perspective_rh(math.radians(fov_deg), width / height, 0.1, 100.0)      # (no y flip: vertex/skybox.hlsl:40 flips y itself)
+    l0 = _ibl.analytic_environment(size).astype(f32)
+    chain = [l0] + [((1.0 + 0.25 * (l + 1)) * m).astype(f32) for l, m in enumerate(_ibl.cube_mips(l0, levels)[1:])]
+    scene = Scene(f"skybox-{camera}-{size}x{levels}", width, height, [], clear_color=(0.01, 0.02, 0.03, 1.0),
+                  sky=SkySpec(inv_view_proj=inverse_view_projection(view, proj), levels=chain))
+    scene.view, scene.proj = view, proj
     return scene
 
 
