@@ -17,6 +17,8 @@ use std::sync::Arc;
 #[derive(Clone, Copy, Debug)] pub struct Viewport { pub x: f32, pub y: f32, pub width: f32, pub height: f32, pub min_depth: f32, pub max_depth: f32 }
 #[derive(Clone, Copy, Debug)] pub struct Rect2D { pub x: i32, pub y: i32, pub width: u32, pub height: u32 }
 #[derive(Clone, Copy, Debug)] pub enum ClearValue { Color([f32; 4]), Depth(f32) }
+#[repr(i32)] #[derive(Clone, Copy, Debug, PartialEq, Eq)] pub enum Filter { Nearest = 0, Linear = 1 }
+pub use mirhi_sys::{mirhi_buffer_copy as BufferCopy, mirhi_buffer_image_copy as BufferImageCopy, mirhi_image_blit as ImageBlit, mirhi_image_copy as ImageCopy};
 
 /// What `RenderingConfig::build` (rendering.rs:908-995) hands to `begin_rendering`: one colour attachment, optional depth.
 pub struct RenderingInfo<'a> {
@@ -141,6 +143,31 @@ impl CommandBuffer {
     pub fn push_constants<T: Copy>(&self, stages: u32, offset: u32, data: &T) -> RhiResult<()> {                            // :732
         let bytes = unsafe { std::slice::from_raw_parts(data as *const T as *const u8, std::mem::size_of::<T>()) };
         self.push_constants_bytes(stages, offset, bytes)
+    }
+    // ---- the transfer group, command.rs:844-1019 (include/mirhi.h "Transfer commands"): recorded outside a rendering scope.  Regions are the sys
+    // crate's `#[repr(C)]` structs (VkBufferCopy, VkBufferImageCopy, VkImageCopy, VkImageBlit cut down to 2-D, one layer); there are no image layouts.
+    pub fn copy_buffer(&self, src: &Buffer, dst: &Buffer, regions: &[BufferCopy]) -> RhiResult<()> {                        // :844
+        check(unsafe { mirhi_sys::mirhi_cmd_copy_buffer(self.raw, src.raw, dst.raw, regions.len() as u32, regions.as_ptr()) })
+    }
+    pub fn copy_buffer_to_image(&self, src: &Buffer, dst: &Image, regions: &[BufferImageCopy]) -> RhiResult<()> {           // :860
+        check(unsafe { mirhi_sys::mirhi_cmd_copy_buffer_to_image(self.raw, src.raw, dst.raw, regions.len() as u32, regions.as_ptr()) })
+    }
+    pub fn copy_image_to_buffer(&self, src: &Image, dst: &Buffer, regions: &[BufferImageCopy]) -> RhiResult<()> {           // :886
+        check(unsafe { mirhi_sys::mirhi_cmd_copy_image_to_buffer(self.raw, src.raw, dst.raw, regions.len() as u32, regions.as_ptr()) })
+    }
+    pub fn copy_image(&self, src: &Image, dst: &Image, regions: &[ImageCopy]) -> RhiResult<()> {                            // :913
+        check(unsafe { mirhi_sys::mirhi_cmd_copy_image(self.raw, src.raw, dst.raw, regions.len() as u32, regions.as_ptr()) })
+    }
+    pub fn blit_image(&self, src: &Image, dst: &Image, regions: &[ImageBlit], filter: Filter) -> RhiResult<()> {            // :943
+        check(unsafe { mirhi_sys::mirhi_cmd_blit_image(self.raw, src.raw, dst.raw, regions.len() as u32, regions.as_ptr(), filter as i32) })
+    }
+    /// The whole image, every level.
+    pub fn clear_color_image(&self, image: &Image, color: &[f32; 4]) -> RhiResult<()> {                                     // :977
+        check(unsafe { mirhi_sys::mirhi_cmd_clear_color_image(self.raw, image.raw, color.as_ptr()) })
+    }
+    /// D32_SFLOAT: the whole image, or the one layer a layer view stands for (the path has no stencil).
+    pub fn clear_depth_stencil_image(&self, image: &Image, depth: f32) -> RhiResult<()> {                                   // :1003
+        check(unsafe { mirhi_sys::mirhi_cmd_clear_depth_stencil_image(self.raw, image.raw, depth) })
     }
     /// Queue lane (`Device::set_queue_lanes`) this command buffer is submitted on; several command buffers handed to one
     /// `Queue::submit` that are frames of the same shape run as one batch of launches on the first one's lane.

@@ -35,7 +35,9 @@ extern "C" {
                                     mirhi_cmd_bind_shadow_cascades;
                                     still 5 (new functions only): mirhi_image_create_cube and the five mirhi_ibl_ passes;
                                     still 5 (one new enum value, one new function): MIRHI_PROGRAM_MODEL_PBR_IBL, mirhi_cmd_bind_ibl;
-                                    still 5 (one new enum value, one new function): MIRHI_PROGRAM_SKYBOX, mirhi_cmd_bind_skybox */
+                                    still 5 (one new enum value, one new function): MIRHI_PROGRAM_SKYBOX, mirhi_cmd_bind_skybox;
+                                    still 5 (new functions, structs and one enum only): the seven transfer commands, mirhi_buffer_copy, mirhi_buffer_image_copy,
+                                    mirhi_image_copy, mirhi_image_blit, mirhi_filter */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -84,7 +86,8 @@ mirhi_result mirhi_device_name(mirhi_device* dev, char* out, uint32_t out_len);
 /* screen-tile-row split: this device rasterizes only the tile rows owned by `rank` of `world` (which ones: the
  * layout below); rank 0 / world 1 = whole frame.  Gathering the rows is mirhi_comm_all_gather_bands, or the caller's collective.
  * Depth-only scopes (shadow maps, MIRHI_PROGRAM_SHADOW) are not split: every rank renders the whole depth image, because each rank's
- * rows of a shadowed MODEL_PBR scope may sample any texel of it. */
+ * rows of a shadowed MODEL_PBR scope may sample any texel of it.  A recorded transfer command ("Transfer commands") is not split either: every
+ * rank moves what its own memory holds. */
 mirhi_result mirhi_device_set_tile_split(mirhi_device* dev, uint32_t rank, uint32_t world);
 /* Which tile rows a rank gets.  BANDS: one contiguous band of ceil(tile rows / world) rows per rank (the last rank's may be short).  INTERLEAVED (the
  * default; MIRHI_SPLIT=bands|interleaved in the environment sets another default): rank r owns tile rows r, r + world, r + 2 world, ... -- every rank then
@@ -455,6 +458,59 @@ mirhi_result mirhi_cmd_draw_indexed_indirect(mirhi_cmd* cmd, mirhi_buffer* buffe
  * with the command buffer (mirhi_cmd_begin* and mirhi_cmd_reset zero them); MIRHI_PROGRAM_SKYBOX reads bytes [0, 64) when its draw is recorded,
  * no other program reads any. */
 mirhi_result mirhi_cmd_push_constants(mirhi_cmd* cmd, uint32_t stage_flags, uint32_t offset, const void* data, uint32_t len);
+
+/* ---- Transfer commands: the transfer group of CommandBuffer (crates/rhi/src/command.rs:844-1019) ------------------------------------------
+ * copy_buffer :844, copy_buffer_to_image :860, copy_image_to_buffer :886, copy_image :913, blit_image :943, clear_color_image :977,
+ * clear_depth_stencil_image :1003.  The semantics are the Vulkan specification's (vkCmdCopyBuffer, vkCmdCopyBufferToImage, vkCmdCopyImageToBuffer,
+ * vkCmdCopyImage, vkCmdBlitImage, vkCmdClearColorImage, vkCmdClearDepthStencilImage), stated here once.
+ *
+ * Where.  Recorded outside a rendering scope; inside one the call returns MIRHI_ERR_DEVICE.  They execute in recording order with the rendering scopes
+ *   of their command buffer, on its queue lane: a scope recorded before a transfer has stored its attachments when the transfer runs, a scope recorded
+ *   after it (LOAD) finds what the transfer wrote.  A command buffer that holds a transfer never takes the batched submit form.
+ * Ordering across lanes.  A destination image is ordered like an attachment and a source image like a sampled shadow map (a layer view stands for
+ *   its array): a submit on another lane that uses the image waits for it and is waited for.  Buffers keep the documented rule: work on different
+ *   lanes is unordered unless a fence is waited.  mirhi_buffer_write waits for the pending submissions whose transfers read or write the buffer.
+ * Images taken.  2-D images, layer views (one layer of a D32_SFLOAT array) and, through mip_level, the levels of an image with a chain (level l has
+ *   max(1, width >> l) x max(1, height >> l) texels).  An array object or a cube as the handle is refused (InvalidHandle), as everywhere else.
+ *   There are no image layouts, no 3-D regions, no aspect masks and no subresource ranges: a clear takes the whole image.
+ * Tile split.  Not split: every rank moves what its own memory holds (mirhi_device_set_tile_split).
+ *
+ * Copies move raw texels, no conversion.  mirhi_cmd_copy_image needs equal texel size and both colour or both D32_SFLOAT (so B8G8R8A8_SRGB <->
+ *   R8G8B8A8_UNORM copies the bytes as they are).  Buffer <-> image copies take every format; texel (x, y) of the region sits at
+ *   buffer_offset + ((y * row_length) + x) * texel size, row_length = buffer_row_length, or image_extent[0] when that is 0 (tightly packed);
+ *   buffer_row_length / buffer_image_height, when not 0, must be at least the extent.
+ * Refused at record time (InvalidHandle; the message names the cause): a region outside its resource, offsets that overflow, a zero extent or
+ *   size, region_count 0 or above 16, overlapping source and destination ranges of one resource, a buffer_offset that is not a multiple of the
+ *   texel size, resources of another device than the command buffer's.
+ *
+ * Blit.  Source and destination are each one of B8G8R8A8_SRGB, R8G8B8A8_UNORM, R8G8B8A8_SRGB, R32G32B32A32_SFLOAT (D32_SFLOAT and R32_UINT are
+ *   refused) and must be different images.  A region maps the source rectangle src_offsets[0] .. src_offsets[1] onto the destination rectangle
+ *   dst_offsets[0] .. dst_offsets[1]; every corner lies inside its level ([0, width] x [0, height]); a rectangle of zero area is refused.
+ *   For destination texel (i, j) of the region, min(xdst0, xdst1) <= i < max(xdst0, xdst1):
+ *       u = (i + 1/2 - xdst0) * (xsrc1 - xsrc0) / (xdst1 - xdst0) + xsrc0,      v likewise from j and the y offsets.
+ *   Reversed offsets on either side flip the image.  NEAREST takes texel (floor(u), floor(v)).  LINEAR takes the four texels (i0, j0), (i0 + 1, j0),
+ *   (i0, j0 + 1), (i0 + 1, j0 + 1), i0 = floor(u - 1/2), j0 = floor(v - 1/2), with the weights a = frac(u - 1/2), b = frac(v - 1/2):
+ *       ((1 - a) t00 + a t10) (1 - b) + ((1 - a) t01 + a t11) b.      Indices are clamped to the level's edge.
+ *   floor and frac are exact (the offsets are integers: the quotient is formed in integer arithmetic), a weight is rounded to float32 once.
+ *   Conversion: an sRGB source is decoded per texel before the filter, through the 256-entry table the samplers use; alpha is linear (a / 255).
+ *   A store to an 8-bit destination is the raster resolve's: saturate, the sRGB OETF on RGB of an _SRGB format, round-to-nearest-even of x * 255,
+ *   in the destination's byte order.  A float destination is stored unclamped.
+ * Clears.  A clear is a blit store of one value to every texel: mirhi_cmd_clear_color_image takes the four blit formats and clears every level of
+ *   the image; mirhi_cmd_clear_depth_stencil_image takes D32_SFLOAT only (the path has no stencil) and stores `depth` as it is -- the whole image,
+ *   or the one layer a layer view stands for. */
+typedef struct { uint64_t src_offset, dst_offset, size; } mirhi_buffer_copy;                     /* VkBufferCopy */
+typedef struct { uint64_t buffer_offset; uint32_t buffer_row_length, buffer_image_height;        /* VkBufferImageCopy, 2-D, one layer; */
+                 uint32_t mip_level; int32_t image_offset[2]; uint32_t image_extent[2]; } mirhi_buffer_image_copy;  /* 0 = tightly packed */
+typedef struct { uint32_t src_mip_level; int32_t src_offset[2]; uint32_t dst_mip_level; int32_t dst_offset[2]; uint32_t extent[2]; } mirhi_image_copy;   /* VkImageCopy */
+typedef struct { uint32_t src_mip_level; int32_t src_offsets[2][2]; uint32_t dst_mip_level; int32_t dst_offsets[2][2]; } mirhi_image_blit;              /* VkImageBlit: offsets[corner][x, y] */
+typedef enum { MIRHI_FILTER_NEAREST = 0, MIRHI_FILTER_LINEAR = 1 } mirhi_filter;                 /* VkFilter */
+mirhi_result mirhi_cmd_copy_buffer(mirhi_cmd* cmd, mirhi_buffer* src, mirhi_buffer* dst, uint32_t region_count, const mirhi_buffer_copy* regions);
+mirhi_result mirhi_cmd_copy_buffer_to_image(mirhi_cmd* cmd, mirhi_buffer* src_buffer, mirhi_image* dst_image, uint32_t region_count, const mirhi_buffer_image_copy* regions);
+mirhi_result mirhi_cmd_copy_image_to_buffer(mirhi_cmd* cmd, mirhi_image* src_image, mirhi_buffer* dst_buffer, uint32_t region_count, const mirhi_buffer_image_copy* regions);
+mirhi_result mirhi_cmd_copy_image(mirhi_cmd* cmd, mirhi_image* src_image, mirhi_image* dst_image, uint32_t region_count, const mirhi_image_copy* regions);
+mirhi_result mirhi_cmd_blit_image(mirhi_cmd* cmd, mirhi_image* src_image, mirhi_image* dst_image, uint32_t region_count, const mirhi_image_blit* regions, mirhi_filter filter);
+mirhi_result mirhi_cmd_clear_color_image(mirhi_cmd* cmd, mirhi_image* image, const float color[4]);          /* the whole image, every level */
+mirhi_result mirhi_cmd_clear_depth_stencil_image(mirhi_cmd* cmd, mirhi_image* image, float depth);           /* D32_SFLOAT: the whole image (a layer view: that layer) */
 
 /* ---- submit + sync: vkQueueSubmit (renderer.rs:407-424, frame_manager.rs:439-462), Fence (sync.rs:168-298) */
 mirhi_result mirhi_queue_submit(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd* const* cmds, mirhi_fence* fence /* may be NULL */);

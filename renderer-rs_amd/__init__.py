@@ -103,6 +103,11 @@ class GatherAlgo:
     DIRECT, BROADCAST = range(2)
 
 
+class Filter:
+    """mirhi_filter (VkFilter) of CommandBuffer.blit_image"""
+    NEAREST, LINEAR = range(2)
+
+
 class SplitLayout:
     """mirhi_split_layout: which tile rows a rank of a tile split rasterizes"""
     BANDS, INTERLEAVED = range(2)
@@ -150,6 +155,43 @@ class Viewport(C.Structure):
 
 class Rect2D(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+# regions of the recorded transfer commands (include/mirhi.h "Transfer commands"); the CommandBuffer methods also take plain tuples in field order
+class BufferCopy(C.Structure):           # VkBufferCopy
+    _fields_ = [("src_offset", C.c_uint64), ("dst_offset", C.c_uint64), ("size", C.c_uint64)]
+
+
+class BufferImageCopy(C.Structure):      # VkBufferImageCopy (2-D, one layer); row length / image height 0 = tightly packed
+    _fields_ = [("buffer_offset", C.c_uint64), ("buffer_row_length", C.c_uint32), ("buffer_image_height", C.c_uint32),
+                ("mip_level", C.c_uint32), ("image_offset", C.c_int32 * 2), ("image_extent", C.c_uint32 * 2)]
+
+
+class ImageCopy(C.Structure):            # VkImageCopy
+    _fields_ = [("src_mip_level", C.c_uint32), ("src_offset", C.c_int32 * 2), ("dst_mip_level", C.c_uint32), ("dst_offset", C.c_int32 * 2),
+                ("extent", C.c_uint32 * 2)]
+
+
+class ImageBlit(C.Structure):            # VkImageBlit: offsets[corner][x, y]
+    _fields_ = [("src_mip_level", C.c_uint32), ("src_offsets", (C.c_int32 * 2) * 2), ("dst_mip_level", C.c_uint32), ("dst_offsets", (C.c_int32 * 2) * 2)]
+
+
+def _regions(cls, regions):
+    """A ctypes array of `cls` from structures of that class or tuples in its field order (nested tuples for the array fields)."""
+    def one(r):
+        if isinstance(r, cls):
+            return r
+        out = cls()
+        for (name, ctype), value in zip(cls._fields_, r):
+            if issubclass(ctype, C.Array):
+                flat = np.asarray(value).reshape(-1).tolist()
+                words = (C.c_int32 * len(flat))(*[int(v) for v in flat])      # (ctypes integers wrap: the bits of a uint32 field too)
+                C.memmove(C.addressof(out) + getattr(cls, name).offset, words, 4 * len(flat))
+            else:
+                setattr(out, name, int(value))
+        return out
+    items = [one(r) for r in regions]
+    return (cls * max(1, len(items)))(*items), len(items)
 
 
 class DispatchTime(C.Structure):
@@ -247,6 +289,13 @@ _SIGNATURES = {
     "mirhi_cmd_bind_shadow_cascades": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "mirhi_cmd_bind_ibl": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mirhi_cmd_bind_skybox": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mirhi_cmd_copy_buffer": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(BufferCopy)]),
+    "mirhi_cmd_copy_buffer_to_image": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(BufferImageCopy)]),
+    "mirhi_cmd_copy_image_to_buffer": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(BufferImageCopy)]),
+    "mirhi_cmd_copy_image": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ImageCopy)]),
+    "mirhi_cmd_blit_image": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ImageBlit), C.c_int32]),
+    "mirhi_cmd_clear_color_image": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "mirhi_cmd_clear_depth_stencil_image": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_float]),
     "mirhi_cmd_set_viewport": (C.c_int32, [C.c_void_p, C.POINTER(Viewport)]),
     "mirhi_cmd_set_scissor": (C.c_int32, [C.c_void_p, C.POINTER(Rect2D)]),
     "mirhi_cmd_draw": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -778,6 +827,37 @@ class CommandBuffer:
     def push_constants(self, stage_flags: int, offset: int, data: bytes):
         buf = (C.c_uint8 * len(data)).from_buffer_copy(data) if data else None
         check(lib().mirhi_cmd_push_constants(self.handle, stage_flags, offset, buf, len(data)))
+
+    # ---- transfer commands (include/mirhi.h "Transfer commands"): recorded outside a rendering scope; regions are the structures above or tuples ----
+    def copy_buffer(self, src: Buffer, dst: Buffer, regions):
+        """regions: BufferCopy or (src_offset, dst_offset, size)"""
+        arr, n = _regions(BufferCopy, regions)
+        check(lib().mirhi_cmd_copy_buffer(self.handle, src.handle, dst.handle, n, arr))
+
+    def copy_buffer_to_image(self, src: Buffer, dst: Image, regions):
+        """regions: BufferImageCopy or (buffer_offset, buffer_row_length, buffer_image_height, mip_level, (x, y), (width, height))"""
+        arr, n = _regions(BufferImageCopy, regions)
+        check(lib().mirhi_cmd_copy_buffer_to_image(self.handle, src.handle, dst.handle, n, arr))
+
+    def copy_image_to_buffer(self, src: Image, dst: Buffer, regions):
+        arr, n = _regions(BufferImageCopy, regions)
+        check(lib().mirhi_cmd_copy_image_to_buffer(self.handle, src.handle, dst.handle, n, arr))
+
+    def copy_image(self, src: Image, dst: Image, regions):
+        """regions: ImageCopy or (src_mip_level, (sx, sy), dst_mip_level, (dx, dy), (width, height))"""
+        arr, n = _regions(ImageCopy, regions)
+        check(lib().mirhi_cmd_copy_image(self.handle, src.handle, dst.handle, n, arr))
+
+    def blit_image(self, src: Image, dst: Image, regions, filter: int = Filter.NEAREST):
+        """regions: ImageBlit or (src_mip_level, ((x0, y0), (x1, y1)), dst_mip_level, ((x0, y0), (x1, y1))); reversed corners flip"""
+        arr, n = _regions(ImageBlit, regions)
+        check(lib().mirhi_cmd_blit_image(self.handle, src.handle, dst.handle, n, arr, filter))
+
+    def clear_color_image(self, image: Image, color):
+        check(lib().mirhi_cmd_clear_color_image(self.handle, image.handle, (C.c_float * 4)(*[float(c) for c in color])))
+
+    def clear_depth_stencil_image(self, image: Image, depth: float):
+        check(lib().mirhi_cmd_clear_depth_stencil_image(self.handle, image.handle, float(depth)))
 
     def set_queue_lane(self, lane: int):
         check(lib().mirhi_cmd_set_queue_lane(self.handle, lane))

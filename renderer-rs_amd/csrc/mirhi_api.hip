@@ -542,6 +542,19 @@ struct RecordedPass {
         SkyDraw() { memset(this, 0, sizeof *this); }
         bool operator==(const SkyDraw& o) const { return memcmp(this, &o, sizeof *this) == 0; }
     } sky;
+    // A recorded transfer command (mirhi_cmd_copy_* / _blit_image / _clear_*): an entry of its own with no attachments, draws, bins or vertex job.
+    // kind: XFER_* (XFER_NONE: the entry is a rendering scope); the regions as the kernels take them, resolved when the command was recorded; the images
+    // are in `sampled` (ordered across lanes like attachments); span: [0, 1) the source buffer's bytes, [2, 3) the destination buffer's (recording_reads).
+    // All bytes defined (memcmp compares two recordings).
+    struct Transfer {
+        uint32_t kind, count, src_format, dst_format;
+        float color[4];
+        uint32_t groups, grid;      // work units of all regions; workgroups of the launch
+        const uint8_t* span[4];
+        Transfer() { memset(this, 0, sizeof *this); }
+        bool operator==(const Transfer& o) const { return memcmp(this, &o, sizeof *this) == 0; }
+    } xfer;
+    std::vector<XferRegion> xfer_regions;
 };
 
 // Words of the counter block that never move (a re-recorded frame of another shape finds them where the last frame's kernels
@@ -2044,6 +2057,247 @@ extern "C" mirhi_result mirhi_cmd_push_constants(mirhi_cmd* cmd, uint32_t stage_
     return MIRHI_OK;
 }
 
+// ---- transfer commands (include/mirhi.h "Transfer commands"; command.rs:844-1019) -------------------------------------------------------
+// A transfer command is an entry of the recording of its own: a RecordedPass with `xfer` set and no attachments, draws, bins or vertex job.  Its
+// regions are resolved here, at record time, into what the kernels of mirhi_transfer.hip.h take (XferRegion); everything that can be refused is.
+struct XferLevel { uint8_t* base; uint32_t w, h, bpp; mirhi_format format; };
+// one 2-D level of `img` as a transfer's source or destination: 2-D images, layer views, the levels of an image with a chain
+static mirhi_result xfer_level(const mirhi_cmd* cmd, const mirhi_image* img, uint32_t level, const char* what, XferLevel* out) {
+    if (!img) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s is null", what);
+    if (img->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the %s belongs to another device than the command buffer", what);
+    if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image is not a transfer's %s", what);
+    if (img->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array is not a transfer's %s: use a layer view (mirhi_image_create_layer_view)", what);
+    if (level >= img->levels) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: mip level %u of the %s out of range (the image has %u)", level, what, img->levels);
+    const uint32_t bpp = format_bpp(img->format);
+    uint32_t w = img->width, h = img->height;
+    size_t texels = 0;
+    for (uint32_t l = 0; l < level; l++) { texels += (size_t)w * h; w = w > 1 ? w >> 1 : 1; h = h > 1 ? h >> 1 : 1; }
+    *out = XferLevel{img->ptr + texels * bpp, w, h, bpp, img->format};
+    return MIRHI_OK;
+}
+static mirhi_result xfer_buffer(const mirhi_cmd* cmd, const mirhi_buffer* buf, const char* what) {
+    if (!buf) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s is null", what);
+    if (buf->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the %s belongs to another device than the command buffer", what);
+    return MIRHI_OK;
+}
+static mirhi_result xfer_begin(mirhi_cmd* cmd, const char* name, uint32_t region_count, const void* regions) {
+    REQUIRE_RECORDING(cmd);
+    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: %s inside an active rendering scope (transfer commands are recorded outside)", name);
+    if (region_count == 0u || region_count > XFER_MAX_REGIONS)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region_count %u must be in [1, %u]", name, region_count, XFER_MAX_REGIONS);
+    NULL_CHECK(regions, "regions");
+    return MIRHI_OK;
+}
+// a rectangle of a level: offset >= 0, extent > 0, offset + extent inside
+static mirhi_result xfer_rect(const char* name, uint32_t i, const char* what, const XferLevel& L, const int32_t off[2], const uint32_t ext[2]) {
+    if (ext[0] == 0u || ext[1] == 0u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u has a zero extent", name, i);
+    if (off[0] < 0 || off[1] < 0 || (uint64_t)off[0] + ext[0] > L.w || (uint64_t)off[1] + ext[1] > L.h)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u is outside its %s (offset %d, %d extent %u x %u, level %u x %u)", name, i, what, off[0], off[1], ext[0], ext[1], L.w, L.h);
+    return MIRHI_OK;
+}
+// the copy of one rectangle; rows that are whole and tight on both sides become one run
+static XferRegion xfer_copy_region(const uint8_t* src, uint64_t src_pitch, uint8_t* dst, uint64_t dst_pitch, uint64_t row_bytes, uint32_t rows) {
+    XferRegion g;
+    memset(&g, 0, sizeof g);
+    if (rows > 1u && src_pitch == row_bytes && dst_pitch == row_bytes) { row_bytes *= rows; rows = 1u; }
+    g.src = src; g.dst = dst; g.src_pitch = src_pitch; g.dst_pitch = dst_pitch; g.row_bytes = row_bytes; g.rows = rows;
+    const uint64_t apart = (uint64_t)(uintptr_t)src ^ (uint64_t)(uintptr_t)dst, pitches = rows > 1u ? (src_pitch ^ dst_pitch) : 0u;
+    g.unit = ((apart | pitches) & 15u) == 0u ? 16u : (((apart | pitches) & 3u) == 0u ? 4u : 1u);      // (x ^ y has the low bits of x - y)
+    const uint64_t accesses = row_bytes / g.unit;
+    g.chunks = (uint32_t)std::max<uint64_t>(1u, (accesses + 1023u) / 1024u);
+    return g;
+}
+// the entry itself: numbers the regions' work units through, notes the images for ordering across lanes and the buffers' spans for mirhi_buffer_write
+static mirhi_result xfer_push(mirhi_cmd* cmd, const char* name, uint32_t kind, std::vector<XferRegion>& regions, const std::vector<uint64_t>& units,
+                              mirhi_image* src_img, mirhi_image* dst_img, const mirhi_buffer* src_buf, const mirhi_buffer* dst_buf,
+                              uint32_t src_format, uint32_t dst_format, const float color[4]) {
+    uint64_t total = 0;
+    for (size_t i = 0; i < regions.size(); i++) { regions[i].first = (uint32_t)total; total += units[i]; if (total >= (1ull << 31)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: too much work for one command", name); }
+    RecordedPass p;
+    memset(&p.info, 0, sizeof p.info);
+    RecordedPass::Transfer& t = p.xfer;
+    t.kind = kind; t.count = (uint32_t)regions.size(); t.src_format = src_format; t.dst_format = dst_format;
+    if (color) memcpy(t.color, color, sizeof t.color);
+    t.groups = (uint32_t)total;
+    t.grid = (kind == XFER_COPY || kind == XFER_FILL) ? (uint32_t)std::min<uint64_t>(total, XFER_MAX_GROUPS) : (uint32_t)total;
+    if (src_buf) { t.span[0] = src_buf->ptr; t.span[1] = src_buf->ptr + src_buf->size; }
+    if (dst_buf) { t.span[2] = dst_buf->ptr; t.span[3] = dst_buf->ptr + dst_buf->size; }
+    p.xfer_regions = std::move(regions);
+    // a destination image is ordered like an attachment, a source image like a sampled shadow map (for_each_attachment; a layer view stands for its array)
+    if (src_img) p.sampled.push_back(src_img);
+    if (dst_img && dst_img != src_img) p.sampled.push_back(dst_img);
+    cmd->passes.push_back(std::move(p));
+    return MIRHI_OK;
+}
+static bool xfer_ranges_overlap(const uint8_t* a, uint64_t an, const uint8_t* b, uint64_t bn) { return a < b + bn && b < a + an; }
+
+extern "C" mirhi_result mirhi_cmd_copy_buffer(mirhi_cmd* cmd, mirhi_buffer* src, mirhi_buffer* dst, uint32_t region_count, const mirhi_buffer_copy* regions) {
+    static const char* const name = "copy_buffer";
+    mirhi_result r = xfer_begin(cmd, name, region_count, regions);
+    if (r != MIRHI_OK || (r = xfer_buffer(cmd, src, "source buffer")) != MIRHI_OK || (r = xfer_buffer(cmd, dst, "destination buffer")) != MIRHI_OK) return r;
+    std::vector<XferRegion> out; std::vector<uint64_t> units;
+    for (uint32_t i = 0; i < region_count; i++) {
+        const mirhi_buffer_copy& c = regions[i];
+        if (c.size == 0u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u has size 0", name, i);
+        if (c.src_offset + c.size < c.src_offset || c.dst_offset + c.size < c.dst_offset)
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u: offset + size overflows", name, i);
+        if (c.src_offset + c.size > src->size || c.dst_offset + c.size > dst->size)
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u is outside its buffer (source %llu + %llu of %llu, destination %llu + %llu of %llu)", name, i,
+                        (unsigned long long)c.src_offset, (unsigned long long)c.size, (unsigned long long)src->size, (unsigned long long)c.dst_offset, (unsigned long long)c.size, (unsigned long long)dst->size);
+        out.push_back(xfer_copy_region(src->ptr + c.src_offset, 0u, dst->ptr + c.dst_offset, 0u, c.size, 1u));
+        units.push_back(out.back().chunks);
+    }
+    // (by address: two handles may wrap one piece of memory)
+    for (uint32_t i = 0; i < region_count; i++)
+        for (uint32_t j = 0; j < region_count; j++)
+            if (xfer_ranges_overlap(out[i].src, out[i].row_bytes, out[j].dst, out[j].row_bytes))
+                return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: the source range of region %u and the destination range of region %u are overlapping", name, i, j);
+    return xfer_push(cmd, name, XFER_COPY, out, units, nullptr, nullptr, src, dst, 0u, 0u, nullptr);
+}
+
+static mirhi_result xfer_buffer_image(mirhi_cmd* cmd, const char* name, mirhi_buffer* buf, mirhi_image* img, bool to_image, uint32_t region_count, const mirhi_buffer_image_copy* regions) {
+    mirhi_result r = xfer_begin(cmd, name, region_count, regions);
+    if (r != MIRHI_OK || (r = xfer_buffer(cmd, buf, to_image ? "source buffer" : "destination buffer")) != MIRHI_OK) return r;
+    std::vector<XferRegion> out; std::vector<uint64_t> units;
+    for (uint32_t i = 0; i < region_count; i++) {
+        const mirhi_buffer_image_copy& c = regions[i];
+        XferLevel L;
+        if ((r = xfer_level(cmd, img, c.mip_level, to_image ? "destination image" : "source image", &L)) != MIRHI_OK) return r;
+        if ((r = xfer_rect(name, i, "image", L, c.image_offset, c.image_extent)) != MIRHI_OK) return r;
+        if ((c.buffer_row_length && c.buffer_row_length < c.image_extent[0]) || (c.buffer_image_height && c.buffer_image_height < c.image_extent[1]))
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u: buffer_row_length %u / buffer_image_height %u must be 0 (tightly packed) or at least the extent %u x %u", name, i,
+                        c.buffer_row_length, c.buffer_image_height, c.image_extent[0], c.image_extent[1]);
+        if (c.buffer_offset % L.bpp) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u: buffer_offset %llu is not a multiple of the texel size %u", name, i, (unsigned long long)c.buffer_offset, L.bpp);
+        const uint64_t pitch = (uint64_t)(c.buffer_row_length ? c.buffer_row_length : c.image_extent[0]) * L.bpp, row_bytes = (uint64_t)c.image_extent[0] * L.bpp;
+        const uint64_t need = pitch * (c.image_extent[1] - 1u) + row_bytes;
+        if (c.buffer_offset + need < c.buffer_offset) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u: buffer_offset + size overflows", name, i);
+        if (c.buffer_offset + need > buf->size)
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u is outside its buffer (offset %llu + %llu bytes of %llu)", name, i, (unsigned long long)c.buffer_offset, (unsigned long long)need, (unsigned long long)buf->size);
+        uint8_t* const ip = L.base + ((size_t)c.image_offset[1] * L.w + (size_t)c.image_offset[0]) * L.bpp;
+        uint8_t* const bp = buf->ptr + c.buffer_offset;
+        const uint64_t ipitch = (uint64_t)L.w * L.bpp;
+        out.push_back(to_image ? xfer_copy_region(bp, pitch, ip, ipitch, row_bytes, c.image_extent[1]) : xfer_copy_region(ip, ipitch, bp, pitch, row_bytes, c.image_extent[1]));
+        units.push_back((uint64_t)out.back().rows * out.back().chunks);
+    }
+    return xfer_push(cmd, name, XFER_COPY, out, units, to_image ? nullptr : img, to_image ? img : nullptr, to_image ? buf : nullptr, to_image ? nullptr : buf, 0u, 0u, nullptr);
+}
+extern "C" mirhi_result mirhi_cmd_copy_buffer_to_image(mirhi_cmd* cmd, mirhi_buffer* src_buffer, mirhi_image* dst_image, uint32_t region_count, const mirhi_buffer_image_copy* regions) {
+    return xfer_buffer_image(cmd, "copy_buffer_to_image", src_buffer, dst_image, true, region_count, regions);
+}
+extern "C" mirhi_result mirhi_cmd_copy_image_to_buffer(mirhi_cmd* cmd, mirhi_image* src_image, mirhi_buffer* dst_buffer, uint32_t region_count, const mirhi_buffer_image_copy* regions) {
+    return xfer_buffer_image(cmd, "copy_image_to_buffer", dst_buffer, src_image, false, region_count, regions);
+}
+
+extern "C" mirhi_result mirhi_cmd_copy_image(mirhi_cmd* cmd, mirhi_image* src_image, mirhi_image* dst_image, uint32_t region_count, const mirhi_image_copy* regions) {
+    static const char* const name = "copy_image";
+    mirhi_result r = xfer_begin(cmd, name, region_count, regions);
+    if (r != MIRHI_OK) return r;
+    std::vector<XferRegion> out; std::vector<uint64_t> units;
+    struct Rect { const uint8_t* base; int32_t x, y; uint32_t w, h; };
+    std::vector<Rect> srcs, dsts;
+    for (uint32_t i = 0; i < region_count; i++) {
+        const mirhi_image_copy& c = regions[i];
+        XferLevel S, D;
+        if ((r = xfer_level(cmd, src_image, c.src_mip_level, "source image", &S)) != MIRHI_OK || (r = xfer_level(cmd, dst_image, c.dst_mip_level, "destination image", &D)) != MIRHI_OK) return r;
+        if (S.bpp != D.bpp || (S.format == MIRHI_FORMAT_D32_SFLOAT) != (D.format == MIRHI_FORMAT_D32_SFLOAT))
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: formats %d and %d are not copy-compatible (equal texel size, both colour or both D32_SFLOAT)", name, (int)S.format, (int)D.format);
+        if ((r = xfer_rect(name, i, "source image", S, c.src_offset, c.extent)) != MIRHI_OK || (r = xfer_rect(name, i, "destination image", D, c.dst_offset, c.extent)) != MIRHI_OK) return r;
+        srcs.push_back(Rect{S.base, c.src_offset[0], c.src_offset[1], c.extent[0], c.extent[1]});
+        dsts.push_back(Rect{D.base, c.dst_offset[0], c.dst_offset[1], c.extent[0], c.extent[1]});
+        out.push_back(xfer_copy_region(S.base + ((size_t)c.src_offset[1] * S.w + (size_t)c.src_offset[0]) * S.bpp, (uint64_t)S.w * S.bpp,
+                                       D.base + ((size_t)c.dst_offset[1] * D.w + (size_t)c.dst_offset[0]) * D.bpp, (uint64_t)D.w * D.bpp, (uint64_t)c.extent[0] * S.bpp, c.extent[1]));
+        units.push_back((uint64_t)out.back().rows * out.back().chunks);
+    }
+    for (const Rect& a : srcs)
+        for (const Rect& b : dsts)
+            if (a.base == b.base && a.x < b.x + (int32_t)b.w && b.x < a.x + (int32_t)a.w && a.y < b.y + (int32_t)b.h && b.y < a.y + (int32_t)a.h)
+                return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: source and destination regions of one image level are overlapping", name);
+    return xfer_push(cmd, name, XFER_COPY, out, units, src_image, dst_image, nullptr, nullptr, 0u, 0u, nullptr);
+}
+
+static bool xfer_blit_format(mirhi_format f) {
+    return f == MIRHI_FORMAT_B8G8R8A8_SRGB || f == MIRHI_FORMAT_R8G8B8A8_UNORM || f == MIRHI_FORMAT_R8G8B8A8_SRGB || f == MIRHI_FORMAT_R32G32B32A32_SFLOAT;
+}
+extern "C" mirhi_result mirhi_cmd_blit_image(mirhi_cmd* cmd, mirhi_image* src_image, mirhi_image* dst_image, uint32_t region_count, const mirhi_image_blit* regions, mirhi_filter filter) {
+    static const char* const name = "blit_image";
+    mirhi_result r = xfer_begin(cmd, name, region_count, regions);
+    if (r != MIRHI_OK) return r;
+    if (filter != MIRHI_FILTER_NEAREST && filter != MIRHI_FILTER_LINEAR) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: unknown filter %d", name, (int)filter);
+    std::vector<XferRegion> out; std::vector<uint64_t> units;
+    uint32_t sf = 0, df = 0;
+    for (uint32_t i = 0; i < region_count; i++) {
+        const mirhi_image_blit& c = regions[i];
+        XferLevel S, D;
+        if ((r = xfer_level(cmd, src_image, c.src_mip_level, "source image", &S)) != MIRHI_OK || (r = xfer_level(cmd, dst_image, c.dst_mip_level, "destination image", &D)) != MIRHI_OK) return r;
+        if (!xfer_blit_format(S.format) || !xfer_blit_format(D.format))
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: unsupported: formats %d -> %d (B8G8R8A8_SRGB, R8G8B8A8_UNORM, R8G8B8A8_SRGB and R32G32B32A32_SFLOAT are blitted)", name, (int)S.format, (int)D.format);
+        if (src_image == dst_image || (src_image->parent && src_image->parent == dst_image->parent))
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: the source image must differ from the destination image", name);
+        sf = (uint32_t)S.format; df = (uint32_t)D.format;
+        for (int a = 0; a < 2; a++) {
+            const int32_t smax = (int32_t)(a ? S.h : S.w), dmax = (int32_t)(a ? D.h : D.w);
+            for (int e = 0; e < 2; e++)
+                if (c.src_offsets[e][a] < 0 || c.src_offsets[e][a] > smax || c.dst_offsets[e][a] < 0 || c.dst_offsets[e][a] > dmax)
+                    return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u is outside its image (source level %u x %u, destination level %u x %u)", name, i, S.w, S.h, D.w, D.h);
+            if (c.src_offsets[0][a] == c.src_offsets[1][a] || c.dst_offsets[0][a] == c.dst_offsets[1][a])
+                return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u has zero area", name, i);
+        }
+        XferRegion g;
+        memset(&g, 0, sizeof g);
+        g.src = S.base; g.dst = D.base; g.src_w = S.w; g.src_h = S.h; g.dst_w = D.w;
+        int32_t* const lo[2] = {&g.dx0, &g.dy0}; int32_t* const hi[2] = {&g.dx1, &g.dy1};
+        int32_t* const s0[2] = {&g.sx0, &g.sy0}; int32_t* const n0[2] = {&g.xn0, &g.yn0}; int32_t* const ns[2] = {&g.xns, &g.yns}; int32_t* const dn[2] = {&g.xd, &g.yd};
+        for (int a = 0; a < 2; a++) {
+            // u = (i + 1/2 - d0) (s1 - s0) / (d1 - d0) + s0  =  s0 + sgn (2 (i - d0) + 1) (s1 - s0) / (2 |d1 - d0|);  LINEAR samples at u - 1/2
+            const int64_t ds = (int64_t)c.src_offsets[1][a] - c.src_offsets[0][a], dd = (int64_t)c.dst_offsets[1][a] - c.dst_offsets[0][a];
+            const int64_t sgn = dd > 0 ? 1 : -1, mag = dd > 0 ? dd : -dd;
+            *lo[a] = std::min(c.dst_offsets[0][a], c.dst_offsets[1][a]); *hi[a] = std::max(c.dst_offsets[0][a], c.dst_offsets[1][a]);
+            const int64_t first = sgn * (2 * ((int64_t)*lo[a] - c.dst_offsets[0][a]) + 1) * ds - (filter == MIRHI_FILTER_LINEAR ? mag : 0), step = sgn * 2 * ds;
+            const int64_t reach = std::llabs(first) + std::llabs(step) * (mag + 64);      // (what a lane of an edge tile may form)
+            if (reach >= (1ll << 31)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: region %u: offsets overflow", name, i);
+            *s0[a] = c.src_offsets[0][a]; *n0[a] = (int32_t)first; *ns[a] = (int32_t)step; *dn[a] = (int32_t)(2 * mag);
+        }
+        g.tiles_x = (uint32_t)(((g.dx1 - 1) >> 5) - (g.dx0 >> 5) + 1);
+        const uint32_t tiles_y = (uint32_t)(((g.dy1 - 1) >> 5) - (g.dy0 >> 5) + 1);
+        out.push_back(g);
+        units.push_back((uint64_t)g.tiles_x * tiles_y);
+    }
+    return xfer_push(cmd, name, filter == MIRHI_FILTER_LINEAR ? XFER_BLIT_LINEAR : XFER_BLIT_NEAREST, out, units, src_image, dst_image, nullptr, nullptr, sf, df, nullptr);
+}
+
+// a clear: one range -- the whole image with every level of its chain, or the one layer a view stands for
+static mirhi_result xfer_clear(mirhi_cmd* cmd, const char* name, mirhi_image* image, const float color[4]) {
+    XferLevel L;
+    mirhi_result r = xfer_level(cmd, image, 0u, "image", &L);
+    if (r != MIRHI_OK) return r;
+    size_t texels = 0;
+    uint32_t w = image->width, h = image->height;
+    for (uint32_t l = 0; l < image->levels; l++) { texels += (size_t)w * h; w = w > 1 ? w >> 1 : 1; h = h > 1 ? h >> 1 : 1; }
+    XferRegion g;
+    memset(&g, 0, sizeof g);
+    g.dst = L.base; g.row_bytes = (uint64_t)texels * L.bpp; g.rows = 1u; g.unit = 16u;
+    g.chunks = (uint32_t)std::max<uint64_t>(1u, (g.row_bytes / 16u + 1023u) / 1024u);
+    std::vector<XferRegion> out{g}; std::vector<uint64_t> units{g.chunks};
+    return xfer_push(cmd, name, XFER_FILL, out, units, nullptr, image, nullptr, nullptr, 0u, (uint32_t)L.format, color);
+}
+extern "C" mirhi_result mirhi_cmd_clear_color_image(mirhi_cmd* cmd, mirhi_image* image, const float color[4]) {
+    static const char* const name = "clear_color_image";
+    REQUIRE_RECORDING(cmd); NULL_CHECK(color, "color");
+    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: %s inside an active rendering scope (transfer commands are recorded outside)", name);
+    if (image && !image->is_cube && !image->is_array && !xfer_blit_format(image->format))
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: unsupported: format %d (B8G8R8A8_SRGB, R8G8B8A8_UNORM, R8G8B8A8_SRGB and R32G32B32A32_SFLOAT are cleared)", name, (int)image->format);
+    return xfer_clear(cmd, name, image, color);
+}
+extern "C" mirhi_result mirhi_cmd_clear_depth_stencil_image(mirhi_cmd* cmd, mirhi_image* image, float depth) {
+    static const char* const name = "clear_depth_stencil_image";
+    REQUIRE_RECORDING(cmd);
+    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: %s inside an active rendering scope (transfer commands are recorded outside)", name);
+    if (image && !image->is_cube && !image->is_array && image->format != MIRHI_FORMAT_D32_SFLOAT)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: format %d is not D32_SFLOAT", name, (int)image->format);
+    const float value[4] = {depth, 0.0f, 0.0f, 0.0f};
+    return xfer_clear(cmd, name, image, value);
+}
+
 // ---- end(): size the workspace and build the launch plan ------------------------------------------
 template <typename T>
 static mirhi_result grow(T** ptr, size_t* have, size_t want_bytes) {
@@ -2083,6 +2337,8 @@ static bool same_recording(const std::vector<RecordedPass>& a, const std::vector
         if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || !(x.state == y.state) ||
             x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
         if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl) || !(x.sky == y.sky)) return false;
+        if (!(x.xfer == y.xfer) || x.xfer_regions.size() != y.xfer_regions.size() ||
+            (!x.xfer_regions.empty() && memcmp(x.xfer_regions.data(), y.xfer_regions.data(), x.xfer_regions.size() * sizeof(XferRegion)) != 0)) return false;
         if (x.draws.size() != y.draws.size() || x.draw_vb_bytes != y.draw_vb_bytes) return false;
         if (!x.draws.empty() && memcmp(x.draws.data(), y.draws.data(), x.draws.size() * sizeof(DrawDesc)) != 0) return false;
     }
@@ -2106,11 +2362,14 @@ static mirhi_result settle_pending(mirhi_cmd* cmd, bool in_submit) {
 
 static bool recording_reads(const std::vector<RecordedPass>& passes, const uint8_t* lo, const uint8_t* hi) {
     auto in = [&](const void* q) { return q && (const uint8_t*)q >= lo && (const uint8_t*)q < hi; };
-    for (const RecordedPass& pass : passes)
+    for (const RecordedPass& pass : passes) {
         for (const DrawDesc& d : pass.draws) {
             if (in(d.vb) || in(d.ib) || in(d.camera) || in(d.object) || in(d.lights) || in(d.material) || in(d.point_lights) || in(d.spot_lights) ||
                 in(d.shadow_data)) return true;
         }
+        // a transfer's buffers, read or written: a host write into either waits for it
+        if (pass.xfer.kind && ((pass.xfer.span[0] && pass.xfer.span[0] < hi && lo < pass.xfer.span[1]) || (pass.xfer.span[2] && pass.xfer.span[2] < hi && lo < pass.xfer.span[3]))) return true;
+    }
     return false;
 }
 static mirhi_result settle_readers(mirhi_device* dev, const uint8_t* lo, const uint8_t* hi) {
@@ -2255,8 +2514,10 @@ static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, c
     s.tiles_x = (pass.color_t.width + TILE - 1) / TILE; s.tiles_y = (pass.color_t.height + TILE - 1) / TILE;
     { uint32_t count; split_rows(dev->split_layout, dev->split_rank, dev->split_world, s.tiles_y, &s.r0, &s.rstep, &count); s.r1 = s.r0 + count; }
     if (pass.depth_only) { s.r0 = 0; s.r1 = s.tiles_y; s.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
+    // (a transfer is not split: every rank moves what its own memory holds; one "tile" for the workspace's sizes, the launch's workgroups are fill_params')
+    if (pass.xfer.kind) { s.tiles_x = 1u; s.tiles_y = 1u; s.r0 = 0u; s.r1 = 1u; s.rstep = 1u; }
     s.tris = pass.total_tris - pass.first_tri;
-    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs, pass.sky.on != 0u);
+    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs, pass.sky.on != 0u, pass.xfer.kind != 0u);
     s.mode = raster_mode(s.cls, s.tiles(), s.tris, w.spread, w.wide, knobs);
     s.bins = bin_geometry(s.tiles(), s.tris, pass.total_tris, s.mode.xcd_bins, w.pool_scale, knobs);
     return s;
@@ -2436,10 +2697,21 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
         memcpy(P.sky_pos0, k.pos0, sizeof P.sky_pos0); memcpy(P.sky_posx, k.posx, sizeof P.sky_posx); memcpy(P.sky_posy, k.posy, sizeof P.sky_posy);
         P.sky_depth_bits = k.depth_bits; P.sky_compare = k.compare; P.sky_write = k.write; P.sky_prim = k.prim;
     }
+    if (pass.xfer.kind) {      // (xfer_regions: build_plan places them in the parameter block)
+        const RecordedPass::Transfer& t = pass.xfer;
+        P.xfer = t.kind; P.xfer_count = t.count; P.xfer_src_format = t.src_format; P.xfer_dst_format = t.dst_format; P.xfer_groups = t.groups;
+        memcpy(P.xfer_color, t.color, sizeof P.xfer_color);
+        P.tiles_x = t.grid;      // the launch's workgroups (raster_variant: a 1-D grid)
+    }
     return P;
 }
 
+// Outside the C ABI (not in include/mirhi.h): how often this process has built a launch plan -- what end() of an unchanged recording does not do.
+static std::atomic<uint64_t> g_plan_builds{0};
+extern "C" uint64_t mirhi_debug_plan_builds(void) { return g_plan_builds.load(std::memory_order_relaxed); }
+
 static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
+    g_plan_builds.fetch_add(1, std::memory_order_relaxed);
     const PlanKnobs knobs = PlanKnobs::read();
     mirhi_device* dev = cmd->dev;
     HIP_TRY(hipSetDevice(dev->ordinal));
@@ -2456,10 +2728,11 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     }
     mirhi_result r;
     std::vector<ScopePlan> scopes;
-    size_t total_draws = 0, max_tiles = 0;
+    size_t total_draws = 0, max_tiles = 0, total_regions = 0;
     for (const RecordedPass& pass : cmd->passes) {
         scopes.push_back(plan_scope(dev, pass, w, knobs));
         total_draws += pass.draws.size();
+        total_regions += pass.xfer_regions.size();
         max_tiles = std::max(max_tiles, scopes.back().tiles());
     }
     if ((r = rearm_workspace(cmd, scopes, max_tiles, stream, knobs)) != MIRHI_OK) return r;
@@ -2467,10 +2740,11 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     size_t jobs_total = 0;
     for (const RecordedPass& pass : cmd->passes) { vertex.push_back(vertex_jobs(pass)); jobs_total += vertex.back().jobs.size(); }
     if ((r = grow_scope_buffers(w, cmd->passes, scopes, vertex)) != MIRHI_OK) return r;
-    // the parameter block: [2 x PassParams per scope][draw descriptors][vertex jobs]
+    // the parameter block: [2 x PassParams per scope][draw descriptors][transfer regions][vertex jobs]
     const size_t params_bytes = n * 2 * sizeof(PassParams);
     w.draws_off = (params_bytes + 255) & ~(size_t)255;
-    w.jobs_off = (w.draws_off + total_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
+    const size_t regions_off = (w.draws_off + total_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
+    w.jobs_off = (regions_off + total_regions * sizeof(XferRegion) + 255) & ~(size_t)255;
     const size_t block_bytes = w.jobs_off + jobs_total * sizeof(VsJob);
     if ((r = pblock_reserve(w, block_bytes ? block_bytes : 256)) != MIRHI_OK) return r;
     w.params = reinterpret_cast<PassParams*>(w.pblock);
@@ -2479,7 +2753,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     w.pimage.assign(block_bytes, 0);
     w.draws_count = total_draws;
 
-    size_t draws_done = 0, jobs_done = 0;
+    size_t draws_done = 0, jobs_done = 0, regions_done = 0;
     w.wide_eligible = false;
     cmd->plan.clear(); cmd->plan_programs.clear(); cmd->plan_tris = 0;
     for (size_t pi = 0; pi < n; pi++) {
@@ -2507,6 +2781,12 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         P.total_slots = slots;
         if (!v.draws.empty()) memcpy(w.pimage.data() + w.draws_off + draws_done * sizeof(DrawDesc), v.draws.data(), v.draws.size() * sizeof(DrawDesc));
         draws_done += v.draws.size();
+        if (P.xfer) {
+            const std::vector<XferRegion>& regions = cmd->passes[pi].xfer_regions;
+            P.xfer_regions = reinterpret_cast<const XferRegion*>(w.pblock + regions_off) + regions_done;
+            memcpy(w.pimage.data() + regions_off + regions_done * sizeof(XferRegion), regions.data(), regions.size() * sizeof(XferRegion));
+            regions_done += regions.size();
+        }
         cmd->plan.push_back(P);
         cmd->plan_programs.push_back(s.cls.programs);
         cmd->plan_tris += s.tris;
@@ -2852,7 +3132,8 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             uint32_t* big_count = c->ws.big_counts + c->ws.parity;
             // (a SKYBOX segment takes no bins and touches no counter: it re-arms nothing and parity stays where it is -- the raster kernel that
             // follows finds the counters as the one before the sky left them)
-            if (!P.sky) c->ws.parity ^= 1u;
+            // (and so a transfer entry)
+            if (!P.sky && !P.xfer) c->ws.parity ^= 1u;
             // ordered segment: slots of primitives that no draw of the segment covers (a Never draw keeps its ids) must read
             // as "no coverage" -- an all-zero record is a degenerate triangle whose edge functions are negative everywhere
             if (P.ordered_recs && P.ordered_count) HIP_TRY(hipMemsetAsync(P.ordered_recs, 0, (size_t)P.ordered_count * sizeof(TriRec), stream));
@@ -2869,7 +3150,7 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
                 tv.native_flags = (head_sys ? NATIVE_ACQUIRE_SYSTEM : 0u) | (sys ? NATIVE_RELEASE_SYSTEM : 0u);
                 tg.native_flags = (((P.vs_total_slots == 0u && head_sys) || sys) ? NATIVE_ACQUIRE_SYSTEM : 0u) | (sys ? NATIVE_RELEASE_SYSTEM : 0u);      // (behind a vertex kernel: that one took the acquire)
                 tr.native_flags = NATIVE_RELEASE_SYSTEM | (sys ? NATIVE_ACQUIRE_SYSTEM : 0u);
-                if (P.sky && head_sys) tr.native_flags |= NATIVE_ACQUIRE_SYSTEM;      // (a SKYBOX segment has no vertex or geometry packet: its only one takes the head's acquire)
+                if ((P.sky || P.xfer) && head_sys) tr.native_flags |= NATIVE_ACQUIRE_SYSTEM;      // (a SKYBOX segment or a transfer has no vertex or geometry packet: its only one takes the head's acquire)
             }
             {   // small scopes: fewer triangles per geometry wave (GeometryHead::tris_per_wave) -- the chip is mostly idle, a shorter wave is a shorter frame
                 const uint32_t geo_waves = P.total_slots / (uint32_t)GEOM_THREADS;
@@ -2893,7 +3174,7 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             HIP_TRY(le);
             const bool has_tiles = P.tile_row_end > P.tile_row_begin && P.tiles_x;
             const uint32_t* winners = nullptr;
-            if (counted && has_tiles && !P.ordered_recs && !P.depth_only && !P.sky) {      // (ordered -- blended -- segments, depth-only scopes and SKYBOX segments are not counted)
+            if (counted && has_tiles && !P.ordered_recs && !P.depth_only && !P.sky && !P.xfer) {      // (ordered -- blended -- segments, depth-only scopes, SKYBOX segments and transfers are not counted)
                 mirhi_result r;
                 if (timed && (r = timing_begin(dev, MIRHI_KERNEL_FRAGMENT_COUNT, c->lane, &tc)) != MIRHI_OK) return r;
                 HIP_TRY(launch_fragment_count(P, dp, big_count, stream, tc));
@@ -2917,7 +3198,7 @@ static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd*
             if (!keep_locked) lock.lock();
             HIP_TRY(le);
             if (winners) HIP_TRY(launch_winner_count(winners, P.width * P.height, dev->frag_stats, stream));
-            dev->stats.frames_submitted++;
+            if (!P.xfer) dev->stats.frames_submitted++;      // (a transfer is no rendering scope)
             dev->stats.triangles_submitted += P.total_tris;
         }
     }

@@ -128,6 +128,29 @@ typedef TriRec BigRec;    // the big list holds TriRecs
 struct BinRec { uint32_t w[8]; };
 static_assert(sizeof(BinRec) == 32, "BinRec is 32 bytes");
 
+// One region of a recorded transfer command, resolved at record time (mirhi_api.hip record_transfer).  `first`: the region's first work unit of the
+// launch -- the units of all regions are numbered through, a workgroup finds its region by these.
+//   copy  a rectangle of `rows` rows of `row_bytes` bytes from src (pitch src_pitch) to dst (pitch dst_pitch); unit = 16, 4 or 1: the widest access
+//         every row's source and destination are co-aligned for; a work unit is 256 such accesses of one row (`chunks` per row)
+//   fill  row_bytes bytes at dst (4-byte texels or float4 ones; a work unit is 256 16-byte stores)
+//   blit  src / dst are the bases of the two levels, src_w x src_h and dst_w their extents in texels; the destination rectangle [dx0, dx1) x [dy0, dy1)
+//         is cut into 32 x 32 tiles aligned to the level's origin (tiles_x per row of tiles; a work unit is a tile).  Column i samples the source at
+//         u = sx0 + (xn0 + xns (i - dx0)) / xd (xd > 0; integers: the texel index of NEAREST and LINEAR is exact, a LINEAR weight is rounded once),
+//         which is include/mirhi.h's u (NEAREST) or u - 1/2 (LINEAR); rows likewise.
+struct XferRegion {
+    const uint8_t* src; uint8_t* dst;
+    uint64_t src_pitch, dst_pitch, row_bytes;
+    uint32_t rows, unit, chunks, first;
+    uint32_t src_w, src_h, dst_w, tiles_x;
+    int32_t  dx0, dy0, dx1, dy1;
+    int32_t  sx0, xn0, xns, xd;
+    int32_t  sy0, yn0, yns, yd;
+};
+static_assert(sizeof(XferRegion) == 120, "XferRegion is 120 bytes");
+enum : uint32_t { XFER_NONE = 0u, XFER_COPY = 1u, XFER_BLIT_NEAREST = 2u, XFER_BLIT_LINEAR = 3u, XFER_FILL = 4u };
+constexpr uint32_t XFER_MAX_REGIONS = 16u;
+constexpr uint32_t XFER_MAX_GROUPS = 2048u;      // workgroups of a copy or fill launch (grid-strided beyond)
+
 struct PassParams {
     uint32_t width, height;           // colour target extent
     uint32_t tiles_x, tiles_y;
@@ -220,6 +243,14 @@ struct PassParams {
     uint32_t sky_depth_bits;          // the viewport's max_depth: the fragment's depth
     uint32_t sky_compare, sky_write;  // mirhi_compare_op (ALWAYS when the depth test is off), 1: passing fragments store sky_depth_bits
     uint32_t sky_prim;                // the draw's primitive id
+    // A transfer command (include/mirhi.h "Transfer commands"; an entry of the recording of its own: no attachments, draws or bins; the kernels of
+    // mirhi_transfer.hip.h alone read these words).  Its regions sit in the parameter block behind the draw descriptors.
+    uint32_t xfer;                    // XFER_NONE, or what the entry is: XFER_COPY, XFER_BLIT_NEAREST, XFER_BLIT_LINEAR, XFER_FILL
+    uint32_t xfer_count;              // regions (1 .. 16)
+    uint32_t xfer_src_format, xfer_dst_format;      // mirhi_format of a blit's source / a blit's or clear's destination
+    const XferRegion* xfer_regions;
+    float    xfer_color[4];           // a clear's value (depth: [0])
+    uint32_t xfer_groups, xfer_pad;   // work units of all regions together (XferRegion::first of a region behind the last)
 };
 static_assert(sizeof(PassParams) % 8 == 0, "PassParams holds pointers");
 

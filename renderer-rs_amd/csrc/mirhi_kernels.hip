@@ -1,6 +1,7 @@
 // mirhi_kernels.hip -- gfx950 (CDNA4) kernels of the compute rasterizer.
 //
-// Two kernels per rendering scope (DESIGN.md "Kernels"; a SKYBOX segment runs sky_kernel alone, mirhi_sky.hip.h):
+// Two kernels per rendering scope (DESIGN.md "Kernels"; a SKYBOX segment runs sky_kernel alone, mirhi_sky.hip.h; a recorded transfer command one
+// kernel of mirhi_transfer.hip.h):
 //   geometry_kernel  one lane per input triangle: index + vertex fetch, vertex-shader position,
 //                    clip / divide / viewport / snap / cull / depth-plane setup, then tile binning.
 //                    Restates SURVEY 8a rows a1, a2, a4, a5 (crates/rhi/src/vertex.rs:20-61,88-170;
@@ -38,6 +39,7 @@ namespace mirhi {
 #include "mirhi_sky.hip.h"
 #include "mirhi_stats.hip.h"
 #include "mirhi_ordered.hip.h"
+#include "mirhi_transfer.hip.h"
 
 // the build this code object belongs to (build.py passes the source hash to both translation units; native_device_open compares)
 #ifndef MIRHI_SOURCE_HASH
@@ -129,6 +131,11 @@ static const RasterEntry k_raster_entries[] = {
     IBL(0, 1, 0), IBL(1, 1, 0), IBL(0, 0, 0), IBL(1, 0, 0), IBL(0, 1, 1), IBL(1, 1, 1), IBL(0, 0, 1), IBL(1, 0, 1), IBL(0, 1, 2), IBL(1, 1, 2), IBL(0, 0, 2), IBL(1, 0, 2),
     // a SKYBOX segment (no key, no bins: one kernel)
     {raster_kernel_id(RASTER_SKY, 0, 0, 0, 1, 0, 4), "sky_kernel", sky_kernel},
+    // a recorded transfer command (progs: PassParams::xfer)
+    {raster_kernel_id(RASTER_TRANSFER, XFER_COPY, 0, 0, 1, 0, 4), "transfer_copy_kernel", transfer_copy_kernel},
+    {raster_kernel_id(RASTER_TRANSFER, XFER_BLIT_NEAREST, 0, 0, 1, 0, 4), "transfer_blit_kernel<0>", transfer_blit_kernel<0>},
+    {raster_kernel_id(RASTER_TRANSFER, XFER_BLIT_LINEAR, 0, 0, 1, 0, 4), "transfer_blit_kernel<1>", transfer_blit_kernel<1>},
+    {raster_kernel_id(RASTER_TRANSFER, XFER_FILL, 0, 0, 1, 0, 4), "transfer_fill_kernel", transfer_fill_kernel},
 };
 #undef IBL
 #undef ORDERED
@@ -205,7 +212,7 @@ hipError_t launch_raster_batch(const PassParams* const* Ps, const PassParams* co
 
 hipError_t launch_fragment_count(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, hipStream_t stream, LaunchTiming t) {
     const uint32_t rows = P.tile_row_end - P.tile_row_begin;
-    if (rows == 0 || P.tiles_x == 0 || P.ordered_recs || P.depth_only || P.sky) return hipSuccess;
+    if (rows == 0 || P.tiles_x == 0 || P.ordered_recs || P.depth_only || P.sky || P.xfer) return hipSuccess;
     MIRHI_LAUNCH(fragment_count_kernel, dim3(P.tiles_x, rows), dim3(RASTER_THREADS), stream, t, dev_params, raster_head(P, big_count));
     return launch_result();
 }
@@ -220,12 +227,14 @@ hipError_t launch_winner_count(const uint32_t* prim, uint32_t pixels, unsigned l
 // Outside the C ABI (not in include/mirhi.h) and without a HIP call: the kernel, grid and block that launch_raster -- with n_batch >= 2: launch_raster_batch
 // of that many scopes -- chooses for a scope of 5 x 4 tiles.  in: programs, allow_wide, then PassParams::pred, zflip, zmask, tp_max_area, raster_teams,
 // raster_wide, alpha_scope, xcd_swizzle, "ordered_recs is set", n_batch (0 = single launch).  Returns 1 where no batched form exists.
+// programs == PROGS_TRANSFER: in[2] is PassParams::xfer and in[3] the launch's workgroups (PassParams::tiles_x of a transfer entry).
 extern "C" int mirhi_debug_raster_choice(const uint32_t in[12], char* name, uint32_t name_len, uint32_t grid_block[4]) {
     static TriRec some_recs;
     PassParams P{};
     P.tiles_x = 5u; P.tile_row_begin = 0u; P.tile_row_end = 4u; P.tile_row_step = 1u;
     P.pred = in[2]; P.zflip = in[3]; P.zmask = in[4]; P.tp_max_area = in[5]; P.raster_teams = in[6]; P.raster_wide = in[7]; P.alpha_scope = in[8]; P.xcd_swizzle = in[9];
     P.ordered_recs = in[10] ? &some_recs : nullptr;
+    if (in[0] == PROGS_TRANSFER) { P.xfer = in[2]; P.tiles_x = in[3]; P.tile_row_end = 1u; }      // (a transfer entry: in[2] is what it is -- XFER_* --, in[3] its workgroups)
     const uint32_t n = in[11];
     const RasterVariant v = raster_variant(P, in[0], n >= 2u || in[1] != 0u);
     const RasterBatchEntry* b = n >= 2u ? raster_batch_entry(v) : nullptr;

@@ -141,11 +141,15 @@ struct ScopeClass {
     // A SKYBOX segment (one SKYBOX draw, always a segment of its own: record_draw): no triangles, vertex jobs or bins; its raster launch is sky_kernel.
     // A family of its own: plain tile order, no wide or two-team variant, no triangle-parallel path.
     bool sky;
+    // A recorded transfer command (include/mirhi.h "Transfer commands"): no scope at all -- no attachments, draws, key or bins; its one launch is a kernel of
+    // mirhi_transfer.hip.h.  A class of its own, treated by the selectors as a sky segment is.
+    bool transfer;
 };
 
-inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const DrawDesc* draws, size_t n, bool depth_only, const PlanKnobs& knobs, bool sky = false) {
+inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const DrawDesc* draws, size_t n, bool depth_only, const PlanKnobs& knobs, bool sky = false, bool transfer = false) {
     ScopeClass c{};
     c.key = depth_key_setup(s, clear_depth);
+    if (transfer) { c.transfer = true; c.own_family = true; c.programs = PROGS_TRANSFER; return c; }
     if (sky) {      // (the depth state is the sky kernel's own business: PassParams::sky_compare / sky_write; nothing of the segment is ordered or masked)
         c.sky = true; c.has_draws = true; c.own_family = true; c.programs = PROGS_SKY;
         return c;
@@ -210,7 +214,7 @@ inline RasterMode raster_mode(const ScopeClass& c, size_t tiles, size_t tris, bo
     }
     m.xcd_swizzle = knobs.xcd_run.set ? (uint32_t)knobs.xcd_run.value : 1u;
     if (c.own_family) { m.xcd_swizzle = 1u; m.wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
-    if (c.sky) { m.tp_max_area = 0u; m.teams = 1u; m.wide_eligible = false; m.xcd_bins = false; }
+    if (c.sky || c.transfer) { m.tp_max_area = 0u; m.teams = 1u; m.wide_eligible = false; m.xcd_bins = false; }
     return m;
 }
 

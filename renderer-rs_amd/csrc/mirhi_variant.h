@@ -16,10 +16,11 @@ enum : uint32_t {
     PROGS_CASCADED = 16u,     // ... whose shadow term is CalculateShadowCSM (always together with PROGS_SHADOWED): raster_kernel_csm
     PROGS_IBL = 32u,          // a MODEL_PBR_IBL draw (always together with PROGS_PBR; with PROGS_SHADOWED / PROGS_CASCADED when its draws are shadowed): raster_kernel_ibl
     PROGS_SKY = 64u,          // the VALUE 64, alone: a SKYBOX segment (one SKYBOX draw, no triangles or bins): sky_kernel
+    PROGS_TRANSFER = 128u,    // the VALUE 128, alone: a recorded transfer command (no scope at all): the kernels of mirhi_transfer.hip.h, by PassParams::xfer
 };
 
-// (RASTER_IBL behind RASTER_ORDERED, RASTER_SKY behind RASTER_IBL: the values of the families before them are recorded in tests/golden/raster_variants.json)
-enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY };
+// (RASTER_IBL behind RASTER_ORDERED, RASTER_SKY behind RASTER_IBL, RASTER_TRANSFER behind RASTER_SKY: the values of the families before them are recorded in tests/golden/raster_variants.json)
+enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY, RASTER_TRANSFER };
 
 // the kernel instantiation alone (no launch shape) as one word
 constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves) {
@@ -50,6 +51,11 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
     if (programs == PROGS_SKY) {
         // a SKYBOX segment: one 256-thread workgroup per tile of the owned rows, always the 2-D grid; no key, no bins, no batched form
         return RasterVariant{RASTER_SKY, 0u, 0u, 0u, 1u, 0u, 4u, {P.tiles_x, rows, 1u}, (uint32_t)RASTER_THREADS, 0u};
+    }
+    if (programs == PROGS_TRANSFER) {
+        // a transfer entry: its kernel by what it is (progs = XFER_*), a 1-D grid of PassParams::tiles_x workgroups (the host's count: a blit's tiles, the
+        // capped work units of a copy or clear); no key, no bins, no batched form
+        return RasterVariant{RASTER_TRANSFER, P.xfer, 0u, 0u, 1u, 0u, 4u, {P.tiles_x * rows, 1u, 1u}, (uint32_t)RASTER_THREADS, 0u};
     }
     const uint32_t progs = programs >= PROGS_PBR ? 4u : ((programs == 2u || programs == 3u) ? programs : 1u);
     const bool mesh = programs == PROGS_MODEL || programs >= PROGS_PBR;      // no TRIANGLE draw: what the two-team and wide variants exist for

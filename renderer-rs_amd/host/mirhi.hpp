@@ -487,6 +487,24 @@ public:
     void draw_indexed(uint32_t index_count, uint32_t instance_count, uint32_t first_index, int32_t vertex_offset, uint32_t first_instance) const {
         check(mirhi_cmd_draw_indexed(h_, index_count, instance_count, first_index, vertex_offset, first_instance));
     }
+    // command.rs:844-1019, the transfer group (include/mirhi.h "Transfer commands"): recorded outside a rendering scope; regions are the C ABI's structs
+    void copy_buffer(const Buffer& src, const Buffer& dst, const std::vector<mirhi_buffer_copy>& regions) const {
+        check(mirhi_cmd_copy_buffer(h_, src.handle(), dst.handle(), (uint32_t)regions.size(), regions.data()));
+    }
+    void copy_buffer_to_image(const Buffer& src, const Image& dst, const std::vector<mirhi_buffer_image_copy>& regions) const {
+        check(mirhi_cmd_copy_buffer_to_image(h_, src.handle(), dst.handle(), (uint32_t)regions.size(), regions.data()));
+    }
+    void copy_image_to_buffer(const Image& src, const Buffer& dst, const std::vector<mirhi_buffer_image_copy>& regions) const {
+        check(mirhi_cmd_copy_image_to_buffer(h_, src.handle(), dst.handle(), (uint32_t)regions.size(), regions.data()));
+    }
+    void copy_image(const Image& src, const Image& dst, const std::vector<mirhi_image_copy>& regions) const {
+        check(mirhi_cmd_copy_image(h_, src.handle(), dst.handle(), (uint32_t)regions.size(), regions.data()));
+    }
+    void blit_image(const Image& src, const Image& dst, const std::vector<mirhi_image_blit>& regions, mirhi_filter filter) const {
+        check(mirhi_cmd_blit_image(h_, src.handle(), dst.handle(), (uint32_t)regions.size(), regions.data(), filter));
+    }
+    void clear_color_image(const Image& image, const float (&color)[4]) const { check(mirhi_cmd_clear_color_image(h_, image.handle(), color)); }
+    void clear_depth_stencil_image(const Image& image, float depth) const { check(mirhi_cmd_clear_depth_stencil_image(h_, image.handle(), depth)); }
 private:
     std::shared_ptr<Device> device_;
     mirhi_cmd* h_ = nullptr;
