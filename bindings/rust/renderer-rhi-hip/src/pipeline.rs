@@ -80,13 +80,13 @@ impl Drop for Pipeline {
 
 /// pipeline.rs:590-1059: same setters, same defaults (TriangleList, Fill, cull Back, CCW, depth test + write, Less; 645-698),
 /// same validation failures from `build` (920-952) -- they are produced by `mirhi_pipeline_create`.
-pub struct GraphicsPipelineBuilder { desc: mirhi_sys::mirhi_pipeline_desc }
+pub struct GraphicsPipelineBuilder { desc: mirhi_sys::mirhi_pipeline_desc, bias: Option<mirhi_sys::mirhi_depth_bias> }
 impl Default for GraphicsPipelineBuilder { fn default() -> Self { Self::new() } }
 impl GraphicsPipelineBuilder {
     pub fn new() -> Self {
         let mut d = std::mem::MaybeUninit::<mirhi_sys::mirhi_pipeline_desc>::zeroed();
         unsafe { mirhi_sys::mirhi_pipeline_desc_default(d.as_mut_ptr()) };
-        Self { desc: unsafe { d.assume_init() } }
+        Self { desc: unsafe { d.assume_init() }, bias: None }
     }
     pub fn vertex_shader(mut self, s: &Shader) -> Self {
         // the vertex stage is TRIANGLE or MODEL: every model fragment program shares vertex/model.hlsl
@@ -110,6 +110,14 @@ impl GraphicsPipelineBuilder {
     pub fn depth_compare_op(mut self, op: CompareOp) -> Self { self.desc.depth_compare_op = op as i32; self }
     /// Alpha-masked MODEL_PBR materials (`discard`, model_pbr.hlsl:176-179): fragments are resolved one by one in primitive order.
     pub fn fragment_discard_enable(mut self, on: bool) -> Self { self.desc.fragment_discard_enable = on as u32; self }
+    /// pipeline.rs:769: no near / far clipping, fragment depth clamped to [0, 1] ("pancaking" for shadow cascades).
+    pub fn depth_clamp_enable(mut self, on: bool) -> Self { self.desc.depth_clamp_enable = on as u32; self }
+    /// pipeline.rs:781-788: enables depth bias; o = max(|dz/dx|, |dz/dy|) * slope_factor + r * constant_factor, clamped by `clamp`.
+    pub fn depth_bias(mut self, constant_factor: f32, clamp: f32, slope_factor: f32) -> Self {
+        self.desc.depth_bias_enable = 1;
+        self.bias = Some(mirhi_sys::mirhi_depth_bias { constant_factor, clamp, slope_factor });
+        self
+    }
     pub fn color_attachment_format(mut self, f: Format) -> Self {
         self.desc.color_attachment_count = 1; self.desc.color_attachment_formats[0] = f as i32; self
     }
@@ -124,7 +132,10 @@ impl GraphicsPipelineBuilder {
     }
     pub fn build(self, device: Arc<Device>) -> RhiResult<Pipeline> {                                   // pipeline.rs:918-1057
         let mut raw = std::ptr::null_mut();
-        check(unsafe { mirhi_sys::mirhi_pipeline_create(device.raw, &self.desc, &mut raw) })?;
+        match &self.bias {
+            Some(b) => check(unsafe { mirhi_sys::mirhi_pipeline_create_with_depth_bias(device.raw, &self.desc, b, &mut raw) })?,
+            None => check(unsafe { mirhi_sys::mirhi_pipeline_create(device.raw, &self.desc, &mut raw) })?,
+        }
         Ok(Pipeline { device, raw })
     }
 }

@@ -305,6 +305,14 @@ typedef struct {
 } mirhi_pipeline_desc;
 void         mirhi_pipeline_desc_default(mirhi_pipeline_desc* desc);                      /* GraphicsPipelineBuilder::new :645-698 */
 mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pipeline_desc* desc, mirhi_pipeline** out); /* build :918-1057 */
+/* Depth bias and depth clamp.  depth_bias_enable adds o = m * slope_factor + r * constant_factor to every fragment depth of a triangle:
+ * m = max(|dz/dx|, |dz/dy|) of its window-space depth plane, r = 2^(e - 23) with e the exponent of the largest |z| of its three vertices (Vulkan's rule
+ * for a floating-point depth attachment); clamp > 0: o = min(o, clamp), clamp < 0: o = max(o, clamp), 0: none.  mirhi_pipeline_create takes
+ * depth_bias_enable = 1 with the builder's default factors (0, 0, 0 :665-667); this call implies depth_bias_enable = 1 and takes the factors.
+ * depth_clamp_enable: no clipping against the near and far planes, fragment depth clamped to [0, 1] -- draws need a viewport depth range of exactly [0, 1].
+ * Refused ("unsupported:"): a NULL or non-finite bias, either state on a SKYBOX pipeline or together with rasterizer_discard_enable. */
+typedef struct { float constant_factor, clamp, slope_factor; } mirhi_depth_bias;          /* GraphicsPipelineBuilder::depth_bias pipeline.rs:781-788 */
+mirhi_result mirhi_pipeline_create_with_depth_bias(mirhi_device* dev, const mirhi_pipeline_desc* desc, const mirhi_depth_bias* bias, mirhi_pipeline** out); /* depth_bias :781-788 + build :918-1057 */
 mirhi_result mirhi_pipeline_destroy(mirhi_pipeline* p);
 
 /* ---- command recording: CommandBuffer (command.rs:297-628) ------------------------------------------ */

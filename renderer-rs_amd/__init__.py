@@ -139,6 +139,11 @@ class PipelineDesc(C.Structure):
     ]
 
 
+class DepthBias(C.Structure):
+    """mirhi_depth_bias: the factors of GraphicsPipelineBuilder::depth_bias (pipeline.rs:781-788)"""
+    _fields_ = [("constant_factor", C.c_float), ("clamp", C.c_float), ("slope_factor", C.c_float)]
+
+
 class RenderingInfo(C.Structure):
     _fields_ = [
         ("color_image", C.c_void_p), ("color_load_op", C.c_int32), ("color_store_op", C.c_int32),
@@ -267,6 +272,7 @@ _SIGNATURES = {
     "mirhi_image_destroy": (C.c_int32, [C.c_void_p]),
     "mirhi_pipeline_desc_default": (None, [C.POINTER(PipelineDesc)]),
     "mirhi_pipeline_create": (C.c_int32, [C.c_void_p, C.POINTER(PipelineDesc), C.POINTER(C.c_void_p)]),
+    "mirhi_pipeline_create_with_depth_bias": (C.c_int32, [C.c_void_p, C.POINTER(PipelineDesc), C.POINTER(DepthBias), C.POINTER(C.c_void_p)]),
     "mirhi_pipeline_destroy": (C.c_int32, [C.c_void_p]),
     "mirhi_rendering_info_default": (None, [C.POINTER(RenderingInfo)]),
     "mirhi_cmd_create": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -641,6 +647,7 @@ class GraphicsPipelineBuilder:
 
     def __init__(self):
         self.desc = PipelineDesc()
+        self.bias = None        # depth_bias(): the factors, built through mirhi_pipeline_create_with_depth_bias
         lib().mirhi_pipeline_desc_default(C.byref(self.desc))
 
     def vertex_shader(self, program: int):
@@ -693,6 +700,17 @@ class GraphicsPipelineBuilder:
         self.desc.blend_enable = int(e)
         return self
 
+    def depth_clamp_enable(self, e: bool):
+        """pipeline.rs:769: no near / far clipping, fragment depth clamped to [0, 1]."""
+        self.desc.depth_clamp_enable = int(e)
+        return self
+
+    def depth_bias(self, constant_factor: float, clamp: float, slope_factor: float):
+        """pipeline.rs:781-788: enables depth bias with the three factors."""
+        self.desc.depth_bias_enable = 1
+        self.bias = DepthBias(constant_factor, clamp, slope_factor)
+        return self
+
     def fragment_discard_enable(self, e: bool):
         """Pipelines of alpha-masked MODEL_PBR materials (model_pbr.hlsl:176-179 `discard`): per-fragment, ordered resolve."""
         self.desc.fragment_discard_enable = int(e)
@@ -723,7 +741,10 @@ class GraphicsPipelineBuilder:
 
     def build(self, device: Device) -> "Pipeline":
         h = C.c_void_p()
-        check(lib().mirhi_pipeline_create(device.handle, C.byref(self.desc), C.byref(h)))
+        if self.bias is not None:
+            check(lib().mirhi_pipeline_create_with_depth_bias(device.handle, C.byref(self.desc), C.byref(self.bias), C.byref(h)))
+        else:
+            check(lib().mirhi_pipeline_create(device.handle, C.byref(self.desc), C.byref(h)))
         return Pipeline(h)
 
 
@@ -930,6 +951,20 @@ class Comm:
 
 
 # ---- scene helper: records a scenes.Scene the way crates/renderer records a frame ---------------------------
+def _depth_state(builder, draw, spec=None):
+    """The depth_bias=(constant, clamp, slope) and depth_clamp=True pipeline arguments of a scenes.DrawSpec -- a shadow caster without its own takes
+    its ShadowSpec's / CascadeSpec's -- applied to `builder`; with builder None: the pair itself (a pipeline cache key)."""
+    bias = draw.depth_bias if draw.depth_bias is not None else getattr(spec, "depth_bias", None)
+    clamp = bool(draw.depth_clamp or getattr(spec, "depth_clamp", False))
+    if builder is None:
+        return (tuple(bias) if bias is not None else None, clamp)
+    if bias is not None:
+        builder.depth_bias(*bias)
+    if clamp:
+        builder.depth_clamp_enable(True)
+    return builder
+
+
 class SceneResources:
     """Uploads a scenes.Scene once (vertex/index/uniform buffers, textures, pipelines) and records it into
     a reusable command buffer, mirroring Renderer::create_triangle_resources + record_commands
@@ -1009,6 +1044,7 @@ class SceneResources:
                 b.color_blend_attachment(*d.blend)
             if getattr(d, "alpha_test", False):
                 b.fragment_discard_enable(True)
+            _depth_state(b, d)
             pipe = b.build(device)
             self.objs.append(pipe)
             st = dict(pipe=pipe, vb=buf(BufferUsage.Vertex, d.vertices),
@@ -1033,6 +1069,7 @@ class SceneResources:
                       .vertex_binding(c.stride).vertex_attributes(SHADOW_VERTEX_OFFSETS)
                       .color_attachment_format(Format.UNDEFINED).depth_attachment_format(Format.D32_SFLOAT)
                       .cull_mode(c.cull_mode).front_face(c.front_face).depth_compare_op(c.depth_compare))
+                _depth_state(pb, c, sh)
                 pipe = pb.build(device)
                 self.objs.append(pipe)
                 self.shadow_state.append(dict(pipe=pipe, vb=buf(BufferUsage.Vertex, c.vertices),
@@ -1052,12 +1089,12 @@ class SceneResources:
             for layer in cs.casters:
                 states = []
                 for c in layer:
-                    pkey = ("shadow-pipe", c.stride, c.cull_mode, c.front_face, c.depth_compare)
+                    pkey = ("shadow-pipe", c.stride, c.cull_mode, c.front_face, c.depth_compare, _depth_state(None, c, cs))
                     if pkey not in cache:
-                        cache[pkey] = (GraphicsPipelineBuilder().vertex_shader(Program.SHADOW).fragment_shader(Program.SHADOW)
-                                       .vertex_binding(c.stride).vertex_attributes(SHADOW_VERTEX_OFFSETS)
-                                       .color_attachment_format(Format.UNDEFINED).depth_attachment_format(Format.D32_SFLOAT)
-                                       .cull_mode(c.cull_mode).front_face(c.front_face).depth_compare_op(c.depth_compare)).build(device)
+                        cache[pkey] = _depth_state(GraphicsPipelineBuilder().vertex_shader(Program.SHADOW).fragment_shader(Program.SHADOW)
+                                                   .vertex_binding(c.stride).vertex_attributes(SHADOW_VERTEX_OFFSETS)
+                                                   .color_attachment_format(Format.UNDEFINED).depth_attachment_format(Format.D32_SFLOAT)
+                                                   .cull_mode(c.cull_mode).front_face(c.front_face).depth_compare_op(c.depth_compare), c, cs).build(device)
                         self.objs.append(cache[pkey])
                     states.append(dict(pipe=cache[pkey], vb=buf(BufferUsage.Vertex, c.vertices),
                                        ib=buf(BufferUsage.Index, c.indices) if c.indices is not None else None,

@@ -502,6 +502,7 @@ struct mirhi_image {
 struct mirhi_pipeline {
     mirhi_device* dev;
     mirhi_pipeline_desc desc;
+    mirhi_depth_bias bias;       // the factors of depth_bias_enable (0, 0, 0 through mirhi_pipeline_create: the builder's defaults, pipeline.rs:665-667)
 };
 
 struct RecordedPass {
@@ -1332,9 +1333,8 @@ extern "C" void mirhi_pipeline_desc_default(mirhi_pipeline_desc* d) {
     d->color_write_mask = 0xFu;
 }
 
-extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pipeline_desc* d, mirhi_pipeline** out) {
-    NULL_CHECK(dev, "device"); NULL_CHECK(d, "desc"); NULL_CHECK(out, "out");
-    *out = nullptr;
+// bias: the factors of a depth_bias_enable pipeline (the desc's word is set by the caller)
+static mirhi_result pipeline_create(mirhi_device* dev, const mirhi_pipeline_desc* d, const mirhi_depth_bias& bias, mirhi_pipeline** out) {
     // --- the reference's own validation, same order and text (pipeline.rs:920-952) ---
     if (d->vertex_program == MIRHI_PROGRAM_NONE) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: Vertex shader is required");
     if (d->fragment_program == MIRHI_PROGRAM_NONE) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: Fragment shader is required");
@@ -1386,11 +1386,18 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
         if (d->color_blend_op < 0 || d->color_blend_op > MIRHI_BLEND_OP_MAX || d->alpha_blend_op < 0 || d->alpha_blend_op > MIRHI_BLEND_OP_MAX)
             return fail(MIRHI_ERR_PIPELINE, "Pipeline error: invalid blend op");
     }
-    if (d->depth_clamp_enable || d->depth_bias_enable) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth clamp / depth bias");
+    // depth bias / depth clamp: geometry-stage state of every program that has geometry
+    if (d->depth_clamp_enable || d->depth_bias_enable) {
+        if (!std::isfinite(bias.constant_factor) || !std::isfinite(bias.clamp) || !std::isfinite(bias.slope_factor))
+            return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth bias factors must be finite (constant %g, clamp %g, slope %g)", (double)bias.constant_factor,
+                        (double)bias.clamp, (double)bias.slope_factor);
+        if (vs_sky) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth bias / depth clamp on a SKYBOX pipeline (its fragments have no depth of their own)");
+        if (d->rasterizer_discard_enable) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: depth bias / depth clamp together with rasterizer_discard_enable");
+    }
     if (vs_sky) {
         // vertex/skybox.hlsl has no vertex input (SV_VertexID alone): no binding, no attributes (a blending or discarding one is refused at the draw)
         if (d->attribute_count != 0) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: program %d (SKYBOX) has no vertex input, got %u vertex attributes", d->vertex_program, d->attribute_count);
-        mirhi_pipeline* p = new (std::nothrow) mirhi_pipeline{dev, *d};
+        mirhi_pipeline* p = new (std::nothrow) mirhi_pipeline{dev, *d, bias};
         if (!p) return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: host allocation failed");
         dev->children++;
         *out = p;
@@ -1405,11 +1412,25 @@ extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pip
     for (uint32_t i = 0; i < want_attrs; i++)
         if (d->attribute_offsets[i] != (vs_model ? model_offsets[i] : tri_offsets[i]))
             return fail(MIRHI_ERR_PIPELINE, "Pipeline error: attribute %u offset %u does not match the reference vertex layout", i, d->attribute_offsets[i]);
-    mirhi_pipeline* p = new (std::nothrow) mirhi_pipeline{dev, *d};
+    mirhi_pipeline* p = new (std::nothrow) mirhi_pipeline{dev, *d, bias};
     if (!p) return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: host allocation failed");
     dev->children++;
     *out = p;
     return MIRHI_OK;
+}
+extern "C" mirhi_result mirhi_pipeline_create(mirhi_device* dev, const mirhi_pipeline_desc* d, mirhi_pipeline** out) {
+    NULL_CHECK(dev, "device"); NULL_CHECK(d, "desc"); NULL_CHECK(out, "out");
+    *out = nullptr;
+    return pipeline_create(dev, d, mirhi_depth_bias{0.0f, 0.0f, 0.0f}, out);
+}
+// GraphicsPipelineBuilder::depth_bias (pipeline.rs:781-788) + build: the desc with depth_bias_enable set and the three factors
+extern "C" mirhi_result mirhi_pipeline_create_with_depth_bias(mirhi_device* dev, const mirhi_pipeline_desc* d, const mirhi_depth_bias* bias, mirhi_pipeline** out) {
+    NULL_CHECK(dev, "device"); NULL_CHECK(d, "desc"); NULL_CHECK(out, "out");
+    *out = nullptr;
+    if (!bias) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported: a NULL depth bias (mirhi_pipeline_create takes pipelines without one)");
+    mirhi_pipeline_desc with = *d;
+    with.depth_bias_enable = 1u;
+    return pipeline_create(dev, &with, *bias, out);
 }
 extern "C" mirhi_result mirhi_pipeline_destroy(mirhi_pipeline* p) {
     NULL_CHECK(p, "pipeline");
@@ -1971,6 +1992,16 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     d.hw = 0.5f * vp.width; d.hh = 0.5f * vp.height;
     d.cx = vp.x + d.hw; d.cy = vp.y + d.hh;
     d.dscale = vp.max_depth - vp.min_depth; d.dmin = vp.min_depth;
+    // depth bias / depth clamp: per draw, read by setup_triangle and the outcodes alone.  The raster's clamp is to [0, 1], not to the viewport's range
+    if (pd.depth_clamp_enable && !(vp.min_depth == 0.0f && vp.max_depth == 1.0f))
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: depth clamp with a viewport depth range other than [0, 1] (got [%g, %g])", (double)vp.min_depth, (double)vp.max_depth);
+    if (pd.depth_bias_enable) {
+        const mirhi_depth_bias& b = cmd->pipeline->bias;
+        d.bias_constant = b.constant_factor; d.bias_clamp = b.clamp; d.bias_slope = b.slope_factor;
+        // (factors of zero add nothing: the draw is the unbiased one, bit for bit, and takes its path)
+        if (b.constant_factor != 0.0f || b.slope_factor != 0.0f) d.depth_flags |= DEPTH_FLAG_BIAS;
+    }
+    if (pd.depth_clamp_enable) d.depth_flags |= DEPTH_FLAG_CLAMP;
     d.gx = (GUARD_PX - std::fabs(d.cx)) / d.hw;
     d.gy = (GUARD_PX - std::fabs(d.cy)) / d.hh;
     int64_t sx0 = cmd->scissor.x, sy0 = cmd->scissor.y;

@@ -48,6 +48,7 @@ typedef const MIRHI_CONST PassParams* ParamsPtr;
 typedef const MIRHI_CONST PassParams& ParamsRef;   // scalar (s_load) access to the pass parameters in device memory
 // opaque to the optimiser: loads through the result cannot be hoisted above this point
 __device__ __forceinline__ ParamsPtr launder_params(ParamsPtr p) { asm volatile("" : "+s"(p)); return p; }
+__device__ __forceinline__ DrawPtr launder_draw(DrawPtr p) { asm volatile("" : "+s"(p)); return p; }
 
 // HLSL mul(M, v), M column-major (vertex/model.hlsl:44,48); accumulation order = oracle's.
 __device__ __forceinline__ f4 mat4_mul(CFloatPtr m, f4 v) {

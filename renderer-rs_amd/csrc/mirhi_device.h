@@ -57,7 +57,12 @@ struct DrawDesc {
     uint32_t tex_w[5], tex_h[5];
     uint32_t tex_levels[5];       // mip levels stored behind level 0 (1 = no chain: bilinear)
     uint32_t tex_srgb;            // bit t: texture t is R8G8B8A8_SRGB (RGB decoded to linear when sampled)
-    uint32_t tex_any_mips;        // some bound texture has a chain: the fragment program evaluates UV derivatives
+    // Depth bias and depth clamp of the draw's pipeline (read by setup_triangle and the outcode step, nowhere else): bit 0
+    // (DEPTH_FLAG_BIAS): add the bias to the depth plane, bit 1 (DEPTH_FLAG_CLAMP): no near / far clipping.  The word sits HERE, in the 64-byte line of
+    // stride / first / tri_count (0x80-0xbf), which every geometry wave reads first whatever its scope: in a line no wave had touched its scalar load
+    // was a cache miss on every wave's dependent chain, 0.08 us of the headline workload's geometry kernel (DESIGN_NOTES.md).  tex_any_mips, which
+    // only the fragment programs read, moved to the pad word beside the shadow words in exchange.
+    uint32_t depth_flags;
     uint32_t stride;
     uint32_t index_type;          // 0 none, 2 u16, 4 u32
     uint32_t first;               // first_vertex / first_index
@@ -81,8 +86,11 @@ struct DrawDesc {
     uint32_t shadow_w, shadow_h;  // the map's extent (with cascades: one layer's)
     uint32_t shadow_layers;       // 0: a single map (CalculateShadow); 4: mirhi_cmd_bind_shadow_cascades -- shadow_map is the base of a D32 array of
                                   // that many tightly packed layers, shadow_data its CSMParams (336 B, shadow_csm.hlsli:23-39): CalculateShadowCSM
-    uint32_t shadow_pad;
+    uint32_t tex_any_mips;        // some bound texture has a chain: the fragment program evaluates UV derivatives
+    float    bias_constant, bias_clamp, bias_slope;      // mirhi_depth_bias; read under DEPTH_FLAG_BIAS only
+    uint32_t bias_pad;
 };
+constexpr uint32_t DEPTH_FLAG_BIAS = 1u, DEPTH_FLAG_CLAMP = 2u;
 static_assert(sizeof(DrawDesc) % 16 == 0, "DrawDesc must stay 16-byte sized");
 
 // Vertex-shader pre-pass (vertex/model.hlsl:39-68 run once per vertex, as a GPU's vertex stage does, instead of three

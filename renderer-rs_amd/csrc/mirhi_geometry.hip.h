@@ -99,6 +99,24 @@ __device__ __forceinline__ bool setup_triangle(ParamsRef P, DrawRef D, const f4 
     t.zx = div_rn(dz1 * fy2 - dz2 * fy1, area);                           // IEEE quotients
     t.zy = div_rn(dz2 * fx1 - dz1 * fx2, area);
     t.z0 = z[0];
+    if (D.depth_flags & DEPTH_FLAG_BIAS) {
+        // (the flags come with the kernel's other descriptor words; the three factors are read behind launder_draw: scalar loads the compiler cannot hoist
+        // to the head of the kernel, where they would hold three more SGPRs for all of it -- the 72-register allocation has none to spare and answered
+        // with a spill to scratch.  An unbiased draw never waits for them)
+        const DrawPtr B = launder_draw(&D);
+        // depth bias (Vulkan "Depth Bias"): o = m * slope + r * constant -- the two products rounded, then their sum, nothing fused --
+        // with m = max(|dz/dx|, |dz/dy|) and r = 2^(e - 23), e the exponent of the largest |z| of the three vertices (zero or denormal: -126);
+        // clamped as the spec has it, added to the plane's constant term alone.  Under the flag: the unbiased draw's instruction stream stays as it was.
+        const float m = fmaxf(fabsf(t.zx), fabsf(t.zy));
+        const float zmax = fmaxf(fabsf(z[0]), fmaxf(fabsf(z[1]), fabsf(z[2])));
+        const uint32_t eb = max((__float_as_uint(zmax) >> 23) & 0xFFu, 1u);                      // biased exponent, >= 1
+        const float r = __uint_as_float(eb > 23u ? (eb - 23u) << 23 : 1u << (eb - 1u));          // (eb <= 23: r is a denormal)
+        const float bclamp = B->bias_clamp;
+        float o = __fadd_rn(__fmul_rn(m, B->bias_slope), __fmul_rn(r, B->bias_constant));
+        if (bclamp > 0.0f) o = fminf(o, bclamp);
+        else if (bclamp < 0.0f) o = fmaxf(o, bclamp);
+        t.z0 = __fadd_rn(z[0], o);
+    }
     const int32_t xmin = min(t.X[0], min(t.X[1], t.X[2])), xmax = max(t.X[0], max(t.X[1], t.X[2]));
     const int32_t ymin = min(t.Y[0], min(t.Y[1], t.Y[2])), ymax = max(t.Y[0], max(t.Y[1], t.Y[2]));
     int32_t px0 = (xmin + 127) >> 8, px1 = (xmax - 128) >> 8;
@@ -613,9 +631,12 @@ __device__ __forceinline__ void geometry_body(const PassParams* __restrict__ par
     }
     if (has_tri && !dropped) {
         GSTAMP_SYNC(5);
+        // depth clamp: the near and far planes neither reject (bits 16 and 32 of the view outcodes) nor clip (planes 1 and 2) -- the
+        // four guard-band planes stay and imply w >= 0.  One mask on each combination of the three vertices' outcodes
+        const bool zclamp = (D.depth_flags & DEPTH_FLAG_CLAMP) != 0u;
         const uint32_t o0 = outcode_view(c[0]), o1 = outcode_view(c[1]), o2 = outcode_view(c[2]);
-        if (!(o0 & o1 & o2)) {
-            any = outcode_clip(c[0], D.gx, D.gy) | outcode_clip(c[1], D.gx, D.gy) | outcode_clip(c[2], D.gx, D.gy);
+        if (!(o0 & o1 & o2 & (zclamp ? ~48u : ~0u))) {
+            any = (outcode_clip(c[0], D.gx, D.gy) | outcode_clip(c[1], D.gx, D.gy) | outcode_clip(c[2], D.gx, D.gy)) & (zclamp ? ~3u : ~0u);
             bool in_band = true;
             if (any == 0 && (P.tile_row_step > 1u || P.tile_row_begin != 0u || P.tile_row_end != P.tiles_y)) {
                 // Tile-row split: every rank sees all triangles and most of them touch none of its rows.  Those are dropped before the setup arithmetic

@@ -367,6 +367,11 @@ public:
     GraphicsPipelineBuilder& depth_write_enable(bool e) { d_.depth_write_enable = e; return *this; }
     GraphicsPipelineBuilder& depth_compare_op(CompareOp op) { d_.depth_compare_op = (int32_t)op; return *this; }
     GraphicsPipelineBuilder& fragment_discard_enable(bool e) { d_.fragment_discard_enable = e; return *this; }   // alpha-masked MODEL_PBR materials (model_pbr.hlsl:176-179)
+    GraphicsPipelineBuilder& depth_clamp_enable(bool e) { d_.depth_clamp_enable = e; return *this; }             // pipeline.rs:769
+    GraphicsPipelineBuilder& depth_bias(float constant_factor, float clamp, float slope_factor) {                // pipeline.rs:781-788
+        d_.depth_bias_enable = 1u; bias_ = {constant_factor, clamp, slope_factor}; has_bias_ = true;
+        return *this;
+    }
     GraphicsPipelineBuilder& color_blend_attachment(const ColorBlendAttachment& a) {      // pipeline.rs color_blend_attachments
         d_.blend_enable = a.blend_enable ? 1u : 0u;
         d_.src_color_blend_factor = (int32_t)a.src_color_blend_factor; d_.dst_color_blend_factor = (int32_t)a.dst_color_blend_factor; d_.color_blend_op = (int32_t)a.color_blend_op;
@@ -379,11 +384,13 @@ public:
     const mirhi_pipeline_desc& desc() const { return d_; }
     Pipeline build(std::shared_ptr<Device> device) const {
         mirhi_pipeline* h = nullptr;
-        check(mirhi_pipeline_create(device->handle(), &d_, &h));
+        check(has_bias_ ? mirhi_pipeline_create_with_depth_bias(device->handle(), &d_, &bias_, &h) : mirhi_pipeline_create(device->handle(), &d_, &h));
         return Pipeline(std::move(device), h);
     }
 private:
     mirhi_pipeline_desc d_;
+    mirhi_depth_bias bias_{0.0f, 0.0f, 0.0f};
+    bool has_bias_ = false;
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -293,6 +293,8 @@ class DrawSpec:
     alpha_test: bool = False              # pipeline fragment_discard_enable: alpha-masked MODEL_PBR material (per-fragment discard)
     instances: int = 1                    # instance_count of the draw call: the same primitives again, instance after instance
     blend: Optional[tuple] = None         # None = opaque; else (src colour, dst colour, colour op, src alpha, dst alpha, alpha op, write mask)
+    depth_bias: Optional[tuple] = None    # pipeline depth bias (constant_factor, clamp, slope_factor), pipeline.rs:781-788; None = off
+    depth_clamp: bool = False             # pipeline depth_clamp_enable (pipeline.rs:769)
 
     @property
     def textures(self):
@@ -322,6 +324,8 @@ class ShadowSpec:
     params: bytes = b""
     clear_depth: float = 1.0
     load_op: int = LOAD_OP_CLEAR
+    depth_bias: Optional[tuple] = None    # the map's pipelines: depth bias (constant_factor, clamp, slope_factor) of casters that set none themselves
+    depth_clamp: bool = False             # ... and depth_clamp_enable ("pancaking": casters in front of the light's near plane stay in the map at depth 0)
 
 
 @dataclass
@@ -334,6 +338,8 @@ class CascadeSpec:
     params: bytes = b""
     clear_depth: float = 1.0
     load_op: int = LOAD_OP_CLEAR
+    depth_bias: Optional[tuple] = None    # the map's pipelines: depth bias (constant_factor, clamp, slope_factor) of casters that set none themselves
+    depth_clamp: bool = False             # ... and depth_clamp_enable ("pancaking": casters in front of the light's near plane stay in the map at depth 0)
 
 
 @dataclass
@@ -1072,6 +1078,34 @@ def skybox_case(width: int = 128, height: int = 96, camera: int = 0, size: int =
 SHADOWED_GROUND_LIGHT = (0.45, -1.0, 0.3)
 SHADOWED_GROUND_BOX = ((0.3, 1.1, 0.2), (0.7, 1.1, 0.7))        # centre, half extent
 SHADOWED_GROUND_EXTENT = 8.0                                      # the light frustum's half extent: covers the whole ground
+
+
+def depth_bias_unit(z_window) -> float:
+    """r of DESIGN.md 8h: 2^(e - 23), e the unbiased binary32 exponent of the largest |z| of a triangle's three window depths (zero or denormal: -126)."""
+    zm = float(np.float32(np.max(np.abs(np.asarray(z_window, dtype=np.float64)))))
+    e = math.frexp(zm)[1] - 1 if zm >= 2.0 ** -126 else -126       # (frexp: zm = f 2^k with 1/2 <= f < 1)
+    return 2.0 ** (e - 23)
+
+
+def depth_bias_offset(z_window, xy_window, factors) -> float:
+    """The float64 model of the depth bias (Vulkan "Depth Bias" with the max form of m and the floating-point rule for r): the offset o
+    added to every fragment depth of the triangle with window depths z_window[3] at window positions xy_window[3] (pixels), for
+    factors = (constant_factor, clamp, slope_factor).  o = m * slope + r * constant, m = max(|dz/dx|, |dz/dy|) of the depth plane, r = depth_bias_unit;
+    clamp > 0: min(o, clamp), clamp < 0: max(o, clamp), 0: none."""
+    z = np.asarray(z_window, dtype=np.float64)
+    p = np.asarray(xy_window, dtype=np.float64)
+    constant, clamp, slope = (float(f) for f in factors)
+    x1, y1 = p[1] - p[0]
+    x2, y2 = p[2] - p[0]
+    area = x1 * y2 - x2 * y1
+    zx = ((z[1] - z[0]) * y2 - (z[2] - z[0]) * y1) / area
+    zy = ((z[2] - z[0]) * x1 - (z[1] - z[0]) * x2) / area
+    o = max(abs(zx), abs(zy)) * slope + depth_bias_unit(z) * constant
+    if clamp > 0.0:
+        o = min(o, clamp)
+    elif clamp < 0.0:
+        o = max(o, clamp)
+    return o
 
 
 def _ground_quad(half: float, n: int) -> tuple:

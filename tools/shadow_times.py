@@ -3,7 +3,8 @@
   (a) depth-only SHADOW scopes of C3's sphere into 2048^2 and of C5's box hall into 4096^2, with bytes and HBM roofline share
       (vertices + indices + W x H x 4 over the raster + geometry + vertex time);
   (b) the same geometry drawn with the MODEL program into RGBA8 + D32 of the same size;
-  (c) the MODEL_PBR main-pass raster of shadowed_ground_case at 1920 x 1080 with and without a bound shadow map.
+  (c) the MODEL_PBR main-pass raster of shadowed_ground_case at 1920 x 1080 with and without a bound shadow map;
+  (d) the depth-only scopes of (a) again with depth bias (constant 1, slope 2) and depth clamp on the map's pipelines.
 Prints one JSON object (median microseconds per dispatch over the timed repeats) with the build id."""
 import json
 import os
@@ -73,9 +74,10 @@ def per_kernel(tl, n_scopes=1):
     return out
 
 
-def depth_only(dev, scene, size):
+def depth_only(dev, scene, size, **depth_state):
+    """depth_state: ShadowSpec's depth_bias=(constant, clamp, slope) / depth_clamp=True for the map's pipelines"""
     ls, casters = caster_scene(scene, size)
-    sc = S.Scene(scene.name + "-shadow", 64, 64, [], shadow=S.ShadowSpec(casters, (size, size), S.shadow_ubo(ls, size=(size, size))))
+    sc = S.Scene(scene.name + "-shadow", 64, 64, [], shadow=S.ShadowSpec(casters, (size, size), S.shadow_ubo(ls, size=(size, size)), **depth_state))
     res = m.SceneResources(dev, sc, m.Format.B8G8R8A8_SRGB, shadow_cmd=True)
     t = per_kernel(timed(dev, lambda: dev.submit([res.shadow_cmd])))
     nbytes = size * size * 4
@@ -110,6 +112,7 @@ def main():
         scene = make()
         out[f"a_{name}_depth_only_{size}"] = depth_only(dev, scene, size)
         out[f"b_{name}_model_rgba8_d32_{size}"] = model_same_geometry(dev, scene, size)
+        out[f"d_{name}_depth_only_bias_clamp_{size}"] = depth_only(dev, scene, size, depth_bias=(1.0, 0.0, 2.0), depth_clamp=True)
     ground = S.shadowed_ground_case(1920, 1080, map_size=2048)
     with_map = m.SceneResources(dev, ground, m.Format.B8G8R8A8_SRGB)
     out["c_pbr_with_map"] = per_kernel(timed(dev, with_map.render), n_scopes=2)
