@@ -32,6 +32,7 @@
 #include "mirhi_launch.h"
 #include "mirhi_variant.h"
 #include "mirhi_scope.h"
+#include "mirhi_submit.h"
 
 using namespace mirhi;
 
@@ -2877,6 +2878,8 @@ extern "C" int mirhi_debug_scope_plan(const uint32_t* in, uint32_t* out, char* n
     const uint32_t choice[12] = {c.programs, in[13], P.pred, P.zflip, P.zmask, P.tp_max_area, P.raster_teams, P.raster_wide, P.alpha_scope, P.xcd_swizzle, P.ordered_recs ? 1u : 0u, 0u};
     return mirhi_debug_raster_choice(choice, name, name_len, out + 28);
 }
+// ... and what mirhi_submit.h decides about a submit, a scope of it and the wide feedback (the words: submit_words there)
+extern "C" int mirhi_debug_submit_path(const uint32_t* in, uint32_t* out) { return submit_words(in, out); }
 
 // ------------------------------------------------------------------------------------------------
 // submit + fences
@@ -3048,213 +3051,201 @@ extern "C" mirhi_result mirhi_queue_submit(mirhi_device* dev, uint32_t cmd_count
     return MIRHI_OK;
 }
 
-static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd* const* cmds, mirhi_fence* fence) {
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    const PlanKnobs knobs = PlanKnobs::read();
-    for (uint32_t i = 0; i < cmd_count; i++)
-        if ((cmds[i]->ws.grow_pool && !knobs.pool_pages.set) || cmds[i]->ws.replan) {   // an earlier submission ran out of bin pages (a bigger pool, the same plan) or showed a spread-out mesh (one team)
-            const mirhi_result rp = build_plan(cmds[i], true);
-            if (rp != MIRHI_OK) return rp;
-        }
-    // dev->mu guards the bookkeeping (unchecked list, statistics, attachment ordering, timed-dispatch events), not the launches: with
-    // the submit thread on, the render thread must be able to complete a fence while this thread is inside hipLaunchKernel
-    std::unique_lock<std::mutex> lock(dev->mu);
-    bool keep_locked = dev->profiling != 0;
-    // Batched form: the command buffers of one submit, when each is one plain rendering scope of the same shape and kernel variants
-    // (the frames of a frame loop), share one vertex, one geometry and one raster launch on the first one's queue lane -- the
-    // ramp-up and drain of a kernel and the latency chain of the geometry kernel are paid once per batch, not once per frame.
-    // Only frames that are independent of each other may share a launch: every scope clears (no LOAD of colour or depth -- what it
-    // would load might be written by another scope of the batch), no two scopes share a colour, depth or primitive-id attachment, and
-    // all command buffers sit on the first one's queue lane (so the batch keeps their order against earlier work of that lane).
-    // Anything else runs command buffer by command buffer, in submission order on each lane.
-    bool batched = cmd_count >= 2 && cmd_count <= (uint32_t)MAX_BATCH && dev->profiling == 0 && !native_env().no_batch;
-    // (a plan that names a wide variant is not batched, whether or not a submit would take it: the variant as with allow_wide)
-    auto variant_of = [](const mirhi_cmd* c) { return raster_variant(c->plan[0], c->plan_programs[0], true); };
-    for (uint32_t i = 0; batched && i < cmd_count; i++) {
-        const mirhi_cmd* c = cmds[i];
-        batched = c->plan.size() == 1 && variant_of(c).batched_form && c->lane == cmds[0]->lane && variant_of(c) == variant_of(cmds[0]) &&
-                  c->plan_programs[0] == cmds[0]->plan_programs[0] && !c->plan[0].color_load && !c->plan[0].depth_load;
-        for (uint32_t j = 0; batched && j < i; j++) {
-            const PassParams& A = cmds[j]->plan[0]; const PassParams& B = c->plan[0];
-            batched = cmds[j] != c && A.color != B.color && !(A.depth && A.depth == B.depth) && !(A.prim_out && A.prim_out == B.prim_out);
-        }
-    }
-    // The fence rides on the submit's last dispatch (its completion signal: hipExtLaunchKernelGGL stop event) when there is one and
-    // everything of the submit runs on one stream -- an event RECORD is a command of its own in the stream: 4.5 us of stream time and
-    // a round trip of 12-14 us against 6-9 us (tools/microbench/fence_latency.hip).
-    // Native dispatch (mirhi_native.h): the submit's kernels go out as AQL packets on the lane's own queue -- when nothing of the submit
-    // needs the HIP stream: no timed dispatches, no batch, no tile split (the band exchange lives on HIP streams), no ordered segment
-    // (its clear is a HIP memset), every command buffer on one lane.
-    // A device made on the caller's stream (mirhi_device_create_on_stream) promised that lane 0's work is issued on that stream: submits to lane 0 stay in
-    // stream order (HIP launches) unless the caller opted in (mirhi_device_set_native_dispatch); lanes the library made itself are the library's.
-    bool use_native = !batched && cmd_count >= 1 && dev->native && dev->native->ok && dev->profiling == 0 &&
-                      (dev->owns_stream || dev->native_on_external || cmds[0]->lane != 0u);
-    for (uint32_t i = 0; use_native && i < cmd_count; i++) {
-        use_native = cmds[i]->lane == cmds[0]->lane && cmds[i]->lane < dev->lanes.size();
-        for (const PassParams& P : cmds[i]->plan) use_native = use_native && !P.ordered_recs;
-    }
-    NativeQueue* nq = use_native ? native_lane(dev, cmds[0]->lane) : nullptr;
-    use_native = nq != nullptr;
-    if (use_native) keep_locked = true;       // (an AQL queue has one producer at a time, and a dispatch takes 0.2 us: the device lock stays held)
-    hipEvent_t fence_stop = nullptr;
-    bool fence_attached = false;
-    if (fence) fence->native_wait = false;
-    if (use_native && dev->native->lost.load(std::memory_order_acquire)) return device_lost(dev);
-    if (fence && use_native) {
-        fence->native_q = nq;
+// What the steps of one submit share.  dev->mu guards the bookkeeping (unchecked list, statistics, attachment ordering, timed-dispatch events), not
+// the launches: with the submit thread on, the render thread must be able to complete a fence while this thread is inside hipLaunchKernel -- a
+// step lets go of the lock around its launches (unlock / relock) unless keep_locked.
+struct Submit {
+    mirhi_device* dev;
+    std::unique_lock<std::mutex> lock;
+    bool keep_locked;
+    SubmitDevice device;              // the facts a submit looks at, in the device, the switches ...
+    SubmitSwitches sw;
+    SubmitPath path;                  // ... and the command buffers: the path they give (mirhi_submit.h: every "whether" of a submit is decided there)
+    NativeQueue* nq;                  // the lane's AQL queue, when the submit goes out as packets
+    mirhi_fence* fence;
+    FenceCarrier carrier;
+    void unlock() { if (!keep_locked) lock.unlock(); }
+    void relock() { if (!keep_locked) lock.lock(); }
+};
+
+static hipStream_t lane_stream(const mirhi_device* dev, uint32_t lane) { return dev->lanes[lane < dev->lanes.size() ? lane : 0]; }
+
+// The fence's signal or event, made on first use, and what of the submit will signal it
+static mirhi_result prepare_fence(Submit& s) {
+    mirhi_fence* fence = s.fence;
+    s.carrier = fence_carrier(s.path, s.device, s.sw, fence != nullptr);
+    if (fence && s.nq) {
+        fence->native_q = s.nq;
         if (!fence->native_sig.handle && hsa_signal_create(0, 0, nullptr, &fence->native_sig) != HSA_STATUS_SUCCESS) return fail(MIRHI_ERR_DEVICE, "Vulkan error: hsa_signal_create for a fence failed");
         hsa_signal_store_relaxed(fence->native_sig, 1);
     }
-    if (fence && !use_native) {
-        if (!fence->event) HIP_TRY(hipEventCreate(&fence->event));
-        bool one_stream = cmd_count >= 1 && dev->profiling == 0 && !native_env().fence_record;
-        for (uint32_t i = 1; one_stream && i < cmd_count && !batched; i++) one_stream = cmds[i]->lane == cmds[0]->lane;
-        if (one_stream) {
-            const mirhi_cmd* last = cmds[cmd_count - 1];
-            const bool has_launch = !last->plan.empty() && last->plan.back().tile_row_end > last->plan.back().tile_row_begin && last->plan.back().tiles_x != 0u;
-            if (has_launch) fence_stop = fence->event;
-        }
-    }
-    if (batched) {
-        hipStream_t stream = dev->lanes[cmds[0]->lane < dev->lanes.size() ? cmds[0]->lane : 0];
-        const PassParams* P[MAX_BATCH]; const PassParams* dp[MAX_BATCH]; uint32_t* big[MAX_BATCH];
-        for (uint32_t i = 0; i < cmd_count; i++) {
-            mirhi_cmd* c = cmds[i];
-            if (c->pending && c->last_stream && c->last_stream != stream) HIP_TRY(hipStreamSynchronize(c->last_stream));   // (its workspace may still be in use there)
-            if (c->pending && c->last_native && !drain_native(dev, c->last_native)) return device_lost(dev);
-            c->last_stream = stream; c->last_native = nullptr; c->pending = true; c->submit_seq++;
-            { const mirhi_result ro = order_attachments(dev, c, stream); if (ro != MIRHI_OK) return ro; }
-            if (std::find(dev->unchecked.begin(), dev->unchecked.end(), c) == dev->unchecked.end()) dev->unchecked.push_back(c);
-            P[i] = &c->plan[0];
-            dp[i] = c->ws.params + c->ws.parity;
-            big[i] = c->ws.big_counts + c->ws.parity;
-            c->ws.parity ^= 1u;
-            dev->stats.frames_submitted++;
-            dev->stats.triangles_submitted += c->plan[0].total_tris;
-        }
-        if (!keep_locked) lock.unlock();
-        hipError_t le = launch_vertex_batch(P, dp, cmd_count, stream);
-        if (le == hipSuccess) le = launch_geometry_batch(P, dp, cmd_count, stream);
-        if (le == hipSuccess) le = launch_raster_batch(P, dp, big, cmd_count, cmds[0]->plan_programs[0], stream, fence_stop);
-        if (!keep_locked) lock.lock();
-        HIP_TRY(le);
-        fence_attached = fence_stop != nullptr;
-    }
-    for (uint32_t i = 0; !batched && i < cmd_count; i++) {
+    if (fence && !s.nq && !fence->event) HIP_TRY(hipEventCreate(&fence->event));
+    return MIRHI_OK;
+}
+
+// `c` is about to run on `stream` (or, natively, on `nq`): wherever else it ran last is drained (its workspace may still be in use there), it is
+// pending on its new place as submission submit_seq, and its attachments are ordered behind their last users
+static mirhi_result claim_cmd(mirhi_device* dev, mirhi_cmd* c, hipStream_t stream, NativeQueue* nq) {
+    if (c->pending && c->last_native && c->last_native != nq && !drain_native(dev, c->last_native)) return device_lost(dev);      // (last_native or last_stream: never both)
+    if (c->pending && c->last_stream && (nq || c->last_stream != stream)) HIP_TRY(hipStreamSynchronize(c->last_stream));
+    c->last_stream = nq ? nullptr : stream; c->last_native = nq; c->pending = true; c->submit_seq++;
+    { const mirhi_result ro = order_attachments(dev, c, stream, nq); if (ro != MIRHI_OK) return ro; }
+    if (std::find(dev->unchecked.begin(), dev->unchecked.end(), c) == dev->unchecked.end()) dev->unchecked.push_back(c);
+    return MIRHI_OK;
+}
+
+// the batched launch triple on the first command buffer's lane
+static mirhi_result issue_batch(Submit& s, uint32_t cmd_count, mirhi_cmd* const* cmds) {
+    mirhi_device* dev = s.dev;
+    hipStream_t stream = lane_stream(dev, cmds[0]->lane);
+    const PassParams* P[MAX_BATCH]; const PassParams* dp[MAX_BATCH]; uint32_t* big[MAX_BATCH];
+    for (uint32_t i = 0; i < cmd_count; i++) {
         mirhi_cmd* c = cmds[i];
-        hipStream_t stream = dev->lanes[c->lane < dev->lanes.size() ? c->lane : 0];
-        if (c->pending && !use_native && c->last_native && !drain_native(dev, c->last_native)) return device_lost(dev);
-        if (c->pending && c->last_stream && (use_native || c->last_stream != stream)) HIP_TRY(hipStreamSynchronize(c->last_stream));
-        if (c->pending && use_native && c->last_native && c->last_native != nq && !drain_native(dev, c->last_native)) return device_lost(dev);
-        // Frames in flight, this one included (command buffers submitted and not yet known to have finished).  The wide mesh variants trade
-        // throughput for latency -- a frame alone on the chip finishes sooner (C3 raster 32 -> 25 us), four frames in flight leave each
-        // other less room (C3 16.2 -> 19.8 us per frame) -- so a submit takes them only while the queue is shallow: the reference's
-        // MAX_FRAMES_IN_FLIGHT = 2 loop does, a loop that keeps four frames queued gets the plain / two-team variants.
+        { const mirhi_result rc = claim_cmd(dev, c, stream, nullptr); if (rc != MIRHI_OK) return rc; }
+        P[i] = &c->plan[0];
+        dp[i] = c->ws.params + c->ws.parity;
+        big[i] = c->ws.big_counts + c->ws.parity;
+        c->ws.parity ^= 1u;
+        dev->stats.frames_submitted++;
+        dev->stats.triangles_submitted += c->plan[0].total_tris;
+    }
+    s.unlock();
+    hipError_t le = launch_vertex_batch(P, dp, cmd_count, stream);
+    if (le == hipSuccess) le = launch_geometry_batch(P, dp, cmd_count, stream);
+    if (le == hipSuccess) le = launch_raster_batch(P, dp, big, cmd_count, cmds[0]->plan_programs[0], stream, s.carrier == FENCE_STOP_EVENT ? s.fence->event : nullptr);
+    s.relock();
+    HIP_TRY(le);
+    return MIRHI_OK;
+}
+
+// One scope of command buffer `c`: its vertex, geometry and raster launch (with_fence: the raster launch carries the submit's fence), and with
+// profiling on their timing events and the statistics pass
+static mirhi_result issue_scope(Submit& s, mirhi_cmd* c, size_t pi, hipStream_t stream, bool wide_allowed, bool with_fence) {
+    mirhi_device* dev = s.dev;
+    const PassParams& P = c->plan[pi];
+    // alternate the big-list counter: the raster kernel zeroes the other one for the next scope
+    const PassParams* dp = c->ws.params + 2 * pi + c->ws.parity;
+    uint32_t* big_count = c->ws.big_counts + c->ws.parity;
+    if (flips_parity(P)) c->ws.parity ^= 1u;
+    // ordered segment: slots of primitives that no draw of the segment covers (a Never draw keeps its ids) must read
+    // as "no coverage" -- an all-zero record is a degenerate triangle whose edge functions are negative everywhere
+    if (P.ordered_recs && P.ordered_count) HIP_TRY(hipMemsetAsync(P.ordered_recs, 0, (size_t)P.ordered_count * sizeof(TriRec), stream));
+    LaunchTiming tv{}, tg{}, tc{}, tr{};
+    if (s.nq) {
+        const uint64_t foreign = dev->foreign_writes.load(std::memory_order_acquire);
+        const PacketScopes scopes = packet_scopes(P, s.sw.system_scope, s.nq->seen_foreign != foreign, c->ws.foreign);
+        s.nq->seen_foreign = foreign; c->ws.foreign = false;
+        tv.native = s.nq; tg.native = s.nq; tr.native = s.nq;
+        tv.native_flags = scopes.vertex; tg.native_flags = scopes.geometry; tr.native_flags = scopes.raster;
+    }
+    tg.tris_per_wave = tris_per_wave(P, s.sw.geom_tpw);
+    if (pi < c->planned.size() && c->planned[pi].draws.size() == 1u) tg.head_draw = &c->planned[pi].draws[0];      // (GeometryHead::vb0: launch_geometry decides)
+    const bool timed = scope_timed(dev->profiling, c->lane);
+    if (timed) {
+        mirhi_result r;
+        if (P.vs_total_slots && (r = timing_begin(dev, MIRHI_KERNEL_VERTEX, c->lane, &tv)) != MIRHI_OK) return r;
+        if (P.total_slots && (r = timing_begin(dev, MIRHI_KERNEL_GEOMETRY, c->lane, &tg)) != MIRHI_OK) return r;
+    }
+    s.unlock();
+    hipError_t le = launch_vertex(P, dp, stream, tv);
+    if (le == hipSuccess) le = launch_geometry(P, dp, stream, tg);
+    s.relock();
+    HIP_TRY(le);
+    const uint32_t* winners = nullptr;
+    if (scope_counted(dev->profiling, P)) {
+        mirhi_result r;
+        if (timed && (r = timing_begin(dev, MIRHI_KERNEL_FRAGMENT_COUNT, c->lane, &tc)) != MIRHI_OK) return r;
+        HIP_TRY(launch_fragment_count(P, dp, big_count, stream, tc));
+        dev->frag_scopes++;
+        // winners are counted from a primitive-id image: the scope's own if every pixel of it is written (no LOAD),
+        // else the workspace's, cleared to NO_PRIM, through a copy of the parameters -- the raster kernels know nothing
+        // of the statistics
+        if (P.prim_out && !P.color_load) winners = P.prim_out;
+        else {
+            if ((r = stats_params_for(c)) != MIRHI_OK) return r;
+            HIP_TRY(hipMemsetAsync(c->ws.stats_prim, 0xFF, (size_t)P.width * P.height * 4, stream));
+            dp = c->ws.stats_params + (dp - c->ws.params);
+            winners = c->ws.stats_prim;
+        }
+    }
+    if (timed && has_tiles(P)) { mirhi_result r = timing_begin(dev, MIRHI_KERNEL_RASTER, c->lane, &tr); if (r != MIRHI_OK) return r; }
+    if (with_fence && s.carrier == FENCE_STOP_EVENT) tr.stop = s.fence->event;
+    if (with_fence && s.carrier == FENCE_NATIVE_SIGNAL) tr.native_signal = s.fence->native_sig.handle;
+    s.unlock();
+    le = launch_raster(P, dp, big_count, c->plan_programs[pi], stream, tr, wide_allowed);
+    s.relock();
+    HIP_TRY(le);
+    if (winners) HIP_TRY(launch_winner_count(winners, P.width * P.height, dev->frag_stats, stream));
+    if (!P.xfer) dev->stats.frames_submitted++;      // (a transfer is no rendering scope)
+    dev->stats.triangles_submitted += P.total_tris;
+    return MIRHI_OK;
+}
+
+// Nothing of the submit carried the fence
+static mirhi_result attach_fence(Submit& s, uint32_t cmd_count, mirhi_cmd* const* cmds) {
+    mirhi_fence* fence = s.fence;
+    if (s.carrier == FENCE_NATIVE_DRAIN) {            // (no tiles to raster): wait here, the fence is signalled at once
+        native_queue_drain(s.nq);
+        hsa_signal_store_relaxed(fence->native_sig, 0);
+    }
+    if (s.carrier == FENCE_EVENT_RECORD) {
+        // the fence follows the last command buffer's lane and waits for the other lanes used by this submit
+        hipStream_t fstream = cmd_count ? cmds[cmd_count - 1]->last_stream : s.dev->stream;
+        for (uint32_t i = 0; i + 1 < cmd_count; i++) {
+            hipStream_t other = cmds[i]->last_stream;
+            if (other != fstream) {
+                if (!fence->join) HIP_TRY(hipEventCreateWithFlags(&fence->join, hipEventDisableTiming));
+                HIP_TRY(hipEventRecord(fence->join, other));
+                HIP_TRY(hipStreamWaitEvent(fstream, fence->join, 0));
+            }
+        }
+        HIP_TRY(hipEventRecord(fence->event, fstream));
+    }
+    return MIRHI_OK;
+}
+
+static mirhi_result submit_now(mirhi_device* dev, uint32_t cmd_count, mirhi_cmd* const* cmds, mirhi_fence* fence) {
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    const PlanKnobs knobs = PlanKnobs::read();
+    // 1. replan where an earlier submission ran out of bin pages (a bigger pool, the same plan) or showed a spread-out mesh (one team)
+    for (uint32_t i = 0; i < cmd_count; i++)
+        if ((cmds[i]->ws.grow_pool && !knobs.pool_pages.set) || cmds[i]->ws.replan) {
+            const mirhi_result rp = build_plan(cmds[i], true);
+            if (rp != MIRHI_OK) return rp;
+        }
+    // 2. the facts, and the path they give
+    const NativeEnv& env = native_env();
+    Submit s{dev, std::unique_lock<std::mutex>(dev->mu), dev->profiling != 0,
+             SubmitDevice{dev->profiling, dev->native && dev->native->ok, dev->owns_stream, dev->native_on_external, (uint32_t)dev->lanes.size()},
+             SubmitSwitches{env.no_batch, env.fence_record, env.system_scope, env.geom_tpw, knobs.raster_wide.set}, SubmitPath{}, nullptr, fence, FENCE_NONE};
+    s.path = submit_path(s.device, s.sw, cmd_count, [&](uint32_t i) { return submit_cmd(cmds[i], cmds[i]->lane, cmds[i]->plan.data(), cmds[i]->plan.size()); },
+                         [&](uint32_t i) { return submit_head(cmds[i]->plan[0], cmds[i]->plan_programs[0]); });
+    s.nq = s.path.native ? native_lane(dev, cmds[0]->lane) : nullptr;
+    s.path.native = s.nq != nullptr;
+    if (s.nq) s.keep_locked = true;       // (an AQL queue has one producer at a time, and a dispatch takes 0.2 us: the device lock stays held)
+    if (fence) fence->native_wait = false;
+    if (s.nq && dev->native->lost.load(std::memory_order_acquire)) return device_lost(dev);
+    // 3. the fence
+    { const mirhi_result rf = prepare_fence(s); if (rf != MIRHI_OK) return rf; }
+    // 4. claim and issue: one batch, or command buffer by command buffer, scope by scope
+    if (s.path.batched) { const mirhi_result rb = issue_batch(s, cmd_count, cmds); if (rb != MIRHI_OK) return rb; }
+    for (uint32_t i = 0; !s.path.batched && i < cmd_count; i++) {
+        mirhi_cmd* c = cmds[i];
+        hipStream_t stream = lane_stream(dev, c->lane);
+        { const mirhi_result rc = claim_cmd(dev, c, stream, s.nq); if (rc != MIRHI_OK) return rc; }
         int in_flight = 1;
         for (const mirhi_cmd* o : dev->cmds) in_flight += (o != c && o->pending) ? 1 : 0;
-        const bool allow_wide = in_flight <= 2 || knobs.raster_wide.set;
-        c->last_stream = use_native ? nullptr : stream; c->last_native = use_native ? nq : nullptr; c->pending = true; c->submit_seq++;
-        { const mirhi_result ro = order_attachments(dev, c, stream, use_native ? nq : nullptr); if (ro != MIRHI_OK) return ro; }
-        if (std::find(dev->unchecked.begin(), dev->unchecked.end(), c) == dev->unchecked.end()) dev->unchecked.push_back(c);
+        const bool wide_allowed = allow_wide(in_flight, s.sw.wide_set);
         for (size_t pi = 0; pi < c->plan.size(); pi++) {
-            const PassParams& P = c->plan[pi];
-            // alternate the big-list counter: the raster kernel zeroes the other one for the next scope
-            const PassParams* dp = c->ws.params + 2 * pi + c->ws.parity;
-            uint32_t* big_count = c->ws.big_counts + c->ws.parity;
-            // (a SKYBOX segment takes no bins and touches no counter: it re-arms nothing and parity stays where it is -- the raster kernel that
-            // follows finds the counters as the one before the sky left them)
-            // (and so a transfer entry)
-            if (!P.sky && !P.xfer) c->ws.parity ^= 1u;
-            // ordered segment: slots of primitives that no draw of the segment covers (a Never draw keeps its ids) must read
-            // as "no coverage" -- an all-zero record is a degenerate triangle whose edge functions are negative everywhere
-            if (P.ordered_recs && P.ordered_count) HIP_TRY(hipMemsetAsync(P.ordered_recs, 0, (size_t)P.ordered_count * sizeof(TriRec), stream));
-            LaunchTiming tv{}, tg{}, tc{}, tr{};
-            if (use_native) {
-                tv.native = nq; tg.native = nq; tr.native = nq;
-                // the scope's first kernels see what the host wrote (parameter block, buffers uploaded since); its raster kernel publishes the frame
-                // -- when something other than this library's kernels wrote device memory since this queue last acquired at system scope
-                const int scope_mode = native_env().system_scope;   // 1: system scope on every packet, 2: on every scope's first (A/B runs)
-                const bool sys = scope_mode == 1;
-                const uint64_t foreign = dev->foreign_writes.load(std::memory_order_acquire);
-                const bool head_sys = sys || scope_mode == 2 || nq->seen_foreign != foreign || c->ws.foreign;
-                nq->seen_foreign = foreign; c->ws.foreign = false;
-                tv.native_flags = (head_sys ? NATIVE_ACQUIRE_SYSTEM : 0u) | (sys ? NATIVE_RELEASE_SYSTEM : 0u);
-                tg.native_flags = (((P.vs_total_slots == 0u && head_sys) || sys) ? NATIVE_ACQUIRE_SYSTEM : 0u) | (sys ? NATIVE_RELEASE_SYSTEM : 0u);      // (behind a vertex kernel: that one took the acquire)
-                tr.native_flags = NATIVE_RELEASE_SYSTEM | (sys ? NATIVE_ACQUIRE_SYSTEM : 0u);
-                if ((P.sky || P.xfer) && head_sys) tr.native_flags |= NATIVE_ACQUIRE_SYSTEM;      // (a SKYBOX segment or a transfer has no vertex or geometry packet: its only one takes the head's acquire)
-            }
-            {   // small scopes: fewer triangles per geometry wave (GeometryHead::tris_per_wave) -- the chip is mostly idle, a shorter wave is a shorter frame
-                const uint32_t geo_waves = P.total_slots / (uint32_t)GEOM_THREADS;
-                tg.tris_per_wave = native_env().geom_tpw ? (uint32_t)native_env().geom_tpw : (geo_waves <= 256u ? 16u : (geo_waves <= 512u ? 32u : 64u));
-                if (pi < c->planned.size() && c->planned[pi].draws.size() == 1u) tg.head_draw = &c->planned[pi].draws[0];      // (GeometryHead::vb0: launch_geometry decides)
-            }
-            // (timing may be restricted to one queue lane -- bits 8..15 of the mask hold lane + 1 -- so that the other lanes run
-            // untimed: a timed dispatch completes through its own signal and does not overlap its neighbours the way an untimed one does)
-            const uint32_t only_lane = (dev->profiling >> 8) & 0xFFu;
-            const bool timed = (dev->profiling & MIRHI_PROFILE_TIMING) != 0 && (only_lane == 0u || only_lane - 1u == c->lane);
-            const bool counted = (dev->profiling & MIRHI_PROFILE_FRAGMENTS) != 0;
-            if (timed) {
-                mirhi_result r;
-                if (P.vs_total_slots && (r = timing_begin(dev, MIRHI_KERNEL_VERTEX, c->lane, &tv)) != MIRHI_OK) return r;
-                if (P.total_slots && (r = timing_begin(dev, MIRHI_KERNEL_GEOMETRY, c->lane, &tg)) != MIRHI_OK) return r;
-            }
-            if (!keep_locked) lock.unlock();
-            hipError_t le = launch_vertex(P, dp, stream, tv);
-            if (le == hipSuccess) le = launch_geometry(P, dp, stream, tg);
-            if (!keep_locked) lock.lock();
-            HIP_TRY(le);
-            const bool has_tiles = P.tile_row_end > P.tile_row_begin && P.tiles_x;
-            const uint32_t* winners = nullptr;
-            if (counted && has_tiles && !P.ordered_recs && !P.depth_only && !P.sky && !P.xfer) {      // (ordered -- blended -- segments, depth-only scopes, SKYBOX segments and transfers are not counted)
-                mirhi_result r;
-                if (timed && (r = timing_begin(dev, MIRHI_KERNEL_FRAGMENT_COUNT, c->lane, &tc)) != MIRHI_OK) return r;
-                HIP_TRY(launch_fragment_count(P, dp, big_count, stream, tc));
-                dev->frag_scopes++;
-                // winners are counted from a primitive-id image: the scope's own if every pixel of it is written (no LOAD),
-                // else the workspace's, cleared to NO_PRIM, through a copy of the parameters -- the raster kernels know nothing
-                // of the statistics
-                if (P.prim_out && !P.color_load) winners = P.prim_out;
-                else {
-                    if ((r = stats_params_for(c)) != MIRHI_OK) return r;
-                    HIP_TRY(hipMemsetAsync(c->ws.stats_prim, 0xFF, (size_t)P.width * P.height * 4, stream));
-                    dp = c->ws.stats_params + (dp - c->ws.params);
-                    winners = c->ws.stats_prim;
-                }
-            }
-            if (timed && has_tiles) { mirhi_result r = timing_begin(dev, MIRHI_KERNEL_RASTER, c->lane, &tr); if (r != MIRHI_OK) return r; }
-            if (fence_stop && i + 1 == cmd_count && pi + 1 == c->plan.size() && has_tiles) { tr.stop = fence_stop; fence_attached = true; }   // (never together with `timed`)
-            if (fence && use_native && i + 1 == cmd_count && pi + 1 == c->plan.size() && has_tiles) { tr.native_signal = fence->native_sig.handle; fence_attached = true; }
-            if (!keep_locked) lock.unlock();
-            le = launch_raster(P, dp, big_count, c->plan_programs[pi], stream, tr, allow_wide);
-            if (!keep_locked) lock.lock();
-            HIP_TRY(le);
-            if (winners) HIP_TRY(launch_winner_count(winners, P.width * P.height, dev->frag_stats, stream));
-            if (!P.xfer) dev->stats.frames_submitted++;      // (a transfer is no rendering scope)
-            dev->stats.triangles_submitted += P.total_tris;
+            const mirhi_result rs = issue_scope(s, c, pi, stream, wide_allowed, carries_fence(s.carrier, s.path, i, pi));
+            if (rs != MIRHI_OK) return rs;
         }
     }
-    if (fence && use_native) {
-        if (!fence_attached) {            // nothing of the submit carried the signal (no tiles to raster): wait here, the fence is signalled at once
-            native_queue_drain(nq);
-            hsa_signal_store_relaxed(fence->native_sig, 0);
-        }
-        fence->native_wait = true;
-    } else if (fence) {
-        if (!fence_attached) {
-            // the fence follows the last command buffer's lane and waits for the other lanes used by this submit
-            hipStream_t fstream = cmd_count ? cmds[cmd_count - 1]->last_stream : dev->stream;
-            for (uint32_t i = 0; i + 1 < cmd_count; i++) {
-                hipStream_t other = cmds[i]->last_stream;
-                if (other != fstream) {
-                    if (!fence->join) HIP_TRY(hipEventCreateWithFlags(&fence->join, hipEventDisableTiming));
-                    HIP_TRY(hipEventRecord(fence->join, other));
-                    HIP_TRY(hipStreamWaitEvent(fstream, fence->join, 0));
-                }
-            }
-            HIP_TRY(hipEventRecord(fence->event, fstream));
-        }
-    }
+    // 5. the fence, if nothing carried it
+    { const mirhi_result ra = attach_fence(s, cmd_count, cmds); if (ra != MIRHI_OK) return ra; }
+    // 6. bookkeeping
     if (fence) {
+        if (s.nq) fence->native_wait = true;
         fence->pending = true; fence->signaled = false;
         fence->cmds.assign(cmds, cmds + cmd_count);
         fence->seqs.resize(cmd_count);
@@ -3291,16 +3282,8 @@ static mirhi_result status_of(mirhi_device* dev, mirhi_cmd* c) {
         }
         if (feedback && (c->ws.status_host[3] & 0x80000000u)) {
             // busy tiles of the scope before this one: few of them = a mesh in a part of the frame = the wide variant (and back), see Workspace::wide
-            // Sixteen waves per tile are one workgroup per CU at a time: for up to ~240 busy tiles (the dancer asset: 232; raster 39 -> 30 us);
-            // eight waves are two per CU: up to ~512 (the 70k-triangle sphere: 419; 32.5 -> 24.8 us, sixteen: 31.7 in two rounds).  Hysteresis
-            // of a quarter so that a frame loop does not flip between two plans.
             c->ws.busy_tiles = c->ws.status_host[3] & 0x7FFFFFFFu; c->ws.busy_known = true;
-            const uint32_t b = c->ws.busy_tiles, cur = c->ws.wide;
-            uint32_t want = cur;
-            if (b == 0u) want = 0u;
-            else if (b <= (cur == 16u ? 300u : 240u)) want = 16u;
-            else if (b <= (cur == 8u ? 640u : 512u)) want = 8u;
-            else want = 0u;
+            const uint32_t cur = c->ws.wide, want = wide_wanted(c->ws.busy_tiles, cur);
             if (want != cur && c->ws.wide_eligible && !PlanKnobs::read().raster_wide.set) { c->ws.wide = want; c->ws.replan = true; }
         }
         if (feedback && !c->ws.spread && c->ws.xcd_tiles_last && c->ws.status_host[2] > 2u * c->ws.xcd_tiles_last) { c->ws.spread = true; c->ws.replan = true; c->ws.spread_tris = c->plan_tris; }

@@ -210,7 +210,7 @@ inline RasterMode raster_mode(const ScopeClass& c, size_t tiles, size_t tris, bo
     if (m.wide_eligible) {
         const uint32_t forced = knobs.raster_wide.set ? (uint32_t)knobs.raster_wide.value : 0xFFFFFFFFu;
         m.wide = forced == 0xFFFFFFFFu ? wide : (forced == 0u ? 0u : (forced == 8u ? 8u : 16u));
-        // (teams stays what the scope gets when a submit decides against the wide variant: see mirhi_queue_submit, "frames in flight")
+        // (teams stays what the scope gets when a submit decides against the wide variant: see allow_wide, mirhi_submit.h)
     }
     m.xcd_swizzle = knobs.xcd_run.set ? (uint32_t)knobs.xcd_run.value : 1u;
     if (c.own_family) { m.xcd_swizzle = 1u; m.wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
