@@ -52,58 +52,87 @@ __device__ __forceinline__ uint32_t clamp_box(int32_t bx0, int32_t bx1, int32_t 
 }
 
 // The arithmetic of a tile record, ONE copy for both record sources (bin records relative to their tile, big-list / ordered records in
-// absolute screen coordinates): X / Y the snapped vertices and (Ptx, Pty) the tile origin's pixel centre in the same 1/256-pixel frame,
-// (bx0..by1) the inclusive pixel box relative to the tile (already clamped; lo > hi: it misses the tile), (fox, foy) the tile origin in
-// pixels of that frame.  Forced inline: every caller keeps its own register allocation (the TRIANGLE-only variants live on 64 VGPRs).
-__device__ __forceinline__ bool tile_rec_core(uint4 out[4], const int32_t X[3], const int32_t Y[3], int32_t Ptx, int32_t Pty,
-                                              int32_t bx0, int32_t bx1, int32_t by0, int32_t by1, float fox, float foy,
-                                              uint32_t z0, uint32_t zx, uint32_t zy, uint32_t idk, uint32_t boxed) {
-    int32_t A[3], B[3], Q[3];
+// absolute screen coordinates), in the pieces a record is made of: its edges (tile_edge, and blocks_outside for their block masks) and its
+// pixel box (tile_box).  tile_rec_core puts them together on one lane; the split bin pass of the sparse variants (raster_bins_split) gives
+// each piece to another wave.  Forced inline: every caller keeps its own register allocation (the TRIANGLE-only variants live on 64 VGPRs).
+//
+// Edge i, from snapped vertex a = (Xa, Ya) to b = (Xb, Yb), with (Ptx, Pty) the tile origin's pixel centre in the same 1/256-pixel frame
+struct TileEdge { int32_t A, B, Q; };
+__device__ __forceinline__ TileEdge tile_edge(int32_t Xa, int32_t Ya, int32_t Xb, int32_t Yb, int32_t Ptx, int32_t Pty) {
+    TileEdge e;
+    const int32_t dx = Xb - Xa, dy = Yb - Ya;
+    e.A = -dy; e.B = dx;
+    const bool topleft = (dy < 0) || (dy == 0 && dx > 0);              // top-left fill rule
+    // E_i + bias at the tile origin; every factor fits 24 bits (|X|,|Y| < 2^22 and |tile origin| < 2^21 in absolute terms)
+    const int64_t e0 = mul24x24(e.A, Ptx - Xa) + mul24x24(e.B, Pty - Ya) + (topleft ? 0 : -1);
+    int64_t q = e0 >> 8;                                 // floor(E/256): E = 256*(q + A*ix + B*iy) + r, 0 <= r < 256
+    q = q > (1 << 30) ? (1 << 30) : (q < -(1 << 30) ? -(1 << 30) : q);
+    e.Q = (int32_t)q;
+    return e;
+}
+// Conservative 8x8 block mask of N edges (3: a whole record; 1: one edge of it, the masks are ANDed later): a block is dropped if it lies
+// outside one edge.  Per edge the value at the most-inside pixel of block (bx,by) is c_i + 8*(A_i*bx + B_i*by).  Straight-line code:
+// an add per edge, one OR of the edge values and one funnel shift that appends the sign bit (set = outside) per
+// block -- no compares, no branches, nothing on the scalar unit.  Returns bit (by*4+bx) set <=> block (bx, by) is outside no edge.
+template <int N>
+__device__ __forceinline__ uint32_t blocks_inside(const TileEdge (&e)[N]) {
+    int32_t c[N], a8[N], b8[N];
 #pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const int a = i, b = (i + 1) % 3;
-        const int32_t dx = X[b] - X[a], dy = Y[b] - Y[a];
-        A[i] = -dy; B[i] = dx;
-        const bool topleft = (dy < 0) || (dy == 0 && dx > 0);              // top-left fill rule
-        // E_i + bias at the tile origin; every factor fits 24 bits (|X|,|Y| < 2^22 and |tile origin| < 2^21 in absolute terms)
-        const int64_t e0 = mul24x24(A[i], Ptx - X[a]) + mul24x24(B[i], Pty - Y[a]) + (topleft ? 0 : -1);
-        int64_t q = e0 >> 8;                                 // floor(E/256): E = 256*(q + A*ix + B*iy) + r, 0 <= r < 256
-        q = q > (1 << 30) ? (1 << 30) : (q < -(1 << 30) ? -(1 << 30) : q);
-        Q[i] = (int32_t)q;
-    }
-    // conservative 8x8 block mask: a block is dropped if it misses the pixel box or lies outside one edge.
-    // Per edge the value at the most-inside pixel of block (bx,by) is c_i + 8*(A_i*bx + B_i*by).  Straight-line code:
-    // three adds, one OR of the three edge values and one funnel shift that appends the sign bit (set = outside) per
-    // block -- no compares, no branches, nothing on the scalar unit.
-    int32_t c[3], a8[3], b8[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        c[i] = Q[i] + (A[i] >= 0 ? A[i] * (BLOCK - 1) : 0) + (B[i] >= 0 ? B[i] * (BLOCK - 1) : 0);
-        a8[i] = A[i] * BLOCK; b8[i] = B[i] * BLOCK;
+    for (int i = 0; i < N; i++) {
+        c[i] = e[i].Q + (e[i].A >= 0 ? e[i].A * (BLOCK - 1) : 0) + (e[i].B >= 0 ? e[i].B * (BLOCK - 1) : 0);
+        a8[i] = e[i].A * BLOCK; b8[i] = e[i].B * BLOCK;
     }
     uint32_t outside = 0;                               // after the loop: bit (15 - (by*4+bx)) set <=> block outside an edge
 #pragma unroll
     for (int by = 0; by < 4; by++) {
-        int32_t v0 = c[0], v1 = c[1], v2 = c[2];
+        int32_t v[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) v[i] = c[i];
 #pragma unroll
         for (int bx = 0; bx < 4; bx++) {
-            outside = __builtin_amdgcn_alignbit(outside, (uint32_t)(v0 | v1 | v2), 31);   // (outside << 1) | sign
-            v0 += a8[0]; v1 += a8[1]; v2 += a8[2];
+            int32_t any = v[0];
+#pragma unroll
+            for (int i = 1; i < N; i++) any |= v[i];
+            outside = __builtin_amdgcn_alignbit(outside, (uint32_t)any, 31);   // (outside << 1) | sign
+#pragma unroll
+            for (int i = 0; i < N; i++) v[i] += a8[i];
         }
-        c[0] += b8[0]; c[1] += b8[1]; c[2] += b8[2];
+#pragma unroll
+        for (int i = 0; i < N; i++) c[i] += b8[i];
     }
+    return __builtin_bitreverse32(~outside) >> 16;
+}
+
+// The pixel box of a record: (bx0..by1) the inclusive box relative to the tile (already clamped; lo > hi: it misses the tile) -> those of
+// the 8x8 blocks `among` (bit by*4+bx) that it touches (0 if it misses the tile); (X0, Y0) snapped vertex 0 and (fox, foy) the tile origin in
+// pixels of the same frame -> (tile origin pixel centre) - (vertex 0) in pixels.  The other words of a record (z0, zx, zy, idk, boxed) pass through.
+struct TileBox { uint32_t mask; float dxt, dyt; };
+__device__ __forceinline__ TileBox tile_box(uint32_t among, int32_t bx0, int32_t bx1, int32_t by0, int32_t by1, float fox, float foy, int32_t X0, int32_t Y0) {
+    TileBox t;
     // pixel box -> block box -> mask of the blocks inside it (4 column bits replicated per row, row bits spread to nibbles)
     const uint32_t cols = ((2u << ((uint32_t)bx1 >> 3)) - 1u) & ~((1u << ((uint32_t)bx0 >> 3)) - 1u);          // bits bx0b..bx1b
     const uint32_t rows = ((2u << ((uint32_t)by1 >> 3)) - 1u) & ~((1u << ((uint32_t)by0 >> 3)) - 1u);
     const uint32_t rowsel = ((rows & 1u) * 0xFu) | ((rows & 2u) * 0x78u) | ((rows & 4u) * 0x3C0u) | ((rows & 8u) * 0x1E00u);
-    const uint32_t inside = __builtin_bitreverse32(~outside) >> 16;         // bit (by*4+bx) set <=> not outside any edge
-    const uint32_t mask = (bx0 <= bx1 && by0 <= by1) ? (inside & (cols * 0x1111u) & rowsel) : 0u;
+    t.mask = (bx0 <= bx1 && by0 <= by1) ? (among & (cols * 0x1111u) & rowsel) : 0u;
     const float inv256 = 1.0f / 256.0f;
-    const float dxt = (fox + 0.5f) - (float)X[0] * inv256;                  // exact: multiples of 2^-8 below 2^15
-    const float dyt = (foy + 0.5f) - (float)Y[0] * inv256;
-    out[0] = make_uint4((uint32_t)Q[0], (uint32_t)Q[1], (uint32_t)Q[2], (uint32_t)A[0]);
-    out[1] = make_uint4((uint32_t)A[1], (uint32_t)A[2], (uint32_t)B[0], (uint32_t)B[1]);
-    out[2] = make_uint4((uint32_t)B[2], __float_as_uint(dxt), __float_as_uint(dyt), z0);
+    t.dxt = (fox + 0.5f) - (float)X0 * inv256;                  // exact: multiples of 2^-8 below 2^15
+    t.dyt = (foy + 0.5f) - (float)Y0 * inv256;
+    return t;
+}
+
+// The whole record on one lane: X / Y the snapped vertices, the other arguments as tile_edge and tile_box take them.  A block is kept if it
+// lies inside the pixel box and outside no edge.
+__device__ __forceinline__ bool tile_rec_core(uint4 out[4], const int32_t X[3], const int32_t Y[3], int32_t Ptx, int32_t Pty,
+                                              int32_t bx0, int32_t bx1, int32_t by0, int32_t by1, float fox, float foy,
+                                              uint32_t z0, uint32_t zx, uint32_t zy, uint32_t idk, uint32_t boxed) {
+    TileEdge e[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) e[i] = tile_edge(X[i], Y[i], X[(i + 1) % 3], Y[(i + 1) % 3], Ptx, Pty);
+    const TileBox t = tile_box(blocks_inside(e), bx0, bx1, by0, by1, fox, foy, X[0], Y[0]);
+    const uint32_t mask = t.mask;
+    out[0] = make_uint4((uint32_t)e[0].Q, (uint32_t)e[1].Q, (uint32_t)e[2].Q, (uint32_t)e[0].A);
+    out[1] = make_uint4((uint32_t)e[1].A, (uint32_t)e[2].A, (uint32_t)e[0].B, (uint32_t)e[1].B);
+    out[2] = make_uint4((uint32_t)e[2].B, __float_as_uint(t.dxt), __float_as_uint(t.dyt), z0);
     out[3] = make_uint4(zx, zy, idk, mask | boxed);
     return mask != 0;
 }
@@ -197,14 +226,14 @@ __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
 }
 
 // NB: 8x8 blocks this wave owns -- 4 (a 16x16 quadrant, four waves per tile) or 1 (the wide mesh variant: sixteen waves per tile)
+// m: the record's block mask (wave-uniform): its word w3.w, or what the split bin pass combined for it (raster_chunk)
 template <int KEYED, bool BOXED, int NB = 4>
-__device__ __forceinline__ void raster_record(const RecRegs& r, uint32_t box, int32_t ix0, int32_t iy0, float fix0,
+__device__ __forceinline__ void raster_record(const RecRegs& r, uint32_t m, uint32_t box, int32_t ix0, int32_t iy0, float fix0,
                                               float fiy0, ParamsRef P, PixelState& st, uint32_t qbit0) {
     const int32_t A0 = (int32_t)r.w0.w, A1 = (int32_t)r.w1.x, A2 = (int32_t)r.w1.y;
     const int32_t B0 = (int32_t)r.w1.z, B1 = (int32_t)r.w1.w, B2 = (int32_t)r.w2.x;
     const float z0 = __uint_as_float(r.w2.w), zx = __uint_as_float(r.w3.x), zy = __uint_as_float(r.w3.y);
     const uint32_t idk = r.w3.z;
-    const uint32_t m = __builtin_amdgcn_readfirstlane(r.w3.w);
     const int32_t s0 = mad24(B0, iy0, mad24(A0, ix0, (int32_t)r.w0.x));
     const int32_t s1 = mad24(B1, iy0, mad24(A1, ix0, (int32_t)r.w0.y));
     const int32_t s2 = mad24(B2, iy0, mad24(A2, ix0, (int32_t)r.w0.z));
@@ -317,14 +346,20 @@ __device__ __forceinline__ void raster_record_masked(const RecRegs& r, int32_t i
 
 // all records of an LDS chunk: per 64 records one ballot builds the bitmap of records that touch this
 // wave's quadrant; LDS latency of the broadcast record reads is hidden by the other waves of the SIMD
-template <int KEYED, int TP, bool MASKED = false, int NB = 4>
+// SIDE: the chunk was staged by the split bin pass (raster_bins_split): record j's mask is the AND of the four 16-bit masks its four
+// builders left in lds_side[j], word w3.w of the record is not written, and no record is scissor-cut (bin records never are).
+template <int KEYED, int TP, bool MASKED = false, int NB = 4, bool SIDE = false>
 __device__ __forceinline__ void raster_chunk(const uint4* lds_rec, const uint32_t* lds_box, uint32_t n, uint32_t qmask,
                                              int32_t ix0, int32_t iy0, float fix0, float fiy0, ParamsRef P,
-                                             PixelState& st, uint32_t qbit0, uint32_t lane, uint32_t tx = 0u, uint32_t ty = 0u) {
+                                             PixelState& st, uint32_t qbit0, uint32_t lane, uint32_t tx = 0u, uint32_t ty = 0u,
+                                             const uint2* lds_side = nullptr) {
     for (uint32_t g = 0; g < n; g += 64u) {
         const uint32_t j = g + lane;
-        const uint32_t mymask = j < n ? lds_rec[j * 4u + 3u].w : 0u;
-        const bool rel = (mymask & qmask) != 0u, boxed = !TP && (mymask & 0x80000000u) != 0u;
+        uint32_t mymask = 0u;
+        if (SIDE) {
+            if (j < n) { const uint2 s = lds_side[j]; const uint32_t m = s.x & s.y; mymask = m & (m >> 16); }      // (one 8-byte read, no bank conflict)
+        } else if (j < n) mymask = lds_rec[j * 4u + 3u].w;
+        const bool rel = (mymask & qmask) != 0u, boxed = !TP && !SIDE && (mymask & 0x80000000u) != 0u;
         const bool mrec = MASKED && (mymask & MIRHI_REC_MASKED) != 0u;
         if (MASKED) {        // (alpha-masked scopes only: no such record exists elsewhere)
             uint64_t mbits = __ballot(rel && mrec);
@@ -342,15 +377,16 @@ __device__ __forceinline__ void raster_chunk(const uint4* lds_rec, const uint32_
             // at the vector unit's rate on this part, and this loop runs once per record and wave)
             asm("s_bitset0_b64 %0, %1" : "+s"(bits) : "s"(bit));
             const RecRegs cur = load_rec(lds_rec, g + bit);
-            raster_record<KEYED, false, NB>(cur, 0u, ix0, iy0, fix0, fiy0, P, st, qbit0);
+            const uint32_t m = SIDE ? (uint32_t)__builtin_amdgcn_readlane((int)mymask, (int)bit) : (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.w3.w);
+            raster_record<KEYED, false, NB>(cur, m, 0u, ix0, iy0, fix0, fiy0, P, st, qbit0);
         }
-        if (!TP) {   // without the triangle-parallel path, scissor-cut triangles (rare) take the per-pixel box test here
+        if (!TP && !SIDE) {   // without the triangle-parallel path, scissor-cut triangles (rare) take the per-pixel box test here
             uint64_t bbits = __ballot(rel && boxed);
             while (bbits) {
                 const uint32_t cur_j = g + (uint32_t)(__ffsll((long long)bbits) - 1);
                 bbits &= bbits - 1;
                 const RecRegs cur = load_rec(lds_rec, cur_j);
-                raster_record<KEYED, true, NB>(cur, lds_box[cur_j], ix0, iy0, fix0, fiy0, P, st, qbit0);
+                raster_record<KEYED, true, NB>(cur, (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.w3.w), lds_box[cur_j], ix0, iy0, fix0, fiy0, P, st, qbit0);
             }
         }
     }
@@ -469,6 +505,68 @@ __device__ __forceinline__ void init_key(ParamsRef P, uint32_t px, uint32_t py, 
     }
 }
 
+// The bin pass of the sparse pixel-parallel variants (raster_split_bins: no triangle-parallel path, one team, four waves per tile), in which
+// a tile holds a few dozen records: all four waves build every record of a pass together, each its own piece.  Lane l of group g of EVERY
+// wave takes record base + 64 g + l; the wave's role says which piece: roles 0, 1, 2 compute edge 0, 1, 2 (tile_edge) from the record's
+// first 16 bytes and write Q_i, A_i, B_i into their words of the LDS tile record, role 3 computes the pixel box (tile_box) and writes dxt, dyt
+// and the depth plane / id words.  A record stays at its own index -- no ballot, no compaction, no LDS counter -- and each role leaves a 16-bit
+// block mask in its quarter of lds_side[j] (edge roles: the blocks inside their edge; box role: the blocks the pixel box touches, 0 if the
+// box misses the tile or the record's page is one the exhausted pool could not supply -- those records come through the big list).  Behind
+// the pass's barrier raster_chunk ANDs the four: a record whose mask is 0 is never relevant to any wave.  Bin records are never cut by a
+// scissor (those go to the big list), so neither the boxed bit nor lds_box exists here, and word w3.w of the record stays unwritten.
+// Why: a whole record is a dependent chain of ~620 vector instructions, and with ~20 records a wave that builds them alone has a third of
+// its lanes busy while the other three hold their slots at the barrier; split, the longest chain is one edge (Stage A).
+// The roles rotate with the tile like the staging wave of raster_list does: wave k of every workgroup sits on the same SIMD.
+constexpr bool raster_split_bins(int TP, int TEAMS, int WPT, bool MASKED) { return TP == 0 && TEAMS == 1 && WPT == 4 && !MASKED; }
+template <int KEYED, int CHUNK>
+__device__ __forceinline__ void raster_bins_split(const uint4* __restrict__ pool, uint32_t n_total, uint32_t tile, uint32_t fixed_recs, const uint32_t* pages,
+                                                  uint4* lds_rec, uint2* lds_side, uint32_t tx, uint32_t ty, uint32_t qmask, int32_t ix0, int32_t iy0,
+                                                  float fix0, float fiy0, ParamsRef P, PixelState& st, uint32_t qbit0, uint32_t tid, uint32_t lane) {
+    const uint32_t role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((tid >> 6) + tx + ty) & 3u));
+    uint32_t* const rec32 = reinterpret_cast<uint32_t*>(lds_rec);
+    uint16_t* const side16 = reinterpret_cast<uint16_t*>(lds_side);
+    for (uint32_t base = 0; base < n_total; base += (uint32_t)CHUNK) {
+        __syncthreads();                              // every wave has left the previous pass's records
+        const uint32_t n = n_total - base < (uint32_t)CHUNK ? n_total - base : (uint32_t)CHUNK;
+        for (uint32_t g = 0; g < n; g += 64u) {
+            const uint32_t j = g + lane, i = base + j;
+            if (j >= n) continue;
+            // flat index -> pool page: the tile's fixed pages, then its row of the page table (LDS copy)
+            const uint32_t page = i < fixed_recs ? (tile * fixed_recs + i) >> BIN_PAGE_LOG2 : pages[i >> BIN_PAGE_LOG2];
+            const bool have = page < PAGE_NONE;       // (a page the exhausted pool could not supply: its records are in the big list)
+            const uint32_t ri = (page * (uint32_t)BIN_PAGE_RECS + (i & (BIN_PAGE_RECS - 1u))) * 2u;      // (pools stay far below 2^32 words)
+            if (role < 3u) {
+                if (have) {
+                    const uint4 w0 = pool[ri];
+                    const int32_t ox = (int32_t)(w0.x << 16) >> 16, oy = (int32_t)w0.x >> 16;
+                    const uint32_t va = role == 0u ? w0.y : (role == 1u ? w0.z : w0.w), vb = role == 0u ? w0.z : (role == 1u ? w0.w : w0.y);
+                    const TileEdge e[1] = {tile_edge(ox + (int32_t)(va & 0xFFFFu), oy + (int32_t)(va >> 16), ox + (int32_t)(vb & 0xFFFFu), oy + (int32_t)(vb >> 16), 128, 128)};
+                    uint32_t* const r = rec32 + j * 16u + role;
+                    r[0] = (uint32_t)e[0].Q; r[3] = (uint32_t)e[0].A; r[6] = (uint32_t)e[0].B;
+                    side16[j * 4u + role] = (uint16_t)blocks_inside(e);
+                }
+            } else {
+                uint32_t m = 0u;
+                if (have) {
+                    TileTri T;
+                    tile_tri_from_bin(T, pool[ri], pool[ri + 1u]);
+                    const TileBox t = tile_box(0xFFFFu, (int32_t)(T.box & 0xFFu), (int32_t)(int8_t)((T.box >> 8) & 0xFFu), (int32_t)((T.box >> 16) & 0xFFu), (int32_t)T.box >> 24,
+                                               0.0f, 0.0f, T.X[0], T.Y[0]);
+                    uint32_t* const r = rec32 + j * 16u;
+                    r[9] = __float_as_uint(t.dxt); r[10] = __float_as_uint(t.dyt); r[11] = T.z0;
+                    r[12] = T.zx; r[13] = T.zy; r[14] = T.idk;
+                    m = t.mask;
+                }
+                side16[j * 4u + 3u] = (uint16_t)m;
+            }
+        }
+        __syncthreads();
+        if (base == 0) { STAMP(5); STAGE_END(2u); }
+        raster_chunk<KEYED, 0, false, 4, true>(lds_rec, nullptr, n, qmask, ix0, iy0, fix0, fiy0, P, st, qbit0, lane, tx, ty, lds_side);
+    }
+}
+
+// Every other variant, and the big list of every variant: one wave builds whole records.
 // Stages up to RASTER_THREADS triangle records of `list` (bin or big list) into LDS as tile records
 // (one record per lane, wave ballot + prefix popcount compaction), then resolves them.
 // TEAMS > 1 (mesh variants): the workgroup is TEAMS sets of four waves; team t stages and rasters chunks t, t + TEAMS, ...
@@ -784,6 +882,10 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
     // spilled triangles).  Two instantiations of raster_list: one body fed from either source has to hold both record forms in
     // registers on the way to the tile record, which the TRIANGLE-only variants (64 VGPRs) pay with ~20 spills.
     constexpr bool MASKED = MASKEDV && PROGS == 4 && TP != 0;
+    if constexpr (raster_split_bins(TP, TEAMS, WPT, MASKED)) {
+        __shared__ uint2 lds_side[CHUNK];         // the four builders' 16-bit block masks of each staged record (raster_bins_split)
+        if (count) raster_bins_split<KEYED, CHUNK>(reinterpret_cast<const uint4*>(H.bin_pool), count, tile, H.fixed_recs, lds_pages, lds_rec[0], lds_side, tx, ty, qmask, ix0, iy0, fix0, fiy0, P, st, qbit0, tid, lane);
+    } else
     if (count) raster_list<KEYED, TP, CHUNK, TEAMS, true, MASKED, WPT>(reinterpret_cast<const uint4*>(H.bin_pool), count, tile, H.fixed_recs, lds_pages, xcd_bins ? lds_seg : nullptr, lds_rec[team], lds_box, lds_count + 2u * team, flip, team, nteams, lds_key, tx, ty, qmask, ix0, iy0, fix0, fiy0, P, st,
                                                          qbit0, tid, lane);
     STAMP(2);

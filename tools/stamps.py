@@ -1,5 +1,6 @@
 import os, sys, ctypes as C, numpy as np
 os.environ["MIRHI_LIB_NAME"] = "libmirhi_stamps.so"
+os.environ.setdefault("MIRHI_NATIVE_DISPATCH", "0")      # the stamps are read from the HIP module's copy of g_stamps: launch through HIP, as tools/stage_counts.sh does
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
