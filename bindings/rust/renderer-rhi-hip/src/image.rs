@@ -74,6 +74,24 @@ impl Image {
         check(unsafe { mirhi_sys::mirhi_image_set_max_anisotropy(self.raw, max_anisotropy) })
     }
     pub fn max_anisotropy(&self) -> u32 { unsafe { mirhi_sys::mirhi_image_max_anisotropy(self.raw) } }
+    /// The rest of the sampler state (include/mirhi.h `mirhi_image_set_sampler`): address modes, mag / min filters and mip mode, for draws
+    /// recorded afterwards.  `default_sampler()` is REPEAT / LINEAR / MIP_LINEAR.
+    pub fn set_sampler(&self, desc: &mirhi_sys::mirhi_sampler_desc) -> RhiResult<()> {
+        check(unsafe { mirhi_sys::mirhi_image_set_sampler(self.raw, desc) })
+    }
+    pub fn sampler(&self) -> RhiResult<mirhi_sys::mirhi_sampler_desc> {
+        let mut desc = Self::default_sampler();
+        check(unsafe { mirhi_sys::mirhi_image_sampler(self.raw, &mut desc) })?;
+        Ok(desc)
+    }
+    pub fn default_sampler() -> mirhi_sys::mirhi_sampler_desc {
+        let mut desc = mirhi_sys::mirhi_sampler_desc {
+            address_u: mirhi_sys::MIRHI_ADDRESS_REPEAT, address_v: mirhi_sys::MIRHI_ADDRESS_REPEAT, mag_filter: mirhi_sys::MIRHI_SAMPLER_FILTER_LINEAR,
+            min_filter: mirhi_sys::MIRHI_SAMPLER_FILTER_LINEAR, mip_mode: mirhi_sys::MIRHI_MIP_LINEAR,
+        };
+        unsafe { mirhi_sys::mirhi_sampler_desc_default(&mut desc) };
+        desc
+    }
 }
 
 impl Drop for Image {

@@ -175,6 +175,35 @@ uint32_t     mirhi_image_mip_levels(const mirhi_image* img);
  * lambda = log2(Pmax / N), averaged (the example filter of the Vulkan specification, "Texel Anisotropic Filtering"). */
 mirhi_result mirhi_image_set_max_anisotropy(mirhi_image* img, uint32_t max_anisotropy);
 uint32_t     mirhi_image_max_anisotropy(const mirhi_image* img);
+/* Sampler state of a texture, beside max_anisotropy (sampler.rs is a stub; per-image state is this build's form of a VkSampler).  The semantics
+ * are the Vulkan specification's, "Texel Coordinate Systems" / "Texel Filtering"; the all-zero state is the sampler every texture had before this
+ * state existed (REPEAT, LINEAR, trilinear with a chain), and a texture in that state is sampled exactly as before.
+ *   Addressing, per axis and per mip level with that level's extent n: REPEAT i mod n; MIRRORED_REPEAT (n - 1) - mirror((i mod 2n) - n) with
+ *     mirror(a) = a >= 0 ? a : -(1 + a); CLAMP_TO_EDGE clamp(i, 0, n - 1).
+ *   Filters: lambda is the level of detail before clamping (mirhi_image_generate_mips above: log2 of the longer footprint axis in texels; with
+ *     anisotropy the filter's own log2(Pmax / N)).  mag_filter applies where lambda <= 0 (and where the footprint is zero), min_filter where
+ *     lambda > 0 -- also on a texture without a chain.  NEAREST reads the one texel at floor(u w), floor(v h); LINEAR the four around
+ *     u w - 1/2, v h - 1/2; both then go through the address modes.
+ *   Mip mode (textures with a chain; one without has level 0 only): MIP_LINEAR two levels around lambda clamped to [0, levels - 1], weighted;
+ *     MIP_NEAREST the single level ceil(lambda + 1/2) - 1 clamped to [0, levels - 1]; MIP_BASE level 0 whatever the chain (glTF's NEAREST / LINEAR
+ *     minification filters).
+ *   Anisotropy applies only when min_filter is LINEAR and mip_mode MIP_LINEAR; otherwise the texture is sampled as if max_anisotropy were 1.
+ *     Its N taps go through the same address modes and filters.
+ * Cost: a texture with state is sampled by a slower path than one in the default state; and a scope of fragment_discard_enable pipelines in which a
+ * MODEL_PBR draw's BASE COLOUR texture (the one the alpha test reads) has state is resolved in primitive order, as a blended scope is, instead of by
+ * the masked depth-key variants.  State on the other textures does not change how a scope is resolved.
+ * Takes effect for draws recorded afterwards, like max_anisotropy.  Refused: a NULL desc and a value outside its enum (Vulkan error, the message
+ * names the field); an image that cannot sit in a material texture slot -- cube, array, layer view, D32 and float formats (InvalidHandle).  The
+ * comparison sampler of MIRHI_TEXTURE_SHADOW_MAP, the cube sampler of the IBL set and the skybox, and mirhi_cmd_blit_image's filter are not
+ * sampler state of an image and stay as stated where they are declared.  (The filter values are an enum of their own: zero has to be LINEAR here,
+ * and mirhi_filter, the blit's VkFilter, counts NEAREST first.) */
+typedef enum { MIRHI_ADDRESS_REPEAT = 0, MIRHI_ADDRESS_MIRRORED_REPEAT = 1, MIRHI_ADDRESS_CLAMP_TO_EDGE = 2 } mirhi_address_mode;
+typedef enum { MIRHI_SAMPLER_FILTER_LINEAR = 0, MIRHI_SAMPLER_FILTER_NEAREST = 1 } mirhi_sampler_filter;
+typedef enum { MIRHI_MIP_LINEAR = 0, MIRHI_MIP_NEAREST = 1, MIRHI_MIP_BASE = 2 } mirhi_mip_mode;
+typedef struct { int32_t address_u, address_v, mag_filter, min_filter, mip_mode; } mirhi_sampler_desc;
+void         mirhi_sampler_desc_default(mirhi_sampler_desc* desc);          /* all zero: REPEAT, REPEAT, LINEAR, LINEAR, MIP_LINEAR */
+mirhi_result mirhi_image_set_sampler(mirhi_image* img, const mirhi_sampler_desc* desc);
+mirhi_result mirhi_image_sampler(const mirhi_image* img, mirhi_sampler_desc* out);
 uint32_t     mirhi_image_width(const mirhi_image* img);
 uint32_t     mirhi_image_height(const mirhi_image* img);
 int32_t      mirhi_image_format(const mirhi_image* img);

@@ -108,6 +108,21 @@ class Filter:
     NEAREST, LINEAR = range(2)
 
 
+class AddressMode:
+    """mirhi_address_mode of a texture's sampler (SamplerDesc.address_u / address_v)"""
+    REPEAT, MIRRORED_REPEAT, CLAMP_TO_EDGE = range(3)
+
+
+class SamplerFilter:
+    """mirhi_sampler_filter of a texture's sampler (SamplerDesc.mag_filter / min_filter): zero is LINEAR, unlike the blit's Filter"""
+    LINEAR, NEAREST = range(2)
+
+
+class MipMode:
+    """mirhi_mip_mode of a texture's sampler: BASE samples level 0 whatever the chain"""
+    LINEAR, NEAREST, BASE = range(3)
+
+
 class SplitLayout:
     """mirhi_split_layout: which tile rows a rank of a tile split rasterizes"""
     BANDS, INTERLEAVED = range(2)
@@ -142,6 +157,14 @@ class PipelineDesc(C.Structure):
 class DepthBias(C.Structure):
     """mirhi_depth_bias: the factors of GraphicsPipelineBuilder::depth_bias (pipeline.rs:781-788)"""
     _fields_ = [("constant_factor", C.c_float), ("clamp", C.c_float), ("slope_factor", C.c_float)]
+
+
+class SamplerDesc(C.Structure):
+    """mirhi_sampler_desc: the sampler state of a texture (Image.set_sampler); all zero = REPEAT / LINEAR / MIP_LINEAR, the default"""
+    _fields_ = [("address_u", C.c_int32), ("address_v", C.c_int32), ("mag_filter", C.c_int32), ("min_filter", C.c_int32), ("mip_mode", C.c_int32)]
+
+    def as_tuple(self):
+        return (self.address_u, self.address_v, self.mag_filter, self.min_filter, self.mip_mode)
 
 
 class RenderingInfo(C.Structure):
@@ -263,6 +286,9 @@ _SIGNATURES = {
     "mirhi_image_generate_mips": (C.c_int32, [C.c_void_p]),
     "mirhi_image_set_max_anisotropy": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "mirhi_image_max_anisotropy": (C.c_uint32, [C.c_void_p]),
+    "mirhi_sampler_desc_default": (None, [C.c_void_p]),
+    "mirhi_image_set_sampler": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mirhi_image_sampler": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_image_mip_levels": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_width": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_height": (C.c_uint32, [C.c_void_p]),
@@ -618,6 +644,26 @@ class Image:
     @property
     def max_anisotropy(self) -> int:
         return int(lib().mirhi_image_max_anisotropy(self.handle))
+
+    def set_sampler(self, desc=None, **fields):
+        """Sampler state of a material texture (include/mirhi.h mirhi_image_set_sampler), for draws recorded afterwards: a SamplerDesc, or its
+        fields by name (address_u, address_v, mag_filter, min_filter, mip_mode; those not named are the default's)."""
+        if desc is None:
+            desc = SamplerDesc()
+            lib().mirhi_sampler_desc_default(C.byref(desc))
+            for k, v in fields.items():
+                if k not in dict(SamplerDesc._fields_):
+                    raise TypeError(f"SamplerDesc has no field {k!r}")
+                setattr(desc, k, int(v))
+        elif fields:
+            raise TypeError("pass a SamplerDesc or fields by name, not both")
+        check(lib().mirhi_image_set_sampler(self.handle, C.byref(desc)))
+
+    @property
+    def sampler(self) -> SamplerDesc:
+        desc = SamplerDesc()
+        check(lib().mirhi_image_sampler(self.handle, C.byref(desc)))
+        return desc
 
     def read(self) -> np.ndarray:
         n = lib().mirhi_image_size_bytes(self.handle)
@@ -1025,6 +1071,9 @@ class SceneResources:
                 img.generate_mips()
             if getattr(t, "max_anisotropy", 1) > 1:
                 img.set_max_anisotropy(t.max_anisotropy)
+            state = tuple(int(getattr(t, k, 0)) for k, _ in SamplerDesc._fields_)
+            if any(state):
+                img.set_sampler(SamplerDesc(*state))
             cache[id(t)] = img
             self.objs.append(img)
             return img

@@ -483,6 +483,7 @@ struct mirhi_image {
     bool owned;
     uint32_t levels = 1;      // mip levels stored contiguously behind level 0 (mirhi_image_generate_mips)
     uint32_t max_anisotropy = 1;   // sampler state (mirhi_image_set_max_anisotropy): 1 = trilinear
+    mirhi_sampler_desc sampler = {0, 0, 0, 0, 0};      // ... and the rest of it (mirhi_image_set_sampler): all zero = REPEAT / LINEAR / MIP_LINEAR
     // Layered images (mirhi_image_create_array): `layers` tightly packed width x height levels in one allocation; is_array marks the array object itself,
     // which is no 2-D image (attachments and MIRHI_TEXTURE_SHADOW_MAP take a layer view).  A layer view (mirhi_image_create_layer_view) is a non-owning
     // 2-D image of one layer: ptr points into the array, `parent` is the array -- what attachment ordering resolves a view to (for_each_attachment).
@@ -1300,6 +1301,28 @@ extern "C" mirhi_result mirhi_image_set_max_anisotropy(mirhi_image* img, uint32_
     img->max_anisotropy = max_anisotropy;        // read when a draw is recorded, like the mip chain
     return MIRHI_OK;
 }
+extern "C" void mirhi_sampler_desc_default(mirhi_sampler_desc* desc) { if (desc) *desc = mirhi_sampler_desc{0, 0, 0, 0, 0}; }
+extern "C" mirhi_result mirhi_image_set_sampler(mirhi_image* img, const mirhi_sampler_desc* desc) {
+    NULL_CHECK(img, "image");
+    NULL_CHECK(desc, "sampler desc");
+    if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image has no sampler state (the cube sampler is fixed, include/mirhi.h)");
+    if (img->is_array || img->parent)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array and its layer views have no sampler state (the shadow comparison sampler is fixed, include/mirhi.h)");
+    if (img->format != MIRHI_FORMAT_R8G8B8A8_UNORM && img->format != MIRHI_FORMAT_R8G8B8A8_SRGB)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: sampler state applies to sampled R8G8B8A8 textures only");
+    const struct { const char* name; int32_t value, count; } fields[5] = {
+        {"address_u", desc->address_u, 3}, {"address_v", desc->address_v, 3}, {"mag_filter", desc->mag_filter, 2}, {"min_filter", desc->min_filter, 2}, {"mip_mode", desc->mip_mode, 3}};
+    for (const auto& f : fields)
+        if (f.value < 0 || f.value >= f.count) return fail(MIRHI_ERR_DEVICE, "Vulkan error: sampler %s %d outside its enum [0, %d]", f.name, f.value, f.count - 1);
+    img->sampler = *desc;        // read when a draw is recorded, like max_anisotropy
+    return MIRHI_OK;
+}
+extern "C" mirhi_result mirhi_image_sampler(const mirhi_image* img, mirhi_sampler_desc* out) {
+    NULL_CHECK(img, "image");
+    NULL_CHECK(out, "sampler desc");
+    *out = img->sampler;
+    return MIRHI_OK;
+}
 extern "C" mirhi_result mirhi_image_destroy(mirhi_image* img) {
     NULL_CHECK(img, "image");
     if (img->views != 0) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: image array still has %u live layer views", img->views);
@@ -1960,7 +1983,13 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                     d.tex[t] = ti->ptr; d.tex_w[t] = ti->width; d.tex_h[t] = ti->height; d.tex_levels[t] = ti->levels;
                     if (ti->format == MIRHI_FORMAT_R8G8B8A8_SRGB) d.tex_srgb |= 1u << t;
                     if (ti->levels > 1) d.tex_any_mips = 1;
-                    if (ti->levels > 1) d.tex_aniso |= (ti->max_anisotropy - 1u) << (4 * t);
+                    // sampler state (mirhi_image_set_sampler).  Anisotropy belongs to LINEAR minification with MIP_LINEAR alone; a texture without a chain whose
+                    // mag and min filters differ needs lambda, that is the UV derivatives tex_any_mips switches on
+                    const mirhi_sampler_desc& sp = ti->sampler;
+                    if (ti->levels > 1 && sp.min_filter == MIRHI_SAMPLER_FILTER_LINEAR && sp.mip_mode == MIRHI_MIP_LINEAR) d.tex_aniso |= (ti->max_anisotropy - 1u) << (4 * t);
+                    d.tex_aniso |= (uint32_t)sp.mip_mode << (TEX_MIP_MODE_SHIFT + 2 * t);
+                    d.tex_sampler |= ((uint32_t)sp.address_u | (uint32_t)sp.address_v << 2 | (uint32_t)sp.mag_filter << 4 | (uint32_t)sp.min_filter << 5) << (6 * t);
+                    if (sp.mag_filter != sp.min_filter) d.tex_any_mips = 1;
                 }
             if (pbr && cmd->textures[MIRHI_TEXTURE_SHADOW_MAP]) {
                 // CalculateShadow (model_pbr.hlsl:238-251): the map and its ShadowParams; the shadowed raster variant resolves ordered depth keys only
@@ -2846,7 +2875,8 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
 // Outside the C ABI (not in include/mirhi.h) and without a HIP call: what build_plan decides for one scope -- class, raster mode (one evaluation),
 // bins -- and the kernel, grid and block that raster_variant then gives at 5 x 4 tiles.  The environment is read as build_plan reads it.
 // in: DepthState key_set, test, compare, write, discard, blend enable; clear-depth float bits; depth_only; tiles; triangles; spread; wide; pool_scale;
-// allow_wide; number of draws (at most 4); per draw: program, shadow kind 0 / 1 / 2, "has a mip chain or an sRGB texture".
+// allow_wide; number of draws (at most 4); per draw: program, shadow kind 0 / 1 / 2, bit 0 "has a mip chain or an sRGB texture" | bit 1 "texture 0 has sampler state" |
+// bit 2 "texture 1 has sampler state".
 // out: the key's eight words; ordered, masked_plain, tri_prog, shadowed, ibl, own_family, programs; tp_max_area, teams, wide_eligible, xcd_bins, wide,
 // xcd_swizzle; bin_cap, sub_cap, fixed_per_tile, fixed_pages, pool pages (low, high word), big_cap; grid x, y, z, block.
 extern "C" int mirhi_debug_raster_choice(const uint32_t in[12], char* name, uint32_t name_len, uint32_t grid_block[4]);
@@ -2863,7 +2893,8 @@ extern "C" int mirhi_debug_scope_plan(const uint32_t* in, uint32_t* out, char* n
     for (uint32_t i = 0; i < n; i++) {
         draws[i].program = in[15 + 3 * i];
         if (in[16 + 3 * i]) { draws[i].shadow_map = &some_map; draws[i].shadow_layers = in[16 + 3 * i] == 2u ? 4u : 0u; }
-        draws[i].tex_any_mips = in[17 + 3 * i];
+        draws[i].tex_any_mips = in[17 + 3 * i] & 1u;
+        draws[i].tex_sampler = ((in[17 + 3 * i] >> 1) & 1u) | (((in[17 + 3 * i] >> 2) & 1u) << 6);
     }
     const ScopeClass c = classify_scope(s, clear_depth, draws, n, in[7] != 0u, knobs, n == 1u && draws[0].program == (uint32_t)MIRHI_PROGRAM_SKYBOX);      // (a SKYBOX draw is a segment of its own)
     const RasterMode m = raster_mode(c, in[8], in[9], in[10] != 0u, in[11], knobs);

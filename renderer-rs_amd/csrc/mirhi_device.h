@@ -78,7 +78,8 @@ struct DrawDesc {
     int32_t  sx0, sy0, sx1, sy1;  // inclusive scissor (already clamped to render area and extent)
     uint32_t scissor_partial;     // scissor smaller than the target: per-pixel box test needed when it cuts a bbox
     uint32_t vs_words;            // 16-byte words per shaded vertex (3 MODEL, 5 MODEL_FULL, 0 = no vertex pre-pass)
-    uint32_t tex_aniso;           // bits 4t..4t+3: max_anisotropy - 1 of texture t (0 = trilinear; set only for textures with a chain)
+    uint32_t tex_aniso;           // bits 4t..4t+3: max_anisotropy - 1 of texture t (0 = trilinear; set only for textures with a chain whose sampler
+                                  // minifies LINEAR / MIP_LINEAR); bits 20+2t..21+2t: mirhi_mip_mode of texture t's sampler (0 = MIP_LINEAR)
     const void* vs_attr;          // shaded vertices, the other words (vs_words - 1 per vertex): see VsJob
     const void* vs_out;           // shaded vertices, clip positions (16 B per vertex), indexed like the vertex buffer: see VsJob
     const float*   shadow_map;    // MODEL_PBR with MIRHI_TEXTURE_SHADOW_MAP bound: the D32 map (t7), else nullptr (shadow = 1)
@@ -88,9 +89,17 @@ struct DrawDesc {
                                   // that many tightly packed layers, shadow_data its CSMParams (336 B, shadow_csm.hlsli:23-39): CalculateShadowCSM
     uint32_t tex_any_mips;        // some bound texture has a chain: the fragment program evaluates UV derivatives
     float    bias_constant, bias_clamp, bias_slope;      // mirhi_depth_bias; read under DEPTH_FLAG_BIAS only
-    uint32_t bias_pad;
+    // Sampler state of the five textures (mirhi_image_set_sampler), read by the fragment programs alone and so kept out of the 0x80-0xbf
+    // line: bits 6t..6t+5 of texture t = address_u | address_v << 2 | mag_filter << 4 | min_filter << 5 (mirhi_address_mode, mirhi_sampler_filter: LINEAR = 0 -- not the blit's mirhi_filter).  With the mip
+    // mode in tex_aniso that is eight bits per texture; all zero = REPEAT / LINEAR / MIP_LINEAR, the sampler of every draw before the state existed.
+    uint32_t tex_sampler;
 };
 constexpr uint32_t DEPTH_FLAG_BIAS = 1u, DEPTH_FLAG_CLAMP = 2u;
+constexpr uint32_t TEX_MIP_MODE_SHIFT = 20u;     // DrawDesc::tex_aniso: where the mip modes start
+// some texture of the draw has a sampler other than REPEAT / LINEAR / MIP_LINEAR: the draw belongs to the full-featured program class (classify_scope)
+inline bool draw_has_sampler_state(const DrawDesc& d) { return d.tex_sampler != 0u || (d.tex_aniso >> TEX_MIP_MODE_SHIFT) != 0u; }
+// ... and its texture 0 has: the one texture the masked raster variants' alpha test reads (pbr_base_alpha, under the default sampler only)
+inline bool draw_has_base_sampler_state(const DrawDesc& d) { return (d.tex_sampler & 63u) != 0u || ((d.tex_aniso >> TEX_MIP_MODE_SHIFT) & 3u) != 0u; }
 static_assert(sizeof(DrawDesc) % 16 == 0, "DrawDesc must stay 16-byte sized");
 
 // Vertex-shader pre-pass (vertex/model.hlsl:39-68 run once per vertex, as a GPU's vertex stage does, instead of three

@@ -154,18 +154,25 @@ inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const D
         c.sky = true; c.has_draws = true; c.own_family = true; c.programs = PROGS_SKY;
         return c;
     }
-    c.masked_plain = s.key_set && s.discard && s.blend[0] == 0 && !s.order_dependent_depth() && !(knobs.masked_ordered.set && knobs.masked_ordered.value != 0) &&
-                     c.key.pred == 0u;
-    c.ordered = s.key_set && (s.blend[0] != 0 || (s.discard != 0 && !c.masked_plain) || s.order_dependent_depth());
     c.has_draws = n != 0;
     uint32_t progs = 0;
+    bool sampler_state = false;
     for (size_t i = 0; i < n; i++) {
         const DrawDesc& dd = draws[i];
+        sampler_state |= dd.program == MIRHI_PROGRAM_MODEL_PBR && draw_has_base_sampler_state(dd);
         c.tri_prog |= dd.program == MIRHI_PROGRAM_TRIANGLE;
         c.shadowed |= dd.shadow_map ? (dd.shadow_layers ? 2u : 1u) : 0u;
         c.ibl |= dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL ? 1u : 0u;
-        progs |= dd.program == MIRHI_PROGRAM_TRIANGLE ? PROGS_TRIANGLE : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL || dd.tex_any_mips || dd.tex_srgb) ? PROGS_PBR : PROGS_MODEL);
+        progs |= dd.program == MIRHI_PROGRAM_TRIANGLE ? PROGS_TRIANGLE : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL || dd.tex_any_mips || dd.tex_srgb || draw_has_sampler_state(dd)) ? PROGS_PBR : PROGS_MODEL);
     }
+    // A MODEL_PBR draw whose BASE COLOUR texture has sampler state (mirhi_image_set_sampler) keeps a discard scope out of the masked raster variants:
+    // their alpha test (pbr_base_alpha: texture 0 of MODEL_PBR draws, nothing else) samples under the default sampler only -- those kernels sit at
+    // their register ceiling, DESIGN.md 8i -- so such a scope takes the ordered resolve, which shades every fragment through the full sampler, as
+    // MIRHI_MASKED_ORDERED=1 makes every discard scope do.  State on the other four textures, or on a draw of another program, changes nothing here:
+    // the variants' shading of the winning fragment knows the state.
+    c.masked_plain = s.key_set && s.discard && s.blend[0] == 0 && !s.order_dependent_depth() && !(knobs.masked_ordered.set && knobs.masked_ordered.value != 0) &&
+                     c.key.pred == 0u && !sampler_state;
+    c.ordered = s.key_set && (s.blend[0] != 0 || (s.discard != 0 && !c.masked_plain) || s.order_dependent_depth());
     c.own_family = depth_only || c.shadowed || c.ibl;
     if (c.shadowed) progs = PROGS_PBR | PROGS_SHADOWED | (c.shadowed == 2u ? PROGS_CASCADED : 0u);
     if (c.ibl) progs = PROGS_PBR | PROGS_IBL | (c.shadowed ? PROGS_SHADOWED : 0u) | (c.shadowed == 2u ? PROGS_CASCADED : 0u);

@@ -98,20 +98,127 @@ __device__ __forceinline__ f4 sample_trilinear(const uint32_t* texels, uint32_t 
     const f4 c1 = sample_level(next, lw > 1u ? lw >> 1 : 1u, lh > 1u ? lh >> 1 : 1u, u, v, srgb);
     return {c0.x + (c1.x - c0.x) * f, c0.y + (c1.y - c0.y) * f, c0.z + (c1.z - c0.z) * f, c0.w + (c1.w - c0.w) * f};
 }
-// Texture slot `slot` of the draw at (u, v).  Without a mip chain: bilinear (the reference never creates a sampler --
-// sampler.rs is a stub -- so VK_FILTER_LINEAR / REPEAT is this build's stated choice).  With a chain
+// ---- sampler state (mirhi_image_set_sampler, include/mirhi.h) ----
+// The state of a slot is wave-uniform (scalar loads of DrawDesc::tex_sampler / tex_aniso), so everything that depends on the state alone is a scalar
+// branch; what depends on lambda (mag or min filter) is the lane's own.  A slot whose state is all zero never gets here: sample_texture keeps the
+// sequence it had before the state existed.
+// One coordinate under an address mode (the Vulkan specification, "Wrapping Operation"), with the level's extent n:
+//   REPEAT i mod n; MIRRORED_REPEAT (n - 1) - mirror((i mod 2n) - n), mirror(a) = a >= 0 ? a : -(1 + a), which is m = i mod 2n folded at n;
+//   CLAMP_TO_EDGE clamp(i, 0, n - 1)
+__device__ __forceinline__ int32_t address_coord(int32_t c, int32_t n, uint32_t mode) {
+    if (mode == 2u) return c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
+    if (mode == 1u) { const int32_t m = wrap_coord(c, 2 * n); return m < n ? m : 2 * n - 1 - m; }
+    return wrap_coord(c, n);
+}
+// adds weight * texel to the accumulator: the texel stays packed until here, so that the four corners of a tap are four registers, not sixteen
+__device__ __forceinline__ void accumulate_texel(f4& acc, uint32_t p, float weight, bool srgb) {
+    const f4 c = unpack_rgba8(p, srgb);
+    acc.x += c.x * weight; acc.y += c.y * weight; acc.z += c.z * weight; acc.w += c.w * weight;
+}
+// A texture under a sampler state `st` = address_u | address_v << 2 | mag_filter << 4 | min_filter << 5 | mip_mode << 6 that is not all zero.
+// lambda is the level of detail sample_texture computes, before clamping: the mag filter where lambda <= 0 (also a zero footprint and NaN, which
+// sample_trilinear treats as magnification too), the min filter where lambda > 0.  Levels: MIP_LINEAR as sample_trilinear; MIP_NEAREST the level
+// ceil(lambda + 1/2) - 1 clamped to [0, levels - 1]; MIP_BASE, or no chain: level 0.  max_aniso > 1 (record_draw sets it only for LINEAR
+// minification with MIP_LINEAR): the taps of sample_texture's anisotropic filter, each through this state, lambda being the filter's own.
+// NEAREST reads the one texel at floor(u w), floor(v h), LINEAR the four around u w - 1/2, v h - 1/2, each coordinate through its address mode.
+// (The +1 neighbour is formed as a float: a coordinate beyond the int32 range saturates in the conversion instead of overflowing, and every
+// mode brings whatever comes out into [0, n).)
+// The result is ONE weighted sum over every texel read -- weight = level weight x column weight x row weight, the sum over N -- in loops that are not
+// unrolled (taps, levels), not the nested lerps of sample_level: the fragment programs sit at their register ceiling, and this form keeps an
+// accumulator and four packed texels live where the other keeps sixteen floats per level.  The two forms differ by roundings of 2^-24.
+__device__ __forceinline__ f4 sample_texture_state(const uint32_t* texels, uint32_t w, uint32_t h, uint32_t levels, float u, float v, const UvGrad& g, bool srgb,
+                                                   uint32_t st, uint32_t max_aniso) {
+    const uint32_t au = st & 3u, av = (st >> 2) & 3u, mip = st >> 6;
+    float lam, nf = 1.0f;
+    bool major_x = false;
+    {
+        const float ax = g.dudx * (float)w, bx = g.dvdx * (float)h, ay = g.dudy * (float)w, by = g.dvdy * (float)h;
+        const float rx = ax * ax + bx * bx, ry = ay * ay + by * by;
+        lam = 0.5f * __builtin_amdgcn_logf(rx > ry ? rx : ry);
+        if (max_aniso > 1u) {                                        // (sample_texture's arithmetic: N has to be the oracle's integer)
+            major_x = rx > ry;
+            const float pmax = __builtin_sqrtf(major_x ? rx : ry), pmin = __builtin_sqrtf(major_x ? ry : rx);
+            nf = __builtin_ceilf(pmax / pmin);
+            if (!(nf <= (float)max_aniso)) nf = (float)max_aniso;
+            if (!(nf >= 1.0f)) nf = 1.0f;
+            lam = __builtin_amdgcn_logf(pmax / nf);
+        }
+    }
+    const bool nearest = ((st >> (lam > 0.0f ? 5 : 4)) & 1u) != 0u;
+    // the first level and the weight of the one behind it (0: that level is not read -- with a weight of exactly 0 it would add exactly nothing)
+    float f = 0.0f;
+    uint32_t l0 = 0u;
+    if (levels > 1u && mip != 2u) {
+        const float top = (float)(levels - 1u);
+        if (mip == 1u) {
+            float d = __builtin_ceilf(lam + 0.5f) - 1.0f;
+            if (!(d > 0.0f)) d = 0.0f;
+            if (d > top) d = top;
+            l0 = (uint32_t)d;
+        } else {
+            if (!(lam > 0.0f)) lam = 0.0f;
+            if (lam > top) lam = top;
+            const float l0f = floorf(lam);
+            f = lam - l0f; l0 = (uint32_t)l0f;             // (lam <= top: f > 0 only where level l0 + 1 exists)
+        }
+    }
+    f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (float fi = 1.0f; fi <= nf; fi += 1.0f) {
+        float tu = u, tv = v;
+        if (max_aniso > 1u) {
+            const float ti = fi / (nf + 1.0f) - 0.5f;
+            tu = u + (major_x ? g.dudx : g.dudy) * ti; tv = v + (major_x ? g.dvdx : g.dvdy) * ti;
+        }
+#pragma unroll 1
+        for (uint32_t k = 0; k < (f > 0.0f ? 2u : 1u); k++) {
+            uint32_t off = 0u, lw = w, lh = h;              // the level's first texel (a chain of a 16384 x 16384 texture is under 2^29 texels) and its extent
+#pragma unroll 1
+            for (uint32_t l = 0; l < l0 + k; l++) { off += lw * lh; lw = lw > 1u ? lw >> 1 : 1u; lh = lh > 1u ? lh >> 1 : 1u; }
+            const float wl = k == 0u ? 1.0f - f : f;
+            if (nearest) {
+                const int32_t x = address_coord((int32_t)floorf(tu * (float)lw), (int32_t)lw, au), y = address_coord((int32_t)floorf(tv * (float)lh), (int32_t)lh, av);
+                accumulate_texel(acc, texels[off + (uint32_t)y * lw + (uint32_t)x], wl, srgb);
+            } else {
+                const float fx = tu * (float)lw - 0.5f, fy = tv * (float)lh - 0.5f;
+                const float x0f = floorf(fx), y0f = floorf(fy);
+                const uint32_t x0 = (uint32_t)address_coord((int32_t)x0f, (int32_t)lw, au), x1 = (uint32_t)address_coord((int32_t)(x0f + 1.0f), (int32_t)lw, au);
+                const uint32_t r0 = off + (uint32_t)address_coord((int32_t)y0f, (int32_t)lh, av) * lw, r1 = off + (uint32_t)address_coord((int32_t)(y0f + 1.0f), (int32_t)lh, av) * lw;
+                const uint32_t p00 = texels[r0 + x0], p10 = texels[r0 + x1], p01 = texels[r1 + x0], p11 = texels[r1 + x1];
+                const float ax = fx - x0f, ay = fy - y0f;
+                const float wt = wl * (1.0f - ay), wb = wl * ay;
+                accumulate_texel(acc, p00, wt * (1.0f - ax), srgb);
+                accumulate_texel(acc, p10, wt * ax, srgb);
+                accumulate_texel(acc, p01, wb * (1.0f - ax), srgb);
+                accumulate_texel(acc, p11, wb * ax, srgb);
+            }
+        }
+    }
+    if (max_aniso > 1u) { const float inv_n = 1.0f / nf; acc.x *= inv_n; acc.y *= inv_n; acc.z *= inv_n; acc.w *= inv_n; }
+    return acc;
+}
+// Texture slot `slot` of the draw at (u, v).  The default sampler (the reference never creates one -- sampler.rs is a stub -- so REPEAT addressing and
+// LINEAR filters are what a texture has until mirhi_image_set_sampler says otherwise).  Without a mip chain: bilinear.  With a chain
 // (mirhi_image_generate_mips): trilinear, LOD = log2 of the longer screen-space footprint axis in texels,
 // lambda = 0.5 * log2(max(|d(uv*size)/dx|^2, |d(uv*size)/dy|^2)) clamped to [0, levels - 1].
 // With a chain and max_anisotropy > 1 (mirhi_image_set_max_anisotropy; device.rs:161-165 enables the feature): the Vulkan
 // specification's example filter -- N = min(ceil(Pmax / Pmin), max_anisotropy) trilinear taps along the longer footprint axis at
 // lambda = log2(Pmax / N), averaged (oracle sample_texture).  N has to be the oracle's integer, so the square roots and the
 // quotient that decide it are the compiler's IEEE expansions (the path is taken by whole draws, rarely: instructions do not matter).
-template <bool MIPS>
+// A slot with sampler state (any bit of its share of tex_sampler / tex_aniso's mip modes; only the full-featured variant sees such draws) leaves
+// through sample_texture_state on one scalar branch; every other slot runs the sequence below unchanged.
+// STATE false: the caller's draws never carry sampler state on the slot it reads (pbr_base_alpha, slot 0: classify_scope keeps such draws out of the
+// masked raster variants).
+template <bool MIPS, bool STATE = MIPS>
 __device__ __forceinline__ f4 sample_texture(DrawRef D, int slot, float u, float v, const UvGrad& g) {
     const uint32_t w = D.tex_w[slot], h = D.tex_h[slot], levels = D.tex_levels[slot];
     const uint32_t* texels = reinterpret_cast<const uint32_t*>(D.tex[slot]);
     if (!texels || w == 0 || h == 0) return {1.0f, 1.0f, 1.0f, 1.0f};
     const bool srgb = MIPS && ((D.tex_srgb >> slot) & 1u);      // (sRGB and mip-mapped textures live in the full-featured variant)
+    if constexpr (STATE) {
+        const uint32_t st = ((D.tex_sampler >> (6 * slot)) & 63u) | (((D.tex_aniso >> (TEX_MIP_MODE_SHIFT + 2 * slot)) & 3u) << 6);      // wave-uniform
+        if (st != 0u) return sample_texture_state(texels, w, h, levels, u, v, g, srgb, st, ((D.tex_aniso >> (4 * slot)) & 15u) + 1u);
+    }
     if (!MIPS || levels <= 1u) return sample_level(texels, w, h, u, v, srgb);
     const float ax = g.dudx * (float)w, bx = g.dvdx * (float)h, ay = g.dudy * (float)w, by = g.dvdy * (float)h;
     const float rx = ax * ax + bx * bx, ry = ay * ay + by * by;
@@ -251,7 +358,8 @@ __device__ __forceinline__ f3 pbr_direct(f3 N, f3 V, f3 L, f3 radiance, const Pb
 }
 
 // alpha the Cook-Torrance program compares with alphaCutoff (pixel/model_pbr.hlsl:166-179) at one pixel of a draw with a base colour
-// texture: the same barycentrics, (u, v), footprint and lookup as shade_model_program / shade_pbr, so the same bits
+// texture: the same barycentrics, (u, v), footprint and lookup as shade_model_program / shade_pbr, so the same bits (default sampler only: a scope
+// with a draw under another sampler is resolved by the ordered kernel, classify_scope)
 __device__ __forceinline__ float pbr_base_alpha(DrawRef D, const f4 c[3], const float uvk[3][2], float pxc, float pyc) {
     float b[3];
     barycentrics<false>(D, c, pxc, pyc, b);
@@ -268,7 +376,7 @@ __device__ __forceinline__ float pbr_base_alpha(DrawRef D, const f4 c[3], const 
         grad.dudy = ((by[0] * uvk[0][0] + by[1] * uvk[1][0]) + by[2] * uvk[2][0]) - u;
         grad.dvdy = ((by[0] * uvk[0][1] + by[1] * uvk[1][1]) + by[2] * uvk[2][1]) - v;
     }
-    return sample_texture<true>(D, 0, u, v, grad).w * ldcf(cb(D.material), 12);
+    return sample_texture<true, false>(D, 0, u, v, grad).w * ldcf(cb(D.material), 12);
 }
 // true if the draw's fragments have to be alpha-tested one by one: MODEL_PBR with a base colour texture whose texel alpha (in [0, 1]
 // times baseColorFactor.a) can fall on both sides of alphaCutoff -- the decision geometry_body takes per draw otherwise

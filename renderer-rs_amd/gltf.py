@@ -10,6 +10,9 @@
   image index behind its baseColor / metallicRoughness / normal / occlusion / emissive texture plus alphaMode / cutoff /
   doubleSided -- what model_full.hlsl / model_pbr.hlsl bind at t0..t4.  An image whose file is absent (the dancer asset
   names three and ships one) becomes None and is listed in `Model.missing_images`.
+* samplers (with images=True): `textures[i].sampler` -> `samplers[]`, per texture slot of a material as a `Sampler` in the values of
+  include/mirhi.h's mirhi_sampler_desc (wrapS / wrapT -> address modes, magFilter / minFilter -> filters and mip mode).  An absent
+  sampler or an absent filter keeps the default (REPEAT / LINEAR / MIP_LINEAR); a code glTF does not define is a ResourceError.
 
 This is SURVEY.md section 8f rank 1 (the caller side of the hot path): it feeds `interleave()` ->
 `Vertex` 48 B streams (crates/rhi/src/vertex.rs:88-170) that the rasterizer consumes.
@@ -32,6 +35,37 @@ class ResourceError(RuntimeError):
     """crates/resources/src/error.rs:6-40"""
 
 
+@dataclass(frozen=True)
+class Sampler:
+    """A glTF sampler in the values of mirhi_sampler_desc (scenes.Texture carries the same five fields): address modes 0 REPEAT, 1 MIRRORED_REPEAT,
+    2 CLAMP_TO_EDGE; filters 0 LINEAR, 1 NEAREST; mip_mode 0 MIP_LINEAR, 1 MIP_NEAREST, 2 MIP_BASE."""
+    address_u: int = 0
+    address_v: int = 0
+    mag_filter: int = 0
+    min_filter: int = 0
+    mip_mode: int = 0
+
+
+_WRAP = {10497: 0, 33648: 1, 33071: 2}                  # REPEAT, MIRRORED_REPEAT, CLAMP_TO_EDGE
+_MAG = {9729: 0, 9728: 1}                               # LINEAR, NEAREST
+# minFilter -> (min_filter, mip_mode): NEAREST / LINEAR look at level 0 only (MIP_BASE); X_MIPMAP_Y filters X within a level and Y between levels
+_MIN = {9728: (1, 2), 9729: (0, 2), 9984: (1, 1), 9985: (0, 1), 9986: (1, 0), 9987: (0, 0)}
+
+
+def _sampler(doc, index) -> Sampler:
+    """samplers[index] -> Sampler; absent properties keep the default, an undefined code is refused"""
+    s = doc["samplers"][index]
+
+    def code(table, key, default):
+        if key not in s:
+            return default
+        if s[key] not in table:
+            raise ResourceError(f"Unknown sampler {key} {s[key]!r} in samplers[{index}]")
+        return table[s[key]]
+    min_filter, mip_mode = code(_MIN, "minFilter", (0, 0))
+    return Sampler(code(_WRAP, "wrapS", 0), code(_WRAP, "wrapT", 0), code(_MAG, "magFilter", 0), min_filter, mip_mode)
+
+
 @dataclass
 class Material:   # crates/resources/src/material.rs:6-30
     base_color: tuple = (1.0, 1.0, 1.0, 1.0)
@@ -45,6 +79,12 @@ class Material:   # crates/resources/src/material.rs:6-30
     normal_image: Optional[int] = None
     occlusion_image: Optional[int] = None
     emissive_image: Optional[int] = None
+    # ... and the sampler of each slot's texture (textures[].sampler); the default where the texture names none.  Filled with the images.
+    base_color_sampler: Sampler = Sampler()
+    metallic_roughness_sampler: Sampler = Sampler()
+    normal_sampler: Sampler = Sampler()
+    occlusion_sampler: Sampler = Sampler()
+    emissive_sampler: Sampler = Sampler()
     normal_scale: float = 1.0
     occlusion_strength: float = 1.0
     alpha_mode: str = "OPAQUE"
@@ -139,6 +179,14 @@ def _texture_image(doc, info) -> Optional[int]:
     return tex.get("source")
 
 
+def _texture_sampler(doc, info) -> Sampler:
+    """textureInfo -> the Sampler behind textures[].sampler"""
+    if not info or "index" not in info:
+        return Sampler()
+    tex = doc.get("textures", [])[info["index"]]
+    return _sampler(doc, tex["sampler"]) if "sampler" in tex else Sampler()
+
+
 def load(path: str, images: bool = False) -> Model:
     """Every failure -- missing file, malformed JSON, an index or accessor that points outside its array or buffer -- is a
     ResourceError, like `gltf::import(path)?` in the reference (model.rs:113-120)."""
@@ -177,6 +225,11 @@ def _load(path: str, images: bool) -> Model:
             mat.normal_image = _texture_image(doc, m.get("normalTexture"))
             mat.occlusion_image = _texture_image(doc, m.get("occlusionTexture"))
             mat.emissive_image = _texture_image(doc, m.get("emissiveTexture"))
+            mat.base_color_sampler = _texture_sampler(doc, pbr.get("baseColorTexture"))
+            mat.metallic_roughness_sampler = _texture_sampler(doc, pbr.get("metallicRoughnessTexture"))
+            mat.normal_sampler = _texture_sampler(doc, m.get("normalTexture"))
+            mat.occlusion_sampler = _texture_sampler(doc, m.get("occlusionTexture"))
+            mat.emissive_sampler = _texture_sampler(doc, m.get("emissiveTexture"))
             mat.normal_scale = float((m.get("normalTexture") or {}).get("scale", 1.0))
             mat.occlusion_strength = float((m.get("occlusionTexture") or {}).get("strength", 1.0))
             mat.alpha_mode = m.get("alphaMode", "OPAQUE")

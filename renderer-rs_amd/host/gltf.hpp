@@ -3,7 +3,7 @@
 // (model.rs:135-144).  Images: the reference lets gltf::import decode them and discards the result (model.rs:120), and so
 // does load(path); load(path, ImagePolicy::Decode) keeps them -- every images[i] (file URI, data: URI, bufferView) goes
 // through image_decode.hpp to RGBA8 and each material records the image behind its five texture slots
-// (model_pbr.hlsl:62-95, t0..t4).  A file that is absent becomes an empty optional and is listed in missing_images.
+// (model_pbr.hlsl:62-95, t0..t4) and the sampler of each slot's texture (MaterialTextures).  A file that is absent becomes an empty optional and is listed in missing_images.
 // Header-only, no dependency: the JSON reader below covers the subset glTF uses (objects, arrays, strings, numbers,
 // true/false/null).
 // the caller side of the hot path -- its output feeds Mesh::interleave() -> `Vertex` streams.
@@ -115,6 +115,10 @@ enum class ImagePolicy { Discard, Decode };
 // what a glTF material says about textures and alpha, next to the reference's `Material` (factors only, material.rs:6-30)
 struct MaterialTextures {
     std::optional<size_t> base_color, metallic_roughness, normal, occlusion, emissive;   // indices into Model::images
+    // the sampler behind each slot's texture (textures[].sampler -> samplers[]): wrapS / wrapT 10497 / 33648 / 33071 -> address modes, magFilter
+    // 9728 / 9729, minFilter 9728 / 9729 (level 0 only: MIP_BASE) / 9984..9987 (X_MIPMAP_Y: X within a level, Y between levels).  An absent sampler or
+    // filter keeps the default; a code glTF does not define is a ResourceError.
+    SamplerDesc base_color_sampler, metallic_roughness_sampler, normal_sampler, occlusion_sampler, emissive_sampler;
     float normal_scale = 1.0f, occlusion_strength = 1.0f, alpha_cutoff = 0.5f;
     std::string alpha_mode = "OPAQUE";
     bool double_sided = false;
@@ -180,10 +184,42 @@ private:
                     if (!tex.has("source")) return std::nullopt;
                     return (size_t)tex.at("source").num;
                 };
+                auto sampler = [&](const json::Value& owner, const char* key) -> SamplerDesc {
+                    SamplerDesc out;
+                    if (!owner.has(key) || !owner.at(key).has("index") || !doc.has("textures")) return out;
+                    const json::Value& tex = doc.at("textures").at((size_t)owner.at(key).at("index").num);
+                    if (!tex.has("sampler")) return out;
+                    const size_t si = (size_t)tex.at("sampler").num;
+                    const json::Value& sv = doc.at("samplers").at(si);
+                    auto refuse = [&](const char* what, long code) -> int32_t {
+                        throw ResourceError("Unknown sampler " + std::string(what) + " " + std::to_string(code) + " in samplers[" + std::to_string(si) + "]");
+                    };
+                    auto wrap = [&](const char* what) -> int32_t {
+                        if (!sv.has(what)) return MIRHI_ADDRESS_REPEAT;
+                        const long code = (long)sv.at(what).num;
+                        return code == 10497 ? MIRHI_ADDRESS_REPEAT : code == 33648 ? MIRHI_ADDRESS_MIRRORED_REPEAT : code == 33071 ? MIRHI_ADDRESS_CLAMP_TO_EDGE : refuse(what, code);
+                    };
+                    out.address_u = wrap("wrapS"); out.address_v = wrap("wrapT");
+                    if (sv.has("magFilter")) {
+                        const long code = (long)sv.at("magFilter").num;
+                        out.mag_filter = code == 9729 ? MIRHI_SAMPLER_FILTER_LINEAR : code == 9728 ? MIRHI_SAMPLER_FILTER_NEAREST : refuse("magFilter", code);
+                    }
+                    if (sv.has("minFilter")) {
+                        const long code = (long)sv.at("minFilter").num;
+                        if (code != 9728 && code != 9729 && (code < 9984 || code > 9987)) refuse("minFilter", code);
+                        const bool base = code < 9984;
+                        out.min_filter = (base ? code == 9728 : ((code - 9984) & 1) == 0) ? MIRHI_SAMPLER_FILTER_NEAREST : MIRHI_SAMPLER_FILTER_LINEAR;
+                        out.mip_mode = base ? MIRHI_MIP_BASE : (code - 9984 >= 2 ? MIRHI_MIP_LINEAR : MIRHI_MIP_NEAREST);
+                    }
+                    return out;
+                };
                 if (m.has("pbrMetallicRoughness")) {
                     t.base_color = source(m.at("pbrMetallicRoughness"), "baseColorTexture");
                     t.metallic_roughness = source(m.at("pbrMetallicRoughness"), "metallicRoughnessTexture");
+                    t.base_color_sampler = sampler(m.at("pbrMetallicRoughness"), "baseColorTexture");
+                    t.metallic_roughness_sampler = sampler(m.at("pbrMetallicRoughness"), "metallicRoughnessTexture");
                 }
+                t.normal_sampler = sampler(m, "normalTexture"); t.occlusion_sampler = sampler(m, "occlusionTexture"); t.emissive_sampler = sampler(m, "emissiveTexture");
                 t.normal = source(m, "normalTexture"); t.occlusion = source(m, "occlusionTexture"); t.emissive = source(m, "emissiveTexture");
                 if (m.has("normalTexture")) t.normal_scale = (float)m.at("normalTexture").get("scale", 1.0);
                 if (m.has("occlusionTexture")) t.occlusion_strength = (float)m.at("occlusionTexture").get("strength", 1.0);

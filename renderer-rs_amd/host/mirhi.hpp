@@ -246,6 +246,18 @@ private:
 
 enum class Format { Undefined = 0, B8G8R8A8_SRGB, R32G32B32A32_SFLOAT, D32_SFLOAT, R8G8B8A8_UNORM, R32_UINT, R8G8B8A8_SRGB };
 
+// mirhi_sampler_desc with its enums' names: default-constructed it is the default sampler (all zero), REPEAT / LINEAR / MIP_LINEAR
+enum class AddressMode : int32_t { Repeat = MIRHI_ADDRESS_REPEAT, MirroredRepeat = MIRHI_ADDRESS_MIRRORED_REPEAT, ClampToEdge = MIRHI_ADDRESS_CLAMP_TO_EDGE };
+enum class SamplerFilter : int32_t { Linear = MIRHI_SAMPLER_FILTER_LINEAR, Nearest = MIRHI_SAMPLER_FILTER_NEAREST };
+enum class MipMode : int32_t { Linear = MIRHI_MIP_LINEAR, Nearest = MIRHI_MIP_NEAREST, Base = MIRHI_MIP_BASE };
+struct SamplerDesc : mirhi_sampler_desc {
+    SamplerDesc() : mirhi_sampler_desc{0, 0, 0, 0, 0} {}      // inline (what the C ABI's default-desc call fills in; test_host.cpp pins the two): host/gltf.hpp links without libmirhi
+    SamplerDesc(AddressMode u, AddressMode v, SamplerFilter mag = SamplerFilter::Linear, SamplerFilter min = SamplerFilter::Linear, MipMode mip = MipMode::Linear)
+        : mirhi_sampler_desc{(int32_t)u, (int32_t)v, (int32_t)mag, (int32_t)min, (int32_t)mip} {}
+    bool operator==(const mirhi_sampler_desc& o) const {
+        return address_u == o.address_u && address_v == o.address_v && mag_filter == o.mag_filter && min_filter == o.min_filter && mip_mode == o.mip_mode;
+    }
+};
 class Image {
 public:
     Image(std::shared_ptr<Device> device, uint32_t w, uint32_t h, Format f) : device_(std::move(device)), w_(w), h_px_(h), f_(f) {
@@ -292,6 +304,9 @@ public:
     uint32_t mip_levels() const { return mirhi_image_mip_levels(h_); }
     void set_max_anisotropy(uint32_t n) { check(mirhi_image_set_max_anisotropy(h_, n)); }          // sampler state (device.rs:161-165)
     uint32_t max_anisotropy() const { return mirhi_image_max_anisotropy(h_); }
+    // the rest of the sampler state (include/mirhi.h mirhi_image_set_sampler): address modes, mag / min filters, mip mode; for draws recorded afterwards
+    void set_sampler(const SamplerDesc& s) { check(mirhi_image_set_sampler(h_, &s)); }
+    SamplerDesc sampler() const { SamplerDesc s; check(mirhi_image_sampler(h_, &s)); return s; }
 private:
     Image(std::shared_ptr<Device> device, mirhi_image* raw, uint32_t w, uint32_t h, Format f) : device_(std::move(device)), h_(raw), w_(w), h_px_(h), f_(f) {}
     std::shared_ptr<Device> device_;

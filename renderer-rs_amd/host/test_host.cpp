@@ -4,7 +4,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
+#include <string>
 #include <vector>
+#include <unistd.h>
 
 #include "mirhi.hpp"
 #include "gltf.hpp"
@@ -73,6 +76,11 @@ static void cpu_tests() {
     CHECK(ri.color_load_op == MIRHI_LOAD_OP_CLEAR && ri.color_store_op == MIRHI_STORE_OP_STORE && ri.clear_color[3] == 1.0f && ri.clear_color[0] == 0.0f);
     CHECK(ri.depth_load_op == MIRHI_LOAD_OP_CLEAR && ri.depth_store_op == MIRHI_STORE_OP_DONT_CARE && ri.clear_depth == 1.0f);
     CHECK(MAX_FRAMES_IN_FLIGHT == 2 && DEFAULT_DEPTH_FORMAT == Format::D32_SFLOAT);
+    // sampler state (include/mirhi.h mirhi_image_set_sampler): the default desc is all zero = REPEAT / LINEAR / MIP_LINEAR, and the mirror names the C values
+    mirhi_sampler_desc sd = {9, 9, 9, 9, 9}; mirhi_sampler_desc_default(&sd);
+    CHECK(SamplerDesc() == sd && sd.address_u == MIRHI_ADDRESS_REPEAT && sd.mag_filter == MIRHI_SAMPLER_FILTER_LINEAR && sd.mip_mode == MIRHI_MIP_LINEAR);
+    const SamplerDesc cm(AddressMode::ClampToEdge, AddressMode::MirroredRepeat, SamplerFilter::Nearest, SamplerFilter::Linear, MipMode::Base);
+    CHECK(cm.address_u == 2 && cm.address_v == 1 && cm.mag_filter == 1 && cm.min_filter == 0 && cm.mip_mode == 2 && !(cm == sd));
     // model.rs defaults through the interleave helper
     Mesh mesh; mesh.positions = {{0, 0, 0}, {1, 0, 0}};
     auto vs = mesh.interleave();
@@ -103,6 +111,48 @@ static void cpu_tests() {
         CHECK(sum[3] == 255ull * 1024 * 1024 && sum[2] > sum[0] && sum[2] > sum[1]);   // opaque, and blue-dominant like any tangent-space normal map
         CHECK(mt.material_textures.size() == 1 && *mt.material_textures[0].normal == 2 && *mt.material_textures[0].base_color == 0 &&
               *mt.material_textures[0].metallic_roughness == 1 && !mt.material_textures[0].occlusion && mt.material_textures[0].double_sided);
+        // its one sampler (9729 / 9987 / 10497 / 10497) is the default sampler
+        CHECK(mt.material_textures[0].normal_sampler == SamplerDesc() && mt.material_textures[0].base_color_sampler == SamplerDesc());
+    }
+    // glTF samplers (host/gltf.hpp): every wrap code, both mag filters, the six min filters (9728 / 9729 look at level 0 only; 9984 + k: bit 0 of k is
+    // the filter within a level, bit 1 the filter between levels), absent properties, an undefined code and an index outside the array
+    {
+        const std::string path = (std::filesystem::temp_directory_path() / ("mirhi_test_host_samplers_" + std::to_string((long)getpid()) + ".gltf")).string();
+        auto load = [&](const std::string& samplers, const std::string& sampler_of_texture_4) {
+            std::ofstream out(path, std::ios::binary);
+            out << "{\"asset\": {\"version\": \"2.0\"}, \"buffers\": [{\"byteLength\": 36, \"uri\": \"data:application/octet-stream;base64,AAAAAAAAAAAAAAAAAACAPwAAAAAAAAAAAAAAAAAAgD8AAAAA\"}],"
+                   " \"bufferViews\": [{\"buffer\": 0, \"byteLength\": 36}], \"accessors\": [{\"bufferView\": 0, \"componentType\": 5126, \"count\": 3, \"type\": \"VEC3\"}],"
+                   " \"meshes\": [{\"primitives\": [{\"attributes\": {\"POSITION\": 0}, \"material\": 0}]}],"
+                   " \"textures\": [{\"sampler\": 0}, {\"sampler\": 1}, {\"sampler\": 2}, {\"sampler\": 3}, {" << sampler_of_texture_4 << "}],"
+                   " \"materials\": [{\"pbrMetallicRoughness\": {\"baseColorTexture\": {\"index\": 0}, \"metallicRoughnessTexture\": {\"index\": 1}},"
+                   " \"normalTexture\": {\"index\": 2}, \"occlusionTexture\": {\"index\": 3}, \"emissiveTexture\": {\"index\": 4}}],"
+                   " \"samplers\": [" << samplers << "]}";
+            out.close();
+            return resources::Model::load(path, resources::ImagePolicy::Decode);
+        };
+        const std::string four = "{\"wrapS\": 33071, \"wrapT\": 33648, \"magFilter\": 9728, \"minFilter\": 9729}, {\"minFilter\": 9984},"
+                                 " {\"wrapS\": 10497, \"wrapT\": 33071, \"magFilter\": 9729, \"minFilter\": 9985}, {\"minFilter\": 9986}";
+        const resources::Model sm = load(four + ", {\"minFilter\": 9728}", "\"sampler\": 4");
+        const resources::MaterialTextures& st = sm.material_textures.at(0);
+        using A = AddressMode; using F = SamplerFilter; using M = MipMode;
+        CHECK(st.base_color_sampler == SamplerDesc(A::ClampToEdge, A::MirroredRepeat, F::Nearest, F::Linear, M::Base));
+        CHECK(st.metallic_roughness_sampler == SamplerDesc(A::Repeat, A::Repeat, F::Linear, F::Nearest, M::Nearest));
+        CHECK(st.normal_sampler == SamplerDesc(A::Repeat, A::ClampToEdge, F::Linear, F::Linear, M::Nearest));
+        CHECK(st.occlusion_sampler == SamplerDesc(A::Repeat, A::Repeat, F::Linear, F::Nearest, M::Linear));
+        CHECK(st.emissive_sampler == SamplerDesc(A::Repeat, A::Repeat, F::Linear, F::Nearest, M::Base));
+        CHECK(load(four + ", {\"minFilter\": 9987, \"magFilter\": 9729}", "\"sampler\": 4").material_textures.at(0).emissive_sampler == SamplerDesc());
+        CHECK(load(four + ", {}", "\"sampler\": 4").material_textures.at(0).emissive_sampler == SamplerDesc());
+        CHECK(load(four, "\"source\": 0").material_textures.at(0).emissive_sampler == SamplerDesc());      // a texture that names no sampler
+        CHECK(resources::Model::load(path).material_textures.empty());                                       // images discarded: nothing said about samplers
+        for (const char* bad : {"{\"wrapS\": 33069}", "{\"wrapT\": 0}", "{\"magFilter\": 9987}", "{\"minFilter\": 9988}", "{\"minFilter\": 9983}", "{\"minFilter\": \"LINEAR\"}"}) {
+            bool refused = false;
+            try { load(four + ", " + bad, "\"sampler\": 4"); } catch (const resources::ResourceError& e) { refused = std::strstr(e.what(), "Unknown sampler") != nullptr; }
+            CHECK(refused);
+        }
+        bool outside = false;
+        try { load(four, "\"sampler\": 4"); } catch (const resources::ResourceError&) { outside = true; }
+        CHECK(outside);
+        std::remove(path.c_str());
     }
     // no GPU -> NoSuitableGpu, never a fallback
     int32_t n = 0; mirhi_device_count(&n);

@@ -238,6 +238,13 @@ class Texture:
     mips: bool = False  # sampled trilinearly through a full mip chain (mirhi_image_generate_mips / mip_chain below)
     srgb: bool = False  # R8G8B8A8_SRGB: the RGB bytes are decoded to linear when sampled
     max_anisotropy: int = 1  # > 1 (at most 16, needs mips): anisotropic filtering (mirhi_image_set_max_anisotropy)
+    # the rest of the sampler state (mirhi_image_set_sampler; the values of mirhi_address_mode, mirhi_sampler_filter, mirhi_mip_mode): all zero =
+    # REPEAT / LINEAR / MIP_LINEAR, the only sampler the oracle has
+    address_u: int = 0
+    address_v: int = 0
+    mag_filter: int = 0
+    min_filter: int = 0
+    mip_mode: int = 0
 
     @property
     def width(self):
