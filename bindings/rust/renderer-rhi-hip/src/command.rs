@@ -33,6 +33,9 @@ impl<'a> RenderingInfo<'a> {
                depth: None, depth_load_op: LoadOp::Clear, depth_store_op: StoreOp::DontCare, clear_depth: 1.0,
                render_area: Rect2D { x: 0, y: 0, width: color.width(), height: color.height() } }
     }
+    /// rendering.rs:818-838: the scope loads, clears, draws and stores inside `area` only; no pixel outside is written.
+    pub fn with_render_area(mut self, area: Rect2D) -> Self { self.render_area = area; self }
+    pub fn with_offset(mut self, x: i32, y: i32) -> Self { self.render_area.x = x; self.render_area.y = y; self }
 }
 
 /// command.rs:52-106.  libmirhi keeps one workspace per command buffer; the pool only carries the device.

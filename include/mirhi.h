@@ -359,7 +359,13 @@ typedef struct {     /* RenderingConfig / ColorAttachment / DepthAttachment (ren
     int32_t      depth_load_op;      /* default CLEAR  :360 */
     int32_t      depth_store_op;     /* default DONT_CARE :361 */
     float        clear_depth;        /* default 1.0    :362-366 */
-    int32_t      render_area[4];     /* x, y, width, height; width==0 -> full extent (rendering.rs:713-726) */
+    int32_t      render_area[4];     /* x, y, width, height in pixels of the attachment; width <= 0 or height <= 0 -> full extent (rendering.rs:713-726,
+                                        with_render_area / with_offset :818-838).  A rectangle inside the attachment (x, y >= 0, x + width and y + height
+                                        within its extent; anything else: MIRHI_ERR_INVALID_HANDLE) -- in colour and in depth-only scopes, on images and
+                                        on layer views.  Load, clear and store ops apply inside it only and no pixel outside is written, colour, depth and
+                                        prim_id_image alike; fragments do not move: viewport and scissor stay in attachment coordinates, a draw gives
+                                        every pixel of the area the bits it gives in a full-extent scope whose scissor is cut to the area.  Only the
+                                        tiles the area touches are launched.  Refused ("unsupported:"): a partial area on a split device. */
     mirhi_image* prim_id_image;      /* optional R32_UINT: winning global primitive id (parity instrumentation) */
 } mirhi_rendering_info;
 void mirhi_rendering_info_default(mirhi_rendering_info* info);

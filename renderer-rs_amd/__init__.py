@@ -809,6 +809,26 @@ SHADOW_VERTEX_OFFSETS = (0,)                                         # vertex/sh
 VERTEX_STRIDE, VERTEX_OFFSETS = 48, (0, 12, 24, 32)                  # vertex.rs:130-170
 
 
+def rendering_info(color=None, clear_color=(0.0, 0.0, 0.0, 1.0), color_load_op=LoadOp.CLEAR, depth=None, clear_depth: float = 1.0,
+                   depth_load_op=LoadOp.CLEAR, depth_store_op=StoreOp.DONT_CARE, prim_id=None, render_area=None) -> RenderingInfo:
+    """The mirhi_rendering_info that CommandBuffer.begin_rendering records: the library's defaults, then the arguments.
+    render_area: None (the full extent) or (x, y, width, height).  Test plumbing: lets a test without a device see what the keyword fills in."""
+    info = RenderingInfo()
+    lib().mirhi_rendering_info_default(C.byref(info))
+    info.color_image = color.handle if color is not None else None
+    info.color_load_op = color_load_op
+    info.clear_color = (C.c_float * 4)(*clear_color)
+    if depth is not None:
+        info.depth_image = depth.handle
+    info.depth_load_op, info.depth_store_op, info.clear_depth = depth_load_op, depth_store_op, clear_depth
+    if prim_id is not None:
+        info.prim_id_image = prim_id.handle
+    if render_area is not None:
+        x, y, w, h = (int(v) for v in render_area)
+        info.render_area = (C.c_int32 * 4)(x, y, w, h)
+    return info
+
+
 class CommandBuffer:
     """rhi::CommandBuffer (crates/rhi/src/command.rs:297-628)."""
 
@@ -831,18 +851,11 @@ class CommandBuffer:
 
     def begin_rendering(self, color: Optional[Image], clear_color=(0.0, 0.0, 0.0, 1.0), color_load_op=LoadOp.CLEAR,
                         depth: Optional[Image] = None, clear_depth: float = 1.0, depth_load_op=LoadOp.CLEAR,
-                        depth_store_op=StoreOp.DONT_CARE, prim_id: Optional[Image] = None):
-        """color=None with a depth image: a depth-only scope (Program.SHADOW draws)."""
-        info = RenderingInfo()
-        lib().mirhi_rendering_info_default(C.byref(info))
-        info.color_image = color.handle if color is not None else None
-        info.color_load_op = color_load_op
-        info.clear_color = (C.c_float * 4)(*clear_color)
-        if depth is not None:
-            info.depth_image = depth.handle
-        info.depth_load_op, info.depth_store_op, info.clear_depth = depth_load_op, depth_store_op, clear_depth
-        if prim_id is not None:
-            info.prim_id_image = prim_id.handle
+                        depth_store_op=StoreOp.DONT_CARE, prim_id: Optional[Image] = None, render_area=None):
+        """color=None with a depth image: a depth-only scope (Program.SHADOW draws).
+        render_area=(x, y, width, height) in pixels of the attachment: the scope loads, clears, draws and stores inside that rectangle only
+        (include/mirhi.h, mirhi_rendering_info::render_area); None: the full extent."""
+        info = rendering_info(color, clear_color, color_load_op, depth, clear_depth, depth_load_op, depth_store_op, prim_id, render_area)
         check(lib().mirhi_cmd_begin_rendering(self.handle, C.byref(info)))
 
     def end_rendering(self):
@@ -1019,7 +1032,8 @@ class SceneResources:
     def __init__(self, device: Device, scene, color_format: int = Format.R32G32B32A32_SFLOAT, want_prim: bool = False,
                  want_depth: bool = False, color_image: Optional[Image] = None, wrap_buffers=None,
                  color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None,
-                 cascade_array: Optional[Image] = None, ibl_images: Optional[Sequence[Image]] = None, sky_image: Optional[Image] = None):
+                 cascade_array: Optional[Image] = None, ibl_images: Optional[Sequence[Image]] = None, sky_image: Optional[Image] = None,
+                 depth_image: Optional[Image] = None, prim_image: Optional[Image] = None, depth_load_op: int = LoadOp.CLEAR):
         """scene.shadow (scenes.ShadowSpec) adds a depth-only shadow scope ahead of the main scope: recorded into the same command
         buffer, or with shadow_cmd=True into a command buffer of its own (self.shadow_cmd; render() submits both, the shadow one first --
         put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames).
@@ -1030,15 +1044,20 @@ class SceneResources:
         arrays and uploaded (self.ibl_images, destroyed with the resources), or the existing three passed as ibl_images= (irradiance cube,
         prefiltered cube, BRDF LUT; shared between frames, the caller's to destroy).
         scene.sky (scenes.SkySpec): a Program.SKYBOX draw behind (or with first=True ahead of) the scene's draws; its environment cube is the spec's
-        image, one created here from its levels (self.sky_image, destroyed with the resources) or the existing one passed as sky_image=."""
+        image, one created here from its levels (self.sky_image, destroyed with the resources) or the existing one passed as sky_image=.
+        scene.render_area ((x, y, width, height) or None): the main scope's render area (include/mirhi.h, mirhi_rendering_info::render_area).
+        depth_image / prim_image / depth_load_op: test plumbing for the render-area tests -- existing attachments to render into, like color_image
+        (the caller's to destroy), and the main scope's depth load op, so that a scope can start from prefilled contents."""
         self.device, self.scene = device, scene
         self.color_load_op = color_load_op
         self.owns_color = color_image is None
         self.objs = []
         self.color = color_image or Image(device, scene.width, scene.height, color_format)
         self.color_format = self.color.format
-        self.prim = Image(device, scene.width, scene.height, Format.R32_UINT) if want_prim else None
-        self.depth = Image(device, scene.width, scene.height, Format.D32_SFLOAT) if want_depth else None
+        self.depth_load_op = depth_load_op
+        self.owns_prim, self.owns_depth = prim_image is None, depth_image is None
+        self.prim = prim_image or (Image(device, scene.width, scene.height, Format.R32_UINT) if want_prim else None)
+        self.depth = depth_image or (Image(device, scene.width, scene.height, Format.D32_SFLOAT) if want_depth else None)
         self.cmd = CommandBuffer(device)
         self.draw_state = []
         cache = {}
@@ -1193,7 +1212,8 @@ class SceneResources:
     @staticmethod
     def _record_depth_scope(cmd: "CommandBuffer", sh, target: Image, states):
         w, h = sh.size
-        cmd.begin_rendering(None, depth=target, clear_depth=sh.clear_depth, depth_load_op=sh.load_op, depth_store_op=StoreOp.STORE)
+        cmd.begin_rendering(None, depth=target, clear_depth=sh.clear_depth, depth_load_op=sh.load_op, depth_store_op=StoreOp.STORE,
+                            render_area=getattr(sh, "render_area", None))      # (sh: a ShadowSpec, or a CascadeSpec, which has no area)
         for st in states:
             d = st["draw"]
             cmd.set_viewport(*(d.viewport or (0.0, 0.0, float(w), float(h), 0.0, 1.0)))
@@ -1218,7 +1238,8 @@ class SceneResources:
         if (self.shadow is not None or self.cascades is not None) and self.shadow_cmd is None:
             self._record_shadow(cmd)
         cmd.begin_rendering(self.color, clear_color=s.clear_color, color_load_op=self.color_load_op, depth=self.depth, clear_depth=s.clear_depth,
-                            depth_store_op=StoreOp.STORE if self.depth else StoreOp.DONT_CARE, prim_id=self.prim)
+                            depth_load_op=self.depth_load_op, depth_store_op=StoreOp.STORE if self.depth else StoreOp.DONT_CARE, prim_id=self.prim,
+                            render_area=s.render_area)
         if self.sky is not None and self.sky.first:
             self._record_sky(cmd)
         for st in self.draw_state:
@@ -1289,7 +1310,7 @@ class SceneResources:
             self.sky_image.destroy()
         for o in self.objs:
             o.destroy()
-        for o in (self.prim, self.depth, self.color):
-            if o is not None:
+        for o, owned in ((self.prim, self.owns_prim), (self.depth, self.owns_depth), (self.color, True)):
+            if o is not None and owned:
                 o.destroy()
         self.objs = []

@@ -1593,6 +1593,30 @@ extern "C" mirhi_result mirhi_cmd_reset(mirhi_cmd* cmd) {
         if ((cmd)->state != CMD_RECORDING) return fail(MIRHI_ERR_DEVICE, "Vulkan error: command buffer is not in the recording state"); \
     } while (0)
 
+// A draw's scissor (inclusive corners) cut to the scope's render area: what a draw may cover lies inside the area, so the geometry kernel bins
+// nothing into a tile the scope does not launch.  A full-extent scope's scissor stays as the attachment's far edges left it.
+// The callers compute scissor_partial AFTER this cut: every draw of a partial-area scope is scissor-partial, so every triangle that crosses the area's
+// edge is a cut one and goes to the big list (correct -- the per-pixel box test is what keeps its fragments inside -- and the reason such scopes are
+// kept off the triangle-parallel variants by density: ScopePlan::density_tiles).
+static void clamp_to_render_area(const RecordedPass& pass, int64_t& sx0, int64_t& sy0, int64_t& sx1, int64_t& sy1) {
+    const int32_t* a = pass.area;
+    if (a[0] == 0 && a[1] == 0 && a[2] == (int32_t)pass.color_t.width && a[3] == (int32_t)pass.color_t.height) return;
+    sx0 = std::max<int64_t>(sx0, a[0]); sy0 = std::max<int64_t>(sy0, a[1]);
+    sx1 = std::min<int64_t>(sx1, (int64_t)a[0] + a[2] - 1); sy1 = std::min<int64_t>(sy1, (int64_t)a[1] + a[3] - 1);
+}
+// The scope's render area as RecordedPass::area keeps it -- the full extent spelled out -- or the refusal (mirhi_scope.h render_area: the rectangle must
+// lie inside the width x height attachment; a partial one is refused on a split device: the band exchange moves whole tile rows)
+static mirhi_result take_render_area(const mirhi_cmd* cmd, const mirhi_rendering_info* info, uint32_t width, uint32_t height, int32_t area[4]) {
+    const RenderArea a = render_area(width, height, info->render_area);
+    if (!a.valid) {
+        char msg[192];
+        render_area_message(msg, sizeof msg, info->render_area, width, height);
+        return fail(MIRHI_ERR_INVALID_HANDLE, "%s", msg);
+    }
+    if (a.partial && cmd->dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a partial render area on a split device");
+    area[0] = (int32_t)a.x; area[1] = (int32_t)a.y; area[2] = (int32_t)a.w; area[3] = (int32_t)a.h;
+    return MIRHI_OK;
+}
 extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_rendering_info* info) {
     REQUIRE_RECORDING(cmd); NULL_CHECK(info, "rendering_info");
     if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
@@ -1610,10 +1634,7 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
         p.depth_only = true;
         p.color_t = {nullptr, di->width, di->height, (uint32_t)MIRHI_FORMAT_UNDEFINED};
         p.depth_t = {di->ptr, di->width, di->height, (uint32_t)di->format};
-        if (info->render_area[2] <= 0 || info->render_area[3] <= 0) { p.area[0] = 0; p.area[1] = 0; p.area[2] = (int32_t)di->width; p.area[3] = (int32_t)di->height; }
-        else memcpy(p.area, info->render_area, sizeof p.area);
-        if (p.area[0] != 0 || p.area[1] != 0 || p.area[2] != (int32_t)di->width || p.area[3] != (int32_t)di->height)
-            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: render area must cover the whole depth attachment");
+        { mirhi_result ra = take_render_area(cmd, info, di->width, di->height, p.area); if (ra != MIRHI_OK) return ra; }
         cmd->passes.push_back(std::move(p));
         cmd->in_rendering = true;
         return MIRHI_OK;
@@ -1640,10 +1661,7 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
     p.color_t = {ci->ptr, ci->width, ci->height, (uint32_t)ci->format};
     if (info->depth_image) p.depth_t = {info->depth_image->ptr, info->depth_image->width, info->depth_image->height, (uint32_t)info->depth_image->format};
     if (info->prim_id_image) p.prim_t = {info->prim_id_image->ptr, info->prim_id_image->width, info->prim_id_image->height, (uint32_t)info->prim_id_image->format};
-    if (info->render_area[2] <= 0 || info->render_area[3] <= 0) { p.area[0] = 0; p.area[1] = 0; p.area[2] = (int32_t)ci->width; p.area[3] = (int32_t)ci->height; }
-    else memcpy(p.area, info->render_area, sizeof p.area);
-    if (p.area[0] != 0 || p.area[1] != 0 || p.area[2] != (int32_t)ci->width || p.area[3] != (int32_t)ci->height)
-        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: render area must cover the whole colour attachment");
+    { mirhi_result ra = take_render_area(cmd, info, ci->width, ci->height, p.area); if (ra != MIRHI_OK) return ra; }
     cmd->passes.push_back(std::move(p));
     cmd->in_rendering = true;
     return MIRHI_OK;
@@ -1846,6 +1864,7 @@ static mirhi_result record_sky_draw(mirhi_cmd* cmd, bool indexed, uint32_t count
     int64_t sx1 = sx0 + (int64_t)cmd->scissor.width - 1, sy1 = sy0 + (int64_t)cmd->scissor.height - 1;
     if (sx1 > (int64_t)ci.width - 1) sx1 = (int64_t)ci.width - 1;
     if (sy1 > (int64_t)ci.height - 1) sy1 = (int64_t)ci.height - 1;
+    clamp_to_render_area(cmd->passes.back(), sx0, sy0, sx1, sy1);
     if (sx0 > sx1 || sy0 > sy1) { visible = false; sx0 = sy0 = 0; sx1 = sy1 = -1; }
     k.scissor[0] = (int32_t)sx0; k.scissor[1] = (int32_t)sy0; k.scissor[2] = (int32_t)sx1; k.scissor[3] = (int32_t)sy1;
     k.visible = visible ? 1u : 0u;
@@ -2038,6 +2057,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     int64_t sx1 = sx0 + (int64_t)cmd->scissor.width - 1, sy1 = sy0 + (int64_t)cmd->scissor.height - 1;
     if (sx1 > (int64_t)ci.width - 1) sx1 = (int64_t)ci.width - 1;
     if (sy1 > (int64_t)ci.height - 1) sy1 = (int64_t)ci.height - 1;
+    clamp_to_render_area(cmd->passes.back(), sx0, sy0, sx1, sy1);
     d.sx0 = (int32_t)sx0; d.sy0 = (int32_t)sy0; d.sx1 = (int32_t)sx1; d.sy1 = (int32_t)sy1;
     d.scissor_partial = (sx0 > 0 || sy0 > 0 || sx1 < (int64_t)ci.width - 1 || sy1 < (int64_t)ci.height - 1) ? 1u : 0u;
     if (sx0 > sx1 || sy0 > sy1) return MIRHI_OK;    // empty scissor: nothing can be covered
@@ -2566,9 +2586,18 @@ static mirhi_result pblock_commit(Workspace& w, hipStream_t stream) {
 // 1. what a scope is and how it is rastered and binned (mirhi_scope.h), on its share of the tile rows
 struct ScopePlan {
     uint32_t tiles_x, tiles_y, r0, r1, rstep;      // r0 / r1 / rstep: PassParams::tile_row_begin / _end / _step
+    RenderArea area;                               // the scope's render area and the tiles it launches (mirhi_scope.h); a transfer has none
     size_t tris;                                   // the segment's own triangles
     ScopeClass cls; RasterMode mode; BinGeometry bins;
-    size_t tiles() const { return (size_t)tiles_x * (r1 - r0); }
+    size_t tiles() const { return (size_t)tiles_x * (r1 - r0); }      // the tiles bins, counters and page table are indexed by
+    // ... and the tiles the scope launches, which the mode and the bins' densities are judged by: fewer under a partial render area
+    size_t launched() const { return area.partial ? (size_t)area.tiles : tiles(); }
+    // ... and the tiles raster_mode judges the density by: the ATTACHMENT's when the area is partial, as for the full-extent scope with a scissor that
+    // such a scope replaces.  A scope's triangle count says nothing about how many of its triangles survive the cut to the area (C2's 10k triangles at
+    // 4K against a 512 x 512 area: 2 %), and every triangle that crosses the area's edge is cut by the scissor and sits in the big list, which the
+    // triangle-parallel variants stage slowly: judged by the launched tiles such a scope took 525-580 us where the sparse variant takes 58
+    // (DESIGN_NOTES.md "Render areas").  The bins' fixed pages are still sized by the launched tiles.
+    size_t density_tiles() const { return area.partial ? (size_t)tiles_x * tiles_y : tiles(); }
 };
 static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, const Workspace& w, const PlanKnobs& knobs) {
     ScopePlan s;
@@ -2577,10 +2606,17 @@ static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, c
     if (pass.depth_only) { s.r0 = 0; s.r1 = s.tiles_y; s.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
     // (a transfer is not split: every rank moves what its own memory holds; one "tile" for the workspace's sizes, the launch's workgroups are fill_params')
     if (pass.xfer.kind) { s.tiles_x = 1u; s.tiles_y = 1u; s.r0 = 0u; s.r1 = 1u; s.rstep = 1u; }
+    // The render area (validated by begin_rendering; never partial on a split device): its tile rows take the place of the band's -- bins, counters and
+    // the raster grid are indexed by the owned row already --, its tile columns are a sub-range of the launch alone.  One evaluation per scope.
+    s.area = RenderArea{};
+    if (!pass.xfer.kind) {
+        s.area = render_area(pass.color_t.width, pass.color_t.height, pass.area);
+        if (s.area.partial) { s.r0 = s.area.row_begin; s.r1 = s.area.row_end; s.rstep = 1; }
+    }
     s.tris = pass.total_tris - pass.first_tri;
     s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs, pass.sky.on != 0u, pass.xfer.kind != 0u);
-    s.mode = raster_mode(s.cls, s.tiles(), s.tris, w.spread, w.wide, knobs);
-    s.bins = bin_geometry(s.tiles(), s.tris, pass.total_tris, s.mode.xcd_bins, w.pool_scale, knobs);
+    s.mode = raster_mode(s.cls, s.density_tiles(), s.tris, w.spread, w.wide, knobs, s.area.partial);
+    s.bins = bin_geometry(s.launched(), s.tris, pass.total_tris, s.mode.xcd_bins, w.pool_scale, knobs, s.tiles());
     return s;
 }
 
@@ -2710,6 +2746,10 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
     memset(&P, 0, sizeof P);
     P.width = ci.width; P.height = ci.height;
     P.tiles_x = s.tiles_x; P.tiles_y = s.tiles_y; P.tile_row_begin = s.r0; P.tile_row_end = s.r1; P.tile_row_step = s.rstep;
+    // (a transfer has no area: its kernels read none of these words)
+    P.area_x0 = s.area.x; P.area_y0 = s.area.y; P.area_w = s.area.valid ? s.area.w : ci.width; P.area_h = s.area.valid ? s.area.h : ci.height;
+    P.area_partial = s.area.partial ? 1u : 0u;
+    P.tile_col_begin = s.area.partial ? s.area.col_begin : 0u; P.tile_cols = s.area.partial ? s.area.col_end - s.area.col_begin : s.tiles_x;
     P.num_draws = (uint32_t)pass.draws.size(); P.total_tris = pass.total_tris;
     set_raster_choice(P, s.cls, mode, pass.state, w.ordered, pass.first_tri, pass.total_tris);
     memcpy(P.clear_color, pass.info.clear_color, sizeof P.clear_color);
@@ -2792,6 +2832,8 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     size_t total_draws = 0, max_tiles = 0, total_regions = 0;
     for (const RecordedPass& pass : cmd->passes) {
         scopes.push_back(plan_scope(dev, pass, w, knobs));
+        // (begin_rendering refuses it; a device split after the recording is met here)
+        if (scopes.back().area.partial && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a partial render area on a split device");
         total_draws += pass.draws.size();
         total_regions += pass.xfer_regions.size();
         max_tiles = std::max(max_tiles, scopes.back().tiles());
@@ -2821,7 +2863,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         const ScopePlan& s = scopes[pi];
         VertexPlan& v = vertex[pi];
         // (the mode is evaluated again, not kept from step 1: hand_over_status in between may have changed w.spread / w.wide)
-        const RasterMode mode = raster_mode(s.cls, s.tiles(), s.tris, w.spread, w.wide, knobs);
+        const RasterMode mode = raster_mode(s.cls, s.density_tiles(), s.tris, w.spread, w.wide, knobs, s.area.partial);
         w.wide_eligible |= mode.wide_eligible;
         PassParams P = fill_params(cmd->passes[pi], s, mode, w, max_tiles, dev->frag_stats);
         P.draws = dev_draws + draws_done;
@@ -2908,6 +2950,21 @@ extern "C" int mirhi_debug_scope_plan(const uint32_t* in, uint32_t* out, char* n
     set_raster_choice(P, c, m, s, &some_recs, 0u, in[9]);
     const uint32_t choice[12] = {c.programs, in[13], P.pred, P.zflip, P.zmask, P.tp_max_area, P.raster_teams, P.raster_wide, P.alpha_scope, P.xcd_swizzle, P.ordered_recs ? 1u : 0u, 0u};
     return mirhi_debug_raster_choice(choice, name, name_len, out + 28);
+}
+// ... what render_area (mirhi_scope.h) decides for an attachment of in[0] x in[1] pixels and the area in[2 .. 5] (x, y, width, height as int32).  Returns 0 and
+// out: x, y, w, h, partial, col_begin, col_end, row_begin, row_end, edge_partial, tiles, index_tiles -- or -1 for an invalid area, with the message
+// begin_rendering refuses it with in `msg` (may be null).  No HIP call.
+extern "C" int mirhi_debug_render_area(const int32_t in[6], uint32_t out[12], char* msg, uint32_t msg_len) {
+    if (in[0] < 0 || in[1] < 0) return -2;
+    const RenderArea a = render_area((uint32_t)in[0], (uint32_t)in[1], in + 2);
+    if (!a.valid) {
+        if (msg && msg_len) render_area_message(msg, msg_len, in + 2, (uint32_t)in[0], (uint32_t)in[1]);
+        return -1;
+    }
+    const uint32_t words[12] = {a.x, a.y, a.w, a.h, a.partial, a.col_begin, a.col_end, a.row_begin, a.row_end, a.edge_partial, a.tiles, a.index_tiles};
+    memcpy(out, words, sizeof words);
+    if (msg && msg_len) msg[0] = 0;
+    return 0;
 }
 // ... and what mirhi_submit.h decides about a submit, a scope of it and the wide feedback (the words: submit_words there)
 extern "C" int mirhi_debug_submit_path(const uint32_t* in, uint32_t* out) { return submit_words(in, out); }
@@ -3191,7 +3248,8 @@ static mirhi_result issue_scope(Submit& s, mirhi_cmd* c, size_t pi, hipStream_t 
         // winners are counted from a primitive-id image: the scope's own if every pixel of it is written (no LOAD),
         // else the workspace's, cleared to NO_PRIM, through a copy of the parameters -- the raster kernels know nothing
         // of the statistics
-        if (P.prim_out && !P.color_load) winners = P.prim_out;
+        // (a partial render area leaves the pixels outside it as they were: not every pixel is written then either)
+        if (P.prim_out && !P.color_load && !P.area_partial) winners = P.prim_out;
         else {
             if ((r = stats_params_for(c)) != MIRHI_OK) return r;
             HIP_TRY(hipMemsetAsync(c->ws.stats_prim, 0xFF, (size_t)P.width * P.height * 4, stream));

@@ -268,6 +268,17 @@ struct PassParams {
     const XferRegion* xfer_regions;
     float    xfer_color[4];           // a clear's value (depth: [0])
     uint32_t xfer_groups, xfer_pad;   // work units of all regions together (XferRegion::first of a region behind the last)
+    // The render area (mirhi_rendering_info::render_area): pixels [area_x0, area_x0 + area_w) x [area_y0, area_y0 + area_h) of the
+    // attachments are the scope's -- loaded, cleared, resolved and stored; no kernel writes a pixel outside.  A full-extent scope: 0, 0, width, height,
+    // and its raster kernels (the AREA = false instantiations of raster_body) never read these words: behind everything else, so that every word in
+    // front of them sits where it sat before there were areas.
+    uint32_t area_x0, area_y0, area_w, area_h;
+    // The launch of a scope with a partial area: the tile grid stays the attachment's and every pixel coordinate absolute; the launch
+    // spans tile columns [tile_col_begin, tile_col_begin + tile_cols) of the rows tile_row_begin .. tile_row_end (tile_cols == 0: all tiles_x columns --
+    // parameters made without a plan).  Bins, counters and the page table keep tiles_x entries per owned row: a draw's scissor lies inside the area,
+    // so the columns outside stay empty and unvisited.
+    uint32_t tile_col_begin, tile_cols;
+    uint32_t area_partial, area_pad;  // 1: the area is smaller than the attachment
 };
 static_assert(sizeof(PassParams) % 8 == 0, "PassParams holds pointers");
 
@@ -283,11 +294,18 @@ struct GeometryHead {
 };
 struct RasterHead {
     uint32_t* bin_count; const BinRec* bin_pool; uint32_t* big_count;
-    uint32_t tiles_x, tile_row_begin, bin_cap, big_cap;
+    uint32_t tiles_x;
+    uint32_t tile_origin;             // PassParams::tile_row_begin | PassParams::tile_col_begin << 16 (both below 2^9: one word, the head stays 56 bytes --
+                                      // with the parameter pointer one 64-byte kernarg load): grid row k / column j is tile row (tile_origin & 0xFFFF) +
+                                      // k * tile_row_step / tile column (tile_origin >> 16) + j; the column origin is 0 unless the render area is partial
+    uint32_t bin_cap, big_cap;
     uint32_t sub_cap, count_stride;   // per-XCD bins (PassParams); read by the two-team variant only
     uint32_t fixed_recs;              // PassParams::fixed_recs
     uint32_t tile_row_step;           // PassParams::tile_row_step: grid row k is tile row tile_row_begin + k * tile_row_step
 };
+static_assert(sizeof(RasterHead) == 56, "RasterHead and the parameter pointer are one 64-byte kernarg load");
+// tile columns a scope's raster launch spans
+inline uint32_t launch_cols(const PassParams& P) { return P.tile_cols ? P.tile_cols : P.tiles_x; }
 
 // A batched launch: the independent rendering scopes of one mirhi_queue_submit (equal target shape, equal raster variant) share
 // one vertex, one geometry and one raster launch; their arguments travel by value in the kernarg segment.

@@ -112,6 +112,10 @@ struct RasterEntry { uint32_t id; const char* name; void (*kernel)(const PassPar
 #define IBL(K, T, S) {raster_kernel_id(RASTER_IBL, S, K, T, 1, 0, 4), "raster_kernel_ibl<" #K ", " #T ", " #S ">", raster_kernel_ibl<K, T, S>}
 #define WIDE(P, K, W) {raster_kernel_id(RASTER_WIDE, P, K, 1, 1, 0, W), "raster_kernel_wide<" #P ", " #K ", " #W ">", raster_kernel_wide<P, K, W>}
 #define PLAIN(P, K, T, TEAMS, M) {raster_kernel_id(RASTER_PLAIN, P, K, T, TEAMS, M, 4 * TEAMS), "raster_kernel<" #P ", " #K ", " #T ", " #TEAMS ", " #M ">", raster_kernel<P, K, T, TEAMS, M>}
+// ... and the AREA instantiations (a partial render area: RasterVariant::area), one team of four waves
+#define OWN_A(FAMILY, KERNEL, K, T) {raster_kernel_id(FAMILY, 0, K, T, 1, 0, 4, 1), #KERNEL "<" #K ", " #T ", true>", KERNEL<K, T, true>}
+#define IBL_A(K, T, S) {raster_kernel_id(RASTER_IBL, S, K, T, 1, 0, 4, 1), "raster_kernel_ibl<" #K ", " #T ", " #S ", true>", raster_kernel_ibl<K, T, S, true>}
+#define PLAIN_A(P, K, T, M) {raster_kernel_id(RASTER_PLAIN, P, K, T, 1, M, 4, 1), "raster_kernel<" #P ", " #K ", " #T ", 1, " #M ", true>", raster_kernel<P, K, T, 1, M, true>}
 static const RasterEntry k_raster_entries[] = {
     ORDERED(2), ORDERED(3), ORDERED(4), ORDERED(1),
     OWN(RASTER_DEPTH, raster_kernel_depth, 0, 1), OWN(RASTER_DEPTH, raster_kernel_depth, 1, 1), OWN(RASTER_DEPTH, raster_kernel_depth, 0, 0), OWN(RASTER_DEPTH, raster_kernel_depth, 1, 0),
@@ -129,6 +133,17 @@ static const RasterEntry k_raster_entries[] = {
     PLAIN(2, 1, 0, 1, false), PLAIN(4, 1, 0, 1, false), PLAIN(3, 1, 0, 1, false), PLAIN(1, 1, 0, 1, false),
     // MODEL_PBR_IBL scopes: per key, with and without the triangle-parallel path, per shadow term (none, single map, cascades)
     IBL(0, 1, 0), IBL(1, 1, 0), IBL(0, 0, 0), IBL(1, 0, 0), IBL(0, 1, 1), IBL(1, 1, 1), IBL(0, 0, 1), IBL(1, 0, 1), IBL(0, 1, 2), IBL(1, 1, 2), IBL(0, 0, 2), IBL(1, 0, 2),
+    // the AREA instantiations, in the order of the rows above
+    OWN_A(RASTER_DEPTH, raster_kernel_depth, 0, 1), OWN_A(RASTER_DEPTH, raster_kernel_depth, 1, 1), OWN_A(RASTER_DEPTH, raster_kernel_depth, 0, 0), OWN_A(RASTER_DEPTH, raster_kernel_depth, 1, 0),
+    OWN_A(RASTER_CSM, raster_kernel_csm, 0, 1), OWN_A(RASTER_CSM, raster_kernel_csm, 1, 1), OWN_A(RASTER_CSM, raster_kernel_csm, 0, 0), OWN_A(RASTER_CSM, raster_kernel_csm, 1, 0),
+    OWN_A(RASTER_SHADOW, raster_kernel_shadow, 0, 1), OWN_A(RASTER_SHADOW, raster_kernel_shadow, 1, 1), OWN_A(RASTER_SHADOW, raster_kernel_shadow, 0, 0), OWN_A(RASTER_SHADOW, raster_kernel_shadow, 1, 0),
+    PLAIN_A(2, 2, 0, false), PLAIN_A(4, 2, 0, false), PLAIN_A(3, 2, 0, false), PLAIN_A(1, 2, 0, false),
+    PLAIN_A(2, 0, 1, false), PLAIN_A(3, 0, 1, false), PLAIN_A(4, 0, 1, false), PLAIN_A(1, 0, 1, false),
+    PLAIN_A(2, 1, 1, false), PLAIN_A(3, 1, 1, false), PLAIN_A(4, 1, 1, false), PLAIN_A(1, 1, 1, false),
+    PLAIN_A(4, 0, 1, true), PLAIN_A(4, 1, 1, true),
+    PLAIN_A(2, 0, 0, false), PLAIN_A(4, 0, 0, false), PLAIN_A(3, 0, 0, false), PLAIN_A(1, 0, 0, false),
+    PLAIN_A(2, 1, 0, false), PLAIN_A(4, 1, 0, false), PLAIN_A(3, 1, 0, false), PLAIN_A(1, 1, 0, false),
+    IBL_A(0, 1, 0), IBL_A(1, 1, 0), IBL_A(0, 0, 0), IBL_A(1, 0, 0), IBL_A(0, 1, 1), IBL_A(1, 1, 1), IBL_A(0, 0, 1), IBL_A(1, 0, 1), IBL_A(0, 1, 2), IBL_A(1, 1, 2), IBL_A(0, 0, 2), IBL_A(1, 0, 2),
     // a SKYBOX segment (no key, no bins: one kernel)
     {raster_kernel_id(RASTER_SKY, 0, 0, 0, 1, 0, 4), "sky_kernel", sky_kernel},
     // a recorded transfer command (progs: PassParams::xfer)
@@ -138,6 +153,9 @@ static const RasterEntry k_raster_entries[] = {
     {raster_kernel_id(RASTER_TRANSFER, XFER_FILL, 0, 0, 1, 0, 4), "transfer_fill_kernel", transfer_fill_kernel},
 };
 #undef IBL
+#undef IBL_A
+#undef OWN_A
+#undef PLAIN_A
 #undef ORDERED
 #undef OWN
 #undef WIDE
@@ -213,7 +231,7 @@ hipError_t launch_raster_batch(const PassParams* const* Ps, const PassParams* co
 hipError_t launch_fragment_count(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, hipStream_t stream, LaunchTiming t) {
     const uint32_t rows = P.tile_row_end - P.tile_row_begin;
     if (rows == 0 || P.tiles_x == 0 || P.ordered_recs || P.depth_only || P.sky || P.xfer) return hipSuccess;
-    MIRHI_LAUNCH(fragment_count_kernel, dim3(P.tiles_x, rows), dim3(RASTER_THREADS), stream, t, dev_params, raster_head(P, big_count));
+    MIRHI_LAUNCH(fragment_count_kernel, dim3(launch_cols(P), rows), dim3(RASTER_THREADS), stream, t, dev_params, raster_head(P, big_count));
     return launch_result();
 }
 

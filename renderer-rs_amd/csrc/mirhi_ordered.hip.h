@@ -134,14 +134,16 @@ __global__ __launch_bounds__(ORDERED_THREADS, 2) void ordered_kernel(const PassP
     __shared__ uint32_t lds_state[6 * 4 * ORDERED_THREADS];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t q = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t tx = blockIdx.x, tyr = blockIdx.y, ty = H.tile_row_begin + tyr * H.tile_row_step, tile = tyr * H.tiles_x + tx;
+    // (grid column j is tile column tile_col_begin + j: a partial render area launches the columns it touches)
+    const uint32_t col_begin = H.tile_origin >> 16;
+    const uint32_t tx = blockIdx.x + col_begin, tyr = blockIdx.y, ty = (H.tile_origin & 0xFFFFu) + tyr * H.tile_row_step, tile = tyr * H.tiles_x + tx;
     const int32_t ix0 = (int32_t)((q & 1u) * 16u + (lane & 7u)), iy0 = (int32_t)((q >> 1) * 16u + (lane >> 3));
     const float fix0 = (float)ix0, fiy0 = (float)iy0;
     const uint32_t qbit0 = 1u << ((q >> 1) * 8u + (q & 1u) * 2u), qmask = qbit0 * 0x33u;
     const uint32_t px0 = tx * TILE + (uint32_t)ix0, py0 = ty * TILE + (uint32_t)iy0;
     const int32_t tpx0 = (int32_t)(tx * TILE), tpy0 = (int32_t)(ty * TILE);
     const uint32_t nbig_raw = *H.big_count;
-    if (tid == 0 && tile == 0) { *P.big_count_next = 0; P.status[1] = nbig_raw; }   // (bins are not used by an ordered segment)
+    if (tid == 0 && tile == col_begin) { *P.big_count_next = 0; P.status[1] = nbig_raw; }   // (bins are not used by an ordered segment)
 
     // The pixel state is set up when the first record of the segment reaches this tile.  A tile no record reaches has nothing
     // to do at all if the segment keeps the colour (and depth) written so far -- the usual case for translucent geometry over
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(ORDERED_THREADS, 2) void ordered_kernel(const PassP
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
-            const bool inb = px < P.width && py < P.height;
+            const bool inb = in_area(P, px, py);
             const size_t pix = (size_t)py * P.width + px;
             f4 c0 = {P.clear_color[0], P.clear_color[1], P.clear_color[2], P.clear_color[3]};
             if (P.color_load && inb) {
@@ -268,7 +270,7 @@ __global__ __launch_bounds__(ORDERED_THREADS, 2) void ordered_kernel(const PassP
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
-        if (!(px < P.width && py < P.height)) continue;
+        if (!in_area(P, px, py)) continue;
         const size_t pix = (size_t)py * P.width + px;
         const uint32_t pw = ORD_STATE(1u, b);
         const bool touched = pw != NO_PRIM;

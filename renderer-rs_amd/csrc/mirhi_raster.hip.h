@@ -490,6 +490,17 @@ __device__ __forceinline__ void raster_small_masked(DrawRef D, uint32_t prim, co
     }
 }
 
+// The pixel lies inside the scope's render area (PassParams::area_*): the one test that says whether a pixel is the scope's to load,
+// clear and store -- a full-extent scope's area is the attachment, so this is also the test against its ragged edge.  One unsigned compare per axis:
+// a coordinate in front of the origin wraps around to a large number.
+__device__ __forceinline__ bool in_area(ParamsRef P, uint32_t px, uint32_t py) { return px - P.area_x0 < P.area_w && py - P.area_y0 < P.area_h; }
+// ... as raster_body asks: its AREA = false instantiations -- every full-extent scope -- keep the test against the extent and never read the area words
+template <bool AREA>
+__device__ __forceinline__ bool in_scope(ParamsRef P, uint32_t px, uint32_t py) {
+    if constexpr (AREA) return in_area(P, px, py);
+    else return px < P.width && py < P.height;
+}
+
 __device__ __forceinline__ void init_key(ParamsRef P, uint32_t px, uint32_t py, bool valid, uint32_t& zk,
                                          uint32_t& idk, uint32_t& zorig) {
     zk = P.init_zk; idk = P.init_idk; zorig = P.clear_depth_bits;
@@ -727,7 +738,10 @@ __device__ __forceinline__ void raster_list(const uint4* __restrict__ list, uint
 // the winner's depth (SV_Position.z) to the fragment program; again a variant of its own, raster_kernel_shadow keeps its registers.
 // IBLV (PROGS = 4, one team, four waves, with any SHADOWV): the scope has MODEL_PBR_IBL draws (raster_kernel_ibl); the fragment program reads the
 // IBL set from the parameter block.  Carries the other programs as every PROGS = 4 kernel does.
-template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4, int SHADOWV = 0, bool IBLV = false>
+// AREA: the scope has a partial render area: the launch spans a sub-range of the tile columns (RasterHead::tile_origin) and every
+// pixel is tested against the area's rectangle instead of the extent.  Variants of their own (one team of four waves: raster_mode), so that the
+// AREA = false instantiations are, instruction for instruction, what they were before there were areas.
+template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4, int SHADOWV = 0, bool IBLV = false, bool AREA = false>
 #ifndef MIRHI_PROGS2_WAVES
 #define MIRHI_PROGS2_WAVES 5
 #endif
@@ -736,6 +750,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
     constexpr bool WIDE = WPT > 4;                      // WPT: waves per tile (and team): 4, or 8 / 16 in the wide variants
     static_assert(WPT == 4 || WPT == 8 || WPT == 16, "waves per tile");
     static_assert(!WIDE || (TEAMS == 1 && TP != 0 && PROGS >= 2), "the wide variants exist for one-team mesh scopes with the triangle-parallel path");
+    static_assert(!AREA || (TEAMS == 1 && WPT == 4), "the area variants exist for one team of four waves");
     constexpr int NB = 16 / WPT;                        // 8x8 blocks per wave
     constexpr uint32_t TT = (uint32_t)WPT * 64u;        // lanes per team
     // mesh variants stage with all four waves: their small records are resolved while staging (triangle-parallel), so a
@@ -763,7 +778,11 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
         }
         tx = t % H.tiles_x; tyr = t / H.tiles_x;
     }
-    const uint32_t tile = tyr * H.tiles_x + tx, ty = H.tile_row_begin + tyr * H.tile_row_step;      // (grid row = owned row: PassParams::tile_row_step)
+    // (a partial render area launches a sub-range of the tile columns: grid column j is tile column tile_col_begin + j; a full-extent
+    // scope's column origin is 0: its tile_origin is the row origin alone)
+    const uint32_t col_begin = AREA ? H.tile_origin >> 16 : 0u;
+    if constexpr (AREA) tx += col_begin;      // (never in the run-length order: raster_mode keeps that to full-extent scopes)
+    const uint32_t tile = tyr * H.tiles_x + tx, ty = (AREA ? H.tile_origin & 0xFFFFu : H.tile_origin) + tyr * H.tile_row_step;      // (grid row = owned row: PassParams::tile_row_step)
     // four waves: wave q owns the 16x16 quadrant q (blocks b: bx = b & 1, by = b >> 1 from its first); eight: the 16x8 strip
     // (q & 1, q >> 1), two blocks side by side; sixteen: block q (bx = q & 3, by = q >> 2)
     const int32_t ix0 = WPT == 16 ? (int32_t)((q & 3u) * 8u + (lane & 7u)) : (int32_t)((q & 1u) * 16u + (lane & 7u));
@@ -809,7 +828,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
     // that uses this workspace is ordered behind this kernel), so nbig_raw need not stay live across the raster loops.
     // The tile's own bin counter is re-armed after the bin pass: every wave of this workgroup reads it above, and the
     // barriers of that pass order those reads before the store.
-    if (tid == 0 && team == 0 && tile == 0) {
+    if (tid == 0 && team == 0 && tile == col_begin) {      // (the launch's first tile)
         *P.big_count_next = 0;                              // the next scope on this workspace appends to the other counter
         P.status[1] = nbig_raw;
         uint32_t pages_used = 0;                            // dynamic bin pages of this scope; no raster workgroup reads the counters,
@@ -836,7 +855,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
 #pragma unroll
             for (int b = 0; b < NB; b++) {
                 const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
-                if (px >= P.width || py >= P.height) continue;
+                if (!in_scope<AREA>(P, px, py)) continue;
                 const size_t pix = (size_t)py * P.width + px;
                 if (write_color) {
                     if (P.color_format == 2) reinterpret_cast<float4*>(P.color)[pix] = make_float4(P.clear_color[0], P.clear_color[1], P.clear_color[2], P.clear_color[3]);
@@ -871,7 +890,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
         for (int b = 0; b < NB; b++) {
             const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
             uint32_t zo;
-            init_key(P, px, py, px < P.width && py < P.height, st.zk[b], st.idk[b], zo);
+            init_key(P, px, py, in_scope<AREA>(P, px, py), st.zk[b], st.idk[b], zo);
         }
     }
 
@@ -954,7 +973,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
 #pragma unroll
         for (int b = 0; b < NB; b++) {
             const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
-            const bool inb = px < P.width && py < P.height;
+            const bool inb = in_scope<AREA>(P, px, py);
             uint32_t izk, iidk, zorig;
             init_key(P, px, py, inb, izk, iidk, zorig);
             const uint32_t zkb = st.zk[b], idb = st.idk[b];
@@ -1004,10 +1023,14 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
                                 (st.idk[2] != init_idk && flat4[2] == 0u) || (st.idk[3] != init_idk && flat4[3] == 0u);
         if (__ballot(need_shade) == 0ull) {
             const uint32_t width = R->width, height = R->height, clear_packed = R->clear_packed;
+            // the rectangle pixels are tested against and its origin: the area (AREA) or the extent; (ax, ay): the tile's origin relative to it
+            const uint32_t ox = AREA ? R->area_x0 : 0u, oy = AREA ? R->area_y0 : 0u, aw = AREA ? R->area_w : width, ah = AREA ? R->area_h : height;
+            const uint32_t ax = tx * TILE - ox, ay = ty * TILE - oy;
             uint8_t* row0 = reinterpret_cast<uint8_t*>(R->color);
             uint8_t* row1 = row0 + (size_t)BLOCK * width * 4u;                 // the lower pair of blocks: uniform base
             const uint32_t off = (py0 * width + px0) * 4u;
-            if ((tx + 1u) * TILE <= width && (ty + 1u) * TILE <= height && !R->color_load) {   // wave-uniform: interior tile
+            const bool whole = AREA ? (ax < aw && ax + TILE <= aw && ay < ah && ay + TILE <= ah) : ((tx + 1u) * TILE <= width && (ty + 1u) * TILE <= height);
+            if (whole && !R->color_load) {   // wave-uniform: interior tile (AREA: a tile wholly inside the area)
                 store_target(reinterpret_cast<uint32_t*>(row0 + off), st.idk[0] != init_idk ? flat4[0] : clear_packed);
                 store_target(reinterpret_cast<uint32_t*>(row0 + off + 4u * BLOCK), st.idk[1] != init_idk ? flat4[1] : clear_packed);
                 store_target(reinterpret_cast<uint32_t*>(row1 + off), st.idk[2] != init_idk ? flat4[2] : clear_packed);
@@ -1018,7 +1041,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
                 for (int b = 0; b < 4; b++) {
                     const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
                     const bool won = st.idk[b] != init_idk;
-                    if (px < width && py < height && (won || !color_load))
+                    if (px - ox < aw && py - oy < ah && (won || !color_load))
                         store_target(reinterpret_cast<uint32_t*>((b >> 1 ? row1 : row0) + off + 4u * BLOCK * (uint32_t)(b & 1)), won ? flat4[b] : clear_packed);
                 }
             }
@@ -1032,7 +1055,7 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
     for (int b = 0; b < NB; b++) {
         if (TEAMS > 1 && !solo && (uint32_t)(b * TEAMS) / 4u != team) continue;      // another team shades this block
         const uint32_t px = px0 + (uint32_t)(b & 1) * BLOCK, py = py0 + (uint32_t)(b >> 1) * BLOCK;
-        const bool inb = px < P.width && py < P.height;
+        const bool inb = in_scope<AREA>(P, px, py);
         uint32_t izk, iidk, zorig;
         init_key(P, px, py, inb, izk, iidk, zorig);
         const uint32_t zkb = b == 0 ? st.zk[0] : (b == 1 ? st.zk[1] : (b == 2 ? st.zk[2] : st.zk[3]));
@@ -1096,10 +1119,10 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
 }
 
 #define MIRHI_RASTER_BOUNDS __launch_bounds__(RASTER_THREADS * TEAMS, (PROGS == 1 ? (TP ? 7 : 8) : (PROGS == 2 ? MIRHI_PROGS2_WAVES : 4)))
-// one rendering scope: grid (tiles_x, tile rows of the band)
-template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false>
+// one rendering scope: grid (tiles_x, tile rows of the band); AREA: (the area's tile columns, the area's tile rows)
+template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, bool AREA = false>
 __global__ MIRHI_RASTER_BOUNDS void raster_kernel(const PassParams* __restrict__ params, const RasterHead H) {
-    raster_body<PROGS, KEYED, TP, TEAMS, MASKEDV>(params, H);
+    raster_body<PROGS, KEYED, TP, TEAMS, MASKEDV, 4, 0, false, AREA>(params, H);
 }
 // the wide mesh variant: sixteen waves per tile (raster_body, WIDE); one workgroup is a CU's four waves per SIMD
 template <int PROGS, int KEYED, int WPT>
@@ -1107,19 +1130,19 @@ __global__ __launch_bounds__(WPT * 64, (PROGS == 2 && WPT == 16 ? 6 : (PROGS == 
     raster_body<PROGS, KEYED, 1, 1, false, WPT>(params, H);
 }
 // a depth-only scope (shadow map): KEYED 0 (LESS / LESS_OR_EQUAL) or 1 (GREATER / GREATER_OR_EQUAL), with or without the triangle-parallel path
-template <int KEYED, int TP>
+template <int KEYED, int TP, bool AREA = false>
 __global__ __launch_bounds__(RASTER_THREADS, (TP ? 7 : 8)) void raster_kernel_depth(const PassParams* __restrict__ params, const RasterHead H) {
-    raster_body<0, KEYED, TP>(params, H);
+    raster_body<0, KEYED, TP, 1, false, 4, 0, false, AREA>(params, H);
 }
 // a scope with a shadowed MODEL_PBR draw (one team, four waves per tile; no predicate, ordered or alpha-masked segment carries one)
-template <int KEYED, int TP>
+template <int KEYED, int TP, bool AREA = false>
 __global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_shadow(const PassParams* __restrict__ params, const RasterHead H) {
-    raster_body<4, KEYED, TP, 1, false, 4, 1>(params, H);
+    raster_body<4, KEYED, TP, 1, false, 4, 1, false, AREA>(params, H);
 }
 // a scope with a cascaded MODEL_PBR draw (mirhi_cmd_bind_shadow_cascades): the same shape of kernel with CalculateShadowCSM
-template <int KEYED, int TP>
+template <int KEYED, int TP, bool AREA = false>
 __global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_csm(const PassParams* __restrict__ params, const RasterHead H) {
-    raster_body<4, KEYED, TP, 1, false, 4, 2>(params, H);
+    raster_body<4, KEYED, TP, 1, false, 4, 2, false, AREA>(params, H);
 }
 // a scope with a MODEL_PBR_IBL draw (mirhi_cmd_bind_ibl): the same shape of kernel again, SHADOWV = the shadow term of its draws (0 none, 1 a single map,
 // 2 cascades: pixel/model_pbr_ibl.hlsl with shadow = 1 / as written, pixel/model_pbr_ibl_csm.hlsl)
@@ -1127,9 +1150,9 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_csm(const Pas
 // spilled, 144 bytes of scratch per lane there); 168 hold them without a spill.  The cascaded variant, which also carries the per-lane cascade matrix
 // and SV_Position.z, still spilled 6 VGPRs at three waves and is compiled for two; running the ambient term ahead of the light loops instead made it 33
 // (DESIGN.md 8e).
-template <int KEYED, int TP, int SHADOWV>
+template <int KEYED, int TP, int SHADOWV, bool AREA = false>
 __global__ __launch_bounds__(RASTER_THREADS, (SHADOWV == 2 ? 2 : 3)) void raster_kernel_ibl(const PassParams* __restrict__ params, const RasterHead H) {
-    raster_body<4, KEYED, TP, 1, false, 4, SHADOWV, true>(params, H);
+    raster_body<4, KEYED, TP, 1, false, 4, SHADOWV, true, AREA>(params, H);
 }
 // up to MAX_BATCH independent rendering scopes of equal shape (the frames of one mirhi_queue_submit): grid (tiles_x, tile rows, scopes).
 // One launch instead of one per frame: the ramp-up and drain of a kernel (5 us of the 11 us an isolated 10k-triangle raster kernel

@@ -4,6 +4,7 @@
 // tested on a machine without a GPU (mirhi_debug_scope_plan, tests/test_scope_plan_cpu.py).
 #pragma once
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <unistd.h>      // environ
@@ -118,6 +119,41 @@ struct PlanKnobs {
     }
 };
 
+// The render area of a scope (mirhi_rendering_info::render_area) on an attachment of W x H pixels: whether it is valid, the rectangle
+// it stands for, and the tiles a scope launches for it.  The tile grid is the attachment's (32 x 32 tiles from pixel (0, 0)) and pixel coordinates
+// stay absolute -- an area only selects the tile columns [col_begin, col_end) and rows [row_begin, row_end) that intersect it; the kernels then
+// test every pixel against the rectangle (in_area).  w <= 0 or h <= 0: the full extent.
+struct RenderArea {
+    bool valid;                 // x >= 0, y >= 0, x + w <= W, y + h <= H (in 64 bits); nothing else below is meaningful otherwise
+    uint32_t x, y, w, h;        // the rectangle in pixels (the full extent spelled out)
+    bool partial;               // smaller than the attachment
+    uint32_t col_begin, col_end, row_begin, row_end;      // tiles launched
+    bool edge_partial;          // some launched tile lies only partly inside the rectangle: an area edge off the tile grid, or the attachment's own ragged edge
+    uint32_t tiles;             // launched tiles: what raster_mode / bin_geometry take as the scope's tile count
+    uint32_t index_tiles;       // tiles the bins, counters and page table are indexed by: all columns of the attachment x the launched rows
+};
+inline RenderArea render_area(uint32_t W, uint32_t H, const int32_t area[4]) {
+    RenderArea a{};
+    const uint32_t T = (uint32_t)TILE;
+    const bool full = area[2] <= 0 || area[3] <= 0;
+    const int64_t x = full ? 0 : area[0], y = full ? 0 : area[1], w = full ? (int64_t)W : area[2], h = full ? (int64_t)H : area[3];
+    a.valid = x >= 0 && y >= 0 && x + w <= (int64_t)W && y + h <= (int64_t)H;
+    if (!a.valid) return a;
+    a.x = (uint32_t)x; a.y = (uint32_t)y; a.w = (uint32_t)w; a.h = (uint32_t)h;
+    a.partial = a.x != 0u || a.y != 0u || a.w != W || a.h != H;
+    const bool none = a.w == 0u || a.h == 0u;      // (an attachment without pixels)
+    a.col_begin = none ? 0u : a.x / T; a.col_end = none ? 0u : (a.x + a.w + T - 1u) / T;
+    a.row_begin = none ? 0u : a.y / T; a.row_end = none ? 0u : (a.y + a.h + T - 1u) / T;
+    a.edge_partial = !none && (a.x % T != 0u || a.y % T != 0u || (a.x + a.w) % T != 0u || (a.y + a.h) % T != 0u);
+    a.tiles = (a.col_end - a.col_begin) * (a.row_end - a.row_begin);
+    a.index_tiles = ((W + T - 1u) / T) * (a.row_end - a.row_begin);
+    return a;
+}
+// what begin_rendering answers an invalid area with
+inline void render_area_message(char* buf, size_t len, const int32_t area[4], uint32_t W, uint32_t H) {
+    snprintf(buf, len, "Invalid handle: render area (x %d, y %d, width %d, height %d) does not lie inside the %u x %u attachment", area[0], area[1], area[2], area[3], W, H);
+}
+
 // What kind of scope a segment is: everything about it that does not depend on how many triangles or tiles it has.
 struct ScopeClass {
     DepthKey key;
@@ -195,7 +231,8 @@ inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const D
 //  MIRHI_TP_MAX_AREA (0 = off), MIRHI_TP_DENSITY, MIRHI_RASTER_TEAMS (1 / 2) override for A/B measurements.
 struct RasterMode { uint32_t tp_max_area, teams; bool wide_eligible; bool xcd_bins; uint32_t wide, xcd_swizzle; };
 // tris: the segment's own triangles; spread / wide: what the command buffer's feedback asks for (Workspace::spread; Workspace::wide: 0 / 8 / 16 waves per tile)
-inline RasterMode raster_mode(const ScopeClass& c, size_t tiles, size_t tris, bool spread, uint32_t wide, const PlanKnobs& knobs) {
+// tiles: the tiles the scope launches (RenderArea::tiles); partial_area: not all of the attachment's
+inline RasterMode raster_mode(const ScopeClass& c, size_t tiles, size_t tris, bool spread, uint32_t wide, const PlanKnobs& knobs, bool partial_area = false) {
     RasterMode m{0u, 1u, false, false, 0u, 1u};
     const size_t avg = tiles ? tris / tiles : 0;
     const size_t density = knobs.tp_density.set ? (size_t)knobs.tp_density.value : (c.tri_prog ? 16 : 4);
@@ -221,6 +258,10 @@ inline RasterMode raster_mode(const ScopeClass& c, size_t tiles, size_t tris, bo
     }
     m.xcd_swizzle = knobs.xcd_run.set ? (uint32_t)knobs.xcd_run.value : 1u;
     if (c.own_family) { m.xcd_swizzle = 1u; m.wide = 0u; }      // (their own variants: plain tile order, four waves per tile)
+    // A partial render area: the run-length order numbers the tiles of whole rows (a measurement knob, left to full-extent scopes), and the AREA raster
+    // variants exist for one team of four waves with single-list bins (an area is a part of a frame: the two-team and wide variants answer a mesh that
+    // sits in a small part of a whole frame's tiles, which launching the area's tiles alone already does)
+    if (partial_area) { m.xcd_swizzle = 1u; m.teams = 1u; m.xcd_bins = false; m.wide = 0u; m.wide_eligible = false; }
     if (c.sky || c.transfer) { m.tp_max_area = 0u; m.teams = 1u; m.wide_eligible = false; m.xcd_bins = false; }
     return m;
 }
@@ -247,8 +288,11 @@ inline void set_raster_choice(PassParams& P, const ScopeClass& c, const RasterMo
 
 // Bins and page pool of one scope.  tris: the segment's own triangles, total_tris: with those of the scope's earlier segments (primitive ids continue)
 struct BinGeometry { uint32_t bin_cap, sub_cap, fixed_per_tile, fixed_pages; size_t pages; uint32_t big_cap; };
-inline BinGeometry bin_geometry(size_t tiles, size_t tris, uint32_t total_tris, bool xcd_bins, uint32_t pool_scale, const PlanKnobs& knobs) {
+// index_tiles (0: = tiles): the tiles the bins are indexed by, where that is more than the scope launches (RenderArea::index_tiles: a tile's fixed pages
+// sit at page = tile * fixed_per_tile, and a partial render area keeps the attachment's columns in the index); densities are judged by `tiles`
+inline BinGeometry bin_geometry(size_t tiles, size_t tris, uint32_t total_tris, bool xcd_bins, uint32_t pool_scale, const PlanKnobs& knobs, size_t index_tiles = 0) {
     BinGeometry g;
+    if (index_tiles == 0) index_tiles = tiles;
     // A tile's bin holds up to BIN_TABLE_ROW pages (4096 records; eight lists of 512 with per-XCD bins) before it spills into
     // the big list, which EVERY tile walks -- the limit costs nothing until it is used: pages come out of one pool, sized by
     // the scope's triangle count, not by tiles x capacity (round 1: 100 MB at 1080p, 400-510 MB at 4K per command buffer).
@@ -267,10 +311,10 @@ inline BinGeometry bin_geometry(size_t tiles, size_t tris, uint32_t total_tris, 
     // dancer asset) opens pages where its triangles are
     g.fixed_per_tile = xcd_bins ? 0u : (uint32_t)std::min<size_t>(8, std::max<size_t>(1, tiles ? (13 * tris / (10 * tiles) + BIN_PAGE_RECS - 1) / BIN_PAGE_RECS : 1));
     if (knobs.fixed_pages.set && !xcd_bins) g.fixed_per_tile = (uint32_t)std::min(8, std::max(1, knobs.fixed_pages.value));   // (tests, A/B runs)
-    g.fixed_pages = g.fixed_per_tile * (uint32_t)tiles;
+    g.fixed_pages = g.fixed_per_tile * (uint32_t)index_tiles;
     // dynamic part: the estimated pairs that the fixed pages will not take (they take at most half of it when the triangles sit
     // in a part of the frame), never less than a quarter of the estimate, plus a partly filled page for one tile in four
-    const size_t fixed_capacity = (size_t)g.fixed_pages * BIN_PAGE_RECS;
+    const size_t fixed_capacity = (size_t)g.fixed_per_tile * tiles * BIN_PAGE_RECS;      // (of the launched tiles: the others' pages take nothing)
     const size_t dyn_records = std::max(pairs > fixed_capacity / 2 ? pairs - fixed_capacity / 2 : 0, pairs / 4) * pool_scale;
     g.pages = g.fixed_pages + ((dyn_records / BIN_PAGE_RECS + tiles * (xcd_bins ? 8 : 1) / 4 + 64 + 7) & ~(size_t)7);
     if (knobs.pool_pages.set) g.pages = g.fixed_pages + 8 * (((size_t)knobs.pool_pages.value + 7) / 8);      // (pool-exhaustion test)

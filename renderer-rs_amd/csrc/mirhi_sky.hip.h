@@ -29,13 +29,15 @@ __device__ __forceinline__ bool sky_depth_passes(uint32_t op, float frag, float 
 __global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams* __restrict__ params, const RasterHead H) {
     ParamsRef P = *(ParamsPtr)(uintptr_t)params;
     const uint32_t tid = threadIdx.x;
-    const uint32_t tx = blockIdx.x, ty = H.tile_row_begin + blockIdx.y * H.tile_row_step;
+    const uint32_t tx = blockIdx.x + (H.tile_origin >> 16), ty = (H.tile_origin & 0xFFFFu) + blockIdx.y * H.tile_row_step;      // (the render area's tile columns)
     const uint32_t px = tx * TILE + (tid & 31u), py0 = ty * TILE + (tid >> 5);
-    const uint32_t width = P.width, height = P.height;
+    const uint32_t width = P.width;
+    // the render area: the pixels this segment loads, fills and stores (the attachment itself in a full-extent scope; the scissor lies inside it)
+    const uint32_t ax0 = P.area_x0, ay0 = P.area_y0, aw = P.area_w, ah = P.area_h;
     const bool load_depth = P.depth_load && P.depth;
     const float frag_depth = __uint_as_float(P.sky_depth_bits);
     const uint32_t visible = P.sky_visible, op = P.sky_compare;
-    const bool in_x = px < width && (int32_t)px >= P.sky_scissor[0] && (int32_t)px <= P.sky_scissor[2];
+    const bool in_x = px - ax0 < aw && (int32_t)px >= P.sky_scissor[0] && (int32_t)px <= P.sky_scissor[2];
 
     bool inb[4], won[4];
     uint32_t zorig[4];
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         const uint32_t py = py0 + 8u * (uint32_t)b;
-        inb[b] = px < width && py < height;
+        inb[b] = px - ax0 < aw && py - ay0 < ah;
         zorig[b] = P.clear_depth_bits;
         if (load_depth && inb[b]) zorig[b] = __float_as_uint(P.depth[(size_t)py * width + px]);
     }
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         const uint32_t py = py0 + 8u * (uint32_t)b;
-        bool w = visible && in_x && py < height && (int32_t)py >= P.sky_scissor[1] && (int32_t)py <= P.sky_scissor[3];
+        bool w = visible && in_x && py - ay0 < ah && (int32_t)py >= P.sky_scissor[1] && (int32_t)py <= P.sky_scissor[3];
         if (w) {
             const long long e0 = P.sky_e0[0] + 256ll * ((long long)P.sky_a[0] * (int32_t)px + (long long)P.sky_b[0] * (int32_t)py);
             const long long e1 = P.sky_e0[1] + 256ll * ((long long)P.sky_a[1] * (int32_t)px + (long long)P.sky_b[1] * (int32_t)py);

@@ -37,12 +37,14 @@ __device__ __forceinline__ uint32_t count_tile_tri(const TileTri& T, int32_t lim
 __global__ __launch_bounds__(RASTER_THREADS) void fragment_count_kernel(const PassParams* __restrict__ params, const RasterHead H) {
     ParamsRef P = *(ParamsPtr)(uintptr_t)params;
     __shared__ uint32_t lds_sum;
-    const uint32_t tx = blockIdx.x, tyr = blockIdx.y, tid = threadIdx.x;
-    const uint32_t tile = tyr * H.tiles_x + tx, ty = H.tile_row_begin + tyr * H.tile_row_step;
+    const uint32_t tx = blockIdx.x + (H.tile_origin >> 16), tyr = blockIdx.y, tid = threadIdx.x;      // (the render area's tile columns)
+    const uint32_t tile = tyr * H.tiles_x + tx, ty = (H.tile_origin & 0xFFFFu) + tyr * H.tile_row_step;
     if (tid == 0) lds_sum = 0;
     __syncthreads();
     uint32_t n = 0;
-    const int32_t lim_x = (int32_t)P.width - 1 - (int32_t)(tx * TILE), lim_y = (int32_t)P.height - 1 - (int32_t)(ty * TILE);
+    // (the area's last pixel: the target's in a full-extent scope.  In front of the area's origin nothing is counted either: a record that reaches
+    // outside was cut by the draw's scissor, which lies inside the area, and carries its box)
+    const int32_t lim_x = (int32_t)(P.area_x0 + P.area_w) - 1 - (int32_t)(tx * TILE), lim_y = (int32_t)(P.area_y0 + P.area_h) - 1 - (int32_t)(ty * TILE);
     const uint4* pool = reinterpret_cast<const uint4*>(H.bin_pool);
     const uint32_t nsub = H.count_stride ? 8u : 1u;
     for (uint32_t k = 0; k < nsub; k++) {

@@ -72,6 +72,8 @@ inline SubmitPath submit_path(const SubmitDevice& d, const SubmitSwitches& sw, u
     // Only frames that are independent of each other may share a launch: every scope clears (no LOAD of colour or depth -- what it
     // would load might be written by another scope of the batch), no two scopes share a colour, depth or primitive-id attachment, and
     // all command buffers sit on the first one's queue lane (so the batch keeps their order against earlier work of that lane).
+    // A scope with a partial render area never joins a batch: the batched raster kernel takes one grid for all its scopes, and an area
+    // scope's grid is its own tile range (RasterVariant::batched_form is 0 for it, so the comparison below fails whatever the other scopes are).
     // Anything else runs command buffer by command buffer, in submission order on each lane.
     p.batched = count >= 2 && count <= (uint32_t)MAX_BATCH && d.profiling == 0 && !sw.no_batch;
     SubmitHead heads[MAX_BATCH];

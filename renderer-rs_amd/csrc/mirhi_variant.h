@@ -23,8 +23,8 @@ enum : uint32_t {
 enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY, RASTER_TRANSFER };
 
 // the kernel instantiation alone (no launch shape) as one word
-constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves) {
-    return family | progs << 4 | keyed << 8 | tp << 12 | teams << 16 | masked << 20 | waves << 24;
+constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves, uint32_t area = 0u) {
+    return family | progs << 4 | keyed << 8 | tp << 12 | teams << 16 | masked << 20 | waves << 24 | area << 30;
 }
 
 // One raster launch: the kernel family and its template arguments, the grid and the block.  Equal values <=> the same kernel
@@ -39,7 +39,8 @@ struct RasterVariant {
     uint32_t waves;           // waves per tile: 4 x teams, or 8 / 16 (raster_kernel_wide)
     uint32_t grid[3], block;
     uint32_t batched_form;    // 1: a raster_kernel_batch instantiation exists for it and the scope may take it (plain tile order, no wide plan)
-    constexpr uint32_t kernel_id() const { return raster_kernel_id(family, progs, keyed, tp, teams, masked, waves); }
+    uint32_t area;            // 1: the AREA instantiation (a partial render area); the ordered, sky and transfer kernels have one form
+    constexpr uint32_t kernel_id() const { return raster_kernel_id(family, progs, keyed, tp, teams, masked, waves, area); }
     bool operator==(const RasterVariant& o) const {
         return kernel_id() == o.kernel_id() && grid[0] == o.grid[0] && grid[1] == o.grid[1] && grid[2] == o.grid[2] && block == o.block && batched_form == o.batched_form;
     }
@@ -48,27 +49,31 @@ struct RasterVariant {
 // allow_wide: false = the scope's plain / two-team variant even if its plan names a wide one (PassParams::raster_wide): a submit's choice
 inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool allow_wide) {
     const uint32_t rows = P.tile_row_end - P.tile_row_begin;
+    const uint32_t cols = launch_cols(P);      // (the render area's tile columns: all of them unless the area is partial)
     if (programs == PROGS_SKY) {
         // a SKYBOX segment: one 256-thread workgroup per tile of the owned rows, always the 2-D grid; no key, no bins, no batched form
-        return RasterVariant{RASTER_SKY, 0u, 0u, 0u, 1u, 0u, 4u, {P.tiles_x, rows, 1u}, (uint32_t)RASTER_THREADS, 0u};
+        return RasterVariant{RASTER_SKY, 0u, 0u, 0u, 1u, 0u, 4u, {cols, rows, 1u}, (uint32_t)RASTER_THREADS, 0u, 0u};
     }
     if (programs == PROGS_TRANSFER) {
         // a transfer entry: its kernel by what it is (progs = XFER_*), a 1-D grid of PassParams::tiles_x workgroups (the host's count: a blit's tiles, the
         // capped work units of a copy or clear); no key, no bins, no batched form
-        return RasterVariant{RASTER_TRANSFER, P.xfer, 0u, 0u, 1u, 0u, 4u, {P.tiles_x * rows, 1u, 1u}, (uint32_t)RASTER_THREADS, 0u};
+        return RasterVariant{RASTER_TRANSFER, P.xfer, 0u, 0u, 1u, 0u, 4u, {P.tiles_x * rows, 1u, 1u}, (uint32_t)RASTER_THREADS, 0u, 0u};
     }
     const uint32_t progs = programs >= PROGS_PBR ? 4u : ((programs == 2u || programs == 3u) ? programs : 1u);
     const bool mesh = programs == PROGS_MODEL || programs >= PROGS_PBR;      // no TRIANGLE draw: what the two-team and wide variants exist for
     // the plain key (raw float bits) serves LESS / LESS_OR_EQUAL; everything else takes the generic key
     const bool plain = P.zflip == 0u && P.zmask == 0xFFFFFFFFu;
     const uint32_t tp = P.tp_max_area ? 1u : 0u;
-    RasterVariant v = {RASTER_PLAIN, progs, plain ? 0u : 1u, tp, 1u, 0u, 4u, {P.tiles_x, rows, 1u}, 0u, 0u};
+    RasterVariant v = {RASTER_PLAIN, progs, plain ? 0u : 1u, tp, 1u, 0u, 4u, {cols, rows, 1u}, 0u, 0u, 0u};
     if (P.ordered_recs) {           // ordered segment: fragments in primitive order (blending); always the 2-D grid
         v.family = RASTER_ORDERED; v.keyed = 0u; v.tp = 0u;
         v.block = (uint32_t)ORDERED_THREADS;
         return v;
     }
-    if (P.xcd_swizzle > 1u) { v.grid[0] = P.tiles_x * rows; v.grid[1] = 1u; }
+    if (P.xcd_swizzle > 1u) { v.grid[0] = P.tiles_x * rows; v.grid[1] = 1u; }      // (never with a partial render area: raster_mode)
+    // a partial render area: the AREA instantiation of whatever is chosen below -- one team of four waves (raster_mode plans neither two teams nor a wide variant for it)
+    const bool area = P.area_partial != 0u;
+    v.area = area ? 1u : 0u;
     if (programs & PROGS_IBL) {
         // a scope with a MODEL_PBR_IBL draw: a family of its own like the shadowed ones (one team of four waves, single-list bins, plain tile order, an
         // ordered key), one kernel per shadow term of its draws
@@ -79,27 +84,27 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
         // them on one team of four waves, single-list bins and the plain tile order; their key is an ordered one, never a predicate)
         v.family = programs == PROGS_DEPTH_ONLY ? RASTER_DEPTH : ((programs & PROGS_CASCADED) ? RASTER_CSM : RASTER_SHADOW);
         v.progs = 0u;
-    } else if (P.raster_wide && allow_wide && !P.pred && tp && !P.alpha_scope && mesh && P.xcd_swizzle <= 1u) {
+    } else if (P.raster_wide && allow_wide && !P.pred && tp && !P.alpha_scope && mesh && P.xcd_swizzle <= 1u && !area) {
         // the wide mesh variants: eight or sixteen waves per tile (host-side choice, PassParams::raster_wide = waves per tile)
         v.family = RASTER_WIDE;
         v.waves = P.raster_wide >= 16u ? 16u : 8u;
     } else if (P.pred) {            // (the host keeps tp_max_area = 0 for predicate scopes)
         v.keyed = 2u; v.tp = 0u;
     } else if (tp) {
-        if (P.raster_teams == 2u && mesh) { v.teams = 2u; v.waves = 8u; }      // only the pure mesh variants exist with two teams
+        if (P.raster_teams == 2u && mesh && !area) { v.teams = 2u; v.waves = 8u; }      // only the pure mesh variants exist with two teams
         if (P.alpha_scope) { v.masked = 1u; v.progs = 4u; }                     // alpha-masked scope: always with the triangle-parallel path and a PBR draw
     }
     v.block = v.waves * 64u;
     // only the variants a frame loop meets are instantiated in batched form: LESS / LESS_OR_EQUAL keys, with and without the triangle-parallel path and
     // the two-team mesh mode.  The XCD run-length order of a 1-D grid is a measurement knob, and a plan that names a wide variant keeps it whether or
-    // not one submit takes it: neither is batched.
-    v.batched_form = (v.family == RASTER_PLAIN && v.keyed == 0u && !P.alpha_scope && P.xcd_swizzle <= 1u && !P.raster_wide) ? 1u : 0u;
+    // not one submit takes it: neither is batched.  Nor is a scope with a partial render area (mirhi_submit.h).
+    v.batched_form = (v.family == RASTER_PLAIN && v.keyed == 0u && !P.alpha_scope && P.xcd_swizzle <= 1u && !P.raster_wide && !P.area_partial) ? 1u : 0u;
     return v;
 }
 
 // The by-value kernel argument of a scope's raster (and fragment-count) kernel
 inline RasterHead raster_head(const PassParams& P, uint32_t* big_count) {
-    return RasterHead{P.bin_count, P.bin_pool, big_count, P.tiles_x, P.tile_row_begin, P.bin_cap, P.big_cap, P.sub_cap, P.count_stride, P.fixed_recs, P.tile_row_step};
+    return RasterHead{P.bin_count, P.bin_pool, big_count, P.tiles_x, P.tile_row_begin | P.tile_col_begin << 16, P.bin_cap, P.big_cap, P.sub_cap, P.count_stride, P.fixed_recs, P.tile_row_step};
 }
 // ... of an ordered segment: nothing is binned, a tile's single list has no fixed pages
 inline RasterHead ordered_head(const PassParams& P, uint32_t* big_count) {

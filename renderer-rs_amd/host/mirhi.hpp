@@ -447,6 +447,17 @@ public:
         info_.clear_depth = a.clear_depth;
         return *this;
     }
+    // rendering.rs:818-838.  The scope loads, clears, draws and stores inside the rectangle only (include/mirhi.h, mirhi_rendering_info::render_area);
+    // without either call the area is the attachment's full extent.  with_offset moves the area and keeps its extent: the config's own (w, h) by default.
+    RenderingConfig& with_render_area(const mirhi_rect2d& area) {
+        info_.render_area[0] = area.x; info_.render_area[1] = area.y; info_.render_area[2] = (int32_t)area.width; info_.render_area[3] = (int32_t)area.height;
+        return *this;
+    }
+    RenderingConfig& with_offset(int32_t x, int32_t y) {
+        if (info_.render_area[2] <= 0 || info_.render_area[3] <= 0) { info_.render_area[2] = (int32_t)w_; info_.render_area[3] = (int32_t)h_; }
+        info_.render_area[0] = x; info_.render_area[1] = y;
+        return *this;
+    }
     uint32_t width() const { return w_; }
     uint32_t height() const { return h_; }
     const mirhi_rendering_info& build() const { return info_; }

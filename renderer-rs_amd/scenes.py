@@ -333,6 +333,7 @@ class ShadowSpec:
     load_op: int = LOAD_OP_CLEAR
     depth_bias: Optional[tuple] = None    # the map's pipelines: depth bias (constant_factor, clamp, slope_factor) of casters that set none themselves
     depth_clamp: bool = False             # ... and depth_clamp_enable ("pancaking": casters in front of the light's near plane stay in the map at depth 0)
+    render_area: Optional[tuple] = None   # (x, y, w, h): the scope clears and draws this rectangle of the map only (a shadow atlas); None = all of it
 
 
 @dataclass
@@ -408,6 +409,7 @@ class Scene:
     cascades: Optional["CascadeSpec"] = None   # shadow cascades (shadow_csm.hlsli): four depth-only scopes ahead of the main scope; not with `shadow`
     ibl: Optional["IblSpec"] = None            # the IBL set of the scene's MODEL_PBR_IBL draws (mirhi_cmd_bind_ibl)
     sky: Optional["SkySpec"] = None            # the environment drawn behind the scene (PROGRAM_SKYBOX, mirhi_cmd_bind_skybox)
+    render_area: Optional[tuple] = None        # (x, y, w, h): the main scope draws into this rectangle of its attachments only; None = full extent
 
     @property
     def num_triangles(self) -> int:
