@@ -108,6 +108,12 @@ impl CommandBuffer {
         let (array, params) = cascades.map_or((std::ptr::null_mut(), std::ptr::null_mut()), |(a, b)| (a.raw, b.raw));
         check(unsafe { mirhi_sys::mirhi_cmd_bind_shadow_cascades(self.raw, array, params, offset, range) })
     }
+    /// The same binding with cascade blending (`CalculateShadowCSMBlended`, shadow_csm.hlsli:212-277): `blend_threshold` in [0, 1] is latched per draw
+    /// with the binding; 0.0 records exactly what `bind_shadow_cascades` records.
+    pub fn bind_shadow_cascades_blended(&self, cascades: Option<(&Image, &Buffer)>, offset: u64, range: u64, blend_threshold: f32) -> RhiResult<()> {
+        let (array, params) = cascades.map_or((std::ptr::null_mut(), std::ptr::null_mut()), |(a, b)| (a.raw, b.raw));
+        check(unsafe { mirhi_sys::mirhi_cmd_bind_shadow_cascades_blended(self.raw, array, params, offset, range, blend_threshold) })
+    }
     /// Set 3 of pixel/model_pbr_ibl.hlsl:133-155: irradiance cube, prefiltered cube and BRDF LUT of `ShaderProgram::ModelPbrIbl` draws; `None` unbinds.
     pub fn bind_ibl(&self, set: Option<(&Image, &Image, &Image)>) -> RhiResult<()> {
         let n = std::ptr::null_mut();

@@ -33,6 +33,7 @@ extern "C" {
                                     pipelines (colour format UNDEFINED) and depth-only rendering scopes (color_image NULL);
                                     still 5 (new functions only): mirhi_image_create_array, mirhi_image_create_layer_view, mirhi_image_layers,
                                     mirhi_cmd_bind_shadow_cascades;
+                                    still 5 (one new function): mirhi_cmd_bind_shadow_cascades_blended;
                                     still 5 (new functions only): mirhi_image_create_cube and the five mirhi_ibl_ passes;
                                     still 5 (one new enum value, one new function): MIRHI_PROGRAM_MODEL_PBR_IBL, mirhi_cmd_bind_ibl;
                                     still 5 (one new enum value, one new function): MIRHI_PROGRAM_SKYBOX, mirhi_cmd_bind_skybox;
@@ -426,6 +427,14 @@ mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slot slot, mir
  * refused (InvalidHandle), as are single-map and cascaded draws in one rendering scope; a cascaded draw's pipeline may not blend, discard fragments
  * or use a predicate depth state, and needs the depth test (its depth key is where SV_Position.z comes from). */
 mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range);
+/* The same binding with cascade blending: a MODEL_PBR / MODEL_PBR_IBL draw recorded under it multiplies the directional light by CalculateShadowCSMBlended
+ * (shadow_csm.hlsli:212-277) -- the selected cascade's PCF and, for a pixel whose depth lies within blend_threshold x (the cascade's split range) in front of
+ * its split, the next cascade's, blended by the distance to the split (no seam at a split depth).  Validation, lifetime and latching are those of
+ * mirhi_cmd_bind_shadow_cascades; blend_threshold is `blendThreshold`, latched per draw with the binding.  A threshold that is not finite, below 0 or above
+ * 1 is refused (InvalidHandle, "unsupported:").  0.0 is legal and records exactly what mirhi_cmd_bind_shadow_cascades records (which implies a threshold
+ * of 0); array == NULL unbinds either way, and mirhi_cmd_begin* / mirhi_cmd_reset clear the threshold with the binding.  Every refusal of a cascaded draw
+ * holds for a blended one; blended and unblended cascaded draws may share a rendering scope.  Cascade 3 never blends; cascade 0 measures its range from 0. */
+mirhi_result mirhi_cmd_bind_shadow_cascades_blended(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range, float blend_threshold);
 /* The IBL set: descriptor set 3 of pixel/model_pbr_ibl.hlsl:133-155 (= model_pbr_ibl_csm.hlsl) -- TextureCube irradianceMap (t7), TextureCube prefilteredMap
  * (t8), Texture2D<float4> brdfLUT (t9): what mirhi_ibl_irradiance, mirhi_ibl_prefilter and mirhi_ibl_brdf_lut make (or any upload of the same shape).  All three
  * NULL unbinds the set; mirhi_cmd_begin* and mirhi_cmd_reset clear it, as they clear the cascades.  The set lives with the command buffer and is latched by

@@ -319,6 +319,7 @@ _SIGNATURES = {
     "mirhi_cmd_bind_uniform": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64]),
     "mirhi_cmd_bind_texture": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mirhi_cmd_bind_shadow_cascades": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "mirhi_cmd_bind_shadow_cascades_blended": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float]),
     "mirhi_cmd_bind_ibl": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mirhi_cmd_bind_skybox": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_cmd_copy_buffer": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(BufferCopy)]),
@@ -878,9 +879,18 @@ class CommandBuffer:
     def bind_texture(self, slot: int, image: Optional[Image]):
         check(lib().mirhi_cmd_bind_texture(self.handle, slot, image.handle if image else None))
 
-    def bind_shadow_cascades(self, array: Optional[Image], params: Optional[Buffer] = None, offset: int = 0, range_: int = 0):
-        """mirhi_cmd_bind_shadow_cascades: the four-layer D32 array and its CSMParams (scenes.csm_ubo); array=None unbinds."""
-        check(lib().mirhi_cmd_bind_shadow_cascades(self.handle, array.handle if array else None, params.handle if params else None, offset, range_))
+    def bind_shadow_cascades(self, array: Optional[Image], params: Optional[Buffer] = None, offset: int = 0, range_: int = 0, blend_threshold: float = 0.0):
+        """mirhi_cmd_bind_shadow_cascades: the four-layer D32 array and its CSMParams (scenes.csm_ubo); array=None unbinds.
+        blend_threshold other than the default goes through mirhi_cmd_bind_shadow_cascades_blended (CalculateShadowCSMBlended's blendThreshold, in [0, 1])."""
+        if isinstance(blend_threshold, (int, float)) and blend_threshold == 0.0:
+            check(lib().mirhi_cmd_bind_shadow_cascades(self.handle, array.handle if array else None, params.handle if params else None, offset, range_))
+        else:
+            self.bind_shadow_cascades_blended(array, params, offset, range_, blend_threshold)
+
+    def bind_shadow_cascades_blended(self, array: Optional[Image], params: Optional[Buffer] = None, offset: int = 0, range_: int = 0, blend_threshold: float = 0.0):
+        """mirhi_cmd_bind_shadow_cascades_blended, whatever the threshold (0.0 records what bind_shadow_cascades records)."""
+        check(lib().mirhi_cmd_bind_shadow_cascades_blended(self.handle, array.handle if array else None, params.handle if params else None, offset, range_,
+                                                           float(blend_threshold)))
 
     def bind_ibl(self, irradiance: Optional[Image], prefiltered: Optional[Image] = None, brdf_lut: Optional[Image] = None):
         """mirhi_cmd_bind_ibl: the irradiance cube, the prefiltered cube and the BRDF LUT Program.MODEL_PBR_IBL draws sample; all None unbinds."""
@@ -1039,7 +1049,7 @@ class SceneResources:
         put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames).
         scene.cascades (scenes.CascadeSpec): four depth-only scopes instead, one per layer view of a D32 array (self.cascade_array, or the
         existing one passed as cascade_array=), in the same command buffer or with shadow_cmd=True in self.shadow_cmd; the MODEL_PBR draws
-        sample the array through bind_shadow_cascades.
+        sample the array through bind_shadow_cascades, with the spec's blend_threshold.
         scene.ibl (scenes.IblSpec): the IBL set bound for the scene's MODEL_PBR_IBL draws -- the spec's own images, images created here from its
         arrays and uploaded (self.ibl_images, destroyed with the resources), or the existing three passed as ibl_images= (irradiance cube,
         prefiltered cube, BRDF LUT; shared between frames, the caller's to destroy).
@@ -1267,7 +1277,9 @@ class SceneResources:
             elif self.shadow is not None:
                 cmd.bind_texture(TextureSlot.SHADOW_MAP, None)
             if self.cascades is not None and pbr:
-                cmd.bind_shadow_cascades(self.cascade_array, self.cascade_params)
+                # (a draw may carry a threshold of its own, DrawSpec.csm_blend; otherwise the spec's holds)
+                blend = getattr(d, "csm_blend", None)
+                cmd.bind_shadow_cascades(self.cascade_array, self.cascade_params, blend_threshold=self.cascades.blend_threshold if blend is None else blend)
             elif self.cascades is not None:
                 cmd.bind_shadow_cascades(None)
             if st["ib"] is not None:

@@ -644,6 +644,7 @@ struct mirhi_cmd {
     mirhi_image* textures[MIRHI_TEXTURE_COUNT] = {};
     mirhi_image* cascades = nullptr;       // mirhi_cmd_bind_shadow_cascades: the D32 array (t10) ...
     struct { mirhi_buffer* buf; uint64_t offset, range; } cascade_params = {};      // ... and its CSMParams (b3 of set 2)
+    float cascade_blend = 0.0f;            // mirhi_cmd_bind_shadow_cascades_blended: blendThreshold, latched per draw with the binding (0: CalculateShadowCSM)
     mirhi_image* ibl[3] = {};              // mirhi_cmd_bind_ibl: irradiance cube, prefiltered cube, BRDF LUT (set 3); all three or none
     mirhi_image* skybox = nullptr;         // mirhi_cmd_bind_skybox: the environment cube of SKYBOX draws (set 0 of pixel/skybox.hlsl)
     bool has_viewport = false, has_scissor = false;
@@ -1563,7 +1564,7 @@ static void reset_recording(mirhi_cmd* c) {
     c->pipeline = nullptr; c->vb = nullptr; c->ib = nullptr;
     for (auto& u : c->uniforms) u = {nullptr, 0, 0};
     for (auto& tx : c->textures) tx = nullptr;
-    c->cascades = nullptr; c->cascade_params = {nullptr, 0, 0};
+    c->cascades = nullptr; c->cascade_params = {nullptr, 0, 0}; c->cascade_blend = 0.0f;
     for (auto& im : c->ibl) im = nullptr;
     c->skybox = nullptr;
     memset(c->push_constants, 0, sizeof c->push_constants);
@@ -1722,9 +1723,12 @@ extern "C" mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slo
     return MIRHI_OK;
 }
 // set 2, bindings 3 and 4 of pixel/model_pbr_ibl_csm.hlsl:115-127: Texture2DArray<float> shadowMap (t10 / s8) and cbuffer ShadowData { CSMParams } (b3)
-extern "C" mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range) {
+// (one body for both calls: blend_threshold is the blendThreshold of CalculateShadowCSMBlended, shadow_csm.hlsli:212-277; 0 = CalculateShadowCSM)
+static mirhi_result bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range, float blend_threshold) {
     REQUIRE_RECORDING(cmd);
-    if (!array) { cmd->cascades = nullptr; cmd->cascade_params = {nullptr, 0, 0}; return MIRHI_OK; }
+    if (!array) { cmd->cascades = nullptr; cmd->cascade_params = {nullptr, 0, 0}; cmd->cascade_blend = 0.0f; return MIRHI_OK; }
+    if (!std::isfinite(blend_threshold) || blend_threshold < 0.0f || blend_threshold > 1.0f)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a cascade blend threshold outside [0, 1] (got %g)", (double)blend_threshold);
     if (array->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array, not a cube image");
     if (array->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array, not a layer view");
     if (!array->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array (mirhi_image_create_array)");
@@ -1738,7 +1742,14 @@ extern "C" mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_ima
                     (unsigned long long)offset, (unsigned long long)range, (unsigned long long)params->size);
     if (range < 336) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: CSMParams range %llu smaller than 336 bytes", (unsigned long long)range);
     cmd->cascades = array; cmd->cascade_params = {params, offset, range};
+    cmd->cascade_blend = blend_threshold > 0.0f ? blend_threshold : 0.0f;      // (-0.0 is 0)
     return MIRHI_OK;
+}
+extern "C" mirhi_result mirhi_cmd_bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range) {
+    return bind_shadow_cascades(cmd, array, params, offset, range, 0.0f);
+}
+extern "C" mirhi_result mirhi_cmd_bind_shadow_cascades_blended(mirhi_cmd* cmd, mirhi_image* array, mirhi_buffer* params, uint64_t offset, uint64_t range, float blend_threshold) {
+    return bind_shadow_cascades(cmd, array, params, offset, range, blend_threshold);
 }
 // set 3 of pixel/model_pbr_ibl.hlsl:133-155: TextureCube irradianceMap (t7 / s5), TextureCube prefilteredMap (t8 / s6), Texture2D<float4> brdfLUT (t9 / s7)
 extern "C" mirhi_result mirhi_cmd_bind_ibl(mirhi_cmd* cmd, mirhi_image* irradiance, mirhi_image* prefiltered, mirhi_image* brdf_lut) {
@@ -2027,6 +2038,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
                     return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: shadow cascades with blending, fragment discard, a predicate depth state or no depth test");
                 d.shadow_map = (const float*)ca->ptr; d.shadow_w = ca->width; d.shadow_h = ca->height; d.shadow_layers = ca->layers;
                 d.shadow_data = cmd->cascade_params.buf->ptr + cmd->cascade_params.offset;
+                d.csm_blend = cmd->cascade_blend;
             }
             if (d.program == MIRHI_PROGRAM_MODEL_PBR_IBL) {
                 // set 3 (mirhi_cmd_bind_ibl).  raster_kernel_ibl resolves ordered depth keys only, like the shadowed variants
@@ -2073,7 +2085,8 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
             if (std::find(pass.sampled.begin(), pass.sampled.end(), im) == pass.sampled.end()) pass.sampled.push_back(im);
     }
     if (d.shadow_map) {
-        // one raster variant per scope: CalculateShadow (raster_kernel_shadow) or CalculateShadowCSM (raster_kernel_csm)
+        // one raster variant per scope: CalculateShadow (raster_kernel_shadow) or CalculateShadowCSM (raster_kernel_csm; raster_kernel_csm_blend when some
+        // cascaded draw blends: blended and unblended cascaded draws share a scope, classify_scope)
         for (const DrawDesc& o : pass.draws)
             if (o.shadow_map && (o.shadow_layers != 0u) != (d.shadow_layers != 0u))
                 return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: draws with a single shadow map and draws with shadow cascades in one rendering scope");
@@ -2917,7 +2930,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
 // Outside the C ABI (not in include/mirhi.h) and without a HIP call: what build_plan decides for one scope -- class, raster mode (one evaluation),
 // bins -- and the kernel, grid and block that raster_variant then gives at 5 x 4 tiles.  The environment is read as build_plan reads it.
 // in: DepthState key_set, test, compare, write, discard, blend enable; clear-depth float bits; depth_only; tiles; triangles; spread; wide; pool_scale;
-// allow_wide; number of draws (at most 4); per draw: program, shadow kind 0 / 1 / 2, bit 0 "has a mip chain or an sRGB texture" | bit 1 "texture 0 has sampler state" |
+// allow_wide; number of draws (at most 4); per draw: program, shadow kind 0 / 1 / 2 / 3 (3: blended cascades), bit 0 "has a mip chain or an sRGB texture" | bit 1 "texture 0 has sampler state" |
 // bit 2 "texture 1 has sampler state".
 // out: the key's eight words; ordered, masked_plain, tri_prog, shadowed, ibl, own_family, programs; tp_max_area, teams, wide_eligible, xcd_bins, wide,
 // xcd_swizzle; bin_cap, sub_cap, fixed_per_tile, fixed_pages, pool pages (low, high word), big_cap; grid x, y, z, block.
@@ -2934,7 +2947,7 @@ extern "C" int mirhi_debug_scope_plan(const uint32_t* in, uint32_t* out, char* n
     memset(draws, 0, sizeof draws);
     for (uint32_t i = 0; i < n; i++) {
         draws[i].program = in[15 + 3 * i];
-        if (in[16 + 3 * i]) { draws[i].shadow_map = &some_map; draws[i].shadow_layers = in[16 + 3 * i] == 2u ? 4u : 0u; }
+        if (in[16 + 3 * i]) { draws[i].shadow_map = &some_map; draws[i].shadow_layers = in[16 + 3 * i] >= 2u ? 4u : 0u; draws[i].csm_blend = in[16 + 3 * i] == 3u ? 0.5f : 0.0f; }
         draws[i].tex_any_mips = in[17 + 3 * i] & 1u;
         draws[i].tex_sampler = ((in[17 + 3 * i] >> 1) & 1u) | (((in[17 + 3 * i] >> 2) & 1u) << 6);
     }

@@ -93,6 +93,10 @@ struct DrawDesc {
     // line: bits 6t..6t+5 of texture t = address_u | address_v << 2 | mag_filter << 4 | min_filter << 5 (mirhi_address_mode, mirhi_sampler_filter: LINEAR = 0 -- not the blit's mirhi_filter).  With the mip
     // mode in tex_aniso that is eight bits per texture; all zero = REPEAT / LINEAR / MIP_LINEAR, the sampler of every draw before the state existed.
     uint32_t tex_sampler;
+    // blendThreshold of CalculateShadowCSMBlended (mirhi_cmd_bind_shadow_cascades_blended), latched with the cascade binding; 0: the draw's
+    // shadow term is CalculateShadowCSM.  Read by the blended fragment programs alone: a line of its own behind everything else, far from 0x80-0xbf.
+    float    csm_blend;
+    uint32_t csm_pad[3];
 };
 constexpr uint32_t DEPTH_FLAG_BIAS = 1u, DEPTH_FLAG_CLAMP = 2u;
 constexpr uint32_t TEX_MIP_MODE_SHIFT = 20u;     // DrawDesc::tex_aniso: where the mip modes start
@@ -239,7 +243,7 @@ struct PassParams {
     unsigned long long* frag_stats;   // device counters of the statistics pass (never touched by geometry / raster kernels): [0] pixels that
                                       // ran a fragment program (winners of the depth resolve), [1] fragments covered before the depth test
     uint32_t depth_only;              // 1: a depth-only scope (SHADOW draws; color == nullptr): raster_kernel_depth stores the depth image and nothing else
-    uint32_t shadowed;                // 1: some MODEL_PBR draw of the scope samples a shadow map (raster_kernel_shadow); 2: a cascade array (raster_kernel_csm)
+    uint32_t shadowed;                // 1: some MODEL_PBR draw of the scope samples a shadow map (raster_kernel_shadow); 2: a cascade array (raster_kernel_csm); 3: ... and some cascaded draw blends (raster_kernel_csm_blend)
     // The IBL set of a scope with MODEL_PBR_IBL draws (mirhi_cmd_bind_ibl: set 3 of pixel/model_pbr_ibl.hlsl; one set per scope; raster_kernel_ibl alone
     // reads these words): base of the irradiance cube (level 0 is sampled), of the prefiltered cube's chain and of the square BRDF LUT -- float4
     // texels in the layouts of include/mirhi.h "IBL precompute" -- with their edge lengths and the prefiltered chain's level count.  0 / nullptr otherwise.

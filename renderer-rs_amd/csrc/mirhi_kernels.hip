@@ -131,7 +131,7 @@ static const RasterEntry k_raster_entries[] = {
     // pixel-parallel only
     PLAIN(2, 0, 0, 1, false), PLAIN(4, 0, 0, 1, false), PLAIN(3, 0, 0, 1, false), PLAIN(1, 0, 0, 1, false),
     PLAIN(2, 1, 0, 1, false), PLAIN(4, 1, 0, 1, false), PLAIN(3, 1, 0, 1, false), PLAIN(1, 1, 0, 1, false),
-    // MODEL_PBR_IBL scopes: per key, with and without the triangle-parallel path, per shadow term (none, single map, cascades)
+    // MODEL_PBR_IBL scopes: per key, with and without the triangle-parallel path, per shadow term (none, single map, cascades, blended cascades)
     IBL(0, 1, 0), IBL(1, 1, 0), IBL(0, 0, 0), IBL(1, 0, 0), IBL(0, 1, 1), IBL(1, 1, 1), IBL(0, 0, 1), IBL(1, 0, 1), IBL(0, 1, 2), IBL(1, 1, 2), IBL(0, 0, 2), IBL(1, 0, 2),
     // the AREA instantiations, in the order of the rows above
     OWN_A(RASTER_DEPTH, raster_kernel_depth, 0, 1), OWN_A(RASTER_DEPTH, raster_kernel_depth, 1, 1), OWN_A(RASTER_DEPTH, raster_kernel_depth, 0, 0), OWN_A(RASTER_DEPTH, raster_kernel_depth, 1, 0),
@@ -144,6 +144,11 @@ static const RasterEntry k_raster_entries[] = {
     PLAIN_A(2, 0, 0, false), PLAIN_A(4, 0, 0, false), PLAIN_A(3, 0, 0, false), PLAIN_A(1, 0, 0, false),
     PLAIN_A(2, 1, 0, false), PLAIN_A(4, 1, 0, false), PLAIN_A(3, 1, 0, false), PLAIN_A(1, 1, 0, false),
     IBL_A(0, 1, 0), IBL_A(1, 1, 0), IBL_A(0, 0, 0), IBL_A(1, 0, 0), IBL_A(0, 1, 1), IBL_A(1, 1, 1), IBL_A(0, 0, 1), IBL_A(1, 0, 1), IBL_A(0, 1, 2), IBL_A(1, 1, 2), IBL_A(0, 0, 2), IBL_A(1, 0, 2),
+    // scopes with a blended cascaded draw, behind every older row so that the code object keeps those in their order: MODEL_PBR, MODEL_PBR_IBL, their AREA forms
+    OWN(RASTER_CSM_BLEND, raster_kernel_csm_blend, 0, 1), OWN(RASTER_CSM_BLEND, raster_kernel_csm_blend, 1, 1), OWN(RASTER_CSM_BLEND, raster_kernel_csm_blend, 0, 0), OWN(RASTER_CSM_BLEND, raster_kernel_csm_blend, 1, 0),
+    IBL(0, 1, 3), IBL(1, 1, 3), IBL(0, 0, 3), IBL(1, 0, 3),
+    OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 0, 1), OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 1, 1), OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 0, 0), OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 1, 0),
+    IBL_A(0, 1, 3), IBL_A(1, 1, 3), IBL_A(0, 0, 3), IBL_A(1, 0, 3),
     // a SKYBOX segment (no key, no bins: one kernel)
     {raster_kernel_id(RASTER_SKY, 0, 0, 0, 1, 0, 4), "sky_kernel", sky_kernel},
     // a recorded transfer command (progs: PassParams::xfer)

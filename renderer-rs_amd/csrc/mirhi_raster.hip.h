@@ -736,6 +736,7 @@ __device__ __forceinline__ void raster_list(const uint4* __restrict__ list, uint
 // draw (PassParams::shadowed, raster_kernel_shadow) -- its own variant, so that the shadow map costs the other PROGS = 4 kernels nothing.
 // SHADOWV = 2: the same with CalculateShadowCSM for scopes with a cascaded draw (PassParams::shadowed = 2, raster_kernel_csm): the resolve hands
 // the winner's depth (SV_Position.z) to the fragment program; again a variant of its own, raster_kernel_shadow keeps its registers.
+// SHADOWV = 3: ... with CalculateShadowCSMBlended for scopes with a blended cascaded draw (PassParams::shadowed = 3, raster_kernel_csm_blend).
 // IBLV (PROGS = 4, one team, four waves, with any SHADOWV): the scope has MODEL_PBR_IBL draws (raster_kernel_ibl); the fragment program reads the
 // IBL set from the parameter block.  Carries the other programs as every PROGS = 4 kernel does.
 // AREA: the scope has a partial render area: the launch spans a sub-range of the tile columns (RasterHead::tile_origin) and every
@@ -1082,10 +1083,10 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
                 const uint32_t tri = prim - D.prim_base;
                 const float pxc = (float)px + 0.5f, pyc = (float)py + 0.5f;
                 if constexpr (IBLV) col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc)
-                                                            : shade_model_program<true, SHADOWV, true>(D, tri, pxc, pyc, SHADOWV == 2 ? __uint_as_float(zkb ^ P.zflip) : 0.0f, R);
+                                                            : shade_model_program<true, SHADOWV, true>(D, tri, pxc, pyc, SHADOWV >= 2 ? __uint_as_float(zkb ^ P.zflip) : 0.0f, R);
                 else if (PROGS == 1) col = shade_triangle_program(D, tri, pxc, pyc);
                 else if (PROGS == 2) col = shade_model_program<false>(D, tri, pxc, pyc);
-                else if (SHADOWV == 2) col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc)      // (a cascaded draw has a depth key: zmask != 0)
+                else if (SHADOWV >= 2) col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc)      // (a cascaded draw has a depth key: zmask != 0)
                                                               : shade_model_program<PROGS == 4, SHADOWV>(D, tri, pxc, pyc, __uint_as_float(zkb ^ P.zflip));
                 else col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc) : shade_model_program<PROGS == 4, SHADOWV>(D, tri, pxc, pyc);
             }
@@ -1144,14 +1145,20 @@ template <int KEYED, int TP, bool AREA = false>
 __global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_csm(const PassParams* __restrict__ params, const RasterHead H) {
     raster_body<4, KEYED, TP, 1, false, 4, 2, false, AREA>(params, H);
 }
+// a scope with a blended cascaded draw (mirhi_cmd_bind_shadow_cascades_blended, threshold > 0): CalculateShadowCSMBlended in the place of CalculateShadowCSM;
+// its unblended cascaded draws run the same program with a threshold of 0
+template <int KEYED, int TP, bool AREA = false>
+__global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_csm_blend(const PassParams* __restrict__ params, const RasterHead H) {
+    raster_body<4, KEYED, TP, 1, false, 4, 3, false, AREA>(params, H);
+}
 // a scope with a MODEL_PBR_IBL draw (mirhi_cmd_bind_ibl): the same shape of kernel again, SHADOWV = the shadow term of its draws (0 none, 1 a single map,
-// 2 cascades: pixel/model_pbr_ibl.hlsl with shadow = 1 / as written, pixel/model_pbr_ibl_csm.hlsl)
+// 2 cascades, 3 blended cascades: pixel/model_pbr_ibl.hlsl with shadow = 1 / as written, pixel/model_pbr_ibl_csm.hlsl, the same with CalculateShadowCSMBlended)
 // Three waves per SIMD, not four: sixteen float4 texels in flight beside the Cook-Torrance state do not fit the 128 registers of occupancy 4 (42 VGPRs
 // spilled, 144 bytes of scratch per lane there); 168 hold them without a spill.  The cascaded variant, which also carries the per-lane cascade matrix
 // and SV_Position.z, still spilled 6 VGPRs at three waves and is compiled for two; running the ambient term ahead of the light loops instead made it 33
 // (DESIGN.md 8e).
 template <int KEYED, int TP, int SHADOWV, bool AREA = false>
-__global__ __launch_bounds__(RASTER_THREADS, (SHADOWV == 2 ? 2 : 3)) void raster_kernel_ibl(const PassParams* __restrict__ params, const RasterHead H) {
+__global__ __launch_bounds__(RASTER_THREADS, (SHADOWV >= 2 ? 2 : 3)) void raster_kernel_ibl(const PassParams* __restrict__ params, const RasterHead H) {
     raster_body<4, KEYED, TP, 1, false, 4, SHADOWV, true, AREA>(params, H);
 }
 // up to MAX_BATCH independent rendering scopes of equal shape (the frames of one mirhi_queue_submit): grid (tiles_x, tile rows, scopes).

@@ -168,7 +168,8 @@ struct ScopeClass {
     bool masked_plain;
     bool tri_prog;            // some draw uses the TRIANGLE program
     bool has_draws;
-    uint32_t shadowed;        // 0, 1: a draw samples a single shadow map, 2: shadow cascades (never both in one scope: record_draw)
+    uint32_t shadowed;        // 0, 1: a draw samples a single shadow map, 2: shadow cascades (never both in one scope: record_draw), 3: cascades, and some cascaded draw
+                              // blends (DrawDesc::csm_blend > 0; an unblended cascaded draw of such a scope is a blended one with threshold 0)
     uint32_t ibl;             // 1: a MODEL_PBR_IBL draw
     // Depth-only scopes, scopes with a shadowed draw and scopes with a MODEL_PBR_IBL draw have raster variants of their own (raster_kernel_depth /
     // _shadow / _csm / _ibl): one team of four waves per tile, single-list bins, plain tile order -- the team and wide selectors leave them alone.
@@ -197,7 +198,7 @@ inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const D
         const DrawDesc& dd = draws[i];
         sampler_state |= dd.program == MIRHI_PROGRAM_MODEL_PBR && draw_has_base_sampler_state(dd);
         c.tri_prog |= dd.program == MIRHI_PROGRAM_TRIANGLE;
-        c.shadowed |= dd.shadow_map ? (dd.shadow_layers ? 2u : 1u) : 0u;
+        c.shadowed |= dd.shadow_map ? (dd.shadow_layers ? (dd.csm_blend > 0.0f ? 3u : 2u) : 1u) : 0u;
         c.ibl |= dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL ? 1u : 0u;
         progs |= dd.program == MIRHI_PROGRAM_TRIANGLE ? PROGS_TRIANGLE : ((dd.program == MIRHI_PROGRAM_MODEL_PBR || dd.program == MIRHI_PROGRAM_MODEL_PBR_IBL || dd.tex_any_mips || dd.tex_srgb || draw_has_sampler_state(dd)) ? PROGS_PBR : PROGS_MODEL);
     }
@@ -210,8 +211,9 @@ inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const D
                      c.key.pred == 0u && !sampler_state;
     c.ordered = s.key_set && (s.blend[0] != 0 || (s.discard != 0 && !c.masked_plain) || s.order_dependent_depth());
     c.own_family = depth_only || c.shadowed || c.ibl;
-    if (c.shadowed) progs = PROGS_PBR | PROGS_SHADOWED | (c.shadowed == 2u ? PROGS_CASCADED : 0u);
-    if (c.ibl) progs = PROGS_PBR | PROGS_IBL | (c.shadowed ? PROGS_SHADOWED : 0u) | (c.shadowed == 2u ? PROGS_CASCADED : 0u);
+    const uint32_t cascaded = (c.shadowed >= 2u ? PROGS_CASCADED : 0u) | (c.shadowed == 3u ? PROGS_CSM_BLEND : 0u);
+    if (c.shadowed) progs = PROGS_PBR | PROGS_SHADOWED | cascaded;
+    if (c.ibl) progs = PROGS_PBR | PROGS_IBL | (c.shadowed ? PROGS_SHADOWED : 0u) | cascaded;
     c.programs = depth_only ? PROGS_DEPTH_ONLY : (progs ? progs : PROGS_TRIANGLE);
     return c;
 }

@@ -439,12 +439,9 @@ __device__ __forceinline__ float calculate_shadow(DrawRef D, f3 worldPos, f3 nor
 // clipSpaceDepth = SV_Position.z: the depth the raster kernel resolved for the pixel (the bits a D32 attachment stores).
 // The cascade index differs from lane to lane, so the selected matrix is fetched with per-lane vector loads (four 16-byte loads from a block
 // every wave of the scope keeps in cache); splits, biases and the map size stay wave-uniform scalar loads.
-__device__ __forceinline__ float calculate_shadow_csm(DrawRef D, f3 worldPos, f3 normal, f3 lightDir, float clipSpaceDepth) {
-    const CBytePtr S = cb(D.shadow_data);
-    uint32_t cascadeIndex = 0;                                                                  // :57
-#pragma unroll
-    for (uint32_t i = 0; i < 3u; ++i)                                                           // :62-68 (the last split passed, not the first)
-        if (clipSpaceDepth > ldcf(S, 80u * i + 64u)) cascadeIndex = i + 1u;
+// SampleCascadePCF (:90-146) of one cascade, written once: CalculateShadowCSM samples the selected cascade with it, CalculateShadowCSMBlended that
+// one and, in a blend region, the next.
+__device__ __forceinline__ float sample_cascade_pcf(DrawRef D, CBytePtr S, uint32_t cascadeIndex, f3 worldPos, f3 normal, f3 lightDir) {
     const float4* const mp = reinterpret_cast<const float4*>(D.shadow_data + 80u * cascadeIndex);   // :176 Cascades[cascadeIndex].ViewProjection
     const float4 c0 = mp[0], c1 = mp[1], c2 = mp[2], c3 = mp[3];                                // (columns: the matrix convention of mat4_mul)
     const float texelSize = rcp_rn_nb(ldcf(S, 328));                                            // :179
@@ -476,6 +473,48 @@ __device__ __forceinline__ float calculate_shadow_csm(DrawRef D, f3 worldPos, f3
             shadow += dref <= layer[(uint32_t)fj * D.shadow_w + (uint32_t)fi] ? 1.0f : 0.0f;
         }
     return div_rn_nb(shadow, 9.0f);                                                             // :145
+}
+__device__ __forceinline__ uint32_t select_cascade(CBytePtr S, float clipSpaceDepth) {
+    uint32_t cascadeIndex = 0;                                                                  // :57
+#pragma unroll
+    for (uint32_t i = 0; i < 3u; ++i)                                                           // :62-68 (the last split passed, not the first)
+        if (clipSpaceDepth > ldcf(S, 80u * i + 64u)) cascadeIndex = i + 1u;
+    return cascadeIndex;
+}
+__device__ __forceinline__ float calculate_shadow_csm(DrawRef D, f3 worldPos, f3 normal, f3 lightDir, float clipSpaceDepth) {
+    const CBytePtr S = cb(D.shadow_data);
+    return sample_cascade_pcf(D, S, select_cascade(S, clipSpaceDepth), worldPos, normal, lightDir);
+}
+// CalculateShadowCSMBlended (shadow_csm.hlsli:212-277), line for line: the primary cascade's PCF and, for a lane within blendThreshold of its
+// cascade's range in front of the split, the next cascade's, blended by the distance to the split.  Cascade index and blend region are per
+// lane, so the second sample is a divergent branch with a second per-lane matrix fetch.  One PCF body walked at most twice (the first trip's result
+// is carried in one register), not two inlined copies: the kernel keeps the registers of raster_kernel_csm.  blendThreshold 0 (an
+// unblended draw in a blended scope): blendRegion = 0, no lane takes the second trip, the bits of calculate_shadow_csm.
+__device__ __forceinline__ float calculate_shadow_csm_blended(DrawRef D, f3 worldPos, f3 normal, f3 lightDir, float clipSpaceDepth, float blendThreshold) {
+    const CBytePtr S = cb(D.shadow_data);
+    const uint32_t cascadeIndex = select_cascade(S, clipSpaceDepth);                            // :223
+    const float s0 = ldcf(S, 64u), s1 = ldcf(S, 144u), s2 = ldcf(S, 224u);
+    const float splitDepth = cascadeIndex == 0u ? s0 : (cascadeIndex == 1u ? s1 : s2);          // :244 (read under cascadeIndex < 3 only)
+    const float prevSplit = cascadeIndex == 0u ? 0.0f : (cascadeIndex == 1u ? s0 : s1);         // :245-246
+    const float cascadeRange = splitDepth - prevSplit;                                          // :247
+    const float blendRegion = cascadeRange * blendThreshold;                                    // :248
+    const float distanceToEdge = splitDepth - clipSpaceDepth;                                   // :251
+    const bool blend = cascadeIndex < 3u && distanceToEdge < blendRegion && distanceToEdge > 0.0f;   // :242, :253
+    float shadow = 0.0f;
+    uint32_t index = cascadeIndex;
+#pragma nounroll
+    for (uint32_t trip = 0u;; ++trip) {
+        const float s = sample_cascade_pcf(D, S, index, worldPos, normal, lightDir);            // :228-239, :258-269
+        if (trip != 0u) {
+            const float blendFactor = div_rn_nb(distanceToEdge, blendRegion);                   // :255
+            shadow = s + blendFactor * (shadow - s);                                            // :272 lerp(nextShadow, shadow, blendFactor)
+            break;
+        }
+        shadow = s;
+        if (!blend) break;
+        index = cascadeIndex + 1u;
+    }
+    return shadow;                                                                              // :276
 }
 
 // The Cook-Torrance programs, pixel/model_pbr.hlsl:159-320 and pixel/model_pbr_ibl.hlsl:199-396 / model_pbr_ibl_csm.hlsl, after the shared varying
@@ -523,7 +562,7 @@ __device__ __forceinline__ PbrSurface pbr_surface(DrawRef D, const float b[3], c
 }
 // Lo of model_pbr.hlsl:229-305 = model_pbr_ibl.hlsl:275-346 (model_pbr_ibl_csm.hlsl:275-347).  SHADOW 1: the directional light's shadow term
 // (model_pbr.hlsl:238-251) for draws with a shadow map bound; 2: CalculateShadowCSM instead (pixel/model_pbr_ibl_csm.hlsl:280-298) for draws with
-// cascades bound, clipz = SV_Position.z
+// cascades bound, clipz = SV_Position.z; 3: CalculateShadowCSMBlended for scopes with a blended cascaded draw (DrawDesc::csm_blend)
 template <int SHADOW>
 __device__ __forceinline__ f3 pbr_direct_lighting(DrawRef D, f3 worldPos, f3 V, f3 N, const PbrMaterial& m, float clipz) {
     f3 lighting = {0.0f, 0.0f, 0.0f};
@@ -535,7 +574,8 @@ __device__ __forceinline__ f3 pbr_direct_lighting(DrawRef D, f3 worldPos, f3 V, 
             if (intensity != 0.0f) lighting = add3(lighting, pbr_direct(N, V, normalize3({-dir.x, -dir.y, -dir.z}), scale3(color, intensity), m));
         } else if (intensity != 0.0f) {                                                  // (intensity 0: exact zeros, shadow or not)
             const f3 L = normalize3({-dir.x, -dir.y, -dir.z});
-            const float shadow = SHADOW == 2 ? calculate_shadow_csm(D, worldPos, N, L, clipz)      // model_pbr_ibl_csm.hlsl:285-293
+            const float shadow = SHADOW == 3 ? calculate_shadow_csm_blended(D, worldPos, N, L, clipz, D.csm_blend)      // (:212-277 in the place of :163-194)
+                               : SHADOW == 2 ? calculate_shadow_csm(D, worldPos, N, L, clipz)      // model_pbr_ibl_csm.hlsl:285-293
                                              : calculate_shadow(D, worldPos, N, L);                // model_pbr.hlsl:238-245
             lighting = add3(lighting, scale3(pbr_direct(N, V, L, scale3(color, intensity), m), shadow));   // :251
         }

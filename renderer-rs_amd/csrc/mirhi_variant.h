@@ -17,10 +17,13 @@ enum : uint32_t {
     PROGS_IBL = 32u,          // a MODEL_PBR_IBL draw (always together with PROGS_PBR; with PROGS_SHADOWED / PROGS_CASCADED when its draws are shadowed): raster_kernel_ibl
     PROGS_SKY = 64u,          // the VALUE 64, alone: a SKYBOX segment (one SKYBOX draw, no triangles or bins): sky_kernel
     PROGS_TRANSFER = 128u,    // the VALUE 128, alone: a recorded transfer command (no scope at all): the kernels of mirhi_transfer.hip.h, by PassParams::xfer
+    PROGS_CSM_BLEND = 256u,   // a bit again (64 and 128 are values used alone: the first free bit above them): some cascaded draw's shadow term is
+                              // CalculateShadowCSMBlended with a threshold > 0 (always together with PROGS_CASCADED): raster_kernel_csm_blend, the blended raster_kernel_ibl
 };
 
-// (RASTER_IBL behind RASTER_ORDERED, RASTER_SKY behind RASTER_IBL, RASTER_TRANSFER behind RASTER_SKY: the values of the families before them are recorded in tests/golden/raster_variants.json)
-enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY, RASTER_TRANSFER };
+// (RASTER_IBL behind RASTER_ORDERED, RASTER_SKY behind RASTER_IBL, RASTER_TRANSFER behind RASTER_SKY, RASTER_CSM_BLEND behind RASTER_TRANSFER: the values of the
+// families before them are recorded in tests/golden/raster_variants.json)
+enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY, RASTER_TRANSFER, RASTER_CSM_BLEND };
 
 // the kernel instantiation alone (no launch shape) as one word
 constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves, uint32_t area = 0u) {
@@ -31,7 +34,7 @@ constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t ke
 // instantiation with the same launch shape.
 struct RasterVariant {
     RasterFamily family;
-    uint32_t progs;           // PROGS of raster_kernel / raster_kernel_wide / ordered_kernel: 1 .. 4 (0: the family takes none); RASTER_IBL: its SHADOWV, 0 .. 2
+    uint32_t progs;           // PROGS of raster_kernel / raster_kernel_wide / ordered_kernel: 1 .. 4 (0: the family takes none); RASTER_IBL: its SHADOWV, 0 .. 3
     uint32_t keyed;           // KEYED: 0 the plain key (raw float bits: LESS / LESS_OR_EQUAL), 1 the generic key, 2 predicate mode
     uint32_t tp;              // TP: 1 = with the triangle-parallel path
     uint32_t teams;           // TEAMS: 1, or 2 (the two-team mesh variants)
@@ -78,11 +81,11 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
         // a scope with a MODEL_PBR_IBL draw: a family of its own like the shadowed ones (one team of four waves, single-list bins, plain tile order, an
         // ordered key), one kernel per shadow term of its draws
         v.family = RASTER_IBL;
-        v.progs = (programs & PROGS_CASCADED) ? 2u : ((programs & PROGS_SHADOWED) ? 1u : 0u);
+        v.progs = (programs & PROGS_CSM_BLEND) ? 3u : ((programs & PROGS_CASCADED) ? 2u : ((programs & PROGS_SHADOWED) ? 1u : 0u));
     } else if (programs == PROGS_DEPTH_ONLY || (programs & PROGS_SHADOWED)) {
         // depth-only scopes and scopes with a shadowed draw have variants of their own, whatever the selectors below would pick (the host keeps
         // them on one team of four waves, single-list bins and the plain tile order; their key is an ordered one, never a predicate)
-        v.family = programs == PROGS_DEPTH_ONLY ? RASTER_DEPTH : ((programs & PROGS_CASCADED) ? RASTER_CSM : RASTER_SHADOW);
+        v.family = programs == PROGS_DEPTH_ONLY ? RASTER_DEPTH : ((programs & PROGS_CSM_BLEND) ? RASTER_CSM_BLEND : ((programs & PROGS_CASCADED) ? RASTER_CSM : RASTER_SHADOW));
         v.progs = 0u;
     } else if (P.raster_wide && allow_wide && !P.pred && tp && !P.alpha_scope && mesh && P.xcd_swizzle <= 1u && !area) {
         // the wide mesh variants: eight or sixteen waves per tile (host-side choice, PassParams::raster_wide = waves per tile)

@@ -508,6 +508,10 @@ public:
     void bind_shadow_cascades(const Image* array, const Buffer* params, uint64_t offset = 0, uint64_t range = 0) const {
         check(mirhi_cmd_bind_shadow_cascades(h_, array ? array->handle() : nullptr, params ? params->handle() : nullptr, offset, range));
     }
+    // ... with cascade blending (CalculateShadowCSMBlended, shadow_csm.hlsli:212-277): blend_threshold in [0, 1]; 0 records what bind_shadow_cascades records
+    void bind_shadow_cascades_blended(const Image* array, const Buffer* params, float blend_threshold, uint64_t offset = 0, uint64_t range = 0) const {
+        check(mirhi_cmd_bind_shadow_cascades_blended(h_, array ? array->handle() : nullptr, params ? params->handle() : nullptr, offset, range, blend_threshold));
+    }
     // set 3 of pixel/model_pbr_ibl.hlsl:133-155: irradiance cube, prefiltered cube, BRDF LUT of ShaderProgram::ModelPbrIbl draws; three nullptr unbind
     void bind_ibl(const Image* irradiance, const Image* prefiltered, const Image* brdf_lut) const {
         check(mirhi_cmd_bind_ibl(h_, irradiance ? irradiance->handle() : nullptr, prefiltered ? prefiltered->handle() : nullptr, brdf_lut ? brdf_lut->handle() : nullptr));

@@ -302,6 +302,7 @@ class DrawSpec:
     blend: Optional[tuple] = None         # None = opaque; else (src colour, dst colour, colour op, src alpha, dst alpha, alpha op, write mask)
     depth_bias: Optional[tuple] = None    # pipeline depth bias (constant_factor, clamp, slope_factor), pipeline.rs:781-788; None = off
     depth_clamp: bool = False             # pipeline depth_clamp_enable (pipeline.rs:769)
+    csm_blend: Optional[float] = None     # a cascaded draw's own blend threshold (bind_shadow_cascades(..., blend_threshold=)); None = CascadeSpec.blend_threshold
 
     @property
     def textures(self):
@@ -348,6 +349,7 @@ class CascadeSpec:
     load_op: int = LOAD_OP_CLEAR
     depth_bias: Optional[tuple] = None    # the map's pipelines: depth bias (constant_factor, clamp, slope_factor) of casters that set none themselves
     depth_clamp: bool = False             # ... and depth_clamp_enable ("pancaking": casters in front of the light's near plane stay in the map at depth 0)
+    blend_threshold: float = 0.0          # blendThreshold of CalculateShadowCSMBlended (bind_shadow_cascades(..., blend_threshold=)); 0: CalculateShadowCSM
 
 
 @dataclass
@@ -1207,14 +1209,29 @@ class Cascades:
     half_extents: List[float]             # per cascade: half the side of its square light frustum (world units)
 
 
+CSM_RADIUS_QUANTUM = 1.0 / 16.0                                     # world units a stabilised cascade's radius is rounded up to
+
+
 def csm_cascades(view: np.ndarray, proj: np.ndarray, light_dir, near: float, far: float, count: int = CASCADE_COUNT, lam: float = 0.5,
-                 caster_margin: float = 8.0) -> Cascades:
+                 caster_margin: float = 8.0, stabilize: bool = False, map_size=None) -> Cascades:
     """Splits the camera frustum between the view distances near and far into `count` slices (csm_split_distances) and gives each an
     orthographic light matrix that encloses it: the light looks along light_dir at the slice's centre, its square frustum is the slice's
     bounding box in light space (padded by 0.1 %), pulled back towards the light by caster_margin so that casters between the light and
     the slice are kept.  The split depth is what the camera's projection gives the split distance, i.e. SV_Position.z of a fragment there
     (viewport depth range 0..1).  The reference has no host code for cascades (no file under crates/ mentions one): this is this build's
-    own, as small as the containment test needs -- no texel snapping, no stabilisation."""
+    own, as small as the containment test needs -- no texel snapping, no stabilisation.
+    stabilize=True (map_size, a layer's edge in texels, is then required): the cascades of a camera that moves.  Cascade k's matrix is a function
+    of the light direction, a quantised radius and a snapped centre, and of nothing else:
+      radius   the bounding sphere of the slice's eight corners about their mean, taken in VIEW space (where the corners do not depend on the
+               pose: the same float for every camera position and orientation), rounded up to a multiple of CSM_RADIUS_QUANTUM and padded by one
+               texel: R = Rq / (1 - 2 / map_size), so that R = Rq + texel with texel = 2 R / map_size -- the snapped frustum still holds the sphere
+      basis    look_at_rh from the origin along light_dir with the fixed up vector: no pose in it
+      frustum  square, side 2 R about the snapped centre; the eye R + caster_margin in front of it, zn = 0.1, zf = 2 R + caster_margin
+      snapping the centre's three light-space coordinates to whole multiples of texel, with floor
+    The matrix is put together in float64 from those numbers and rounded to float32 once: only its translation column knows the pose, in whole
+    texels, so a fixed world point's texel coordinates move by whole texels from pose to pose and no shadow edge crawls.  half_extents[k] = R."""
+    if stabilize:
+        assert map_size is not None and int(map_size) > 2, "stabilize=True needs map_size"
     dist = np.concatenate([[float(near)], csm_split_distances(near, far, count, lam)])
     p64, inv_view = proj.astype(np.float64), np.linalg.inv(view.astype(np.float64).T)      # maths (row-major) inverse view
     tx, ty = 1.0 / abs(p64[0, 0]), 1.0 / abs(p64[1, 1])                                  # tan of the half angles
@@ -1228,6 +1245,24 @@ def csm_cascades(view: np.ndarray, proj: np.ndarray, light_dir, near: float, far
                 for sy in (-1.0, 1.0):
                     cs.append((inv_view @ np.array([sx * dd * tx, sy * dd * ty, -dd, 1.0]))[:3])
         cs = np.array(cs)
+        if stabilize:
+            vs = np.array([[sx * dd * tx, sy * dd * ty, -dd] for dd in (dist[k], dist[k + 1]) for sx in (-1.0, 1.0) for sy in (-1.0, 1.0)])
+            vc = vs.mean(axis=0)
+            rq = math.ceil(float(np.linalg.norm(vs - vc, axis=1).max()) / CSM_RADIUS_QUANTUM) * CSM_RADIUS_QUANTUM
+            r = rq / (1.0 - 2.0 / float(map_size))
+            texel = 2.0 * r / float(map_size)
+            rot = look_at_rh((0.0, 0.0, 0.0), d, up).astype(np.float64)[:3, :3]                   # the light basis: p @ rot = (p.s, p.u, -p.f)
+            lc = (inv_view @ np.array([vc[0], vc[1], vc[2], 1.0]))[:3] @ rot
+            cx, cy, dc = (math.floor(float(c) / texel) * texel for c in (lc[0], lc[1], -lc[2]))
+            zn, zf = 0.1, 2.0 * r + float(caster_margin)
+            e = dc - (r + float(caster_margin))                                                  # the eye's depth along the light
+            m = np.zeros((4, 4), dtype=np.float64)
+            m[:3, 0], m[:3, 1], m[:3, 2] = rot[:, 0] / r, rot[:, 1] / r, -rot[:, 2] / (zf - zn)
+            m[3] = [-cx / r, -cy / r, -(e + zn) / (zf - zn), 1.0]
+            mats.append(m.astype(f32))
+            corners_all.append(cs)
+            halves.append(float(r))
+            continue
         centre = cs.mean(axis=0)
         radius = float(np.linalg.norm(cs - centre, axis=1).max())
         eye = centre - d * (radius + caster_margin)
@@ -1259,23 +1294,78 @@ def csm_factor(layers, matrices, split_depths, world_pos, normal, light_dir, cli
     (outside: 1.0), adaptive bias max(bias * (1 - N.L), 0.0005), nine taps at uv + (x, y) / map_size, / 9.  Geometry in float64; the
     texel decisions and the comparison as the sampler is specified.  layers: (4, H, W); world_pos (..., 3); normal (..., 3) or (3,);
     light_dir: towards the light; clip_depth (...)."""
+    idx = csm_select(split_depths, clip_depth)
+    per = csm_cascade_samples(layers, matrices, world_pos, normal, light_dir, bias, normal_bias, map_size)
+    out = np.ones(idx.shape, dtype=np.float64)
+    for k in range(CASCADE_COUNT):
+        out = np.where(idx == k, per[k], out)
+    return out
+
+
+def csm_cascade_samples(layers, matrices, world_pos, normal, light_dir, bias: float, normal_bias: float, map_size: float) -> np.ndarray:
+    """SampleCascadePCF (shadow_csm.hlsli:90-146) of every sample in every cascade, (4, ...): the per-cascade sampler that csm_factor and
+    csm_factor_blended share (csm_factor says what it computes)."""
     wp = np.asarray(world_pos, dtype=np.float64)
     n = np.broadcast_to(np.asarray(normal, dtype=np.float64), wp.shape)
     l = np.asarray(light_dir, dtype=np.float64)
-    idx = csm_select(split_depths, clip_depth)
     off = wp + n * float(normal_bias)
     p4 = np.concatenate([off, np.ones(off.shape[:-1] + (1,))], axis=-1)
     ndotl = (n * l).sum(axis=-1)
     ab = np.maximum(float(bias) * (1.0 - ndotl), 0.0005)
-    out = np.ones(idx.shape, dtype=np.float64)
+    out = []
     for k in range(CASCADE_COUNT):
         clip = p4 @ np.asarray(matrices[k], dtype=np.float64)
         pc = clip[..., :3] / clip[..., 3:4]
         u, v, z = pc[..., 0] * 0.5 + 0.5, 1.0 - (pc[..., 1] * 0.5 + 0.5), pc[..., 2]
         inside = (u >= 0.0) & (u <= 1.0) & (v >= 0.0) & (v <= 1.0) & (z >= 0.0) & (z <= 1.0)
         s = pcf_factor(np.asarray(layers[k]), u, v, z - ab, texel=(1.0 / map_size, 1.0 / map_size))
-        out = np.where(idx == k, np.where(inside, s, 1.0), out)
-    return out
+        out.append(np.where(inside, s, 1.0))
+    return np.array(out, dtype=np.float64)
+
+
+def csm_blend_terms(split_depths, clip_depth, blend_threshold: float, dtype=f32):
+    """The per-sample decisions of CalculateShadowCSMBlended (shadow_csm.hlsli:242-255) in float32, as the device takes them and as csm_select
+    compares: (idx, blending, distanceToEdge, blendRegion).  blending: cascadeIndex < 3 and 0 < distanceToEdge < blendRegion; prevSplit of
+    cascade 0 is 0.  dtype=np.float64: the same in float64 -- the function of a real depth, for statements about its continuity."""
+    cd = np.asarray(clip_depth, dtype=dtype)
+    sd = np.array([split_depths[i] for i in range(CASCADE_COUNT - 1)], dtype=dtype)
+    idx = np.zeros(cd.shape, dtype=np.int64)
+    for i in range(CASCADE_COUNT - 1):                             # csm_select, in dtype
+        idx = np.where(cd > sd[i], i + 1, idx)
+    k = np.minimum(idx, CASCADE_COUNT - 2)
+    split = sd[k]
+    prev = np.where(k == 0, dtype(0.0), sd[np.maximum(k - 1, 0)]).astype(dtype)
+    region = ((split - prev).astype(dtype) * dtype(blend_threshold)).astype(dtype)
+    dist = (split - cd).astype(dtype)
+    blending = (idx < CASCADE_COUNT - 1) & (dist < region) & (dist > dtype(0.0))
+    return idx, blending, dist, region
+
+
+def csm_factor_blended(layers, matrices, split_depths, world_pos, normal, light_dir, clip_depth, bias: float, normal_bias: float,
+                       map_size: float, blend_threshold: float, depth_dtype=f32) -> np.ndarray:
+    """Numpy model of CalculateShadowCSMBlended (shadow_csm.hlsli:212-277) over csm_factor's per-cascade sampler: the selected cascade's
+    SampleCascadePCF and, where csm_blend_terms says the sample blends, lerp(nextShadow, shadow, distanceToEdge / blendRegion) =
+    nextShadow + f (shadow - nextShadow) with the next cascade's, in float64."""
+    idx, blending, dist, region = csm_blend_terms(split_depths, clip_depth, blend_threshold, depth_dtype)
+    per = csm_cascade_samples(layers, matrices, world_pos, normal, light_dir, bias, normal_bias, map_size)
+    shadow = np.ones(idx.shape, dtype=np.float64)
+    nxt = np.ones(idx.shape, dtype=np.float64)
+    for k in range(CASCADE_COUNT):
+        shadow = np.where(idx == k, per[k], shadow)
+        if k + 1 < CASCADE_COUNT:
+            nxt = np.where(idx == k, per[k + 1], nxt)
+    f = np.where(blending, dist.astype(np.float64) / np.where(blending, region, 1.0).astype(np.float64), 1.0)
+    return np.where(blending, nxt + f * (shadow - nxt), shadow)
+
+
+CSM_DEBUG_COLORS = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [1.0, 1.0, 0.0]], dtype=f32)      # shadow_csm.hlsli:293-298
+
+
+def csm_debug_colors(split_depths, depth) -> np.ndarray:
+    """GetCascadeDebugColor (shadow_csm.hlsli:289-301) on a read-back depth image: red, green, blue, yellow for cascades 0 .. 3 of SelectCascade,
+    (..., 3) float32.  Host only -- the reference calls the function nowhere, and a read-back D32 attachment holds SV_Position.z: a way to look at
+    the split layout of a frame."""
+    return CSM_DEBUG_COLORS[csm_select(split_depths, depth)]
 
 
 CASCADED_GROUND_LIGHT = (0.6, -1.0, 0.2)
@@ -1301,12 +1391,14 @@ def cascaded_ground_boxes(lam: float = CASCADED_GROUND_LAM):
 
 
 def cascaded_ground_case(width: int = 480, height: int = 360, map_size: int = 2048, light_dir=CASCADED_GROUND_LIGHT,
-                         intensity: float = 2.0, lam: float = CASCADED_GROUND_LAM) -> Scene:
+                         intensity: float = 2.0, lam: float = CASCADED_GROUND_LAM, stabilize: bool = False, blend_threshold: float = 0.0,
+                         eye=CASCADED_GROUND_EYE, target=CASCADED_GROUND_TARGET) -> Scene:
     """A long MODEL_PBR ground strip receding from a perspective camera, a caster box in each cascade's depth range and the displaced
-    sphere, under one directional light; every box and the sphere are casters of all four cascade scopes."""
-    view, proj, cam = default_camera(width, height, eye=CASCADED_GROUND_EYE, target=CASCADED_GROUND_TARGET)
+    sphere, under one directional light; every box and the sphere are casters of all four cascade scopes.  stabilize: texel-snapped cascades
+    (csm_cascades); blend_threshold: CascadeSpec.blend_threshold; eye / target: the camera's pose (a camera that moves over the fixed scene)."""
+    view, proj, cam = default_camera(width, height, eye=eye, target=target)
     light = light_ubo(direction=light_dir, intensity=intensity, color=(1.0, 0.97, 0.9))
-    cas = csm_cascades(view, proj, light_dir, *CASCADED_GROUND_RANGE, lam=lam)
+    cas = csm_cascades(view, proj, light_dir, *CASCADED_GROUND_RANGE, lam=lam, stabilize=stabilize, map_size=map_size if stabilize else None)
     pos = np.array([[-40.0, 0.0, 8.0], [40.0, 0.0, 8.0], [40.0, 0.0, -90.0], [-40.0, 0.0, -90.0]])
     gv = _pack_vertex48(pos, np.tile(np.array([0.0, 1.0, 0.0]), (4, 1)), np.array([[0, 0], [1, 0], [1, 1], [0, 1]], dtype=f32),
                         np.tile(np.array([1.0, 0.0, 0.0, 1.0]), (4, 1)))
@@ -1329,5 +1421,6 @@ def cascaded_ground_case(width: int = 480, height: int = 360, map_size: int = 20
                           material=pbr_material_ubo((0.2, 0.4, 0.8, 1.0), 0.3, 0.4)))
     casters = [[DrawSpec(vertices=v, stride=48, count=int(i.size), indices=i, program=PROGRAM_SHADOW, cull_mode=cull,
                          camera=shadow_constants_ubo(flip_clip_y(m), model)) for v, i, model, cull in meshes] for m in cas.matrices]
-    spec = CascadeSpec(casters, (map_size, map_size), csm_ubo(cas.matrices, cas.split_depths, 0.005, 0.01, float(map_size)))
+    spec = CascadeSpec(casters, (map_size, map_size), csm_ubo(cas.matrices, cas.split_depths, 0.005, 0.01, float(map_size)),
+                       blend_threshold=float(blend_threshold))
     return Scene("cascaded-ground", width, height, draws, clear_color=(0.02, 0.02, 0.03, 1.0), cascades=spec)

@@ -2,7 +2,8 @@
 """Per-dispatch device times of cascaded shadow maps (mirhi_device_timeline), one GPU process, the method of tools/shadow_times.py:
   (d) the lit MODEL_PBR raster of cascaded_ground_case at 1920 x 1080 with the cascade array bound (raster_kernel_csm), with nothing bound
       (variant 4) and with one single shadow map bound (raster_kernel_shadow);
-  (e) its four depth-only scopes (vertex / geometry / raster per layer) at 1024^2 and 2048^2 layers.
+  (e) its four depth-only scopes (vertex / geometry / raster per layer) at 1024^2 and 2048^2 layers;
+  (f) the lit raster with blended cascades (raster_kernel_csm_blend) at thresholds 0.1 and 1.0, and with stabilised cascades.
 Prints one JSON object (median microseconds per dispatch over the timed repeats) with the build id."""
 import dataclasses
 import json
@@ -27,6 +28,15 @@ def main():
         res.destroy()
         out[f"e_four_depth_scopes_{size}"] = {k: v for k, v in t.items() if not k.endswith("[4]")}
         out[f"d_pbr_with_cascades_{size}"] = {k: v for k, v in t.items() if k.endswith("[4]")}
+    # (f) the lit scope with blended cascades (raster_kernel_csm_blend) at thresholds 0.1 and 1.0, beside d_pbr_with_cascades_2048 of this run: 0.1 is what
+    # a frame uses (few lanes take the second sample), 1.0 bounds the cost from above (every lane of cascades 0..2 takes it); stabilised cascades and
+    # threshold 0 (raster_kernel_csm again) beside them, for the cost of the coarser texels alone
+    for name, kw in (("f_pbr_blended_0.1_2048", dict(blend_threshold=0.1)), ("f_pbr_blended_1.0_2048", dict(blend_threshold=1.0)),
+                     ("f_pbr_stabilised_unblended_2048", dict(stabilize=True)), ("f_pbr_stabilised_blended_0.1_2048", dict(stabilize=True, blend_threshold=0.1))):
+        res = m.SceneResources(dev, S.cascaded_ground_case(1920, 1080, map_size=2048, **kw), m.Format.B8G8R8A8_SRGB)
+        t = st.per_kernel(st.timed(dev, res.render), n_scopes=5)
+        res.destroy()
+        out[name] = {k: v for k, v in t.items() if k.endswith("[4]")}
     scene = S.cascaded_ground_case(1920, 1080, map_size=2048)
     plain = dataclasses.replace(scene, cascades=None)
     res = m.SceneResources(dev, plain, m.Format.B8G8R8A8_SRGB)
