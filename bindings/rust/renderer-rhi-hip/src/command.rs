@@ -25,14 +25,21 @@ pub struct RenderingInfo<'a> {
     pub color: &'a Image, pub color_load_op: LoadOp, pub color_store_op: StoreOp, pub clear_color: [f32; 4],
     pub depth: Option<&'a Image>, pub depth_load_op: LoadOp, pub depth_store_op: StoreOp, pub clear_depth: f32,
     pub render_area: Rect2D,
+    /// ColorAttachment::with_resolve / DepthAttachment::with_resolve (rendering.rs:238, :477): the 1x images a multisampled scope resolves to
+    pub color_resolve: Option<&'a Image>, pub depth_resolve: Option<&'a Image>,
 }
 impl<'a> RenderingInfo<'a> {
     /// rendering.rs defaults: colour CLEAR/STORE to (0,0,0,1); depth CLEAR/DONT_CARE to 1.0 (1027-1073)
     pub fn new(color: &'a Image) -> Self {
         Self { color, color_load_op: LoadOp::Clear, color_store_op: StoreOp::Store, clear_color: [0.0, 0.0, 0.0, 1.0],
                depth: None, depth_load_op: LoadOp::Clear, depth_store_op: StoreOp::DontCare, clear_depth: 1.0,
-               render_area: Rect2D { x: 0, y: 0, width: color.width(), height: color.height() } }
+               render_area: Rect2D { x: 0, y: 0, width: color.width(), height: color.height() }, color_resolve: None, depth_resolve: None }
     }
+    /// rendering.rs:238: `color` is a multisampled image (`Image::new_multisampled`) whose four samples are averaged into `target` (AVERAGE); the
+    /// multisampled contents are transient (store DONT_CARE).
+    pub fn with_resolve(mut self, target: &'a Image) -> Self { self.color_resolve = Some(target); self.color_store_op = StoreOp::DontCare; self }
+    /// rendering.rs:477: sample 0 of the multisampled depth attachment is written to `target` (SAMPLE_ZERO).
+    pub fn with_depth_resolve(mut self, target: &'a Image) -> Self { self.depth_resolve = Some(target); self }
     /// rendering.rs:818-838: the scope loads, clears, draws and stores inside `area` only; no pixel outside is written.
     pub fn with_render_area(mut self, area: Rect2D) -> Self { self.render_area = area; self }
     pub fn with_offset(mut self, x: i32, y: i32) -> Self { self.render_area.x = x; self.render_area.y = y; self }
@@ -73,7 +80,14 @@ impl CommandBuffer {
         ri.depth_image = info.depth.map_or(std::ptr::null_mut(), |d| d.raw);
         ri.depth_load_op = info.depth_load_op as i32; ri.depth_store_op = info.depth_store_op as i32; ri.clear_depth = info.clear_depth;
         ri.render_area = [info.render_area.x, info.render_area.y, info.render_area.width as i32, info.render_area.height as i32];
-        check(unsafe { mirhi_sys::mirhi_cmd_begin_rendering(self.raw, &ri) })
+        let res = mirhi_sys::mirhi_resolve_info {
+            color_resolve_image: info.color_resolve.map_or(std::ptr::null_mut(), |i| i.raw),
+            color_resolve_mode: if info.color_resolve.is_some() { mirhi_sys::MIRHI_RESOLVE_AVERAGE } else { mirhi_sys::MIRHI_RESOLVE_NONE },
+            depth_resolve_image: info.depth_resolve.map_or(std::ptr::null_mut(), |i| i.raw),
+            depth_resolve_mode: if info.depth_resolve.is_some() { mirhi_sys::MIRHI_RESOLVE_SAMPLE_ZERO } else { mirhi_sys::MIRHI_RESOLVE_NONE },
+        };
+        // (no resolve on a 1x scope: exactly mirhi_cmd_begin_rendering)
+        check(unsafe { mirhi_sys::mirhi_cmd_begin_rendering_resolve(self.raw, &ri, &res) })
     }
     /// A depth-only scope (shadow pass, ShaderProgram::Shadow draws only): no colour attachment, `depth` stored; its extent is the render area.
     pub fn begin_rendering_depth_only(&self, depth: &Image, depth_load_op: LoadOp, clear_depth: f32) -> RhiResult<()> {

@@ -33,6 +33,15 @@ impl Image {
         check(unsafe { mirhi_sys::mirhi_image_create_layer_view(self.raw, layer, &mut raw) })?;
         Ok(Self { device: self.device.clone(), raw })
     }
+    /// The transient attachment of a 4x multisampled scope (`samples` = 4): it owns no memory and is nothing but an attachment --
+    /// `RenderingInfo::with_resolve` names the 1x image its averaged colour is written to.
+    pub fn new_multisampled(device: Arc<Device>, width: u32, height: u32, format: Format, samples: u32) -> RhiResult<Self> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { mirhi_sys::mirhi_image_create_multisampled(device.raw, width, height, format as i32, samples, &mut raw) })?;
+        Ok(Self { device, raw })
+    }
+    /// 4 for a multisampled image, 1 for every other.
+    pub fn samples(&self) -> u32 { unsafe { mirhi_sys::mirhi_image_samples(self.raw) } }
     /// Six faces (+X, -X, +Y, -Y, +Z, -Z) and `levels` mip levels in one allocation (R32G32B32A32Sfloat only): level-major, then face-major,
     /// then row-major.  What the IBL precompute passes below read and write.
     pub fn new_cube(device: Arc<Device>, size: u32, levels: u32, format: Format) -> RhiResult<Self> {

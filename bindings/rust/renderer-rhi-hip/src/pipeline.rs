@@ -112,6 +112,8 @@ impl GraphicsPipelineBuilder {
     pub fn fragment_discard_enable(mut self, on: bool) -> Self { self.desc.fragment_discard_enable = on as u32; self }
     /// pipeline.rs:769: no near / far clipping, fragment depth clamped to [0, 1] ("pancaking" for shadow cascades).
     pub fn depth_clamp_enable(mut self, on: bool) -> Self { self.desc.depth_clamp_enable = on as u32; self }
+    /// pipeline.rs:796: 1, or 4 for a pipeline that draws in 4x multisampled scopes (`RenderingInfo::with_resolve`).
+    pub fn rasterization_samples(mut self, samples: u32) -> Self { self.desc.rasterization_samples = samples; self }
     /// pipeline.rs:781-788: enables depth bias; o = max(|dz/dx|, |dz/dy|) * slope_factor + r * constant_factor, clamped by `clamp`.
     pub fn depth_bias(mut self, constant_factor: f32, clamp: f32, slope_factor: f32) -> Self {
         self.desc.depth_bias_enable = 1;

@@ -38,7 +38,9 @@ extern "C" {
                                     still 5 (one new enum value, one new function): MIRHI_PROGRAM_MODEL_PBR_IBL, mirhi_cmd_bind_ibl;
                                     still 5 (one new enum value, one new function): MIRHI_PROGRAM_SKYBOX, mirhi_cmd_bind_skybox;
                                     still 5 (new functions, structs and one enum only): the seven transfer commands, mirhi_buffer_copy, mirhi_buffer_image_copy,
-                                    mirhi_image_copy, mirhi_image_blit, mirhi_filter */
+                                    mirhi_image_copy, mirhi_image_blit, mirhi_filter;
+                                    still 5 (new functions, one struct and one enum only; rasterization_samples = 4 accepted): mirhi_image_create_multisampled,
+                                    mirhi_image_samples, mirhi_resolve_mode, mirhi_resolve_info, mirhi_cmd_begin_rendering_resolve */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -162,6 +164,13 @@ mirhi_result mirhi_image_create_array(mirhi_device* dev, uint32_t width, uint32_
  * round; two scopes that write different layers of one array may be serialised. */
 mirhi_result mirhi_image_create_layer_view(mirhi_image* array, uint32_t layer, mirhi_image** out);
 uint32_t     mirhi_image_layers(const mirhi_image* img);   /* layers of an array; 1 for every other image (views included) */
+/* Multisampled images: the TRANSIENT attachments of a 4x multisampled rendering scope (mirhi_cmd_begin_rendering_resolve).  samples = 4
+ * only (1: InvalidHandle "use mirhi_image_create"; anything else: InvalidHandle "unsupported: sample count"); format B8G8R8A8_SRGB, R32G32B32A32_SFLOAT or
+ * D32_SFLOAT.  Such an image owns NO memory -- its samples live on the chip while a tile is rasterized and only the resolved pixel is written --:
+ * mirhi_image_size_bytes is 0, mirhi_image_device_ptr NULL.  It is an attachment and nothing else: upload, read, every texture slot, the cascade, IBL
+ * and skybox bindings, the transfer commands, layer views, mirhi_image_generate_mips and the sampler setters refuse it (InvalidHandle, "multisampled"). */
+mirhi_result mirhi_image_create_multisampled(mirhi_device* dev, uint32_t width, uint32_t height, mirhi_format format, uint32_t samples, mirhi_image** out);
+uint32_t     mirhi_image_samples(const mirhi_image* img);  /* 4, or 1 for every other image */
 mirhi_result mirhi_image_upload(mirhi_image* img, const void* src, uint64_t len);
 mirhi_result mirhi_image_read(mirhi_image* img, void* dst, uint64_t len);   /* added: swapchain images have no readback (swapchain.rs:255) */
 /* Texture fidelity (image.rs / sampler.rs / texture.rs are stubs in the reference, the shaders assume
@@ -311,7 +320,7 @@ typedef struct {
     uint32_t depth_clamp_enable;        /* default 0               :662 */
     uint32_t rasterizer_discard_enable; /* default 0               :663 */
     uint32_t depth_bias_enable;         /* default 0               :664 */
-    uint32_t rasterization_samples;     /* default 1               :671 */
+    uint32_t rasterization_samples;     /* default 1               :671; 4: a pipeline for 4x multisampled scopes (mirhi_cmd_begin_rendering_resolve) */
     uint32_t depth_test_enable;         /* default 1               :676 */
     uint32_t depth_write_enable;        /* default 1               :677 */
     int32_t  depth_compare_op;          /* default LESS            :678 */
@@ -409,6 +418,36 @@ mirhi_result mirhi_cmd_begin_reusable(mirhi_cmd* cmd);                          
 mirhi_result mirhi_cmd_end(mirhi_cmd* cmd);                                         /* end :372 */
 mirhi_result mirhi_cmd_reset(mirhi_cmd* cmd);                                       /* reset :387 */
 mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_rendering_info* info);  /* begin_rendering :408 */
+/* 4x MSAA (ColorAttachment::with_resolve / DepthAttachment::with_resolve rendering.rs:238,:477, rasterization_samples pipeline.rs:796).
+ * A scope whose color_image is multisampled (mirhi_image_create_multisampled).  Semantics:
+ *   samples   Vulkan's standard 4x positions inside pixel (px, py): s0 (0.375, 0.125), s1 (0.875, 0.375), s2 (0.125, 0.625), s3 (0.625, 0.875).
+ *   coverage  per sample: the 1x path's snapped vertices, edge functions and fill rule at the sample position.  The scissor applies to the pixel, so to all four.
+ *   depth     per sample: the triangle's depth plane (with depth bias and clamp) at the sample position; compare, write and tie-break as at 1x.
+ *   shading   once per pixel for each distinct primitive that wins at least one of its samples, at the pixel centre (px + 1/2, py + 1/2) whether or not the
+ *             primitive covers the centre (attributes extrapolate): no centroid interpolation, no sample shading.  A sample no primitive won has the clear colour.
+ *   resolve   AVERAGE: per channel, alpha included, ((c0 + c1) + (c2 + c3)) * 0.25f in binary32, in this order, nothing fused; a B8G8R8A8_SRGB target
+ *             averages the linear values and encodes once.  SAMPLE_ZERO (depth): the depth of sample 0, the clear depth where no primitive reached it.
+ *   prim_id_image  R32_UINT of 4 * width x height texels: texel (4 px + s, py) is the winning global primitive id of sample s, or 0xFFFFFFFF.
+ * Attachments: color_load_op CLEAR and color_store_op DONT_CARE (anything else: "unsupported: multisampled attachments are transient"); color_resolve_image a 1x
+ * image of the same format, extent and device with MIRHI_RESOLVE_AVERAGE; depth_image NULL (depth stays on chip) or a multisampled D32_SFLOAT with load CLEAR,
+ * store DONT_CARE; depth_resolve_image optional, a 1x D32_SFLOAT image or layer view with MIRHI_RESOLVE_SAMPLE_ZERO (a later 1x scope can LOAD it) -- also
+ * with depth_image NULL: the per-sample depth is then the scope's on-chip depth (cleared to clear_depth), and sample 0 of it is what is written.
+ * Ordering across queue lanes goes by the resolve images: they are what the scope writes.
+ * A pipeline with rasterization_samples = 4 draws in such a scope and nowhere else (a draw whose pipeline's sample count differs from its scope's is refused
+ * when it is recorded).  Taken: TRIANGLE, MODEL, MODEL_FULL and MODEL_PBR without a shadow binding (mip chains, sRGB textures, anisotropy, sampler state); depth
+ * test and write with LESS, LESS_OR_EQUAL, GREATER or GREATER_OR_EQUAL; depth bias and clamp; scissor and viewport; indexed, instanced and indirect draws.
+ * Refused with "unsupported:" where it is recorded: blending, fragment_discard_enable, predicate depth states, a depth state change inside the scope, SKYBOX,
+ * SHADOW, MODEL_PBR_IBL, shadowed or cascaded draws, a partial render area, a split device, fragment statistics.
+ * resolve NULL, or all NONE / NULL, with a 1x color_image: exactly mirhi_cmd_begin_rendering. */
+typedef enum { MIRHI_RESOLVE_NONE = 0, MIRHI_RESOLVE_SAMPLE_ZERO = 1, MIRHI_RESOLVE_AVERAGE = 2 } mirhi_resolve_mode;   /* VkResolveModeFlagBits */
+typedef struct {
+    mirhi_image* color_resolve_image;  /* NULL, or the 1x image the averaged colour is written to */
+    int32_t      color_resolve_mode;   /* mirhi_resolve_mode: NONE or AVERAGE */
+    mirhi_image* depth_resolve_image;  /* NULL, or the 1x D32_SFLOAT image (or layer view) sample 0's depth is written to */
+    int32_t      depth_resolve_mode;   /* mirhi_resolve_mode: NONE or SAMPLE_ZERO */
+} mirhi_resolve_info;
+void         mirhi_resolve_info_default(mirhi_resolve_info* resolve);   /* NULL / NONE */
+mirhi_result mirhi_cmd_begin_rendering_resolve(mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_resolve_info* resolve);
 mirhi_result mirhi_cmd_end_rendering(mirhi_cmd* cmd);                               /* end_rendering :417 */
 mirhi_result mirhi_cmd_bind_pipeline(mirhi_cmd* cmd, mirhi_pipeline* pipeline);     /* bind_pipeline :433 */
 mirhi_result mirhi_cmd_bind_vertex_buffers(mirhi_cmd* cmd, uint32_t first_binding, uint32_t count, mirhi_buffer* const* buffers, const uint64_t* offsets); /* :448 */

@@ -176,6 +176,15 @@ class RenderingInfo(C.Structure):
     ]
 
 
+class ResolveMode:   # mirhi_resolve_mode (VkResolveModeFlagBits)
+    NONE, SAMPLE_ZERO, AVERAGE = range(3)
+
+
+class ResolveInfo(C.Structure):      # mirhi_resolve_info
+    _fields_ = [("color_resolve_image", C.c_void_p), ("color_resolve_mode", C.c_int32),
+                ("depth_resolve_image", C.c_void_p), ("depth_resolve_mode", C.c_int32)]
+
+
 class Viewport(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("width", C.c_float), ("height", C.c_float),
                 ("min_depth", C.c_float), ("max_depth", C.c_float)]
@@ -275,6 +284,8 @@ _SIGNATURES = {
     "mirhi_image_create_array": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mirhi_image_create_layer_view": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mirhi_image_layers": (C.c_uint32, [C.c_void_p]),
+    "mirhi_image_create_multisampled": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mirhi_image_samples": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_create_cube": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mirhi_ibl_equirect_to_cube": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_ibl_cube_generate_mips": (C.c_int32, [C.c_void_p]),
@@ -312,6 +323,8 @@ _SIGNATURES = {
     "mirhi_cmd_end": (C.c_int32, [C.c_void_p]),
     "mirhi_cmd_reset": (C.c_int32, [C.c_void_p]),
     "mirhi_cmd_begin_rendering": (C.c_int32, [C.c_void_p, C.POINTER(RenderingInfo)]),
+    "mirhi_resolve_info_default": (None, [C.POINTER(ResolveInfo)]),
+    "mirhi_cmd_begin_rendering_resolve": (C.c_int32, [C.c_void_p, C.POINTER(RenderingInfo), C.POINTER(ResolveInfo)]),
     "mirhi_cmd_end_rendering": (C.c_int32, [C.c_void_p]),
     "mirhi_cmd_bind_pipeline": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_cmd_bind_vertex_buffers": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
@@ -579,6 +592,18 @@ class Image:
         return cls._adopt(h, device, width, height, fmt)
 
     @classmethod
+    def multisampled(cls, device: Device, width: int, height: int, fmt: int, samples: int = 4) -> "Image":
+        """mirhi_image_create_multisampled: the transient attachment of a 4x multisampled scope (include/mirhi.h "4x MSAA").  It owns no memory and is
+        nothing but an attachment: CommandBuffer.begin_rendering_resolve takes it with a resolve target."""
+        h = C.c_void_p()
+        check(lib().mirhi_image_create_multisampled(device.handle, width, height, fmt, samples, C.byref(h)))
+        return cls._adopt(h, device, width, height, fmt)
+
+    @property
+    def samples(self) -> int:
+        return int(lib().mirhi_image_samples(self.handle))
+
+    @classmethod
     def create_cube(cls, device: Device, size: int, levels: int = 1, fmt: int = Format.R32G32B32A32_SFLOAT) -> "Image":
         """mirhi_image_create_cube: six faces and `levels` mip levels in one allocation (R32G32B32A32_SFLOAT only); level-major, then
         face-major (+X, -X, +Y, -Y, +Z, -Z), then row-major."""
@@ -758,6 +783,11 @@ class GraphicsPipelineBuilder:
         self.bias = DepthBias(constant_factor, clamp, slope_factor)
         return self
 
+    def rasterization_samples(self, samples: int):
+        """pipeline.rs:796: 1, or 4 for a pipeline that draws in 4x multisampled scopes (include/mirhi.h "4x MSAA")."""
+        self.desc.rasterization_samples = int(samples)
+        return self
+
     def fragment_discard_enable(self, e: bool):
         """Pipelines of alpha-masked MODEL_PBR materials (model_pbr.hlsl:176-179 `discard`): per-fragment, ordered resolve."""
         self.desc.fragment_discard_enable = int(e)
@@ -830,6 +860,54 @@ def rendering_info(color=None, clear_color=(0.0, 0.0, 0.0, 1.0), color_load_op=L
     return info
 
 
+def resolve_info(color_resolve=None, depth_resolve=None, color_mode=None, depth_mode=None) -> ResolveInfo:
+    """The mirhi_resolve_info of CommandBuffer.begin_rendering_resolve: an image names its usual mode (AVERAGE for colour, SAMPLE_ZERO for depth) unless
+    a mode is given."""
+    r = ResolveInfo()
+    lib().mirhi_resolve_info_default(C.byref(r))
+    if color_resolve is not None:
+        r.color_resolve_image = color_resolve.handle
+    if depth_resolve is not None:
+        r.depth_resolve_image = depth_resolve.handle
+    r.color_resolve_mode = color_mode if color_mode is not None else (ResolveMode.AVERAGE if color_resolve is not None else ResolveMode.NONE)
+    r.depth_resolve_mode = depth_mode if depth_mode is not None else (ResolveMode.SAMPLE_ZERO if depth_resolve is not None else ResolveMode.NONE)
+    return r
+
+
+class ColorAttachment:
+    """rhi::ColorAttachment (rendering.rs:65-115): the image with its ops; with_resolve (rendering.rs:238) names the 1x image a multisampled one resolves to."""
+
+    def __init__(self, image: "Image", load_op=LoadOp.CLEAR, store_op=StoreOp.STORE, clear_color=(0.0, 0.0, 0.0, 1.0)):
+        self.image, self.load_op, self.store_op, self.clear_color = image, load_op, store_op, tuple(clear_color)
+        self.resolve_image, self.resolve_mode = None, ResolveMode.NONE
+
+    def with_resolve(self, image: "Image", mode: int = ResolveMode.AVERAGE):
+        self.resolve_image, self.resolve_mode = image, mode
+        self.store_op = StoreOp.DONT_CARE      # (the multisampled contents are transient: what is kept is the resolve)
+        return self
+
+
+class DepthAttachment:
+    """rhi::DepthAttachment (rendering.rs:319-370); with_resolve (rendering.rs:477): the 1x D32_SFLOAT image sample 0's depth is written to."""
+
+    def __init__(self, image: "Image", load_op=LoadOp.CLEAR, store_op=StoreOp.DONT_CARE, clear_depth: float = 1.0):
+        self.image, self.load_op, self.store_op, self.clear_depth = image, load_op, store_op, clear_depth
+        self.resolve_image, self.resolve_mode = None, ResolveMode.NONE
+
+    def with_resolve(self, image: "Image", mode: int = ResolveMode.SAMPLE_ZERO):
+        self.resolve_image, self.resolve_mode = image, mode
+        return self
+
+
+def attachment_infos(color: ColorAttachment, depth: Optional[DepthAttachment] = None, prim_id=None, render_area=None):
+    """(RenderingInfo, ResolveInfo) of a scope given by attachments.  Test plumbing as rendering_info is."""
+    info = rendering_info(color.image, color.clear_color, color.load_op, depth.image if depth else None, depth.clear_depth if depth else 1.0,
+                          depth.load_op if depth else LoadOp.CLEAR, depth.store_op if depth else StoreOp.DONT_CARE, prim_id, render_area)
+    info.color_store_op = color.store_op
+    res = resolve_info(color.resolve_image, depth.resolve_image if depth else None, color.resolve_mode, depth.resolve_mode if depth else ResolveMode.NONE)
+    return info, res
+
+
 class CommandBuffer:
     """rhi::CommandBuffer (crates/rhi/src/command.rs:297-628)."""
 
@@ -858,6 +936,22 @@ class CommandBuffer:
         (include/mirhi.h, mirhi_rendering_info::render_area); None: the full extent."""
         info = rendering_info(color, clear_color, color_load_op, depth, clear_depth, depth_load_op, depth_store_op, prim_id, render_area)
         check(lib().mirhi_cmd_begin_rendering(self.handle, C.byref(info)))
+
+    def begin_rendering_resolve(self, color: Image, color_resolve: Optional[Image], clear_color=(0.0, 0.0, 0.0, 1.0), depth: Optional[Image] = None,
+                                depth_resolve: Optional[Image] = None, clear_depth: float = 1.0, prim_id: Optional[Image] = None, color_load_op=LoadOp.CLEAR,
+                                color_store_op=StoreOp.DONT_CARE, depth_load_op=LoadOp.CLEAR, depth_store_op=StoreOp.DONT_CARE, color_mode=None, depth_mode=None,
+                                render_area=None):
+        """mirhi_cmd_begin_rendering_resolve: a 4x multisampled scope (color: Image.multisampled) whose averaged colour goes to color_resolve and, optionally,
+        whose sample-0 depth goes to depth_resolve.  prim_id: R32_UINT of 4 * width x height, texel (4 px + s, py) the winner of sample s."""
+        info = rendering_info(color, clear_color, color_load_op, depth, clear_depth, depth_load_op, depth_store_op, prim_id, render_area)
+        info.color_store_op = color_store_op
+        res = resolve_info(color_resolve, depth_resolve, color_mode, depth_mode)
+        check(lib().mirhi_cmd_begin_rendering_resolve(self.handle, C.byref(info), C.byref(res)))
+
+    def begin_rendering_attachments(self, color: ColorAttachment, depth: Optional[DepthAttachment] = None, prim_id: Optional[Image] = None, render_area=None):
+        """The scope given by attachments, as the reference's RenderingConfig takes them; a with_resolve attachment makes it a multisampled scope."""
+        info, res = attachment_infos(color, depth, prim_id, render_area)
+        check(lib().mirhi_cmd_begin_rendering_resolve(self.handle, C.byref(info), C.byref(res)))
 
     def end_rendering(self):
         check(lib().mirhi_cmd_end_rendering(self.handle))
@@ -1043,7 +1137,7 @@ class SceneResources:
                  want_depth: bool = False, color_image: Optional[Image] = None, wrap_buffers=None,
                  color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None,
                  cascade_array: Optional[Image] = None, ibl_images: Optional[Sequence[Image]] = None, sky_image: Optional[Image] = None,
-                 depth_image: Optional[Image] = None, prim_image: Optional[Image] = None, depth_load_op: int = LoadOp.CLEAR):
+                 depth_image: Optional[Image] = None, prim_image: Optional[Image] = None, depth_load_op: int = LoadOp.CLEAR, samples: int = 1):
         """scene.shadow (scenes.ShadowSpec) adds a depth-only shadow scope ahead of the main scope: recorded into the same command
         buffer, or with shadow_cmd=True into a command buffer of its own (self.shadow_cmd; render() submits both, the shadow one first --
         put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames).
@@ -1057,8 +1151,13 @@ class SceneResources:
         image, one created here from its levels (self.sky_image, destroyed with the resources) or the existing one passed as sky_image=.
         scene.render_area ((x, y, width, height) or None): the main scope's render area (include/mirhi.h, mirhi_rendering_info::render_area).
         depth_image / prim_image / depth_load_op: test plumbing for the render-area tests -- existing attachments to render into, like color_image
-        (the caller's to destroy), and the main scope's depth load op, so that a scope can start from prefilled contents."""
+        (the caller's to destroy), and the main scope's depth load op, so that a scope can start from prefilled contents.
+        samples=4: the main scope is a 4x multisampled one (include/mirhi.h "4x MSAA"): transient multisampled colour and depth images are built here
+        (self.ms_color, self.ms_depth), the pipelines get rasterization_samples = 4, and the scope is recorded through begin_rendering_resolve --
+        self.color is the colour resolve target, self.depth (want_depth) the sample-0 depth resolve, self.prim (want_prim) the 4 * width x height
+        image of per-sample winners, which read() returns as [height, width, 4]."""
         self.device, self.scene = device, scene
+        self.samples = int(samples)
         self.color_load_op = color_load_op
         self.owns_color = color_image is None
         self.objs = []
@@ -1066,8 +1165,13 @@ class SceneResources:
         self.color_format = self.color.format
         self.depth_load_op = depth_load_op
         self.owns_prim, self.owns_depth = prim_image is None, depth_image is None
-        self.prim = prim_image or (Image(device, scene.width, scene.height, Format.R32_UINT) if want_prim else None)
+        self.prim = prim_image or (Image(device, scene.width * (4 if self.samples == 4 else 1), scene.height, Format.R32_UINT) if want_prim else None)
         self.depth = depth_image or (Image(device, scene.width, scene.height, Format.D32_SFLOAT) if want_depth else None)
+        self.ms_color = self.ms_depth = None
+        if self.samples != 1:
+            self.ms_color = Image.multisampled(device, scene.width, scene.height, self.color_format, self.samples)
+            self.ms_depth = Image.multisampled(device, scene.width, scene.height, Format.D32_SFLOAT, self.samples)
+            self.objs += [self.ms_color, self.ms_depth]
         self.cmd = CommandBuffer(device)
         self.draw_state = []
         cache = {}
@@ -1123,6 +1227,8 @@ class SceneResources:
             if getattr(d, "alpha_test", False):
                 b.fragment_discard_enable(True)
             _depth_state(b, d)
+            if self.samples != 1:
+                b.rasterization_samples(self.samples)
             pipe = b.build(device)
             self.objs.append(pipe)
             st = dict(pipe=pipe, vb=buf(BufferUsage.Vertex, d.vertices),
@@ -1245,11 +1351,22 @@ class SceneResources:
             self._record_shadow(self.shadow_cmd)
             self.shadow_cmd.end()
         cmd.begin_reusable()
+        self.record_scopes(cmd)
+        cmd.end()
+
+    def record_scopes(self, cmd: "CommandBuffer"):
+        """The scene's scopes (shadow scopes unless they have a command buffer of their own, then the main scope) into `cmd`, which is recording: several
+        scenes can share one command buffer."""
+        s = self.scene
         if (self.shadow is not None or self.cascades is not None) and self.shadow_cmd is None:
             self._record_shadow(cmd)
-        cmd.begin_rendering(self.color, clear_color=s.clear_color, color_load_op=self.color_load_op, depth=self.depth, clear_depth=s.clear_depth,
-                            depth_load_op=self.depth_load_op, depth_store_op=StoreOp.STORE if self.depth else StoreOp.DONT_CARE, prim_id=self.prim,
-                            render_area=s.render_area)
+        if self.samples != 1:
+            cmd.begin_rendering_resolve(self.ms_color, self.color, clear_color=s.clear_color, depth=self.ms_depth, depth_resolve=self.depth, clear_depth=s.clear_depth,
+                                        prim_id=self.prim, color_load_op=self.color_load_op, depth_load_op=self.depth_load_op, render_area=s.render_area)
+        else:
+            cmd.begin_rendering(self.color, clear_color=s.clear_color, color_load_op=self.color_load_op, depth=self.depth, clear_depth=s.clear_depth,
+                                depth_load_op=self.depth_load_op, depth_store_op=StoreOp.STORE if self.depth else StoreOp.DONT_CARE, prim_id=self.prim,
+                                render_area=s.render_area)
         if self.sky is not None and self.sky.first:
             self._record_sky(cmd)
         for st in self.draw_state:
@@ -1290,7 +1407,6 @@ class SceneResources:
         if self.sky is not None and not self.sky.first:
             self._record_sky(cmd)
         cmd.end_rendering()
-        cmd.end()
 
     def render(self, fence: Optional[Fence] = None):
         self.device.submit([self.shadow_cmd, self.cmd] if self.shadow_cmd is not None else [self.cmd], fence)
@@ -1300,6 +1416,8 @@ class SceneResources:
         out = {"color": self.color.read()}
         if self.prim:
             out["prim"] = self.prim.read()
+            if self.samples == 4:      # texel (4 px + s, py) is sample s of pixel (px, py)
+                out["prim"] = out["prim"].reshape(self.scene.height, self.scene.width, 4)
         if self.depth:
             out["depth"] = self.depth.read()
         return out

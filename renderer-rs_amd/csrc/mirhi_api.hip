@@ -491,6 +491,9 @@ struct mirhi_image {
     // Cube images (mirhi_image_create_cube): six faces and `levels` mip levels in one allocation, level-major, then face-major, then row-major; width =
     // height = the edge of level 0, layers = 6.  A cube is neither a 2-D image nor an array: only the mirhi_ibl_* passes, upload and read take one.
     bool is_cube = false;
+    // Multisampled images (mirhi_image_create_multisampled): samples = 4, the transient attachment of a multisampled scope.  It owns no memory
+    // (ptr nullptr, owned false) and is nothing but an attachment: whatever would read or write its texels refuses it (refuse_multisampled).
+    uint32_t samples = 1;
     mirhi_image* parent = nullptr;
     uint32_t views = 0;            // live layer views of an array (it cannot be destroyed before them)
     // Attachment ordering across queue lanes: the reference submits everything to one queue, so a scope that LOADs (or overwrites)
@@ -523,6 +526,7 @@ struct RecordedPass {
     bool carry_in = false, carry_out = false;
     int32_t area[4] = {0, 0, 0, 0};
     bool depth_only = false;               // color_image NULL: SHADOW draws into the depth image (raster_kernel_depth)
+    uint32_t samples = 1;                  // 4: a multisampled scope (mirhi_cmd_begin_rendering_resolve): info / color_t / depth_t name its RESOLVE images
     std::vector<mirhi_image*> sampled;     // shadow maps the scope's draws sample (MIRHI_TEXTURE_SHADOW_MAP): ordered like attachments
     // the IBL set the scope's MODEL_PBR_IBL draws were recorded under (mirhi_cmd_bind_ibl; one per scope, all its segments): resolved like the targets
     struct IblSet {
@@ -1031,6 +1035,12 @@ extern "C" mirhi_result mirhi_buffer_destroy(mirhi_buffer* buf) {
 // images
 // ------------------------------------------------------------------------------------------------
 #include "mirhi_ibl.hip.h"   // cube layout (ibl_level_offset) and the IBL precompute kernels, launched further down beside mip_kernel
+// a multisampled image where only an image with memory will do; what: what the caller would have done with it
+static mirhi_result refuse_multisampled(const mirhi_image* img, const char* what) {
+    if (img && img->samples != 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a multisampled image is a transient attachment without memory: it cannot be %s", what);
+    return MIRHI_OK;
+}
+#define REFUSE_MULTISAMPLED(img, what) do { mirhi_result rm__ = refuse_multisampled((img), (what)); if (rm__ != MIRHI_OK) return rm__; } while (0)
 static mirhi_result image_common(mirhi_device* dev, uint32_t w, uint32_t h, mirhi_format f, void* ext, mirhi_image** out) {
     NULL_CHECK(dev, "device"); NULL_CHECK(out, "out");
     *out = nullptr;
@@ -1058,11 +1068,29 @@ extern "C" mirhi_result mirhi_image_wrap_device_memory(mirhi_device* dev, uint32
     if (dev) dev->foreign_writes++;
     return image_common(dev, w, h, f, ptr, out);
 }
+extern "C" mirhi_result mirhi_image_create_multisampled(mirhi_device* dev, uint32_t w, uint32_t h, mirhi_format f, uint32_t samples, mirhi_image** out) {
+    NULL_CHECK(dev, "device"); NULL_CHECK(out, "out");
+    *out = nullptr;
+    if (const char* why = msaa_sample_count_refusal(samples)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s (got %u)", why, samples);
+    if (w == 0 || h == 0) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: Image dimensions must be greater than 0 (got %ux%u)", w, h);
+    if (w > 16384 || h > 16384) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: Image dimensions exceed 16384 (got %ux%u)", w, h);
+    if (f != MIRHI_FORMAT_B8G8R8A8_SRGB && f != MIRHI_FORMAT_R32G32B32A32_SFLOAT && f != MIRHI_FORMAT_D32_SFLOAT)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: multisampled images of format %d (B8G8R8A8_SRGB, R32G32B32A32_SFLOAT or D32_SFLOAT)", (int)f);
+    mirhi_image* img = new (std::nothrow) mirhi_image{dev, w, h, f, nullptr, false};      // (transient: no memory)
+    if (!img) return fail(MIRHI_ERR_ALLOCATOR, "Allocator error: host allocation failed");
+    img->samples = samples;
+    { std::lock_guard<std::mutex> lock(dev->mu); dev->images.push_back(img); }
+    dev->children++;
+    *out = img;
+    return MIRHI_OK;
+}
+extern "C" uint32_t mirhi_image_samples(const mirhi_image* img) { return img ? img->samples : 0; }
 extern "C" uint32_t mirhi_image_width(const mirhi_image* img) { return img ? img->width : 0; }
 extern "C" uint32_t mirhi_image_height(const mirhi_image* img) { return img ? img->height : 0; }
 extern "C" int32_t mirhi_image_format(const mirhi_image* img) { return img ? (int32_t)img->format : 0; }
 extern "C" uint64_t mirhi_image_size_bytes(const mirhi_image* img) {
     if (!img) return 0;
+    if (img->samples != 1u) return 0;      // (a multisampled image is transient: it owns no memory)
     if (img->is_cube) return (uint64_t)ibl_chain_texels(img->width, img->levels) * format_bpp(img->format);       // the whole chain
     return (uint64_t)img->width * img->height * format_bpp(img->format) * img->layers;
 }
@@ -1093,6 +1121,7 @@ extern "C" mirhi_result mirhi_image_create_array(mirhi_device* dev, uint32_t w, 
 extern "C" mirhi_result mirhi_image_create_layer_view(mirhi_image* array, uint32_t layer, mirhi_image** out) {
     NULL_CHECK(array, "image"); NULL_CHECK(out, "out");
     *out = nullptr;
+    REFUSE_MULTISAMPLED(array, "viewed by layer");
     if (array->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image has no layer views");
     if (!array->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: layer views are made of array images (mirhi_image_create_array)");
     if (layer >= array->layers) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: layer %u out of range (the array has %u layers)", layer, array->layers);
@@ -1109,6 +1138,7 @@ extern "C" mirhi_result mirhi_image_create_layer_view(mirhi_image* array, uint32
 extern "C" void* mirhi_image_device_ptr(const mirhi_image* img) { return img ? img->ptr : nullptr; }
 extern "C" mirhi_result mirhi_image_upload(mirhi_image* img, const void* src, uint64_t len) {
     NULL_CHECK(img, "image"); NULL_CHECK(src, "src");
+    REFUSE_MULTISAMPLED(img, "uploaded to");
     if (len != mirhi_image_size_bytes(img))
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: image upload size %llu != image size %llu", (unsigned long long)len, (unsigned long long)mirhi_image_size_bytes(img));
     { mirhi_result r0 = sync_all_lanes(img->dev); if (r0 != MIRHI_OK) return r0; }
@@ -1119,6 +1149,7 @@ extern "C" mirhi_result mirhi_image_upload(mirhi_image* img, const void* src, ui
 }
 extern "C" mirhi_result mirhi_image_read(mirhi_image* img, void* dst, uint64_t len) {
     NULL_CHECK(img, "image"); NULL_CHECK(dst, "dst");
+    REFUSE_MULTISAMPLED(img, "read");
     if (len != mirhi_image_size_bytes(img))
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: image read size %llu != image size %llu", (unsigned long long)len, (unsigned long long)mirhi_image_size_bytes(img));
     { mirhi_result r0 = sync_all_lanes(img->dev); if (r0 != MIRHI_OK) return r0; }
@@ -1141,6 +1172,7 @@ __global__ void mip_kernel(const uint32_t* __restrict__ src, uint32_t sw, uint32
 extern "C" uint32_t mirhi_image_mip_levels(const mirhi_image* img) { return img ? img->levels : 0; }
 extern "C" mirhi_result mirhi_image_generate_mips(mirhi_image* img) {
     NULL_CHECK(img, "image");
+    REFUSE_MULTISAMPLED(img, "given a mip chain");
     if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image's mip chain is built by mirhi_ibl_cube_generate_mips");
     if (img->format != MIRHI_FORMAT_R8G8B8A8_UNORM && img->format != MIRHI_FORMAT_R8G8B8A8_SRGB)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: mip chains are built for R8G8B8A8 textures only");
@@ -1198,11 +1230,13 @@ extern "C" mirhi_result mirhi_image_create_cube(mirhi_device* dev, uint32_t size
 }
 static mirhi_result ibl_cube_arg(const mirhi_image* img, const char* what) {
     if (!img) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s is null", what);
+    REFUSE_MULTISAMPLED(img, "an IBL pass's image");
     if (!img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s must be a cube image (mirhi_image_create_cube)", what);
     return MIRHI_OK;
 }
 static mirhi_result ibl_2d_arg(const mirhi_image* img, const char* what) {
     if (!img) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s is null", what);
+    REFUSE_MULTISAMPLED(img, "an IBL pass's image");
     if (img->is_cube || img->is_array || img->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s must be a 2-D image", what);
     if (img->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s must be R32G32B32A32_SFLOAT (format %d)", what, (int)img->format);
     return MIRHI_OK;
@@ -1294,6 +1328,7 @@ extern "C" mirhi_result mirhi_ibl_brdf_lut(mirhi_image* out2d) {
 extern "C" uint32_t mirhi_image_max_anisotropy(const mirhi_image* img) { return img ? img->max_anisotropy : 0; }
 extern "C" mirhi_result mirhi_image_set_max_anisotropy(mirhi_image* img, uint32_t max_anisotropy) {
     NULL_CHECK(img, "image");
+    REFUSE_MULTISAMPLED(img, "sampled (it has no sampler state)");
     if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image has no anisotropic sampler (the cube sampler is fixed, include/mirhi.h)");
     if (img->format != MIRHI_FORMAT_R8G8B8A8_UNORM && img->format != MIRHI_FORMAT_R8G8B8A8_SRGB)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: anisotropic filtering applies to sampled R8G8B8A8 textures only");
@@ -1306,6 +1341,7 @@ extern "C" void mirhi_sampler_desc_default(mirhi_sampler_desc* desc) { if (desc)
 extern "C" mirhi_result mirhi_image_set_sampler(mirhi_image* img, const mirhi_sampler_desc* desc) {
     NULL_CHECK(img, "image");
     NULL_CHECK(desc, "sampler desc");
+    REFUSE_MULTISAMPLED(img, "sampled (it has no sampler state)");
     if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image has no sampler state (the cube sampler is fixed, include/mirhi.h)");
     if (img->is_array || img->parent)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array and its layer views have no sampler state (the shadow comparison sampler is fixed, include/mirhi.h)");
@@ -1400,7 +1436,7 @@ static mirhi_result pipeline_create(mirhi_device* dev, const mirhi_pipeline_desc
     if (d->polygon_mode != MIRHI_POLYGON_FILL) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported polygon mode %d (Fill only)", d->polygon_mode);
     if (d->cull_mode < 0 || d->cull_mode > 3 || d->front_face < 0 || d->front_face > 1) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: invalid cull mode / front face");
     if (d->depth_compare_op < 0 || d->depth_compare_op > 7) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: invalid depth compare op %d", d->depth_compare_op);
-    if (d->rasterization_samples != 1) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported sample count %u", d->rasterization_samples);
+    if (d->rasterization_samples != 1 && d->rasterization_samples != 4) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: unsupported sample count %u", d->rasterization_samples);
     if (d->blend_enable) {
         const int32_t f[4] = {d->src_color_blend_factor, d->dst_color_blend_factor, d->src_alpha_blend_factor, d->dst_alpha_blend_factor};
         for (int32_t v : f) {
@@ -1621,6 +1657,9 @@ static mirhi_result take_render_area(const mirhi_cmd* cmd, const mirhi_rendering
 extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_rendering_info* info) {
     REQUIRE_RECORDING(cmd); NULL_CHECK(info, "rendering_info");
     if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
+    for (const mirhi_image* img : {(const mirhi_image*)info->color_image, (const mirhi_image*)info->depth_image, (const mirhi_image*)info->prim_id_image})
+        if (img && img->samples != 1u)
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a multisampled attachment needs a resolve target: mirhi_cmd_begin_rendering_resolve with a multisampled color_image");
     if (!info->color_image && info->depth_image) {
         // depth-only scope (MIRHI_PROGRAM_SHADOW): the depth image's extent is the render area; only SHADOW draws are recorded here
         const mirhi_image* di = info->depth_image;
@@ -1667,6 +1706,60 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
     cmd->in_rendering = true;
     return MIRHI_OK;
 }
+// A 4x multisampled scope.  What the scope WRITES are the resolve images: the recorded pass names them as its attachments (RecordedPass::info,
+// color_t, depth_t -- attachment ordering, the plan cache and fill_params then see a scope that stores colour and, with a depth resolve, depth), and samples = 4
+// says that its kernels are geometry_kernel_msaa and raster_kernel_msaa.  The refusals are mirhi_scope.h's (msaa_scope_refusal).
+extern "C" void mirhi_resolve_info_default(mirhi_resolve_info* r) { if (r) memset(r, 0, sizeof *r); }
+extern "C" mirhi_result mirhi_cmd_begin_rendering_resolve(mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_resolve_info* resolve) {
+    REQUIRE_RECORDING(cmd); NULL_CHECK(info, "rendering_info");
+    const bool any_resolve = resolve && (resolve->color_resolve_image || resolve->depth_resolve_image || resolve->color_resolve_mode != MIRHI_RESOLVE_NONE ||
+                                         resolve->depth_resolve_mode != MIRHI_RESOLVE_NONE);
+    const mirhi_image* ci = info->color_image;
+    if (!ci || ci->samples == 1u) {
+        if (any_resolve) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a resolve needs a multisampled color_image (mirhi_image_create_multisampled)");
+        return mirhi_cmd_begin_rendering(cmd, info);
+    }
+    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
+    if (ci->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the color_image belongs to another device than the command buffer");
+    const mirhi_image* di = info->depth_image; const mirhi_image* pi = info->prim_id_image;
+    const mirhi_image* cr = resolve ? resolve->color_resolve_image : nullptr; const mirhi_image* dr = resolve ? resolve->depth_resolve_image : nullptr;
+    for (const mirhi_image* img : {cr, dr, pi})
+        if (img && (img->is_cube || img->is_array)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image or an image array is not an attachment (an array: use a layer view)");
+    const RenderArea area = render_area(ci->width, ci->height, info->render_area);
+    if (!area.valid) {
+        char msg[192];
+        render_area_message(msg, sizeof msg, info->render_area, ci->width, ci->height);
+        return fail(MIRHI_ERR_INVALID_HANDLE, "%s", msg);
+    }
+    MsaaScopeFacts f{};
+    f.color_samples = ci->samples; f.color_format = (uint32_t)ci->format; f.color_w = ci->width; f.color_h = ci->height;
+    f.color_load_op = info->color_load_op; f.color_store_op = info->color_store_op;
+    if (di) { f.has_depth = 1u; f.depth_samples = di->samples; f.depth_format = (uint32_t)di->format; f.depth_w = di->width; f.depth_h = di->height; }
+    f.depth_load_op = info->depth_load_op; f.depth_store_op = info->depth_store_op;
+    if (cr) { f.has_color_resolve = 1u; f.cr_samples = cr->samples; f.cr_format = (uint32_t)cr->format; f.cr_w = cr->width; f.cr_h = cr->height; f.cr_same_device = cr->dev == ci->dev; }
+    f.color_resolve_mode = resolve ? resolve->color_resolve_mode : (int32_t)MIRHI_RESOLVE_NONE;
+    if (dr) { f.has_depth_resolve = 1u; f.dr_samples = dr->samples; f.dr_format = (uint32_t)dr->format; f.dr_w = dr->width; f.dr_h = dr->height; f.dr_same_device = dr->dev == ci->dev; }
+    f.depth_resolve_mode = resolve ? resolve->depth_resolve_mode : (int32_t)MIRHI_RESOLVE_NONE;
+    if (pi) { f.has_prim = 1u; f.prim_format = (uint32_t)pi->format; f.prim_w = pi->width; f.prim_h = pi->height; }
+    if (pi && pi->samples != 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the prim_id_image is multisampled itself");
+    if (pi && pi->dev != ci->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the prim_id_image belongs to another device");
+    if (di && di->dev != ci->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the depth_image belongs to another device");
+    f.area_partial = area.partial; f.split_device = cmd->dev->split_world > 1; f.fragment_stats = (cmd->dev->profiling & MIRHI_PROFILE_FRAGMENTS) != 0;
+    if (const char* why = msaa_scope_refusal(f)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", why);
+    RecordedPass p;
+    p.info = *info;
+    p.samples = 4u;
+    p.info.color_image = resolve->color_resolve_image; p.info.color_store_op = MIRHI_STORE_OP_STORE;
+    p.info.depth_image = resolve->depth_resolve_image; p.info.depth_load_op = MIRHI_LOAD_OP_CLEAR;
+    p.info.depth_store_op = dr ? MIRHI_STORE_OP_STORE : MIRHI_STORE_OP_DONT_CARE;
+    p.color_t = {cr->ptr, cr->width, cr->height, (uint32_t)cr->format};
+    if (dr) p.depth_t = {dr->ptr, dr->width, dr->height, (uint32_t)dr->format};
+    if (pi) p.prim_t = {pi->ptr, pi->width, pi->height, (uint32_t)pi->format};
+    p.area[0] = 0; p.area[1] = 0; p.area[2] = (int32_t)ci->width; p.area[3] = (int32_t)ci->height;
+    cmd->passes.push_back(std::move(p));
+    cmd->in_rendering = true;
+    return MIRHI_OK;
+}
 extern "C" mirhi_result mirhi_cmd_end_rendering(mirhi_cmd* cmd) {
     REQUIRE_RECORDING(cmd);
     if (!cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: end_rendering without begin_rendering");
@@ -1709,6 +1802,7 @@ extern "C" mirhi_result mirhi_cmd_bind_uniform(mirhi_cmd* cmd, mirhi_uniform_slo
 extern "C" mirhi_result mirhi_cmd_bind_texture(mirhi_cmd* cmd, mirhi_texture_slot slot, mirhi_image* image) {
     REQUIRE_RECORDING(cmd);
     if ((int)slot < 0 || (int)slot >= MIRHI_TEXTURE_COUNT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unknown texture slot %d", (int)slot);
+    REFUSE_MULTISAMPLED(image, "bound at a texture slot");
     if (image && image->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image cannot be bound at a texture slot (the IBL cubes are bound with mirhi_cmd_bind_ibl)");
     if (slot == MIRHI_TEXTURE_SHADOW_MAP) {       // t7 / s5 (model_pbr.hlsl:103-108): a depth image, sampled with the comparison sampler
         if (image && image->format != MIRHI_FORMAT_D32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the shadow map must be D32_SFLOAT");
@@ -1729,6 +1823,7 @@ static mirhi_result bind_shadow_cascades(mirhi_cmd* cmd, mirhi_image* array, mir
     if (!array) { cmd->cascades = nullptr; cmd->cascade_params = {nullptr, 0, 0}; cmd->cascade_blend = 0.0f; return MIRHI_OK; }
     if (!std::isfinite(blend_threshold) || blend_threshold < 0.0f || blend_threshold > 1.0f)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a cascade blend threshold outside [0, 1] (got %g)", (double)blend_threshold);
+    REFUSE_MULTISAMPLED(array, "bound as shadow cascades");
     if (array->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array, not a cube image");
     if (array->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array, not a layer view");
     if (!array->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: shadow cascades are an image array (mirhi_image_create_array)");
@@ -1757,6 +1852,7 @@ extern "C" mirhi_result mirhi_cmd_bind_ibl(mirhi_cmd* cmd, mirhi_image* irradian
     if (!irradiance && !prefiltered && !brdf_lut) { for (auto& im : cmd->ibl) im = nullptr; return MIRHI_OK; }
     if (!irradiance || !prefiltered || !brdf_lut)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the IBL set is three images (irradiance, prefiltered, BRDF LUT): all of them, or all NULL to unbind");
+    for (const mirhi_image* im : {(const mirhi_image*)irradiance, (const mirhi_image*)prefiltered, (const mirhi_image*)brdf_lut}) REFUSE_MULTISAMPLED(im, "bound in an IBL set");
     if (irradiance->dev != prefiltered->dev || irradiance->dev != brdf_lut->dev)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the IBL images belong to two devices");
     if (irradiance->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the IBL images belong to another device than the command buffer");
@@ -1773,6 +1869,7 @@ extern "C" mirhi_result mirhi_cmd_bind_ibl(mirhi_cmd* cmd, mirhi_image* irradian
 extern "C" mirhi_result mirhi_cmd_bind_skybox(mirhi_cmd* cmd, mirhi_image* environment) {
     REQUIRE_RECORDING(cmd);
     if (!environment) { cmd->skybox = nullptr; return MIRHI_OK; }
+    REFUSE_MULTISAMPLED(environment, "bound as the skybox environment");
     if (!environment->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the skybox environment must be a cube image (mirhi_image_create_cube)");
     if (environment->format != MIRHI_FORMAT_R32G32B32A32_SFLOAT) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the skybox environment must be R32G32B32A32_SFLOAT");
     if (environment->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the skybox environment belongs to another device than the command buffer");
@@ -1820,6 +1917,7 @@ static mirhi_result record_sky_draw(mirhi_cmd* cmd, bool indexed, uint32_t count
     const mirhi_pipeline_desc& pd = cmd->pipeline->desc;
     if (indexed) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX pipeline draws with mirhi_cmd_draw(cmd, 3, 1, 0, 0): draw_indexed has nothing to index");
     if (cmd->passes.back().depth_only) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX draw in a depth-only rendering scope (pixel/skybox.hlsl writes colour)");
+    if (cmd->passes.back().samples != 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a SKYBOX draw in a multisampled scope");
     if (pd.blend_enable || pd.fragment_discard_enable) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a SKYBOX draw with blending or fragment discard");
     if (count != 3u || first != 0u || instance_count > 1u)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX draw is vertex_count 3, first_vertex 0, instance_count 1 (got %u, %u, %u)", count, first, instance_count);
@@ -1922,11 +2020,16 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     }
     const mirhi_pipeline_desc& pd = cmd->pipeline->desc;
     const bool shadow_prog = pd.vertex_program == MIRHI_PROGRAM_SHADOW;
+    // (a multisampled scope refuses a SHADOW draw in its own words, ahead of the 1x scope's "needs a depth-only rendering scope")
+    if (cmd->passes.back().samples == 4u && shadow_prog) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", msaa_program_refusal(pd.fragment_program, false));
     if (cmd->passes.back().depth_only && !shadow_prog)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: only SHADOW draws may be recorded in a depth-only rendering scope (program %d)", pd.vertex_program);
     if (!cmd->passes.back().depth_only && shadow_prog)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: SHADOW draws need a depth-only rendering scope (color_image NULL, depth_image set)");
     const RecordedPass::Target ci = cmd->passes.back().color_t;      // (a depth-only scope: the depth image's extent, format UNDEFINED)
+    if (pd.rasterization_samples != cmd->passes.back().samples)
+        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline rasterization_samples %u does not match the rendering scope's sample count %u", pd.rasterization_samples,
+                    cmd->passes.back().samples);
     if (pd.color_attachment_formats[0] != (int32_t)ci.format)
         return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)ci.format);
     // depth state must be uniform within a rendering scope (DESIGN.md "Depth key")
@@ -1938,6 +2041,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     const bool never = pd.depth_test_enable && pd.depth_compare_op == MIRHI_COMPARE_NEVER;
     const uint32_t tri_count = count / 3u;
     if (instance_count == 0 || tri_count == 0) return MIRHI_OK;
+    if (never && cmd->passes.back().samples == 4u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", msaa_draw_refusal(ds, pd.fragment_program, false, false));      // (a predicate state)
     if (never) { cmd->passes.back().total_tris += tri_count; return MIRHI_OK; }     // draws nothing, but its primitives keep their ids
     if (pd.blend_enable) {
         uint32_t* blend = ds.blend;
@@ -1946,6 +2050,14 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         blend[7] = pd.color_write_mask & 0xFu;
     }
     ds.discard = pd.fragment_discard_enable ? 1u : 0u;
+    if (cmd->passes.back().samples == 4u) {
+        // a multisampled scope is one segment of what raster_kernel_msaa takes: everything else is refused here, never drawn differently (mirhi_scope.h)
+        const RecordedPass& mp = cmd->passes.back();
+        const bool pbr_prog = pd.fragment_program == MIRHI_PROGRAM_MODEL_PBR || pd.fragment_program == MIRHI_PROGRAM_MODEL_PBR_IBL;
+        const bool shadowed = pbr_prog && (cmd->textures[MIRHI_TEXTURE_SHADOW_MAP] || cmd->cascades);
+        if (const char* why = msaa_draw_refusal(ds, pd.fragment_program, shadowed, mp.state.key_set && !(mp.state == ds)))
+            return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", why);
+    }
     if (!cmd->passes.back().state.key_set) cmd->passes.back().state = ds;
     else if (!(cmd->passes.back().state == ds) || cmd->passes.back().sky.on) {
         // One raster launch resolves one depth state (DESIGN.md "Depth key"): the scope continues in a new segment that
@@ -2159,6 +2271,7 @@ struct XferLevel { uint8_t* base; uint32_t w, h, bpp; mirhi_format format; };
 static mirhi_result xfer_level(const mirhi_cmd* cmd, const mirhi_image* img, uint32_t level, const char* what, XferLevel* out) {
     if (!img) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s is null", what);
     if (img->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the %s belongs to another device than the command buffer", what);
+    REFUSE_MULTISAMPLED(img, "a transfer's source or destination");
     if (img->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image is not a transfer's %s", what);
     if (img->is_array) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: an image array is not a transfer's %s: use a layer view (mirhi_image_create_layer_view)", what);
     if (level >= img->levels) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: mip level %u of the %s out of range (the image has %u)", level, what, img->levels);
@@ -2430,6 +2543,7 @@ static bool same_recording(const std::vector<RecordedPass>& a, const std::vector
             memcmp(&x.info.clear_depth, &y.info.clear_depth, sizeof(float)) != 0) return false;
         if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || !(x.state == y.state) ||
             x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
+        if (x.samples != y.samples) return false;
         if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl) || !(x.sky == y.sky)) return false;
         if (!(x.xfer == y.xfer) || x.xfer_regions.size() != y.xfer_regions.size() ||
             (!x.xfer_regions.empty() && memcmp(x.xfer_regions.data(), y.xfer_regions.data(), x.xfer_regions.size() * sizeof(XferRegion)) != 0)) return false;
@@ -2627,7 +2741,7 @@ static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, c
         if (s.area.partial) { s.r0 = s.area.row_begin; s.r1 = s.area.row_end; s.rstep = 1; }
     }
     s.tris = pass.total_tris - pass.first_tri;
-    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs, pass.sky.on != 0u, pass.xfer.kind != 0u);
+    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs, pass.sky.on != 0u, pass.xfer.kind != 0u, pass.samples);
     s.mode = raster_mode(s.cls, s.density_tiles(), s.tris, w.spread, w.wide, knobs, s.area.partial);
     s.bins = bin_geometry(s.launched(), s.tris, pass.total_tris, s.mode.xcd_bins, w.pool_scale, knobs, s.tiles());
     return s;
@@ -2794,7 +2908,8 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
     P.frag_stats = frag_stats;
     P.first_prim = pass.first_tri;
     P.prim_draw = pass.draws.size() > 1 ? w.prim_draw : nullptr;
-    P.flat_color = (s.cls.tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB) ? w.flat_color : nullptr;
+    // (a multisampled scope averages linear colours: no packed flat colours)
+    P.flat_color = (s.cls.tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB && pass.samples == 1u) ? w.flat_color : nullptr;
     P.resolve_flat_only = (P.flat_color && !P.depth_load && P.color_format != 2u && !P.prim_out && !(P.depth && P.depth_store)) ? 1u : 0u;
     P.sub_cap = s.bins.sub_cap;                                       // (the bins are those the workspace was sized for: s.mode, not `mode`)
     P.count_stride = s.mode.xcd_bins ? (uint32_t)max_tiles : 0u;
@@ -2847,6 +2962,8 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         scopes.push_back(plan_scope(dev, pass, w, knobs));
         // (begin_rendering refuses it; a device split after the recording is met here)
         if (scopes.back().area.partial && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a partial render area on a split device");
+        if (pass.samples != 1u && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a multisampled scope on a split device");
+        if (pass.samples != 1u && (dev->profiling & MIRHI_PROFILE_FRAGMENTS)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: fragment statistics of a multisampled scope");
         total_draws += pass.draws.size();
         total_regions += pass.xfer_regions.size();
         max_tiles = std::max(max_tiles, scopes.back().tiles());
@@ -3014,6 +3131,35 @@ static mirhi_result stats_params_for(mirhi_cmd* c) {
     }
     w.stats_params_valid = true;
     return MIRHI_OK;
+}
+
+// Outside the C ABI (not in include/mirhi.h) and without a HIP call: what a 4x multisampled scope refuses (mirhi_scope.h), as words.  in[0] says what is asked:
+// 0  a sample count: in[1].  1  a scope: the words of MsaaScopeFacts in their order, from in[1].  2  a draw: blend enable, discard, depth test, depth write,
+// compare op, program, "samples a shadow map or cascades", "the segment holds draws of another depth state".  3  the variant of a 5 x 4 tile scope: programs,
+// zflip, zmask, samples -> msg: the kernel's name, out of the launch table (mirhi_debug_raster_choice knows no sample count).
+// Returns 0 (accepted; msg empty), 1 (refused; msg: the words behind "Invalid handle: "), -1 for words it cannot take.
+extern "C" int mirhi_debug_msaa(const uint32_t* in, char* msg, uint32_t msg_len) {
+    const char* why = nullptr;
+    if (in[0] == 0u) why = msaa_sample_count_refusal(in[1]);
+    else if (in[0] == 1u) {
+        MsaaScopeFacts f;
+        static_assert(sizeof(MsaaScopeFacts) % 4 == 0, "MsaaScopeFacts is made of 32-bit words");
+        memcpy(&f, in + 1, sizeof f);
+        why = msaa_scope_refusal(f);
+    } else if (in[0] == 2u) {
+        DepthState s;
+        s.key_set = true; s.blend[0] = in[1]; s.discard = in[2]; s.test = in[3]; s.write = in[4]; s.compare = in[5];
+        why = msaa_draw_refusal(s, (int32_t)in[6], in[7] != 0u, in[8] != 0u);
+    } else if (in[0] == 3u) {
+        PassParams P{};
+        P.tiles_x = 5u; P.tile_row_end = 4u; P.tile_row_step = 1u; P.zflip = in[2]; P.zmask = in[3]; P.samples = in[4];
+        const RasterVariant v = raster_variant(P, in[1], true);
+        snprintf(msg, msg_len, "%s family %u progs %u keyed %u tp %u grid %u %u block %u batched %u", v.family == RASTER_MSAA ? "msaa" : "other", (uint32_t)v.family, v.progs, v.keyed,
+                 v.tp, v.grid[0], v.grid[1], v.block, v.batched_form);
+        return 0;
+    } else return -1;
+    snprintf(msg, msg_len, "%s", why ? why : "");
+    return why ? 1 : 0;
 }
 
 static mirhi_result timing_begin(mirhi_device* dev, uint32_t kernel, uint32_t lane, LaunchTiming* t) {
@@ -3800,6 +3946,7 @@ extern "C" uint32_t mirhi_comm_rank(const mirhi_comm* comm) { return comm ? comm
 
 extern "C" mirhi_result mirhi_comm_all_gather_bands(mirhi_comm* comm, mirhi_image* frame, mirhi_cmd* after, mirhi_gather_algo algo) {
     NULL_CHECK(comm, "comm"); NULL_CHECK(frame, "frame");
+    REFUSE_MULTISAMPLED(frame, "gathered");
     mirhi_device* dev = comm->dev;
     if (frame->dev != dev || (after && after->dev != dev)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: frame / command buffer belongs to another device");
     if (algo != MIRHI_GATHER_DIRECT && algo != MIRHI_GATHER_BROADCAST) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unknown gather algorithm %d", (int)algo);

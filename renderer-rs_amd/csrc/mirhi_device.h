@@ -283,6 +283,10 @@ struct PassParams {
     // so the columns outside stay empty and unvisited.
     uint32_t tile_col_begin, tile_cols;
     uint32_t area_partial, area_pad;  // 1: the area is smaller than the attachment
+    // A 4x multisampled scope (mirhi_cmd_begin_rendering_resolve; geometry_kernel_msaa and raster_kernel_msaa alone read the word): 4, else 0.
+    // The attachments are transient: `color` is the colour RESOLVE target (1x), `depth` the depth resolve target (sample 0; depth_store = 1) or nullptr,
+    // `prim_out` an image of 4 * width x height texels, texel (4 px + s, py) the winner of sample s.  Behind everything else, like the area words.
+    uint32_t samples, samples_pad;
 };
 static_assert(sizeof(PassParams) % 8 == 0, "PassParams holds pointers");
 

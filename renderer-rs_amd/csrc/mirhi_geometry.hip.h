@@ -64,6 +64,9 @@ __device__ __forceinline__ void owned_rows(ParamsRef P, int32_t ty0, int32_t ty1
 // ------------------------------------------------------------------------------------------------
 // a5: clip-space triangle (all w > 0) -> snapped, culled, oriented screen triangle + depth plane
 // ------------------------------------------------------------------------------------------------
+// MSAA (a 4x multisampled scope; the geometry kernels of its own: geometry_kernel_msaa): the pixel box holds every pixel that has a SAMPLE
+// inside the vertex bounds, not every pixel whose centre is -- the one place of the geometry stage that knows where a pixel is sampled.
+template <bool MSAA = false>
 __device__ __forceinline__ bool setup_triangle(ParamsRef P, DrawRef D, const f4 c[3], uint32_t prim,
                                                ScreenTri& t) {
     float z[3];
@@ -119,8 +122,10 @@ __device__ __forceinline__ bool setup_triangle(ParamsRef P, DrawRef D, const f4 
     }
     const int32_t xmin = min(t.X[0], min(t.X[1], t.X[2])), xmax = max(t.X[0], max(t.X[1], t.X[2]));
     const int32_t ymin = min(t.Y[0], min(t.Y[1], t.Y[2])), ymax = max(t.Y[0], max(t.Y[1], t.Y[2]));
-    int32_t px0 = (xmin + 127) >> 8, px1 = (xmax - 128) >> 8;
-    int32_t py0 = (ymin + 127) >> 8, py1 = (ymax - 128) >> 8;
+    // pixel centres sit at 128 of 256; the standard 4x sample positions span 32 .. 224 on either axis (mirhi_msaa.hip.h)
+    constexpr int32_t LO = MSAA ? 31 : 127, HI = MSAA ? 32 : 128;
+    int32_t px0 = (xmin + LO) >> 8, px1 = (xmax - HI) >> 8;
+    int32_t py0 = (ymin + LO) >> 8, py1 = (ymax - HI) >> 8;
     const bool cut = D.scissor_partial && (px0 < D.sx0 || px1 > D.sx1 || py0 < D.sy0 || py1 > D.sy1);
     px0 = max(px0, D.sx0); px1 = min(px1, D.sx1); py0 = max(py0, D.sy0); py1 = min(py1, D.sy1);
     if (px0 > px1 || py0 > py1) return false;
@@ -179,6 +184,7 @@ __device__ __forceinline__ uint32_t outcode_view(f4 c) {
 constexpr int CLIP_MAX_VERTS = 10;     // 3 + one per plane (near, far, 4 guard-band planes) = 9
 constexpr int CLIP_BATCH = 8;          // lanes clipping concurrently per wave (LDS polygon slots)
 
+template <bool MSAA = false>
 __device__ __forceinline__ void clip_and_emit(ParamsRef P, DrawRef D, f4 (*poly)[CLIP_MAX_VERTS],
                                               f4 c0, f4 c1, f4 c2, uint32_t any, uint32_t prim) {
     f4* in = poly[0]; f4* tmp = poly[1];
@@ -206,7 +212,7 @@ __device__ __forceinline__ void clip_and_emit(ParamsRef P, DrawRef D, f4 (*poly)
         for (int i = 1; i + 1 < n; i++) {
             const f4 tri[3] = {in[0], in[i], in[i + 1]};
             ScreenTri t;
-            if (setup_triangle(P, D, tri, prim, t)) emit_big(P, t);
+            if (setup_triangle<MSAA>(P, D, tri, prim, t)) emit_big(P, t);
         }
         return;
     }
@@ -217,7 +223,7 @@ __device__ __forceinline__ void clip_and_emit(ParamsRef P, DrawRef D, f4 (*poly)
     for (int i = 1; i + 1 < n; i++) {
         const f4 tri[3] = {in[0], in[i], in[i + 1]};
         ScreenTri t;
-        if (setup_triangle(P, D, tri, prim, t)) pieces++;
+        if (setup_triangle<MSAA>(P, D, tri, prim, t)) pieces++;
     }
     uint4* slot = reinterpret_cast<uint4*>(P.ordered_recs) + (size_t)(prim - P.ordered_first) * 3u;
     uint32_t first = 0;
@@ -232,7 +238,7 @@ __device__ __forceinline__ void clip_and_emit(ParamsRef P, DrawRef D, f4 (*poly)
     for (int i = 1; i + 1 < n && pieces; i++) {
         const f4 tri[3] = {in[0], in[i], in[i + 1]};
         ScreenTri t;
-        if (setup_triangle(P, D, tri, prim, t)) store_tri(reinterpret_cast<uint4*>(P.big_recs) + (size_t)(first + k++) * 3u, t);
+        if (setup_triangle<MSAA>(P, D, tri, prim, t)) store_tri(reinterpret_cast<uint4*>(P.big_recs) + (size_t)(first + k++) * 3u, t);
     }
 }
 
@@ -532,7 +538,7 @@ __device__ __forceinline__ void bin_triangle_pairs(ParamsRef P, bool valid, cons
 // WAVES: resident waves per SIMD the register allocation aims at.  7 (72 VGPRs) for scopes with enough triangles to fill the
 // chip several times over (C4 geometry 61.4 -> 57.4 us); 5 (up to 102) for small scopes, where a wave is alone on its SIMD
 // and only the length of its dependent instruction stream counts (C2: 7.4 us against 8.2 with the tighter allocation).
-template <int WAVES>
+template <int WAVES, bool MSAA = false>
 __device__ __forceinline__ void geometry_body(const PassParams* __restrict__ params, const GeometryHead& H) {
     ParamsRef P = *(ParamsPtr)(uintptr_t)params;
     // 5.4 KB of LDS per one-wave workgroup: 30 fit a CU, which is what lets 7 waves per SIMD be resident (at 7.9 KB the LDS
@@ -654,7 +660,7 @@ __device__ __forceinline__ void geometry_body(const PassParams* __restrict__ par
                     in_band = k1 >= k0;
                 }
             }
-            if (any == 0 && in_band) valid = setup_triangle(P, D, c, prim, t);
+            if (any == 0 && in_band) valid = setup_triangle<MSAA>(P, D, c, prim, t);
         }
     }
     GSTAMP_SYNC(6);
@@ -697,7 +703,7 @@ __device__ __forceinline__ void geometry_body(const PassParams* __restrict__ par
     while (todo) {                                   // rare: triangles crossing the near / far / guard planes
         const uint32_t rank = (uint32_t)__popcll(todo & ((1ull << (threadIdx.x & 63u)) - 1ull));
         const bool mine = any != 0 && ((todo >> (threadIdx.x & 63u)) & 1ull) && rank < CLIP_BATCH;
-        if (mine) clip_and_emit(P, D, poly[rank], c[0], c[1], c[2], any, prim);
+        if (mine) clip_and_emit<MSAA>(P, D, poly[rank], c[0], c[1], c[2], any, prim);
         todo &= ~__ballot(mine);
     }
     GSTAMP(3);
@@ -706,6 +712,12 @@ __device__ __forceinline__ void geometry_body(const PassParams* __restrict__ par
 template <int WAVES>
 __global__ __launch_bounds__(GEOM_THREADS) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void geometry_kernel(const PassParams* __restrict__ params, const GeometryHead H) {
     geometry_body<WAVES>(params, H);
+}
+// a 4x multisampled scope (PassParams::samples == 4): the same kernel with the sample-conservative pixel box -- an instantiation of its own, so
+// that the 1x instruction stream stays what it was
+template <int WAVES>
+__global__ __launch_bounds__(GEOM_THREADS) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void geometry_kernel_msaa(const PassParams* __restrict__ params, const GeometryHead H) {
+    geometry_body<WAVES, true>(params, H);
 }
 // the scopes of one batched submit (see raster_kernel_batch): grid (waves of the largest scope, scopes)
 template <int WAVES>

@@ -36,6 +36,7 @@ namespace mirhi {
 #include "mirhi_ibl_sample.hip.h"
 #include "mirhi_shading.hip.h"
 #include "mirhi_raster.hip.h"
+#include "mirhi_msaa.hip.h"
 #include "mirhi_sky.hip.h"
 #include "mirhi_stats.hip.h"
 #include "mirhi_ordered.hip.h"
@@ -98,6 +99,11 @@ hipError_t launch_geometry(const PassParams& P, const PassParams* dev_params, hi
         H.vb0 = t.head_draw->vb; H.stride0 = t.head_draw->stride; H.first0 = t.head_draw->first; H.tris0 = t.head_draw->tri_count;
     }
     // (more waves than the chip holds at five per SIMD: the occupancy-oriented variant)
+    if (P.samples == 4u) {      // a 4x multisampled scope: the sample-conservative pixel box (setup_triangle<true>)
+        if (blocks > 5u * 1024u) MIRHI_LAUNCH(geometry_kernel_msaa<7>, dim3(blocks), dim3(GEOM_THREADS), stream, t, dev_params, H);
+        else MIRHI_LAUNCH(geometry_kernel_msaa<5>, dim3(blocks), dim3(GEOM_THREADS), stream, t, dev_params, H);
+        return launch_result();
+    }
     if (blocks > 5u * 1024u) MIRHI_LAUNCH(geometry_kernel<7>, dim3(blocks), dim3(GEOM_THREADS), stream, t, dev_params, H);
     else MIRHI_LAUNCH(geometry_kernel<5>, dim3(blocks), dim3(GEOM_THREADS), stream, t, dev_params, H);
     return launch_result();
@@ -116,6 +122,7 @@ struct RasterEntry { uint32_t id; const char* name; void (*kernel)(const PassPar
 #define OWN_A(FAMILY, KERNEL, K, T) {raster_kernel_id(FAMILY, 0, K, T, 1, 0, 4, 1), #KERNEL "<" #K ", " #T ", true>", KERNEL<K, T, true>}
 #define IBL_A(K, T, S) {raster_kernel_id(RASTER_IBL, S, K, T, 1, 0, 4, 1), "raster_kernel_ibl<" #K ", " #T ", " #S ", true>", raster_kernel_ibl<K, T, S, true>}
 #define PLAIN_A(P, K, T, M) {raster_kernel_id(RASTER_PLAIN, P, K, T, 1, M, 4, 1), "raster_kernel<" #P ", " #K ", " #T ", 1, " #M ", true>", raster_kernel<P, K, T, 1, M, true>}
+#define MSAA(P, K) {raster_kernel_id(RASTER_MSAA, P, K, 0, 1, 0, 4), "raster_kernel_msaa<" #P ", " #K ">", raster_kernel_msaa<P, K>}
 static const RasterEntry k_raster_entries[] = {
     ORDERED(2), ORDERED(3), ORDERED(4), ORDERED(1),
     OWN(RASTER_DEPTH, raster_kernel_depth, 0, 1), OWN(RASTER_DEPTH, raster_kernel_depth, 1, 1), OWN(RASTER_DEPTH, raster_kernel_depth, 0, 0), OWN(RASTER_DEPTH, raster_kernel_depth, 1, 0),
@@ -149,6 +156,8 @@ static const RasterEntry k_raster_entries[] = {
     IBL(0, 1, 3), IBL(1, 1, 3), IBL(0, 0, 3), IBL(1, 0, 3),
     OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 0, 1), OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 1, 1), OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 0, 0), OWN_A(RASTER_CSM_BLEND, raster_kernel_csm_blend, 1, 0),
     IBL_A(0, 1, 3), IBL_A(1, 1, 3), IBL_A(0, 0, 3), IBL_A(1, 0, 3),
+    // 4x multisampled scopes, behind every older raster row: per program set and key
+    MSAA(2, 0), MSAA(4, 0), MSAA(3, 0), MSAA(1, 0), MSAA(2, 1), MSAA(4, 1), MSAA(3, 1), MSAA(1, 1),
     // a SKYBOX segment (no key, no bins: one kernel)
     {raster_kernel_id(RASTER_SKY, 0, 0, 0, 1, 0, 4), "sky_kernel", sky_kernel},
     // a recorded transfer command (progs: PassParams::xfer)
@@ -157,6 +166,7 @@ static const RasterEntry k_raster_entries[] = {
     {raster_kernel_id(RASTER_TRANSFER, XFER_BLIT_LINEAR, 0, 0, 1, 0, 4), "transfer_blit_kernel<1>", transfer_blit_kernel<1>},
     {raster_kernel_id(RASTER_TRANSFER, XFER_FILL, 0, 0, 1, 0, 4), "transfer_fill_kernel", transfer_fill_kernel},
 };
+#undef MSAA
 #undef IBL
 #undef IBL_A
 #undef OWN_A

@@ -181,10 +181,81 @@ struct ScopeClass {
     // A recorded transfer command (include/mirhi.h "Transfer commands"): no scope at all -- no attachments, draws, key or bins; its one launch is a kernel of
     // mirhi_transfer.hip.h.  A class of its own, treated by the selectors as a sky segment is.
     bool transfer;
+    // A 4x multisampled scope (mirhi_cmd_begin_rendering_resolve): 4, else 1.  A family of its own (raster_kernel_msaa): one team of four waves,
+    // single-list bins, plain tile order, pixel-parallel only; what its kernel does not take is refused where it is recorded (msaa_scope_refusal, msaa_draw_refusal).
+    uint32_t samples;
 };
 
-inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const DrawDesc* draws, size_t n, bool depth_only, const PlanKnobs& knobs, bool sky = false, bool transfer = false) {
+// ---- 4x multisampled scopes: what is refused, with the words it is refused in ("Invalid handle: " in front, mirhi_api.hip) ----
+// the sample count of mirhi_image_create_multisampled; nullptr: accepted (4)
+inline const char* msaa_sample_count_refusal(uint32_t samples) {
+    if (samples == 4u) return nullptr;
+    if (samples == 1u) return "a multisampled image has more than one sample: use mirhi_image_create";
+    return "unsupported: sample count";
+}
+// What begin_rendering_resolve looks at, as numbers (images: 0 = NULL; formats mirhi_format; modes mirhi_resolve_mode)
+struct MsaaScopeFacts {
+    uint32_t color_samples, color_format, color_w, color_h;
+    int32_t color_load_op, color_store_op;
+    uint32_t has_depth, depth_samples, depth_format, depth_w, depth_h;
+    int32_t depth_load_op, depth_store_op;
+    uint32_t has_color_resolve, cr_samples, cr_format, cr_w, cr_h, cr_same_device; int32_t color_resolve_mode;
+    uint32_t has_depth_resolve, dr_samples, dr_format, dr_w, dr_h, dr_same_device; int32_t depth_resolve_mode;
+    uint32_t has_prim, prim_format, prim_w, prim_h;
+    uint32_t area_partial, split_device, fragment_stats;
+};
+// nullptr: the scope is accepted.  (The colour image is multisampled: the 1x case never gets here.)
+inline const char* msaa_scope_refusal(const MsaaScopeFacts& f) {
+    if (f.color_format != MIRHI_FORMAT_B8G8R8A8_SRGB && f.color_format != MIRHI_FORMAT_R32G32B32A32_SFLOAT) return "a multisampled color attachment has a non-colour format";
+    if (f.color_load_op != MIRHI_LOAD_OP_CLEAR || f.color_store_op != MIRHI_STORE_OP_DONT_CARE)
+        return "unsupported: multisampled attachments are transient (colour: load CLEAR, store DONT_CARE)";
+    if (!f.has_color_resolve || f.color_resolve_mode != MIRHI_RESOLVE_AVERAGE) return "a multisampled color attachment needs a color_resolve_image with MIRHI_RESOLVE_AVERAGE";
+    if (f.cr_samples != 1u) return "the color_resolve_image is multisampled itself";
+    if (!f.cr_same_device) return "the color_resolve_image belongs to another device";
+    if (f.cr_format != f.color_format || f.cr_w != f.color_w || f.cr_h != f.color_h) return "the color_resolve_image must have the multisampled attachment's format and extent";
+    if (f.has_depth) {
+        if (f.depth_samples != 4u) return "a multisampled color attachment with a single-sampled depth attachment (depth_image: NULL, or a multisampled D32_SFLOAT)";
+        if (f.depth_format != MIRHI_FORMAT_D32_SFLOAT) return "depth attachment is not D32_SFLOAT";
+        if (f.depth_w != f.color_w || f.depth_h != f.color_h) return "depth attachment extent does not match the colour attachment";
+        if (f.depth_load_op != MIRHI_LOAD_OP_CLEAR || f.depth_store_op != MIRHI_STORE_OP_DONT_CARE)
+            return "unsupported: multisampled attachments are transient (depth: load CLEAR, store DONT_CARE)";
+    }
+    if (f.has_depth_resolve || f.depth_resolve_mode != MIRHI_RESOLVE_NONE) {
+        if (!f.has_depth_resolve || f.depth_resolve_mode != MIRHI_RESOLVE_SAMPLE_ZERO) return "unsupported: a depth resolve is a depth_resolve_image with MIRHI_RESOLVE_SAMPLE_ZERO";
+        if (f.dr_samples != 1u) return "the depth_resolve_image is multisampled itself";
+        if (!f.dr_same_device) return "the depth_resolve_image belongs to another device";
+        if (f.dr_format != MIRHI_FORMAT_D32_SFLOAT || f.dr_w != f.color_w || f.dr_h != f.color_h) return "the depth_resolve_image must be D32_SFLOAT with the multisampled attachment's extent";
+    }
+    if (f.has_prim && (f.prim_format != MIRHI_FORMAT_R32_UINT || f.prim_w != 4u * f.color_w || f.prim_h != f.color_h))
+        return "prim_id_image of a multisampled scope must be R32_UINT of 4 * width x height texels (texel (4 px + s, py): sample s)";
+    if (f.area_partial) return "unsupported: a partial render area in a multisampled scope";
+    if (f.split_device) return "unsupported: a multisampled scope on a split device";
+    if (f.fragment_stats) return "unsupported: fragment statistics of a multisampled scope";
+    return nullptr;
+}
+// The program of a draw recorded in a multisampled scope (mirhi_program) and whether it samples a shadow map or cascades.  record_draw asks this for a SHADOW
+// pipeline ahead of its depth-only check, so that the draw gets this refusal and not the 1x one.  nullptr: accepted.
+inline const char* msaa_program_refusal(int32_t program, bool shadowed) {
+    if (program == MIRHI_PROGRAM_SKYBOX) return "unsupported: a SKYBOX draw in a multisampled scope";
+    if (program == MIRHI_PROGRAM_SHADOW) return "unsupported: a SHADOW draw in a multisampled scope";
+    if (program == MIRHI_PROGRAM_MODEL_PBR_IBL) return "unsupported: a MODEL_PBR_IBL draw in a multisampled scope";
+    if (shadowed) return "unsupported: a shadowed or cascaded draw in a multisampled scope";
+    return nullptr;
+}
+// A draw recorded in a multisampled scope: its depth / blend state, its program (mirhi_program), whether it samples a shadow map or cascades, and whether
+// the segment already holds draws of another state (which would cut the scope into a second segment).  nullptr: accepted.
+inline const char* msaa_draw_refusal(const DepthState& s, int32_t program, bool shadowed, bool state_change) {
+    if (s.blend[0]) return "unsupported: blending in a multisampled scope";
+    if (s.discard) return "unsupported: fragment_discard_enable in a multisampled scope";
+    if (!ordered_key_only(s, true)) return "unsupported: a predicate depth state in a multisampled scope (depth test and write with LESS, LESS_OR_EQUAL, GREATER or GREATER_OR_EQUAL)";
+    if (state_change) return "unsupported: a depth state change inside a multisampled scope (it would cut the scope into a second segment)";
+    return msaa_program_refusal(program, shadowed);
+}
+
+inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const DrawDesc* draws, size_t n, bool depth_only, const PlanKnobs& knobs, bool sky = false, bool transfer = false,
+                                 uint32_t samples = 1u) {
     ScopeClass c{};
+    c.samples = samples == 4u ? 4u : 1u;
     c.key = depth_key_setup(s, clear_depth);
     if (transfer) { c.transfer = true; c.own_family = true; c.programs = PROGS_TRANSFER; return c; }
     if (sky) {      // (the depth state is the sky kernel's own business: PassParams::sky_compare / sky_write; nothing of the segment is ordered or masked)
@@ -210,7 +281,7 @@ inline ScopeClass classify_scope(const DepthState& s, float clear_depth, const D
     c.masked_plain = s.key_set && s.discard && s.blend[0] == 0 && !s.order_dependent_depth() && !(knobs.masked_ordered.set && knobs.masked_ordered.value != 0) &&
                      c.key.pred == 0u && !sampler_state;
     c.ordered = s.key_set && (s.blend[0] != 0 || (s.discard != 0 && !c.masked_plain) || s.order_dependent_depth());
-    c.own_family = depth_only || c.shadowed || c.ibl;
+    c.own_family = depth_only || c.shadowed || c.ibl || c.samples == 4u;
     const uint32_t cascaded = (c.shadowed >= 2u ? PROGS_CASCADED : 0u) | (c.shadowed == 3u ? PROGS_CSM_BLEND : 0u);
     if (c.shadowed) progs = PROGS_PBR | PROGS_SHADOWED | cascaded;
     if (c.ibl) progs = PROGS_PBR | PROGS_IBL | (c.shadowed ? PROGS_SHADOWED : 0u) | cascaded;
@@ -265,6 +336,8 @@ inline RasterMode raster_mode(const ScopeClass& c, size_t tiles, size_t tris, bo
     // sits in a small part of a whole frame's tiles, which launching the area's tiles alone already does)
     if (partial_area) { m.xcd_swizzle = 1u; m.teams = 1u; m.xcd_bins = false; m.wide = 0u; m.wide_eligible = false; }
     if (c.sky || c.transfer) { m.tp_max_area = 0u; m.teams = 1u; m.wide_eligible = false; m.xcd_bins = false; }
+    // a 4x multisampled scope (raster_kernel_msaa): pixel-parallel only -- its four keys per pixel live in LDS where the triangle-parallel path keeps its one
+    if (c.samples == 4u) { m.tp_max_area = 0u; m.teams = 1u; m.wide_eligible = false; m.xcd_bins = false; m.wide = 0u; m.xcd_swizzle = 1u; }
     return m;
 }
 
@@ -286,6 +359,7 @@ inline void set_raster_choice(PassParams& P, const ScopeClass& c, const RasterMo
     P.shadowed = c.shadowed;
     P.ibl = c.ibl;
     P.sky = c.sky ? 1u : 0u;
+    P.samples = c.samples == 4u ? 4u : 0u;
 }
 
 // Bins and page pool of one scope.  tris: the segment's own triangles, total_tris: with those of the scope's earlier segments (primitive ids continue)

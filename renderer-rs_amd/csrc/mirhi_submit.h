@@ -74,6 +74,7 @@ inline SubmitPath submit_path(const SubmitDevice& d, const SubmitSwitches& sw, u
     // all command buffers sit on the first one's queue lane (so the batch keeps their order against earlier work of that lane).
     // A scope with a partial render area never joins a batch: the batched raster kernel takes one grid for all its scopes, and an area
     // scope's grid is its own tile range (RasterVariant::batched_form is 0 for it, so the comparison below fails whatever the other scopes are).
+    // Nor does a 4x multisampled scope: its family has no batched form (RasterVariant::batched_form is 0), and its geometry kernel is not the batch's.
     // Anything else runs command buffer by command buffer, in submission order on each lane.
     p.batched = count >= 2 && count <= (uint32_t)MAX_BATCH && d.profiling == 0 && !sw.no_batch;
     SubmitHead heads[MAX_BATCH];
@@ -175,7 +176,7 @@ inline bool scope_timed(uint32_t profiling, uint32_t lane) {
 }
 // the statistics pass runs for the scope (ordered -- blended -- segments, depth-only scopes, SKYBOX segments and transfers are not counted)
 inline bool scope_counted(uint32_t profiling, const PassParams& P) {
-    return (profiling & MIRHI_PROFILE_FRAGMENTS) != 0 && has_tiles(P) && !P.ordered_recs && !P.depth_only && !P.sky && !P.xfer;
+    return (profiling & MIRHI_PROFILE_FRAGMENTS) != 0 && has_tiles(P) && !P.ordered_recs && !P.depth_only && !P.sky && !P.xfer && !P.samples;      // (a multisampled scope: refused by build_plan)
 }
 
 // ---- feedback (status_of) ----

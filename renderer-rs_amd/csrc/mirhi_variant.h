@@ -21,9 +21,9 @@ enum : uint32_t {
                               // CalculateShadowCSMBlended with a threshold > 0 (always together with PROGS_CASCADED): raster_kernel_csm_blend, the blended raster_kernel_ibl
 };
 
-// (RASTER_IBL behind RASTER_ORDERED, RASTER_SKY behind RASTER_IBL, RASTER_TRANSFER behind RASTER_SKY, RASTER_CSM_BLEND behind RASTER_TRANSFER: the values of the
-// families before them are recorded in tests/golden/raster_variants.json)
-enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY, RASTER_TRANSFER, RASTER_CSM_BLEND };
+// (RASTER_IBL behind RASTER_ORDERED, RASTER_SKY behind RASTER_IBL, RASTER_TRANSFER behind RASTER_SKY, RASTER_CSM_BLEND behind RASTER_TRANSFER, RASTER_MSAA behind
+// RASTER_CSM_BLEND: the values of the families before them are recorded in tests/golden/raster_variants.json)
+enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY, RASTER_TRANSFER, RASTER_CSM_BLEND, RASTER_MSAA };
 
 // the kernel instantiation alone (no launch shape) as one word
 constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves, uint32_t area = 0u) {
@@ -63,6 +63,11 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
         return RasterVariant{RASTER_TRANSFER, P.xfer, 0u, 0u, 1u, 0u, 4u, {P.tiles_x * rows, 1u, 1u}, (uint32_t)RASTER_THREADS, 0u, 0u};
     }
     const uint32_t progs = programs >= PROGS_PBR ? 4u : ((programs == 2u || programs == 3u) ? programs : 1u);
+    if (P.samples == 4u) {
+        // a 4x multisampled scope: a family of its own like the shadowed and IBL ones -- one team of four waves, single-list bins, plain tile
+        // order, an ordered key, pixel-parallel only (mirhi_scope.h refuses everything else where it is recorded); never batched
+        return RasterVariant{RASTER_MSAA, progs, (P.zflip == 0u && P.zmask == 0xFFFFFFFFu) ? 0u : 1u, 0u, 1u, 0u, 4u, {cols, rows, 1u}, (uint32_t)RASTER_THREADS, 0u, 0u};
+    }
     const bool mesh = programs == PROGS_MODEL || programs >= PROGS_PBR;      // no TRIANGLE draw: what the two-team and wide variants exist for
     // the plain key (raw float bits) serves LESS / LESS_OR_EQUAL; everything else takes the generic key
     const bool plain = P.zflip == 0u && P.zmask == 0xFFFFFFFFu;

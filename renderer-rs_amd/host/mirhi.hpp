@@ -276,6 +276,14 @@ public:
         return Image(device_, raw, w_, h_px_, f_);
     }
     uint32_t layers() const { return mirhi_image_layers(h_); }
+    // mirhi_image_create_multisampled: the transient attachment of a 4x multisampled scope (samples = 4): no memory, an attachment and nothing else;
+    // ColorAttachment::with_resolve names the 1x image it resolves to
+    static Image multisampled(std::shared_ptr<Device> device, uint32_t w, uint32_t h, Format f, uint32_t samples = 4) {
+        mirhi_image* raw = nullptr;
+        check(mirhi_image_create_multisampled(device->handle(), w, h, (mirhi_format)f, samples, &raw));
+        return Image(std::move(device), raw, w, h, f);
+    }
+    uint32_t samples() const { return mirhi_image_samples(h_); }
     // mirhi_image_create_cube: six faces and `levels` mip levels in one allocation (R32G32B32A32_SFLOAT), level-major, then face-major, then row-major
     static Image cube(std::shared_ptr<Device> device, uint32_t size, uint32_t levels = 1, Format f = Format::R32G32B32A32_SFLOAT) {
         mirhi_image* raw = nullptr;
@@ -383,6 +391,7 @@ public:
     GraphicsPipelineBuilder& depth_compare_op(CompareOp op) { d_.depth_compare_op = (int32_t)op; return *this; }
     GraphicsPipelineBuilder& fragment_discard_enable(bool e) { d_.fragment_discard_enable = e; return *this; }   // alpha-masked MODEL_PBR materials (model_pbr.hlsl:176-179)
     GraphicsPipelineBuilder& depth_clamp_enable(bool e) { d_.depth_clamp_enable = e; return *this; }             // pipeline.rs:769
+    GraphicsPipelineBuilder& rasterization_samples(uint32_t samples) { d_.rasterization_samples = samples; return *this; }   // pipeline.rs:796: 1, or 4
     GraphicsPipelineBuilder& depth_bias(float constant_factor, float clamp, float slope_factor) {                // pipeline.rs:781-788
         d_.depth_bias_enable = 1u; bias_ = {constant_factor, clamp, slope_factor}; has_bias_ = true;
         return *this;
@@ -413,6 +422,7 @@ private:
 // ------------------------------------------------------------------------------------------------
 enum class AttachmentLoadOp { Load = 0, Clear, DontCare };
 enum class AttachmentStoreOp { Store = 0, DontCare };
+enum class ResolveMode : int32_t { None = MIRHI_RESOLVE_NONE, SampleZero = MIRHI_RESOLVE_SAMPLE_ZERO, Average = MIRHI_RESOLVE_AVERAGE };   // VkResolveModeFlagBits
 
 struct ColorAttachment {   // rendering.rs:65-115
     const Image* image;
@@ -423,6 +433,13 @@ struct ColorAttachment {   // rendering.rs:65-115
     ColorAttachment& with_clear_color(std::array<float, 4> c) { clear_color = c; return *this; }
     ColorAttachment& with_load_op(AttachmentLoadOp op) { load_op = op; return *this; }
     ColorAttachment& load() { load_op = AttachmentLoadOp::Load; return *this; }
+    // rendering.rs:238: `image` is multisampled (Image::multisampled) and its four samples are averaged into `target`; the multisampled contents are transient
+    const Image* resolve_image = nullptr;
+    ResolveMode resolve_mode = ResolveMode::None;
+    ColorAttachment& with_resolve(const Image& target, ResolveMode mode = ResolveMode::Average) {
+        resolve_image = &target; resolve_mode = mode; store_op = AttachmentStoreOp::DontCare;
+        return *this;
+    }
 };
 struct DepthAttachment {   // rendering.rs:319-370
     const Image* image;
@@ -433,18 +450,24 @@ struct DepthAttachment {   // rendering.rs:319-370
     DepthAttachment& with_clear_depth(float d) { clear_depth = d; return *this; }
     DepthAttachment& load() { load_op = AttachmentLoadOp::Load; return *this; }
     DepthAttachment& store() { store_op = AttachmentStoreOp::Store; return *this; }
+    // rendering.rs:477: sample 0 of the multisampled depth attachment is written to `target` (a 1x D32_SFLOAT image or layer view)
+    const Image* resolve_image = nullptr;
+    ResolveMode resolve_mode = ResolveMode::None;
+    DepthAttachment& with_resolve(const Image& target, ResolveMode mode = ResolveMode::SampleZero) { resolve_image = &target; resolve_mode = mode; return *this; }
 };
 class RenderingConfig {    // rendering.rs:680-726
 public:
-    RenderingConfig(uint32_t w, uint32_t h) : w_(w), h_(h) { mirhi_rendering_info_default(&info_); }
+    RenderingConfig(uint32_t w, uint32_t h) : w_(w), h_(h) { mirhi_rendering_info_default(&info_); mirhi_resolve_info_default(&resolve_); }
     RenderingConfig& with_color_attachment(const ColorAttachment& a) {
         info_.color_image = a.image->handle(); info_.color_load_op = (int32_t)a.load_op; info_.color_store_op = (int32_t)a.store_op;
         std::memcpy(info_.clear_color, a.clear_color.data(), 16);
+        resolve_.color_resolve_image = a.resolve_image ? a.resolve_image->handle() : nullptr; resolve_.color_resolve_mode = (int32_t)a.resolve_mode;
         return *this;
     }
     RenderingConfig& with_depth_attachment(const DepthAttachment& a) {
         info_.depth_image = a.image->handle(); info_.depth_load_op = (int32_t)a.load_op; info_.depth_store_op = (int32_t)a.store_op;
         info_.clear_depth = a.clear_depth;
+        resolve_.depth_resolve_image = a.resolve_image ? a.resolve_image->handle() : nullptr; resolve_.depth_resolve_mode = (int32_t)a.resolve_mode;
         return *this;
     }
     // rendering.rs:818-838.  The scope loads, clears, draws and stores inside the rectangle only (include/mirhi.h, mirhi_rendering_info::render_area);
@@ -461,9 +484,11 @@ public:
     uint32_t width() const { return w_; }
     uint32_t height() const { return h_; }
     const mirhi_rendering_info& build() const { return info_; }
+    const mirhi_resolve_info& resolve() const { return resolve_; }      // all NULL / NONE unless an attachment came with_resolve
 private:
     uint32_t w_, h_;
     mirhi_rendering_info info_;
+    mirhi_resolve_info resolve_;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -495,6 +520,8 @@ public:
     void end() const { check(mirhi_cmd_end(h_)); }
     void reset() const { check(mirhi_cmd_reset(h_)); }
     void begin_rendering(const mirhi_rendering_info& info) const { check(mirhi_cmd_begin_rendering(h_, &info)); }
+    // a config whose attachments came with_resolve opens a 4x multisampled scope; without one this is begin_rendering(cfg.build())
+    void begin_rendering(const RenderingConfig& cfg) const { check(mirhi_cmd_begin_rendering_resolve(h_, &cfg.build(), &cfg.resolve())); }
     void end_rendering() const { check(mirhi_cmd_end_rendering(h_)); }
     void bind_pipeline(const Pipeline& p) const { check(mirhi_cmd_bind_pipeline(h_, p.handle())); }
     void bind_vertex_buffers(uint32_t first_binding, const Buffer& b, uint64_t offset) const {

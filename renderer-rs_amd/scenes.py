@@ -1424,3 +1424,133 @@ def cascaded_ground_case(width: int = 480, height: int = 360, map_size: int = 20
     spec = CascadeSpec(casters, (map_size, map_size), csm_ubo(cas.matrices, cas.split_depths, 0.005, 0.01, float(map_size)),
                        blend_threshold=float(blend_threshold))
     return Scene("cascaded-ground", width, height, draws, clear_color=(0.02, 0.02, 0.03, 1.0), cascades=spec)
+
+
+# ------------------------------------------------------------------------------------------------
+# 4x MSAA (include/mirhi.h "4x MSAA"): the float64 model of a multisampled scope
+# ------------------------------------------------------------------------------------------------
+# Vulkan's standard 4x sample positions inside a pixel, as (x, y) fractions; in 1/256 px (96, 32), (224, 96), (32, 160), (160, 224)
+MSAA_SAMPLES = ((0.375, 0.125), (0.875, 0.375), (0.125, 0.625), (0.625, 0.875))
+NO_PRIM = 0xFFFFFFFF
+
+
+def msaa_resolve(c0, c1, c2, c3, dtype=np.float64):
+    """AVERAGE: ((c0 + c1) + (c2 + c3)) / 4 per channel, every operation rounded to `dtype` (np.float32: the bits the kernel stores)."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=dtype) for c in (c0, c1, c2, c3))
+    return (((c0 + c1).astype(dtype) + (c2 + c3).astype(dtype)).astype(dtype) * dtype(0.25)).astype(dtype)
+
+
+def msaa_sample_scene(scene: "Scene", s: int) -> "Scene":
+    """The 1x scene whose frame is sample `s` of the multisampled frame of `scene`: every viewport moved by (1/2 - sx, 1/2 - sy), the scissors
+    unchanged -- a pixel centre of the moved frame then sits where sample s of that pixel sat.  Bit for bit in winner and depth under the condition
+    tests/msaa_cases.py states (the moved viewport must move every SNAPPED vertex by exactly that offset)."""
+    import dataclasses
+    sx, sy = MSAA_SAMPLES[s]
+    draws = []
+    for d in scene.draws:
+        x, y, w, h, n, f = d.viewport or (0.0, 0.0, float(scene.width), float(scene.height), 0.0, 1.0)
+        draws.append(dataclasses.replace(d, viewport=(x + (0.5 - sx), y + (0.5 - sy), w, h, n, f)))
+    return dataclasses.replace(scene, draws=draws)
+
+
+def _msaa_triangles(scene: "Scene"):
+    """The TRIANGLE-program triangles of `scene` in primitive order: (snapped X, Y in 1/256 px oriented so that the interior has E > 0, window x / y / z
+    of the three vertices as float64 in the ORIGINAL order, their colours, the draw) -- or None where the draw culls it.  The model takes vertices with
+    w = 1 inside the guard band and depth range; it knows no clipping."""
+    out = []
+    for d in scene.draws:
+        if d.program != PROGRAM_TRIANGLE:
+            raise NotImplementedError("the float64 MSAA model shades the TRIANGLE program only")
+        v = np.ascontiguousarray(d.vertices).view(np.uint8).reshape(-1, d.stride)[:, :24].copy().view(f32).reshape(-1, 6)
+        idx = (np.asarray(d.indices, dtype=np.int64)[d.first:d.first + d.count] + d.vertex_offset) if d.indices is not None else np.arange(d.first, d.first + d.count)
+        vx, vy, vw, vh, zn, zf = d.viewport or (0.0, 0.0, float(scene.width), float(scene.height), 0.0, 1.0)
+        for _ in range(max(0, int(d.instances))):
+            for t in range(d.count // 3):
+                p = v[idx[3 * t:3 * t + 3]].astype(np.float64)
+                # (the kernels' binary32 viewport transform, then the snap: round-half-even to 8 sub-pixel bits)
+                xs = (p[:, 0].astype(f32) * f32(0.5 * vw) + f32(vx + 0.5 * vw)).astype(f32)
+                ys = (p[:, 1].astype(f32) * f32(0.5 * vh) + f32(vy + 0.5 * vh)).astype(f32)
+                zs = (p[:, 2].astype(f32) * f32(zf - zn) + f32(zn)).astype(f32).astype(np.float64)
+                X = np.rint(xs.astype(np.float64) * 256.0).astype(np.int64)
+                Y = np.rint(ys.astype(np.float64) * 256.0).astype(np.int64)
+                S = (X[1] - X[0]) * (Y[2] - Y[0]) - (X[2] - X[0]) * (Y[1] - Y[0])
+                front = S < 0 if d.front_face == FRONT_CCW else S > 0
+                culled = S == 0 or d.cull_mode == CULL_FRONT_AND_BACK or (d.cull_mode == CULL_BACK and not front) or (d.cull_mode == CULL_FRONT and front)
+                if culled:
+                    out.append(None)
+                    continue
+                order = [0, 2, 1] if S < 0 else [0, 1, 2]
+                out.append(dict(X=X[order], Y=Y[order], z=zs[order], win=np.stack([xs, ys], axis=1).astype(np.float64), col=p[:, 3:6], draw=d))
+    return out
+
+
+def msaa_model(scene: "Scene", positions=MSAA_SAMPLES) -> dict:
+    """The float64 model of one 4x multisampled scope of TRIANGLE-program draws (one depth state: test and write with an ordering compare op).
+    Returns prim [H, W, 4] uint32 (the winner of each sample, NO_PRIM where none), depth [H, W, 4] float64 (the winner's depth plane at the sample,
+    the clear depth where none), sample_color [H, W, 4 samples, 4] (the winner's colour at the PIXEL CENTRE, extrapolated where it does not cover
+    the centre; the clear colour where none) and color [H, W, 4] = msaa_resolve of the four.  positions: the sample positions (a single (0.5, 0.5)
+    repeated gives the 1x frame four times)."""
+    H, W = scene.height, scene.width
+    tris = _msaa_triangles(scene)
+    prim = np.full((H, W, 4), NO_PRIM, dtype=np.uint32)
+    depth = np.full((H, W, 4), float(np.float32(min(max(scene.clear_depth, 0.0), 1.0))), dtype=np.float64)
+    scol = np.empty((H, W, 4, 4), dtype=np.float64)
+    scol[:] = np.asarray(scene.clear_color, dtype=np.float32).astype(np.float64)
+    ops = {d.depth_compare for d in scene.draws}
+    assert len(ops) <= 1 and all(d.depth_test and d.depth_write for d in scene.draws), "one ordering depth state per multisampled scope"
+    op = ops.pop() if ops else CMP_LESS
+    for pid, t in enumerate(tris):
+        if t is None:
+            continue
+        d, X, Y, z = t["draw"], t["X"], t["Y"], t["z"]
+        sx0, sy0, sw, sh = d.scissor or (0, 0, W, H)
+        x0, x1 = max(int(X.min()) >> 8, sx0, 0), min((int(X.max()) >> 8) + 1, sx0 + sw, W)
+        y0, y1 = max(int(Y.min()) >> 8, sy0, 0), min((int(Y.max()) >> 8) + 1, sy0 + sh, H)
+        if x0 >= x1 or y0 >= y1:
+            continue
+        px, py = np.meshgrid(np.arange(x0, x1), np.arange(y0, y1))
+        # depth plane through the snapped vertices (float64; the kernels' binary32 plane agrees to rounding, exactly on dyadic inputs)
+        fx1, fy1, fx2, fy2 = (X[1] - X[0]) / 256.0, (Y[1] - Y[0]) / 256.0, (X[2] - X[0]) / 256.0, (Y[2] - Y[0]) / 256.0
+        area = fx1 * fy2 - fx2 * fy1
+        zx = ((z[1] - z[0]) * fy2 - (z[2] - z[0]) * fy1) / area
+        zy = ((z[2] - z[0]) * fx1 - (z[1] - z[0]) * fx2) / area
+        # the colour at the pixel centre from the unsnapped window positions (pixel/triangle.hlsl through shade_triangle_program), extrapolating
+        ax = t["win"][:, 0][:, None, None] - (px + 0.5)[None]
+        ay = t["win"][:, 1][:, None, None] - (py + 0.5)[None]
+        l = np.stack([ax[1] * ay[2] - ax[2] * ay[1], ax[2] * ay[0] - ax[0] * ay[2], ax[0] * ay[1] - ax[1] * ay[0]])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            b = l / l.sum(axis=0)
+        rgb = np.einsum("kyx,kc->yxc", b, t["col"])
+        rgba = np.concatenate([rgb, np.ones(rgb.shape[:2] + (1,))], axis=2)
+        for s, (fx, fy) in enumerate(positions):
+            SX, SY = px * 256 + int(round(fx * 256)), py * 256 + int(round(fy * 256))
+            inside = np.ones(px.shape, dtype=bool)
+            for i in range(3):
+                a, c = i, (i + 1) % 3
+                dx, dy = int(X[c] - X[a]), int(Y[c] - Y[a])
+                E = -dy * (SX - int(X[a])) + dx * (SY - int(Y[a]))
+                topleft = dy < 0 or (dy == 0 and dx > 0)
+                inside &= (E >= 0) if topleft else (E > 0)
+            zz = np.clip(z[0] + (SX / 256.0 - X[0] / 256.0) * zx + (SY / 256.0 - Y[0] / 256.0) * zy, 0.0, 1.0)
+            old = depth[y0:y1, x0:x1, s]
+            if op in (CMP_LESS, CMP_GREATER):       # strict: a tie keeps the earlier primitive (and the clear depth); or-equal: the later one wins
+                win = (zz < old) if op == CMP_LESS else (zz > old)
+            else:
+                win = (zz <= old) if op == CMP_LESS_OR_EQUAL else (zz >= old)
+            win &= inside
+            depth[y0:y1, x0:x1, s] = np.where(win, zz, old)
+            prim[y0:y1, x0:x1, s] = np.where(win, np.uint32(pid), prim[y0:y1, x0:x1, s])
+            scol[y0:y1, x0:x1, s] = np.where(win[..., None], rgba, scol[y0:y1, x0:x1, s])
+    return dict(prim=prim, depth=depth, sample_color=scol, color=msaa_resolve(scol[:, :, 0], scol[:, :, 1], scol[:, :, 2], scol[:, :, 3]))
+
+
+def msaa_triangle_colour(scene: "Scene", pid: int) -> np.ndarray:
+    """[H, W, 4] float64: the colour the TRIANGLE program gives primitive `pid` of the scene at every pixel centre, extrapolated outside the triangle
+    (what a multisampled scope shades for a winner that does not cover the centre)."""
+    t = _msaa_triangles(scene)[pid]
+    px, py = np.meshgrid(np.arange(scene.width), np.arange(scene.height))
+    ax = t["win"][:, 0][:, None, None] - (px + 0.5)[None]
+    ay = t["win"][:, 1][:, None, None] - (py + 0.5)[None]
+    l = np.stack([ax[1] * ay[2] - ax[2] * ay[1], ax[2] * ay[0] - ax[0] * ay[2], ax[0] * ay[1] - ax[1] * ay[0]])
+    rgb = np.einsum("kyx,kc->yxc", l / l.sum(axis=0), t["col"])
+    return np.concatenate([rgb, np.ones(rgb.shape[:2] + (1,))], axis=2)
