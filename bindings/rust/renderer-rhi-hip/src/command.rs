@@ -99,6 +99,20 @@ impl CommandBuffer {
         ri.depth_load_op = depth_load_op as i32; ri.depth_store_op = StoreOp::Store as i32; ri.clear_depth = clear_depth;
         check(unsafe { mirhi_sys::mirhi_cmd_begin_rendering(self.raw, &ri) })
     }
+    /// A multiview depth scope (RenderingConfig::with_view_mask, rendering.rs:841-862): the Shadow draws recorded in it are rendered once per set bit `v` of
+    /// `view_mask` into layer `v` of `depth_array` (`Image::new_array`), with view `v`'s 64-byte light matrix read at `view_offset + v * view_stride` of
+    /// `view_constants` when the scope executes; the draw's own Camera block still supplies `model`.  One scope, one launch per stage, all cascades.
+    pub fn begin_rendering_multiview(&self, depth_array: &Image, depth_load_op: LoadOp, clear_depth: f32, view_mask: u32, view_constants: &Buffer,
+                                     view_offset: u64, view_stride: u32) -> RhiResult<()> {
+        let mut ri = std::mem::MaybeUninit::<mirhi_sys::mirhi_rendering_info>::zeroed();
+        unsafe { mirhi_sys::mirhi_rendering_info_default(ri.as_mut_ptr()) };
+        let mut ri = unsafe { ri.assume_init() };
+        ri.color_image = std::ptr::null_mut();
+        ri.depth_image = depth_array.raw;
+        ri.depth_load_op = depth_load_op as i32; ri.depth_store_op = StoreOp::Store as i32; ri.clear_depth = clear_depth;
+        let mv = mirhi_sys::mirhi_multiview_info { view_mask, view_constants: view_constants.raw, view_offset, view_stride };
+        check(unsafe { mirhi_sys::mirhi_cmd_begin_rendering_multiview(self.raw, &ri, &mv) })
+    }
     pub fn end_rendering(&self) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_cmd_end_rendering(self.raw) }) }  // :417
     pub fn bind_pipeline(&self, pipeline: &Pipeline) -> RhiResult<()> {                                              // :433
         check(unsafe { mirhi_sys::mirhi_cmd_bind_pipeline(self.raw, pipeline.raw) })

@@ -40,7 +40,9 @@ extern "C" {
                                     still 5 (new functions, structs and one enum only): the seven transfer commands, mirhi_buffer_copy, mirhi_buffer_image_copy,
                                     mirhi_image_copy, mirhi_image_blit, mirhi_filter;
                                     still 5 (new functions, one struct and one enum only; rasterization_samples = 4 accepted): mirhi_image_create_multisampled,
-                                    mirhi_image_samples, mirhi_resolve_mode, mirhi_resolve_info, mirhi_cmd_begin_rendering_resolve */
+                                    mirhi_image_samples, mirhi_resolve_mode, mirhi_resolve_info, mirhi_cmd_begin_rendering_resolve;
+                                    still 5 (two new functions and one struct only): mirhi_multiview_info, mirhi_multiview_info_default,
+                                    mirhi_cmd_begin_rendering_multiview */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -448,6 +450,34 @@ typedef struct {
 } mirhi_resolve_info;
 void         mirhi_resolve_info_default(mirhi_resolve_info* resolve);   /* NULL / NONE */
 mirhi_result mirhi_cmd_begin_rendering_resolve(mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_resolve_info* resolve);
+/* Multiview depth scopes (RenderingConfig::with_view_mask / with_layer_count rendering.rs:841-862): ONE depth-only scope that renders its draws
+ * once per set bit of view_mask, view v into layer v of a D32_SFLOAT image array -- all cascades of a cascaded shadow map recorded once and dispatched as one
+ * vertex, one geometry and one raster launch.  Semantics: the scope is, bit for bit in every layer, the single-view depth-only scopes of
+ * mirhi_cmd_begin_rendering: for each set bit v the same binds and draws into the layer view of layer v, with the first 64 bytes of the ShadowConstants at
+ * MIRHI_SLOT_CAMERA (lightSpaceMatrix) replaced by the 64 bytes at view_offset + v * view_stride of view_constants; `model` @64 still comes from the draw's own
+ * CAMERA block, which must be bound as for any SHADOW draw.  v is Vulkan's ViewIndex.  The matrices are read when the scope EXECUTES, like every uniform.
+ *   info   depth_image is the ARRAY itself (mirhi_image_create_array), not a layer view; color_image and prim_id_image NULL; depth_load_op CLEAR or LOAD;
+ *          depth_store_op STORE; the full extent.  Layers whose bit is clear are not touched.
+ *   state  viewport, scissor, depth bias and clamp, cull mode and front face, indexed, instanced and indirect draws apply to every view alike.
+ *   order  across queue lanes by the array ("ordering is by the parent").  mirhi_device_stats: frames_submitted counts the scope once, triangles_submitted its
+ *          triangles once per view.
+ * Matrix storage: as ShadowConstants stores lightSpaceMatrix (16 floats, the order of every matrix of this interface).  With view_stride = 80 and view_offset = 0
+ * the layout is CSMParams' (Cascades[k].ViewProjection @80k, shadow_csm.hlsli:23-28), so one buffer can feed the shadow pass and mirhi_cmd_bind_shadow_cascades --
+ * PROVIDED the shadow pass renders with the very matrix the lookup uses.  A shadow pass that renders into a plain viewport with clip y negated (the lookup's
+ * v = 1 - (y * 0.5 + 0.5), shadow.hlsli:65-66: what the scenes of this repository do, scenes.flip_clip_y) needs view constants of its own: the CSMParams
+ * matrices with the second component of every column negated, at the same stride.
+ * Refused with "unsupported:" where it is recorded: a colour attachment or prim_id_image; a depth image that is not an array, or is multisampled; load / store ops
+ * other than the above; an empty mask, more than 8 bits, a bit at or above mirhi_image_layers; NULL, misaligned or too short view constants, a view_stride below 64
+ * or not a multiple of 16; a partial render area; a split device; MIRHI_PROFILE_FRAGMENTS; any draw whose program is not SHADOW.  The scope ends with
+ * mirhi_cmd_end_rendering.  mirhi_cmd_begin_rendering itself keeps refusing an array. */
+typedef struct {
+    uint32_t      view_mask;        /* bit v: view v is rendered into layer v of the depth array; 1..8 bits set, every set bit < mirhi_image_layers */
+    mirhi_buffer* view_constants;   /* per-view constants, read when the scope executes (not latched at record time) */
+    uint64_t      view_offset;      /* view v reads its 64-byte lightSpaceMatrix at view_offset + v * view_stride; a multiple of 16 */
+    uint32_t      view_stride;      /* >= 64, a multiple of 16 */
+} mirhi_multiview_info;
+void         mirhi_multiview_info_default(mirhi_multiview_info* multiview);   /* mask 0, NULL, offset 0, stride 64 */
+mirhi_result mirhi_cmd_begin_rendering_multiview(mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_multiview_info* multiview);
 mirhi_result mirhi_cmd_end_rendering(mirhi_cmd* cmd);                               /* end_rendering :417 */
 mirhi_result mirhi_cmd_bind_pipeline(mirhi_cmd* cmd, mirhi_pipeline* pipeline);     /* bind_pipeline :433 */
 mirhi_result mirhi_cmd_bind_vertex_buffers(mirhi_cmd* cmd, uint32_t first_binding, uint32_t count, mirhi_buffer* const* buffers, const uint64_t* offsets); /* :448 */

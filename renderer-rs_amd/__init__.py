@@ -185,6 +185,10 @@ class ResolveInfo(C.Structure):      # mirhi_resolve_info
                 ("depth_resolve_image", C.c_void_p), ("depth_resolve_mode", C.c_int32)]
 
 
+class MultiviewInfo(C.Structure):      # mirhi_multiview_info
+    _fields_ = [("view_mask", C.c_uint32), ("view_constants", C.c_void_p), ("view_offset", C.c_uint64), ("view_stride", C.c_uint32)]
+
+
 class Viewport(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("width", C.c_float), ("height", C.c_float),
                 ("min_depth", C.c_float), ("max_depth", C.c_float)]
@@ -325,6 +329,8 @@ _SIGNATURES = {
     "mirhi_cmd_begin_rendering": (C.c_int32, [C.c_void_p, C.POINTER(RenderingInfo)]),
     "mirhi_resolve_info_default": (None, [C.POINTER(ResolveInfo)]),
     "mirhi_cmd_begin_rendering_resolve": (C.c_int32, [C.c_void_p, C.POINTER(RenderingInfo), C.POINTER(ResolveInfo)]),
+    "mirhi_multiview_info_default": (None, [C.POINTER(MultiviewInfo)]),
+    "mirhi_cmd_begin_rendering_multiview": (C.c_int32, [C.c_void_p, C.POINTER(RenderingInfo), C.POINTER(MultiviewInfo)]),
     "mirhi_cmd_end_rendering": (C.c_int32, [C.c_void_p]),
     "mirhi_cmd_bind_pipeline": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_cmd_bind_vertex_buffers": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
@@ -874,6 +880,16 @@ def resolve_info(color_resolve=None, depth_resolve=None, color_mode=None, depth_
     return r
 
 
+def multiview_info(view_mask: int, view_constants=None, view_offset: int = 0, view_stride: int = 64) -> MultiviewInfo:
+    """The mirhi_multiview_info of CommandBuffer.begin_rendering_multiview: the library's defaults, then the arguments."""
+    m = MultiviewInfo()
+    lib().mirhi_multiview_info_default(C.byref(m))
+    m.view_mask = int(view_mask)
+    m.view_constants = view_constants.handle if view_constants is not None else None
+    m.view_offset, m.view_stride = int(view_offset), int(view_stride)
+    return m
+
+
 class ColorAttachment:
     """rhi::ColorAttachment (rendering.rs:65-115): the image with its ops; with_resolve (rendering.rs:238) names the 1x image a multisampled one resolves to."""
 
@@ -947,6 +963,17 @@ class CommandBuffer:
         info.color_store_op = color_store_op
         res = resolve_info(color_resolve, depth_resolve, color_mode, depth_mode)
         check(lib().mirhi_cmd_begin_rendering_resolve(self.handle, C.byref(info), C.byref(res)))
+
+    def begin_rendering_multiview(self, depth_array: Optional[Image], view_mask: int, view_constants: Optional["Buffer"], view_offset: int = 0, view_stride: int = 64,
+                                  clear_depth: float = 1.0, depth_load_op=LoadOp.CLEAR, depth_store_op=StoreOp.STORE, color: Optional[Image] = None,
+                                  prim_id: Optional[Image] = None, render_area=None):
+        """mirhi_cmd_begin_rendering_multiview: ONE depth-only scope whose Program.SHADOW draws are rendered once per set bit v of view_mask into layer v of
+        depth_array (Image.array), with the light matrix of view v read at view_offset + v * view_stride of view_constants when the scope executes (the draw's own
+        CAMERA block still supplies `model` @64).  color / prim_id / render_area exist to show the refusals."""
+        info = rendering_info(color, depth=depth_array, clear_depth=clear_depth, depth_load_op=depth_load_op, depth_store_op=depth_store_op, prim_id=prim_id,
+                              render_area=render_area)
+        mv = multiview_info(view_mask, view_constants, view_offset, view_stride)
+        check(lib().mirhi_cmd_begin_rendering_multiview(self.handle, C.byref(info), C.byref(mv)))
 
     def begin_rendering_attachments(self, color: ColorAttachment, depth: Optional[DepthAttachment] = None, prim_id: Optional[Image] = None, render_area=None):
         """The scope given by attachments, as the reference's RenderingConfig takes them; a with_resolve attachment makes it a multisampled scope."""
@@ -1137,7 +1164,8 @@ class SceneResources:
                  want_depth: bool = False, color_image: Optional[Image] = None, wrap_buffers=None,
                  color_load_op: int = LoadOp.CLEAR, shadow_cmd: bool = False, shadow_map: Optional[Image] = None,
                  cascade_array: Optional[Image] = None, ibl_images: Optional[Sequence[Image]] = None, sky_image: Optional[Image] = None,
-                 depth_image: Optional[Image] = None, prim_image: Optional[Image] = None, depth_load_op: int = LoadOp.CLEAR, samples: int = 1):
+                 depth_image: Optional[Image] = None, prim_image: Optional[Image] = None, depth_load_op: int = LoadOp.CLEAR, samples: int = 1,
+                 multiview: bool = False):
         """scene.shadow (scenes.ShadowSpec) adds a depth-only shadow scope ahead of the main scope: recorded into the same command
         buffer, or with shadow_cmd=True into a command buffer of its own (self.shadow_cmd; render() submits both, the shadow one first --
         put it on another queue lane with set_queue_lane).  shadow_map: an existing D32 image to render into (shared between frames).
@@ -1158,6 +1186,7 @@ class SceneResources:
         image of per-sample winners, which read() returns as [height, width, 4]."""
         self.device, self.scene = device, scene
         self.samples = int(samples)
+        self.multiview = bool(multiview)      # scene.cascades: ONE multiview scope for all cascades (scenes.record_cascades_multiview) instead of one scope per layer view
         self.color_load_op = color_load_op
         self.owns_color = color_image is None
         self.objs = []
@@ -1270,6 +1299,10 @@ class SceneResources:
                 self.cascade_array, self.owns_cascade_array = Image.array(device, cs.size[0], cs.size[1], len(cs.casters), Format.D32_SFLOAT), True
             self.cascade_views = [self.cascade_array.layer_view(k) for k in range(len(cs.casters))]
             self.cascade_params = buf(BufferUsage.Uniform, cs.params, key=("u", cs.params))
+            self.view_constants = None
+            if self.multiview:
+                vc = scenes.cascade_view_constants(cs)
+                self.view_constants = buf(BufferUsage.Uniform, vc, key=("u", vc))
             for layer in cs.casters:
                 states = []
                 for c in layer:
@@ -1319,7 +1352,9 @@ class SceneResources:
         cmd.draw(3, 1, 0, 0)
 
     def _record_shadow(self, cmd: "CommandBuffer"):
-        if self.cascades is not None:
+        if self.cascades is not None and self.multiview:
+            scenes.record_cascades_multiview(cmd, self.cascades, self.cascade_array, self.cascade_state[0], self.view_constants)
+        elif self.cascades is not None:
             for view, states in zip(self.cascade_views, self.cascade_state):
                 self._record_depth_scope(cmd, self.cascades, view, states)
         else:

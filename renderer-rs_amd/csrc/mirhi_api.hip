@@ -527,6 +527,10 @@ struct RecordedPass {
     int32_t area[4] = {0, 0, 0, 0};
     bool depth_only = false;               // color_image NULL: SHADOW draws into the depth image (raster_kernel_depth)
     uint32_t samples = 1;                  // 4: a multisampled scope (mirhi_cmd_begin_rendering_resolve): info / color_t / depth_t name its RESOLVE images
+    // A multiview depth scope (mirhi_cmd_begin_rendering_multiview): view_mask != 0; depth_only is set, info.depth_image is the ARRAY and depth_t its
+    // base with ONE layer's extent; view v reads its light matrix at view_base + v * view_stride (view_base: the constants buffer's address + view_offset)
+    uint32_t view_mask = 0, view_stride = 0;
+    const uint8_t* view_base = nullptr;
     std::vector<mirhi_image*> sampled;     // shadow maps the scope's draws sample (MIRHI_TEXTURE_SHADOW_MAP): ordered like attachments
     // the IBL set the scope's MODEL_PBR_IBL draws were recorded under (mirhi_cmd_bind_ibl; one per scope, all its segments): resolved like the targets
     struct IblSet {
@@ -609,14 +613,33 @@ struct Workspace {
     uint32_t* prim_draw = nullptr; size_t prim_draw_bytes = 0;     // per primitive: its draw (scopes with several draws)
     uint32_t* status_host = nullptr;                             // pinned, device-mapped: [status bits, big-list length]
     uint32_t* status_dev = nullptr;                              // device view of status_host
-    void clear_status() { status_host[0] = 0; status_host[1] = 0; status_host[2] = 0; status_host[3] = 0; }      // re-arms the four words the kernels report in
+    // re-arms the four words the kernels report in, and the four of each view slot of a multiview scope behind them (STATUS_WORDS in all)
+    static constexpr uint32_t STATUS_VIEWS = 16u, STATUS_WORDS = STATUS_VIEWS + 4u * (uint32_t)MAX_BATCH;
+    void clear_status() { for (uint32_t i = 0; i < STATUS_WORDS; i++) status_host[i] = 0; }
+    // status bits of the last submission: the scopes' own and those of every view slot
+    uint32_t status_bits() const { uint32_t b = status_host[0]; for (uint32_t j = 0; j < (uint32_t)MAX_BATCH; j++) b |= status_host[STATUS_VIEWS + 4u * j]; return b; }
+    bool any_status() const { uint32_t b = 0; for (uint32_t i = 0; i < STATUS_WORDS; i++) b |= status_host[i]; return b != 0; }
+    // Multiview depth scopes: view slot j has bins, page table, counters, big list and vertex output of its own -- the j-th slice of these
+    // buffers (strides in the units named) -- so that the views of a scope can run side by side; the single-view buffers above are not touched by such a scope.
+    // Like those, the slices only grow, and their counters and tables are left re-armed by the kernels; a slot's big-list parity (bit j of mv_parity) flips
+    // when the slot is used, whatever the other scopes of the command buffer do.
+    BinRec* mv_pool = nullptr; size_t mv_pool_bytes = 0, mv_pool_pages = 0;
+    uint32_t* mv_table = nullptr; size_t mv_table_bytes = 0, mv_tiles = 0;
+    uint32_t* mv_counters = nullptr; size_t mv_counters_bytes = 0, mv_counter_words = 0;
+    BigRec* mv_big = nullptr; size_t mv_big_bytes = 0, mv_big_cap = 0;
+    uint8_t* mv_vs = nullptr; size_t mv_vs_bytes = 0, mv_vs_stride = 0;
+    uint32_t mv_slots = 0, mv_parity = 0; bool mv_dirty = true;
+    size_t mv_params_off = 0;                                    // where the views' PassParams start in the parameter block (two per view slot: parity 0 / 1)
     uint32_t* big_counts = nullptr;                              // two counters, used alternately (parity)
     uint32_t parity = 0;
     // statistics pass (MIRHI_PROFILE_FRAGMENTS), built on first use: a primitive-id image of the workspace's own and copies
     // of the scopes' parameters that write it, so that the product kernels and parameters stay untouched
     uint32_t* stats_prim = nullptr; size_t stats_prim_bytes = 0;
     PassParams* stats_params = nullptr; size_t stats_params_bytes = 0; bool stats_params_valid = false;
-    size_t bytes() const { return pblock_bytes + bin_pool_bytes + bin_table_bytes + counters_words * 4 + big_recs_bytes + vs_out_bytes + flat_color_bytes; }
+    size_t bytes() const {
+        return pblock_bytes + bin_pool_bytes + bin_table_bytes + counters_words * 4 + big_recs_bytes + vs_out_bytes + flat_color_bytes + mv_pool_bytes + mv_table_bytes +
+               mv_counters_bytes + mv_big_bytes + mv_vs_bytes;
+    }
 };
 
 enum CmdState { CMD_INITIAL = 0, CMD_RECORDING = 1, CMD_EXECUTABLE = 2 };
@@ -660,6 +683,11 @@ struct mirhi_cmd {
     std::vector<PassParams> plan;
     std::vector<uint32_t> plan_programs;
     uint64_t plan_tris = 0;
+    // multiview scopes of the plan: per entry of `plan` its view slots (count 0: a single-view scope) and where their parameters start -- `first` counts view
+    // slots of the whole plan: plan_view_params[first + j] is slot j's host copy, its two device copies are PassParams 2 * (first + j) + parity behind mv_params_off
+    struct ViewSet { uint32_t count = 0; size_t first = 0; };
+    std::vector<ViewSet> plan_views;
+    std::vector<PassParams> plan_view_params;
 };
 
 struct mirhi_fence {
@@ -1528,6 +1556,7 @@ static void free_workspace(mirhi_cmd* c) {
     if (w.stats_prim) (void)hipFree(w.stats_prim);
     if (w.stats_params) (void)hipFree(w.stats_params);
     if (w.status_host) (void)hipHostFree(w.status_host);
+    for (void* p : {(void*)w.mv_pool, (void*)w.mv_table, (void*)w.mv_counters, (void*)w.mv_big, (void*)w.mv_vs}) if (p) (void)hipFree(p);
     w = Workspace();
 }
 
@@ -1760,6 +1789,49 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering_resolve(mirhi_cmd* cmd, const 
     cmd->in_rendering = true;
     return MIRHI_OK;
 }
+// A multiview depth scope: ONE recorded pass -- a depth-only one whose depth target is the array's base with one layer's extent -- that carries
+// the view mask and where the views' matrices are.  Its draws are recorded once, like a single-view scope's; build_plan expands them to one parameter block per
+// view, submit_now sends the views as one launch per stage.  The refusals are mirhi_scope.h's (multiview_scope_refusal).
+static MultiviewFacts multiview_facts(const mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_multiview_info* mv, bool area_partial) {
+    MultiviewFacts f{};
+    const mirhi_image* di = info->depth_image;
+    f.has_color = info->color_image != nullptr; f.has_prim = info->prim_id_image != nullptr; f.has_depth = di != nullptr;
+    if (di) { f.depth_is_array = di->is_array && !di->is_cube; f.depth_samples = di->samples; f.depth_format = (uint32_t)di->format; f.layers = di->layers; }
+    f.depth_load_op = info->depth_load_op; f.depth_store_op = info->depth_store_op;
+    f.view_mask = mv->view_mask; f.has_constants = mv->view_constants != nullptr; f.view_stride = mv->view_stride; f.view_offset = mv->view_offset;
+    f.constants_bytes = mv->view_constants ? mv->view_constants->size : 0u;
+    f.area_partial = area_partial; f.split_device = cmd->dev->split_world > 1; f.fragment_stats = (cmd->dev->profiling & MIRHI_PROFILE_FRAGMENTS) != 0;
+    return f;
+}
+extern "C" void mirhi_multiview_info_default(mirhi_multiview_info* m) { if (m) { memset(m, 0, sizeof *m); m->view_stride = 64u; } }
+extern "C" mirhi_result mirhi_cmd_begin_rendering_multiview(mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_multiview_info* multiview) {
+    REQUIRE_RECORDING(cmd); NULL_CHECK(info, "rendering_info"); NULL_CHECK(multiview, "multiview_info");
+    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
+    const mirhi_image* di = info->depth_image;
+    bool area_partial = false;
+    if (di && di->is_array) {
+        const RenderArea area = render_area(di->width, di->height, info->render_area);
+        if (!area.valid) {
+            char msg[192];
+            render_area_message(msg, sizeof msg, info->render_area, di->width, di->height);
+            return fail(MIRHI_ERR_INVALID_HANDLE, "%s", msg);
+        }
+        area_partial = area.partial;
+    }
+    if (const char* why = multiview_scope_refusal(multiview_facts(cmd, info, multiview, area_partial))) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", why);
+    if (di->dev != cmd->dev || multiview->view_constants->dev != cmd->dev)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the depth array or the view constants belong to another device than the command buffer");
+    RecordedPass p;
+    p.info = *info;
+    p.depth_only = true;
+    p.color_t = {nullptr, di->width, di->height, (uint32_t)MIRHI_FORMAT_UNDEFINED};
+    p.depth_t = {di->ptr, di->width, di->height, (uint32_t)di->format};
+    p.area[0] = 0; p.area[1] = 0; p.area[2] = (int32_t)di->width; p.area[3] = (int32_t)di->height;
+    p.view_mask = multiview->view_mask; p.view_stride = multiview->view_stride; p.view_base = multiview->view_constants->ptr + multiview->view_offset;
+    cmd->passes.push_back(std::move(p));
+    cmd->in_rendering = true;
+    return MIRHI_OK;
+}
 extern "C" mirhi_result mirhi_cmd_end_rendering(mirhi_cmd* cmd) {
     REQUIRE_RECORDING(cmd);
     if (!cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: end_rendering without begin_rendering");
@@ -1902,6 +1974,7 @@ static void cut_segment(mirhi_cmd* cmd) {
         next.info = prev.info;
         next.color_t = prev.color_t; next.depth_t = prev.depth_t; next.prim_t = prev.prim_t;
         next.depth_only = prev.depth_only; next.ibl = prev.ibl;
+        next.view_mask = prev.view_mask; next.view_stride = prev.view_stride; next.view_base = prev.view_base;
         memcpy(next.area, prev.area, sizeof next.area);
         next.info.color_load_op = MIRHI_LOAD_OP_LOAD;
         next.carry_in = true;
@@ -2004,6 +2077,8 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     REQUIRE_RECORDING(cmd);
     if (!cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: draw outside a rendering scope");
     if (!cmd->pipeline) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: no pipeline bound");
+    if (cmd->passes.back().view_mask)      // (a multiview scope refuses every program but SHADOW in its own words, ahead of the depth-only scope's)
+        if (const char* why = multiview_program_refusal(cmd->pipeline->desc.vertex_program)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", why);
     if (cmd->pipeline->desc.vertex_program == MIRHI_PROGRAM_SKYBOX) return record_sky_draw(cmd, indexed, count, instance_count, first);
     if (!cmd->vb) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: no vertex buffer bound to binding 0");
     if (indexed && !cmd->ib) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: no index buffer bound");
@@ -2543,7 +2618,7 @@ static bool same_recording(const std::vector<RecordedPass>& a, const std::vector
             memcmp(&x.info.clear_depth, &y.info.clear_depth, sizeof(float)) != 0) return false;
         if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || !(x.state == y.state) ||
             x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
-        if (x.samples != y.samples) return false;
+        if (x.samples != y.samples || x.view_mask != y.view_mask || x.view_stride != y.view_stride || x.view_base != y.view_base) return false;
         if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl) || !(x.sky == y.sky)) return false;
         if (!(x.xfer == y.xfer) || x.xfer_regions.size() != y.xfer_regions.size() ||
             (!x.xfer_regions.empty() && memcmp(x.xfer_regions.data(), y.xfer_regions.data(), x.xfer_regions.size() * sizeof(XferRegion)) != 0)) return false;
@@ -2575,6 +2650,8 @@ static bool recording_reads(const std::vector<RecordedPass>& passes, const uint8
             if (in(d.vb) || in(d.ib) || in(d.camera) || in(d.object) || in(d.lights) || in(d.material) || in(d.point_lights) || in(d.spot_lights) ||
                 in(d.shadow_data)) return true;
         }
+        // the view constants of a multiview scope (read when it executes): [view_base, the highest view's matrix]
+        if (pass.view_mask && pass.view_base < hi && lo < pass.view_base + (size_t)(31 - __builtin_clz(pass.view_mask)) * pass.view_stride + 64) return true;
         // a transfer's buffers, read or written: a host write into either waits for it
         if (pass.xfer.kind && ((pass.xfer.span[0] && pass.xfer.span[0] < hi && lo < pass.xfer.span[1]) || (pass.xfer.span[2] && pass.xfer.span[2] < hi && lo < pass.xfer.span[3]))) return true;
     }
@@ -2616,7 +2693,7 @@ extern "C" mirhi_result mirhi_cmd_end(mirhi_cmd* cmd) {
         mirhi_result r = settle_pending(cmd);
         if (r != MIRHI_OK) return r;
         HP(1);
-        if (cmd->ws.status_host && (cmd->ws.status_host[0] | cmd->ws.status_host[1] | cmd->ws.status_host[2] | cmd->ws.status_host[3])) {
+        if (cmd->ws.status_host && cmd->ws.any_status()) {
             HP(2);
             hand_over_status(cmd);
             HP(3);
@@ -2633,7 +2710,7 @@ extern "C" mirhi_result mirhi_cmd_end(mirhi_cmd* cmd) {
         // The same frame into another swapchain image: the plan stands, PassParams::color of every scope is rewritten (host copy, both parities in the parameter block).
         mirhi_result r = settle_pending(cmd);                  // (the block is read by a submission that is still pending: wait for it -- a fenced loop has)
         if (r != MIRHI_OK) return r;
-        if (cmd->ws.status_host && (cmd->ws.status_host[0] | cmd->ws.status_host[1] | cmd->ws.status_host[2] | cmd->ws.status_host[3])) {
+        if (cmd->ws.status_host && cmd->ws.any_status()) {
             hand_over_status(cmd);
             cmd->ws.clear_status();
         }
@@ -2777,7 +2854,7 @@ static mirhi_result rearm_workspace(mirhi_cmd* cmd, const std::vector<ScopePlan>
     }
     if (knobs.always_clear.set) w.dirty = true;             // (A/B runs: the round-2 behaviour, two memsets per recording)
     if (!w.status_host) {
-        HIP_TRY(hipHostMalloc((void**)&w.status_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostMalloc((void**)&w.status_host, Workspace::STATUS_WORDS * 4u, hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(hipHostGetDevicePointer((void**)&w.status_dev, w.status_host, 0));
     }
     w.stats_params_valid = false;
@@ -2804,6 +2881,7 @@ static mirhi_result rearm_workspace(mirhi_cmd* cmd, const std::vector<ScopePlan>
         cmd->dev->foreign_writes++;
         w.parity = 0;
         w.dirty = false;
+        w.mv_dirty = true;      // (whatever asked for the clears asked for those of the view slots too: grow_multiview)
         cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true;      // (a submit on another stream or queue waits for the clears)
     }
     return MIRHI_OK;
@@ -2862,6 +2940,57 @@ static mirhi_result grow_scope_buffers(Workspace& w, const std::vector<RecordedP
     if (ord && (r = grow(&w.ordered, &w.ordered_bytes, ord)) != MIRHI_OK) return r;
     if (flat_tris && (r = grow(&w.flat_color, &w.flat_color_bytes, flat_tris * 4)) != MIRHI_OK) return r;
     if (pd && (r = grow(&w.prim_draw, &w.prim_draw_bytes, pd * 4)) != MIRHI_OK) return r;
+    return MIRHI_OK;
+}
+
+// ... and the view slots of the command buffer's multiview scopes (Workspace::mv_*): slices for the most views, each sized for the largest such scope.  A
+// slice that moves (any of the strides grew) or was never used is cleared; otherwise the kernels left it re-armed, which MIRHI_VERIFY_IDLE checks here as
+// rearm_workspace does for the single-view buffers.
+static mirhi_result grow_multiview(mirhi_cmd* cmd, const std::vector<ScopePlan>& scopes, const std::vector<VertexPlan>& vertex, hipStream_t stream, const PlanKnobs& knobs) {
+    Workspace& w = cmd->ws;
+    size_t slots = 0, pages = 0, tiles = 0, big = 0, vs = 0;
+    for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
+        if (!cmd->passes[pi].view_mask) continue;
+        slots = std::max<size_t>(slots, multiview_count(cmd->passes[pi].view_mask));
+        pages = std::max(pages, scopes[pi].bins.pages); tiles = std::max(tiles, scopes[pi].tiles());
+        big = std::max<size_t>(big, scopes[pi].bins.big_cap); vs = std::max(vs, vertex[pi].out_bytes);
+    }
+    if (!slots) return MIRHI_OK;
+    const size_t words = CTR_BINS + tiles * (size_t)BIN_COUNT_STRIDE;
+    vs = std::max<size_t>(256, (vs + 255) & ~(size_t)255);
+    mirhi_result r;
+    if (slots > w.mv_slots || pages > w.mv_pool_pages || tiles > w.mv_tiles || words > w.mv_counter_words || big > w.mv_big_cap || vs > w.mv_vs_stride) {
+        w.mv_slots = (uint32_t)std::max<size_t>(slots, w.mv_slots); w.mv_pool_pages = std::max(pages, w.mv_pool_pages); w.mv_tiles = std::max(tiles, w.mv_tiles);
+        w.mv_counter_words = std::max(words, w.mv_counter_words); w.mv_big_cap = std::max(big, w.mv_big_cap); w.mv_vs_stride = std::max(vs, w.mv_vs_stride);
+        const size_t n = w.mv_slots;
+        if ((r = grow(&w.mv_pool, &w.mv_pool_bytes, n * w.mv_pool_pages * BIN_PAGE_RECS * sizeof(BinRec))) != MIRHI_OK) return r;
+        if ((r = grow(&w.mv_table, &w.mv_table_bytes, n * w.mv_tiles * BIN_TABLE_ROW * sizeof(uint32_t))) != MIRHI_OK) return r;
+        if ((r = grow(&w.mv_counters, &w.mv_counters_bytes, n * w.mv_counter_words * sizeof(uint32_t))) != MIRHI_OK) return r;
+        if ((r = grow(&w.mv_big, &w.mv_big_bytes, n * w.mv_big_cap * sizeof(BigRec))) != MIRHI_OK) return r;
+        if ((r = grow(&w.mv_vs, &w.mv_vs_bytes, n * w.mv_vs_stride)) != MIRHI_OK) return r;
+        w.mv_dirty = true;
+    }
+    if (!w.mv_dirty && knobs.verify_idle.set) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        const size_t cw = (size_t)w.mv_slots * w.mv_counter_words, tw = (size_t)w.mv_slots * w.mv_tiles * BIN_TABLE_ROW;
+        std::vector<uint32_t> c(cw), t(tw);
+        HIP_TRY(hipMemcpy(c.data(), w.mv_counters, cw * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t.data(), w.mv_table, tw * 4, hipMemcpyDeviceToHost));
+        size_t bad_c = 0, bad_t = 0;
+        for (size_t j = 0; j < w.mv_slots; j++)
+            for (size_t i = 0; i < w.mv_counter_words; i++)       // (as in rearm_workspace: the last length of the slot's big list, the busy-tile counters)
+                bad_c += (c[j * w.mv_counter_words + i] != 0u && i != (size_t)(CTR_BIG + (((w.mv_parity >> j) & 1u) ^ 1u)) && !(i >= CTR_ACTIVE && i < CTR_ACTIVE + 2u * 8u * 32u)) ? 1 : 0;
+        for (uint32_t v : t) bad_t += v != PAGE_EMPTY ? 1 : 0;
+        if (bad_c || bad_t) return fail(MIRHI_ERR_DEVICE, "Vulkan error: multiview workspace not idle between frames: %zu counter words, %zu page-table entries left set", bad_c, bad_t);
+    }
+    if (w.mv_dirty) {
+        HIP_TRY(hipMemsetAsync(w.mv_table, 0xFF, w.mv_table_bytes, stream));          // PAGE_EMPTY
+        HIP_TRY(hipMemsetAsync(w.mv_counters, 0, w.mv_counters_bytes, stream));
+        cmd->dev->foreign_writes++;
+        w.mv_parity = 0;
+        w.mv_dirty = false;
+        cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true;      // (a submit on another stream or queue waits for the clears)
+    }
     return MIRHI_OK;
 }
 
@@ -2964,6 +3093,8 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         if (scopes.back().area.partial && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a partial render area on a split device");
         if (pass.samples != 1u && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a multisampled scope on a split device");
         if (pass.samples != 1u && (dev->profiling & MIRHI_PROFILE_FRAGMENTS)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: fragment statistics of a multisampled scope");
+        if (pass.view_mask && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a multiview scope on a split device");
+        if (pass.view_mask && (dev->profiling & MIRHI_PROFILE_FRAGMENTS)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: fragment statistics of a multiview scope");
         total_draws += pass.draws.size();
         total_regions += pass.xfer_regions.size();
         max_tiles = std::max(max_tiles, scopes.back().tiles());
@@ -2973,12 +3104,21 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     size_t jobs_total = 0;
     for (const RecordedPass& pass : cmd->passes) { vertex.push_back(vertex_jobs(pass)); jobs_total += vertex.back().jobs.size(); }
     if ((r = grow_scope_buffers(w, cmd->passes, scopes, vertex)) != MIRHI_OK) return r;
-    // the parameter block: [2 x PassParams per scope][draw descriptors][transfer regions][vertex jobs]
+    if ((r = grow_multiview(cmd, scopes, vertex, stream, knobs)) != MIRHI_OK) return r;
+    // the parameter block: [2 x PassParams per scope][draw descriptors][transfer regions][vertex jobs], and behind them what the views of multiview scopes
+    // read: [2 x PassParams per view slot][their draw descriptors][their vertex jobs]
+    size_t mv_views = 0, mv_draws = 0, mv_jobs = 0;
+    for (size_t pi = 0; pi < n; pi++)
+        if (const uint32_t views = multiview_count(cmd->passes[pi].view_mask)) { mv_views += views; mv_draws += views * cmd->passes[pi].draws.size(); mv_jobs += views * vertex[pi].jobs.size(); }
     const size_t params_bytes = n * 2 * sizeof(PassParams);
     w.draws_off = (params_bytes + 255) & ~(size_t)255;
     const size_t regions_off = (w.draws_off + total_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
     w.jobs_off = (regions_off + total_regions * sizeof(XferRegion) + 255) & ~(size_t)255;
-    const size_t block_bytes = w.jobs_off + jobs_total * sizeof(VsJob);
+    size_t block_bytes = w.jobs_off + jobs_total * sizeof(VsJob);
+    w.mv_params_off = (block_bytes + 255) & ~(size_t)255;
+    const size_t mv_draws_off = (w.mv_params_off + mv_views * 2 * sizeof(PassParams) + 255) & ~(size_t)255;
+    const size_t mv_jobs_off = (mv_draws_off + mv_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
+    if (mv_views) block_bytes = mv_jobs_off + mv_jobs * sizeof(VsJob);
     if ((r = pblock_reserve(w, block_bytes ? block_bytes : 256)) != MIRHI_OK) return r;
     w.params = reinterpret_cast<PassParams*>(w.pblock);
     DrawDesc* const dev_draws = reinterpret_cast<DrawDesc*>(w.pblock + w.draws_off);
@@ -2986,9 +3126,10 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     w.pimage.assign(block_bytes, 0);
     w.draws_count = total_draws;
 
-    size_t draws_done = 0, jobs_done = 0, regions_done = 0;
+    size_t draws_done = 0, jobs_done = 0, regions_done = 0, views_done = 0, mv_draws_done = 0, mv_jobs_done = 0;
     w.wide_eligible = false;
     cmd->plan.clear(); cmd->plan_programs.clear(); cmd->plan_tris = 0;
+    cmd->plan_views.clear(); cmd->plan_view_params.clear();
     for (size_t pi = 0; pi < n; pi++) {
         const ScopePlan& s = scopes[pi];
         VertexPlan& v = vertex[pi];
@@ -3033,6 +3174,61 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
             Q.active_prev = w.counters + CTR_ACTIVE + (parity ^ 1u) * 8u * 32u;
             memcpy(w.pimage.data() + (2 * pi + parity) * sizeof(PassParams), &Q, sizeof Q);
         }
+        // A multiview scope: the parameters above once per view slot -- depth base = the view's layer, bins / page table / counters / big list / vertex output /
+        // status words = the slot's (Workspace::mv_*) -- with copies of the draws and vertex jobs that differ in the light matrix's address (and in where the
+        // slot's shaded vertices are) alone.  (plan[pi] itself stays: the host's idea of the scope's launch shape; its device copies are not launched.)
+        mirhi_cmd::ViewSet vset;
+        const RecordedPass& pass = cmd->passes[pi];
+        if (pass.view_mask) {
+            MultiviewSlot slot[MAX_BATCH];
+            vset.count = multiview_slots(pass.view_mask, pass.color_t.width, pass.color_t.height, 0u, pass.view_stride, slot);
+            vset.first = views_done;
+            for (uint32_t j = 0; j < vset.count; j++) {
+                const float* matrix = reinterpret_cast<const float*>(pass.view_base + slot[j].matrix_offset);
+                uint8_t* const vs_base = w.mv_vs + (size_t)j * w.mv_vs_stride;
+                uint32_t* const ctr = w.mv_counters + (size_t)j * w.mv_counter_words;
+                PassParams V = P;
+                V.depth = reinterpret_cast<float*>(const_cast<uint8_t*>(pass.depth_t.ptr) + slot[j].layer_offset);
+                V.bin_pool = w.mv_pool + (size_t)j * w.mv_pool_pages * BIN_PAGE_RECS;
+                V.bin_table = w.mv_table + (size_t)j * w.mv_tiles * BIN_TABLE_ROW;
+                V.bin_count = ctr + CTR_BINS; V.pool_next = ctr + CTR_POOL;
+                V.pool_dyn_pages = (uint32_t)((w.mv_pool_pages - s.bins.fixed_pages) / 8);
+                V.big_recs = w.mv_big + (size_t)j * w.mv_big_cap;
+                V.status = w.status_dev + Workspace::STATUS_VIEWS + 4u * j;
+                V.draws = reinterpret_cast<DrawDesc*>(w.pblock + mv_draws_off) + mv_draws_done;
+                DrawDesc* const img_draws = reinterpret_cast<DrawDesc*>(w.pimage.data() + mv_draws_off) + mv_draws_done;
+                for (size_t di = 0; di < v.draws.size(); di++) {
+                    DrawDesc c = v.draws[di];
+                    c.camera = matrix;
+                    if (c.vs_words) {
+                        c.vs_out = vs_base + (static_cast<const uint8_t*>(c.vs_out) - w.vs_out);
+                        c.vs_attr = vs_base + (static_cast<const uint8_t*>(c.vs_attr) - w.vs_out);
+                    }
+                    img_draws[di] = c;
+                }
+                mv_draws_done += v.draws.size();
+                V.vs_jobs = reinterpret_cast<VsJob*>(w.pblock + mv_jobs_off) + mv_jobs_done;
+                VsJob* const img_view_jobs = reinterpret_cast<VsJob*>(w.pimage.data() + mv_jobs_off) + mv_jobs_done;
+                for (size_t k = 0; k < v.jobs.size(); k++) {
+                    VsJob job = v.jobs[k];
+                    job.camera = matrix;
+                    job.out = vs_base + v.out_off[k];
+                    img_view_jobs[k] = job;
+                }
+                mv_jobs_done += v.jobs.size();
+                for (uint32_t parity = 0; parity < 2; parity++) {
+                    PassParams Q = V;
+                    Q.big_count = ctr + CTR_BIG + parity;
+                    Q.big_count_next = ctr + CTR_BIG + (parity ^ 1u);
+                    Q.active = ctr + CTR_ACTIVE + parity * 8u * 32u;
+                    Q.active_prev = ctr + CTR_ACTIVE + (parity ^ 1u) * 8u * 32u;
+                    if (parity == 0u) cmd->plan_view_params.push_back(Q);
+                    memcpy(w.pimage.data() + w.mv_params_off + (2 * (views_done + j) + parity) * sizeof(PassParams), &Q, sizeof Q);
+                }
+            }
+            views_done += vset.count;
+        }
+        cmd->plan_views.push_back(vset);
     }
     // 5. commit
     if ((r = pblock_commit(w, stream)) != MIRHI_OK) return r;
@@ -3157,6 +3353,49 @@ extern "C" int mirhi_debug_msaa(const uint32_t* in, char* msg, uint32_t msg_len)
         snprintf(msg, msg_len, "%s family %u progs %u keyed %u tp %u grid %u %u block %u batched %u", v.family == RASTER_MSAA ? "msaa" : "other", (uint32_t)v.family, v.progs, v.keyed,
                  v.tp, v.grid[0], v.grid[1], v.block, v.batched_form);
         return 0;
+    } else return -1;
+    snprintf(msg, msg_len, "%s", why ? why : "");
+    return why ? 1 : 0;
+}
+
+// ... and what a multiview depth scope refuses and plans (mirhi_scope.h, mirhi_variant.h), as words; no HIP call.  in[0] says what is asked:
+// 0  a scope: has_color, has_prim, has_depth, depth_is_array, depth_samples, depth_format, layers, depth_load_op, depth_store_op, view_mask, has_constants,
+//    view_stride, view_offset (low, high word), the constants buffer's size (low, high word), area_partial, split_device, fragment_stats.
+// 1  a draw's program: in[1].
+// 2  the per-view plan: view_mask, layer width, layer height, view_offset (low, high), view_stride -> out: the number of view slots, then per slot five words:
+//    view index, byte offset of its layer in the array (low, high), byte offset of its matrix in the view constants (low, high).
+// 3  the raster launch of a 5 x 4 tile scope: zflip, zmask, tp_max_area, views -> msg: the kernel's name out of the launch table; out: family, keyed, tp, grid x, y, z,
+//    block, batched_form, and the family value of the last older row (RASTER_MSAA).
+// Returns 0 (accepted / answered; msg empty for 0 and 1), 1 (refused; msg: the words behind "Invalid handle: "), -1 for words it cannot take.
+extern "C" int mirhi_debug_multiview(const uint32_t* in, uint32_t* out, char* msg, uint32_t msg_len) {
+    const char* why = nullptr;
+    auto u64 = [](uint32_t lo, uint32_t hi) { return (uint64_t)lo | (uint64_t)hi << 32; };
+    if (in[0] == 0u) {
+        MultiviewFacts f{};
+        f.has_color = in[1]; f.has_prim = in[2]; f.has_depth = in[3]; f.depth_is_array = in[4]; f.depth_samples = in[5]; f.depth_format = in[6]; f.layers = in[7];
+        f.depth_load_op = (int32_t)in[8]; f.depth_store_op = (int32_t)in[9]; f.view_mask = in[10]; f.has_constants = in[11]; f.view_stride = in[12];
+        f.view_offset = u64(in[13], in[14]); f.constants_bytes = u64(in[15], in[16]); f.area_partial = in[17]; f.split_device = in[18]; f.fragment_stats = in[19];
+        why = multiview_scope_refusal(f);
+    } else if (in[0] == 1u) why = multiview_program_refusal((int32_t)in[1]);
+    else if (in[0] == 2u) {
+        MultiviewSlot slot[MAX_BATCH];
+        const uint32_t n = multiview_slots(in[1], in[2], in[3], u64(in[4], in[5]), in[6], slot);
+        out[0] = n;
+        for (uint32_t j = 0; j < n; j++) {
+            const uint32_t words[5] = {slot[j].view, (uint32_t)slot[j].layer_offset, (uint32_t)(slot[j].layer_offset >> 32), (uint32_t)slot[j].matrix_offset, (uint32_t)(slot[j].matrix_offset >> 32)};
+            memcpy(out + 1 + 5 * j, words, sizeof words);
+        }
+        if (msg && msg_len) msg[0] = 0;
+        return 0;
+    } else if (in[0] == 3u) {
+        PassParams P{};
+        P.tiles_x = 5u; P.tile_row_end = 4u; P.tile_row_step = 1u; P.zflip = in[1]; P.zmask = in[2]; P.tp_max_area = in[3]; P.depth_only = 1u;
+        const RasterVariant v = multiview_variant(P, in[4]);
+        const char* name = multiview_raster_name(v);
+        const uint32_t words[9] = {(uint32_t)v.family, v.keyed, v.tp, v.grid[0], v.grid[1], v.grid[2], v.block, v.batched_form, (uint32_t)RASTER_MSAA};
+        memcpy(out, words, sizeof words);
+        snprintf(msg, msg_len, "%s", name ? name : "");
+        return name ? 0 : -1;
     } else return -1;
     snprintf(msg, msg_len, "%s", why ? why : "");
     return why ? 1 : 0;
@@ -3367,7 +3606,53 @@ static mirhi_result issue_batch(Submit& s, uint32_t cmd_count, mirhi_cmd* const*
 
 // One scope of command buffer `c`: its vertex, geometry and raster launch (with_fence: the raster launch carries the submit's fence), and with
 // profiling on their timing events and the statistics pass
+// A multiview depth scope: the views of scope `pi` as ONE vertex, ONE geometry and ONE raster launch, on either dispatch path.  CLEAR and LOAD
+// alike: a view loads, tests and stores its own layer and nothing else, so no view depends on another.  Every view slot works on its own slice of the workspace
+// with its own big-list parity; the single-view buffers and their parity are left alone.
+static mirhi_result issue_multiview(Submit& s, mirhi_cmd* c, size_t pi, hipStream_t stream, bool with_fence) {
+    mirhi_device* dev = s.dev;
+    const mirhi_cmd::ViewSet& vs = c->plan_views[pi];
+    Workspace& w = c->ws;
+    const PassParams* hp[MAX_BATCH]; const PassParams* dp[MAX_BATCH]; uint32_t* big[MAX_BATCH];
+    const PassParams* const dev_views = reinterpret_cast<const PassParams*>(w.pblock + w.mv_params_off);
+    for (uint32_t j = 0; j < vs.count; j++) {
+        const uint32_t parity = (w.mv_parity >> j) & 1u;
+        hp[j] = &c->plan_view_params[vs.first + j];
+        dp[j] = dev_views + 2 * (vs.first + j) + parity;
+        big[j] = hp[j]->big_count + parity;      // (the host copy is the parity-0 one)
+        w.mv_parity ^= 1u << j;
+    }
+    const PassParams& P = *hp[0];
+    LaunchTiming tv{}, tg{}, tr{};
+    if (s.nq) {
+        const uint64_t foreign = dev->foreign_writes.load(std::memory_order_acquire);
+        const PacketScopes scopes = packet_scopes(P, s.sw.system_scope, s.nq->seen_foreign != foreign, w.foreign);
+        s.nq->seen_foreign = foreign; w.foreign = false;
+        tv.native = s.nq; tg.native = s.nq; tr.native = s.nq;
+        tv.native_flags = scopes.vertex; tg.native_flags = scopes.geometry; tr.native_flags = scopes.raster;
+    }
+    tg.tris_per_wave = tris_per_wave(P, s.sw.geom_tpw);
+    if (scope_timed(dev->profiling, c->lane)) {
+        mirhi_result r;
+        if (P.vs_total_slots && (r = timing_begin(dev, MIRHI_KERNEL_VERTEX, c->lane, &tv)) != MIRHI_OK) return r;
+        if (P.total_slots && (r = timing_begin(dev, MIRHI_KERNEL_GEOMETRY, c->lane, &tg)) != MIRHI_OK) return r;
+        if (has_tiles(P) && (r = timing_begin(dev, MIRHI_KERNEL_RASTER, c->lane, &tr)) != MIRHI_OK) return r;
+    }
+    if (with_fence && s.carrier == FENCE_STOP_EVENT) tr.stop = s.fence->event;
+    if (with_fence && s.carrier == FENCE_NATIVE_SIGNAL) tr.native_signal = s.fence->native_sig.handle;
+    s.unlock();
+    hipError_t le = launch_multiview_vertex(hp, dp, vs.count, stream, tv);
+    if (le == hipSuccess) le = launch_multiview_geometry(hp, dp, vs.count, stream, tg);
+    if (le == hipSuccess) le = launch_multiview_raster(hp, dp, big, vs.count, stream, tr);
+    s.relock();
+    HIP_TRY(le);
+    dev->stats.frames_submitted++;
+    dev->stats.triangles_submitted += (uint64_t)P.total_tris * vs.count;
+    return MIRHI_OK;
+}
+
 static mirhi_result issue_scope(Submit& s, mirhi_cmd* c, size_t pi, hipStream_t stream, bool wide_allowed, bool with_fence) {
+    if (pi < c->plan_views.size() && c->plan_views[pi].count) return issue_multiview(s, c, pi, stream, with_fence);
     mirhi_device* dev = s.dev;
     const PassParams& P = c->plan[pi];
     // alternate the big-list counter: the raster kernel zeroes the other one for the next scope
@@ -3517,13 +3802,17 @@ extern "C" mirhi_result mirhi_fence_create(mirhi_device* dev, uint32_t signaled,
 static mirhi_result status_of(mirhi_device* dev, mirhi_cmd* c) {
     mirhi_result r = MIRHI_OK;
     if (c->ws.status_host) {
-        dev->stats.last_status = c->ws.status_host[0];
-        dev->stats.last_big_list = c->ws.status_host[1];
+        // (the view slots of a multiview scope report in words of their own behind the scopes': their bits count like a scope's, their big lists by the longest)
+        const uint32_t bits = c->ws.status_bits();
+        uint32_t big_list = c->ws.status_host[1];
+        for (uint32_t j = 0; j < (uint32_t)MAX_BATCH; j++) big_list = std::max(big_list, c->ws.status_host[Workspace::STATUS_VIEWS + 4u * j + 1u]);
+        dev->stats.last_status = bits;
+        dev->stats.last_big_list = big_list;
         dev->stats.last_bin_pages = c->ws.status_host[2];
         // (the plan feedback below rewrites flags build_plan reads: not while the submit thread may be re-planning a queued submission of this command
         // buffer -- the status words stay set and the next look at them, with nothing queued, acts on them)
         const bool feedback = c->queued.load(std::memory_order_acquire) == 0;
-        if (feedback && (c->ws.status_host[0] & STATUS_POOL_EXHAUSTED) && !c->ws.grow_pool) {
+        if (feedback && (bits & STATUS_POOL_EXHAUSTED) && !c->ws.grow_pool) {
             // not an error: the records went to the big list and the frame is complete; the pool is doubled in front of the next submit
             c->ws.grow_pool = true;
             if (c->ws.pool_scale < 64u) c->ws.pool_scale *= 2u;
@@ -3535,13 +3824,13 @@ static mirhi_result status_of(mirhi_device* dev, mirhi_cmd* c) {
             if (want != cur && c->ws.wide_eligible && !PlanKnobs::read().raster_wide.set) { c->ws.wide = want; c->ws.replan = true; }
         }
         if (feedback && !c->ws.spread && c->ws.xcd_tiles_last && c->ws.status_host[2] > 2u * c->ws.xcd_tiles_last) { c->ws.spread = true; c->ws.replan = true; c->ws.spread_tris = c->plan_tris; }
-        if (c->ws.status_host[0] & (STATUS_PAGE_TIMEOUT | STATUS_BIG_OVERFLOW)) c->ws.dirty = true;     // counters / page table are cleared before the next frame
-        if (c->ws.status_host[0] & STATUS_PAGE_TIMEOUT)
+        if (bits & (STATUS_PAGE_TIMEOUT | STATUS_BIG_OVERFLOW)) c->ws.dirty = true;     // counters / page table are cleared before the next frame
+        if (bits & STATUS_PAGE_TIMEOUT)
             r = fail(MIRHI_ERR_DEVICE, "Vulkan error: rasterizer bin page was never published; frame is incomplete");
-        if (c->ws.status_host[0] & STATUS_ALPHA_TEST_TEXTURED)
+        if (bits & STATUS_ALPHA_TEST_TEXTURED)
             r = fail(MIRHI_ERR_PIPELINE, "Pipeline error: MODEL_PBR alpha cutoff together with a base colour texture needs a per-fragment discard: set mirhi_pipeline_desc.fragment_discard_enable on that pipeline; the draw was skipped");
-        if (c->ws.status_host[0] & STATUS_BIG_OVERFLOW)
-            r = fail(MIRHI_ERR_DEVICE, "Vulkan error: rasterizer large-triangle list overflowed (%u entries); frame is incomplete", c->ws.status_host[1]);
+        if (bits & STATUS_BIG_OVERFLOW)
+            r = fail(MIRHI_ERR_DEVICE, "Vulkan error: rasterizer large-triangle list overflowed (%u entries); frame is incomplete", big_list);
     }
     return r;
 }

@@ -41,6 +41,7 @@ namespace mirhi {
 #include "mirhi_stats.hip.h"
 #include "mirhi_ordered.hip.h"
 #include "mirhi_transfer.hip.h"
+#include "mirhi_multiview.hip.h"
 
 // the build this code object belongs to (build.py passes the source hash to both translation units; native_device_open compares)
 #ifndef MIRHI_SOURCE_HASH
@@ -240,6 +241,55 @@ hipError_t launch_raster_batch(const PassParams* const* Ps, const PassParams* co
     RasterBatch B{};
     for (uint32_t i = 0; i < n; i++) { B.params[i] = dev_params[i]; B.head[i] = raster_head(*Ps[i], big_count[i]); }
     MIRHI_LAUNCH(e->kernel, dim3(v.grid[0], v.grid[1], n), dim3(v.block), stream, t, B);
+    return launch_result();
+}
+
+// ---- multiview depth scopes: the views of one scope in one launch per stage, timed or native like a single scope's launches -----
+// P[j]: view slot j's host parameters, dev_params[j] / big_count[j]: its device copy and big-list counter of this submit's parity
+hipError_t launch_multiview_vertex(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream, LaunchTiming t) {
+    GeometryBatch B{};
+    uint32_t most = 0;
+    for (uint32_t i = 0; i < n; i++) { B.params[i] = dev_params[i]; most = P[i]->vs_total_slots > most ? P[i]->vs_total_slots : most; }
+    if (most == 0) return hipSuccess;
+    MIRHI_LAUNCH(vertex_kernel_shadow_batch, dim3(most / GEOM_THREADS, n), dim3(GEOM_THREADS), stream, t, B);
+    return launch_result();
+}
+
+hipError_t launch_multiview_geometry(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream, LaunchTiming t) {
+    GeometryBatch B{};
+    const uint32_t tpw = (t.tris_per_wave == 16u || t.tris_per_wave == 32u) ? t.tris_per_wave : (uint32_t)GEOM_THREADS;
+    uint32_t most = 0, total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        B.params[i] = dev_params[i];
+        B.head[i] = GeometryHead{P[i]->draws, P[i]->num_draws, tpw, nullptr, 0u, 0u, 0u};
+        B.blocks[i] = P[i]->total_slots / tpw;
+        most = B.blocks[i] > most ? B.blocks[i] : most; total += B.blocks[i];
+    }
+    if (most == 0) return hipSuccess;
+    if (total > 5u * 1024u) MIRHI_LAUNCH(geometry_kernel_batch<7>, dim3(most, n), dim3(GEOM_THREADS), stream, t, B);
+    else MIRHI_LAUNCH(geometry_kernel_batch<5>, dim3(most, n), dim3(GEOM_THREADS), stream, t, B);
+    return launch_result();
+}
+
+// the four instantiations of raster_kernel_depth_batch, each named once, in the order of raster_kernel_depth's rows above
+#define VIEWS(K, T) {raster_kernel_id(RASTER_DEPTH_VIEWS, 0, K, T, 1, 0, 4), "raster_kernel_depth_batch<" #K ", " #T ">", raster_kernel_depth_batch<K, T>}
+static const RasterBatchEntry k_raster_view_entries[] = { VIEWS(0, 1), VIEWS(1, 1), VIEWS(0, 0), VIEWS(1, 0) };
+#undef VIEWS
+static const RasterBatchEntry* raster_view_entry(const RasterVariant& v) {
+    for (const RasterBatchEntry& e : k_raster_view_entries) if (e.id == v.kernel_id()) return &e;
+    return nullptr;
+}
+const char* multiview_raster_name(const RasterVariant& v) { const RasterBatchEntry* e = raster_view_entry(v); return e ? e->name : nullptr; }
+
+hipError_t launch_multiview_raster(const PassParams* const* Ps, const PassParams* const* dev_params, uint32_t* const* big_count, uint32_t n, hipStream_t stream, LaunchTiming t) {
+    const PassParams& P = *Ps[0];
+    if (P.tile_row_end == P.tile_row_begin || P.tiles_x == 0) return hipSuccess;
+    const RasterVariant v = multiview_variant(P, n);
+    const RasterBatchEntry* e = raster_view_entry(v);
+    if (!e) return hipErrorInvalidDeviceFunction;
+    RasterBatch B{};
+    for (uint32_t i = 0; i < n; i++) { B.params[i] = dev_params[i]; B.head[i] = raster_head(*Ps[i], big_count[i]); }
+    MIRHI_LAUNCH(e->kernel, dim3(v.grid[0], v.grid[1], v.grid[2]), dim3(v.block), stream, t, B);
     return launch_result();
 }
 

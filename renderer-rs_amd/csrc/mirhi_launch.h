@@ -28,6 +28,14 @@ hipError_t launch_vertex_batch(const PassParams* const* P, const PassParams* con
 hipError_t launch_geometry_batch(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream);
 hipError_t launch_raster_batch(const PassParams* const* P, const PassParams* const* dev_params, uint32_t* const* big_count, uint32_t n, uint32_t programs, hipStream_t stream,
                                hipEvent_t stop = nullptr);      // stop: signalled by the dispatch's completion (a submit's fence)
+// A multiview depth scope (mirhi_cmd_begin_rendering_multiview): its n (1 .. MAX_BATCH) views in one launch per stage.  P[j] / dev_params[j] /
+// big_count[j]: view slot j's host parameters, their device copy and its big-list counter, as for a single scope; t as for a single scope's launches (timed,
+// native, tris_per_wave).  The raster kernel is multiview_variant's (mirhi_variant.h); multiview_raster_name: its entry's name, nullptr where the table has none.
+hipError_t launch_multiview_vertex(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream, LaunchTiming t = {});
+hipError_t launch_multiview_geometry(const PassParams* const* P, const PassParams* const* dev_params, uint32_t n, hipStream_t stream, LaunchTiming t = {});
+hipError_t launch_multiview_raster(const PassParams* const* P, const PassParams* const* dev_params, uint32_t* const* big_count, uint32_t n, hipStream_t stream, LaunchTiming t = {});
+struct RasterVariant;
+const char* multiview_raster_name(const RasterVariant& v);
 // profiling only: counts the fragments the scope's binned triangles cover (before any depth test) into P.frag_stats[1];
 // runs between the geometry and the raster kernel (the raster kernel re-arms the bin counters)
 hipError_t launch_fragment_count(const PassParams& P, const PassParams* dev_params, uint32_t* big_count, hipStream_t stream, LaunchTiming t = {});

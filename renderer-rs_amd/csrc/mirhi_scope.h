@@ -398,4 +398,52 @@ inline BinGeometry bin_geometry(size_t tiles, size_t tris, uint32_t total_tris, 
     return g;
 }
 
+// ---- multiview depth scopes (mirhi_cmd_begin_rendering_multiview): what is refused, in what words, and the per-view plan ----
+// What begin_rendering_multiview looks at, as numbers (images and buffers: 0 = NULL; formats mirhi_format; ops mirhi_load_op / mirhi_store_op)
+struct MultiviewFacts {
+    uint32_t has_color, has_prim, has_depth, depth_is_array, depth_samples, depth_format, layers;
+    int32_t depth_load_op, depth_store_op;
+    uint32_t view_mask, has_constants, view_stride;
+    uint64_t view_offset, constants_bytes;      // constants_bytes: the buffer's size
+    uint32_t area_partial, split_device, fragment_stats;
+};
+inline uint32_t multiview_count(uint32_t mask) { return (uint32_t)__builtin_popcount(mask); }
+// nullptr: the scope is accepted
+inline const char* multiview_scope_refusal(const MultiviewFacts& f) {
+    if (f.has_color || f.has_prim) return "unsupported: a multiview scope is depth-only (color_image and prim_id_image NULL)";
+    if (f.has_depth && f.depth_samples != 1u) return "unsupported: a multisampled depth image in a multiview scope";
+    if (!f.has_depth || !f.depth_is_array) return "unsupported: a multiview scope renders into an image array (mirhi_image_create_array), not a 2-D image or a layer view";
+    if (f.depth_format != MIRHI_FORMAT_D32_SFLOAT) return "unsupported: a multiview depth array that is not D32_SFLOAT";
+    if (f.depth_load_op != MIRHI_LOAD_OP_CLEAR && f.depth_load_op != MIRHI_LOAD_OP_LOAD) return "unsupported: the depth load op of a multiview scope is CLEAR or LOAD";
+    if (f.depth_store_op != MIRHI_STORE_OP_STORE) return "unsupported: a multiview scope must store its depth (STORE)";
+    if (f.view_mask == 0u) return "unsupported: an empty view mask";
+    if (multiview_count(f.view_mask) > (uint32_t)MAX_BATCH) return "unsupported: more than 8 views in one multiview scope";
+    if (f.layers < 32u && (f.view_mask >> f.layers) != 0u) return "unsupported: a view mask bit at or above the array's layer count";
+    if (!f.has_constants) return "unsupported: a multiview scope without view_constants";
+    if (f.view_stride < 64u || f.view_stride % 16u != 0u) return "unsupported: view_stride must be at least 64 and a multiple of 16";
+    if (f.view_offset % 16u != 0u) return "unsupported: view_offset must be a multiple of 16";
+    {
+        const uint32_t top = 31u - (uint32_t)__builtin_clz(f.view_mask);
+        if (f.view_offset > f.constants_bytes || (uint64_t)top * f.view_stride + 64u > f.constants_bytes - f.view_offset)
+            return "unsupported: the view_constants buffer is too short for the highest view's matrix";
+    }
+    if (f.area_partial) return "unsupported: a partial render area in a multiview scope";
+    if (f.split_device) return "unsupported: a multiview scope on a split device";
+    if (f.fragment_stats) return "unsupported: fragment statistics of a multiview scope";
+    return nullptr;
+}
+// the program of a draw recorded in a multiview scope (mirhi_program); nullptr: accepted
+inline const char* multiview_program_refusal(int32_t program) {
+    return program == MIRHI_PROGRAM_SHADOW ? nullptr : "unsupported: only SHADOW draws may be recorded in a multiview scope";
+}
+// View slot j of a scope (the j-th set bit of the mask, lowest first): its view index, where its layer starts in the array (bytes from the array's base)
+// and where its matrix sits in the view constants (bytes from the buffer's base).  Returns the number of slots.
+struct MultiviewSlot { uint32_t view; uint64_t layer_offset, matrix_offset; };
+inline uint32_t multiview_slots(uint32_t mask, uint32_t width, uint32_t height, uint64_t view_offset, uint32_t view_stride, MultiviewSlot out[MAX_BATCH]) {
+    uint32_t n = 0;
+    for (uint32_t v = 0; v < 32u && n < (uint32_t)MAX_BATCH; v++)
+        if ((mask >> v) & 1u) out[n++] = MultiviewSlot{v, (uint64_t)v * width * height * 4u, view_offset + (uint64_t)v * view_stride};
+    return n;
+}
+
 }  // namespace mirhi

@@ -24,6 +24,9 @@ enum : uint32_t {
 // (RASTER_IBL behind RASTER_ORDERED, RASTER_SKY behind RASTER_IBL, RASTER_TRANSFER behind RASTER_SKY, RASTER_CSM_BLEND behind RASTER_TRANSFER, RASTER_MSAA behind
 // RASTER_CSM_BLEND: the values of the families before them are recorded in tests/golden/raster_variants.json)
 enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_SHADOW, RASTER_CSM, RASTER_ORDERED, RASTER_IBL, RASTER_SKY, RASTER_TRANSFER, RASTER_CSM_BLEND, RASTER_MSAA };
+// ... and behind RASTER_MSAA, the last value of the list above: the views of a multiview depth scope in one launch (raster_kernel_depth_batch).  Never
+// what raster_variant answers: multiview_variant below is the one place that names it.
+constexpr RasterFamily RASTER_DEPTH_VIEWS = (RasterFamily)(RASTER_MSAA + 1u);
 
 // the kernel instantiation alone (no launch shape) as one word
 constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves, uint32_t area = 0u) {
@@ -107,6 +110,15 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
     // the two-team mesh mode.  The XCD run-length order of a 1-D grid is a measurement knob, and a plan that names a wide variant keeps it whether or
     // not one submit takes it: neither is batched.  Nor is a scope with a partial render area (mirhi_submit.h).
     v.batched_form = (v.family == RASTER_PLAIN && v.keyed == 0u && !P.alpha_scope && P.xcd_swizzle <= 1u && !P.raster_wide && !P.area_partial) ? 1u : 0u;
+    return v;
+}
+
+// The raster launch of a multiview depth scope (mirhi_cmd_begin_rendering_multiview) of `views` views: what a single view's depth-only scope would
+// run (P: any view's parameters -- they differ in addresses alone), as the batched depth kernel raster_kernel_depth_batch with one grid layer per view.  Never
+// an AREA form (a partial render area is refused where the scope is recorded), never batched across command buffers.
+inline RasterVariant multiview_variant(const PassParams& P, uint32_t views) {
+    RasterVariant v = raster_variant(P, PROGS_DEPTH_ONLY, false);
+    v.family = RASTER_DEPTH_VIEWS; v.grid[2] = views; v.batched_form = 0u; v.area = 0u;
     return v;
 }
 

@@ -457,7 +457,7 @@ struct DepthAttachment {   // rendering.rs:319-370
 };
 class RenderingConfig {    // rendering.rs:680-726
 public:
-    RenderingConfig(uint32_t w, uint32_t h) : w_(w), h_(h) { mirhi_rendering_info_default(&info_); mirhi_resolve_info_default(&resolve_); }
+    RenderingConfig(uint32_t w, uint32_t h) : w_(w), h_(h) { mirhi_rendering_info_default(&info_); mirhi_resolve_info_default(&resolve_); mirhi_multiview_info_default(&multiview_); }
     RenderingConfig& with_color_attachment(const ColorAttachment& a) {
         info_.color_image = a.image->handle(); info_.color_load_op = (int32_t)a.load_op; info_.color_store_op = (int32_t)a.store_op;
         std::memcpy(info_.clear_color, a.clear_color.data(), 16);
@@ -476,6 +476,15 @@ public:
         info_.render_area[0] = area.x; info_.render_area[1] = area.y; info_.render_area[2] = (int32_t)area.width; info_.render_area[3] = (int32_t)area.height;
         return *this;
     }
+    // rendering.rs:841-862.  A multiview depth scope (include/mirhi.h "Multiview depth scopes"): the depth attachment is an image ARRAY, view v of the mask renders
+    // into layer v with the light matrix at offset + v * stride of `view_constants` (read when the scope executes).  begin_rendering then opens the scope
+    // through mirhi_cmd_begin_rendering_multiview.
+    RenderingConfig& with_view_mask(uint32_t mask, const Buffer& view_constants, uint64_t offset = 0, uint32_t stride = 64) {
+        multiview_.view_mask = mask; multiview_.view_constants = view_constants.handle(); multiview_.view_offset = offset; multiview_.view_stride = stride;
+        return *this;
+    }
+    bool multiview() const { return multiview_.view_mask != 0u || multiview_.view_constants != nullptr; }
+    const mirhi_multiview_info& views() const { return multiview_; }
     RenderingConfig& with_offset(int32_t x, int32_t y) {
         if (info_.render_area[2] <= 0 || info_.render_area[3] <= 0) { info_.render_area[2] = (int32_t)w_; info_.render_area[3] = (int32_t)h_; }
         info_.render_area[0] = x; info_.render_area[1] = y;
@@ -489,6 +498,7 @@ private:
     uint32_t w_, h_;
     mirhi_rendering_info info_;
     mirhi_resolve_info resolve_;
+    mirhi_multiview_info multiview_;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -521,7 +531,12 @@ public:
     void reset() const { check(mirhi_cmd_reset(h_)); }
     void begin_rendering(const mirhi_rendering_info& info) const { check(mirhi_cmd_begin_rendering(h_, &info)); }
     // a config whose attachments came with_resolve opens a 4x multisampled scope; without one this is begin_rendering(cfg.build())
-    void begin_rendering(const RenderingConfig& cfg) const { check(mirhi_cmd_begin_rendering_resolve(h_, &cfg.build(), &cfg.resolve())); }
+    // ... and one built with_view_mask a multiview depth scope
+    void begin_rendering(const RenderingConfig& cfg) const {
+        if (cfg.multiview()) check(mirhi_cmd_begin_rendering_multiview(h_, &cfg.build(), &cfg.views()));
+        else check(mirhi_cmd_begin_rendering_resolve(h_, &cfg.build(), &cfg.resolve()));
+    }
+    void begin_rendering_multiview(const mirhi_rendering_info& info, const mirhi_multiview_info& views) const { check(mirhi_cmd_begin_rendering_multiview(h_, &info, &views)); }
     void end_rendering() const { check(mirhi_cmd_end_rendering(h_)); }
     void bind_pipeline(const Pipeline& p) const { check(mirhi_cmd_bind_pipeline(h_, p.handle())); }
     void bind_vertex_buffers(uint32_t first_binding, const Buffer& b, uint64_t offset) const {

@@ -1427,6 +1427,48 @@ def cascaded_ground_case(width: int = 480, height: int = 360, map_size: int = 20
 
 
 # ------------------------------------------------------------------------------------------------
+# Multiview depth scopes (include/mirhi.h "Multiview depth scopes"): all cascades of a CascadeSpec in ONE rendering scope
+# ------------------------------------------------------------------------------------------------
+MULTIVIEW_STRIDE = 80                                               # the stride of CSMParams' cascades (shadow_csm.hlsli:23-28)
+
+
+def cascade_view_constants(spec: CascadeSpec, stride: int = MULTIVIEW_STRIDE) -> bytes:
+    """The view constants of a multiview shadow scope over spec's cascades: view k's 64-byte light matrix at k * stride, in the layout of
+    CSMParams' cascades.  The matrix is the one cascade k's casters render with (the first 64 bytes of their ShadowConstants): flip_clip_y(M_k),
+    NOT the M_k that csm_ubo stores for the lookup -- these scenes render the map with clip y negated, so the shadow pass and the lookup
+    cannot share one buffer; what they share is the layout."""
+    out = bytearray(stride * len(spec.casters))
+    for k, layer in enumerate(spec.casters):
+        mats = {bytes(c.camera[:64]) for c in layer}
+        assert len(mats) == 1, "the casters of one cascade render with one light matrix"
+        out[k * stride:k * stride + 64] = mats.pop()
+    return bytes(out)
+
+
+def record_cascades_multiview(cmd, spec: CascadeSpec, array, states, view_constants, view_mask: Optional[int] = None, stride: int = MULTIVIEW_STRIDE):
+    """Records all cascades of `spec` as ONE multiview scope into `cmd` (a recording CommandBuffer): the casters once -- `states`: per caster of ONE
+    cascade a dict of pipe / vb / ib / camera buffers and the DrawSpec (`draw`), what SceneResources keeps per layer; every cascade has the same casters
+    under another light matrix, and the caster's own CAMERA block still supplies `model` @64 -- into the layers of `array` that view_mask names (all of
+    them by default), with view k's matrix at k * stride of the buffer view_constants (cascade_view_constants)."""
+    w, h = spec.size
+    mask = (1 << len(spec.casters)) - 1 if view_mask is None else int(view_mask)
+    cmd.begin_rendering_multiview(array, mask, view_constants, 0, stride, clear_depth=spec.clear_depth, depth_load_op=spec.load_op)
+    for st in states:
+        d = st["draw"]
+        cmd.set_viewport(*(d.viewport or (0.0, 0.0, float(w), float(h), 0.0, 1.0)))
+        cmd.set_scissor(*(d.scissor or (0, 0, w, h)))
+        cmd.bind_pipeline(st["pipe"])
+        cmd.bind_vertex_buffers(0, [st["vb"]], [0])
+        cmd.bind_uniform(0, st["camera"])                          # Slot.CAMERA
+        if st["ib"] is not None:
+            cmd.bind_index_buffer(st["ib"], 0, 0 if d.index_type == 2 else 1)      # IndexType.UINT16 / UINT32
+            cmd.draw_indexed(d.count, 1, d.first, d.vertex_offset, 0)
+        else:
+            cmd.draw(d.count, 1, d.first, 0)
+    cmd.end_rendering()
+
+
+# ------------------------------------------------------------------------------------------------
 # 4x MSAA (include/mirhi.h "4x MSAA", DESIGN.md 8l): the float64 model of a multisampled scope
 # ------------------------------------------------------------------------------------------------
 # Vulkan's standard 4x sample positions inside a pixel, as (x, y) fractions; in 1/256 px (96, 32), (224, 96), (32, 160), (160, 224)
