@@ -19,6 +19,7 @@ import numpy as np
 from . import build as _build
 from . import scenes  # noqa: F401  (re-export)
 from . import ibl  # noqa: F401  (re-export: the numpy model of the IBL precompute passes)
+from . import lighting  # noqa: F401  (re-export: the numpy model of the lit fragment programs)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, os.environ.get("MIRHI_LIB_NAME", "libmirhi.so"))   # MIRHI_LIB_NAME: diagnostic builds only

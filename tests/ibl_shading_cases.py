@@ -87,10 +87,10 @@ def keep_mask(scene, py, px, facet):
 
 
 def hemisphere_ambient(N, albedo, metallic, ao):
-    """CalculateHemisphereAmbient (pbr.hlsli:483-492) as model_pbr.hlsl applies it: lerp(ground, sky, N.y / 2 + 1 / 2) * albedo * ao * (1 - metallic)."""
-    up = N[:, 1:2] * 0.5 + 0.5
-    ground, sky = np.array([0.08, 0.06, 0.04]), np.array([0.15, 0.18, 0.25])
-    return (ground + (sky - ground) * up) * albedo * np.asarray(ao)[..., None] * (1.0 - metallic)[:, None]
+    """CalculateHemisphereAmbient as model_pbr.hlsl applies it: the model's (renderer_rs_amd.lighting), imported here like this module's other
+    uses of the package, when called."""
+    from renderer_rs_amd import lighting
+    return lighting.hemisphere_ambient(N, albedo, metallic, ao)
 
 
 def with_program(scene, program, **material_overrides):
