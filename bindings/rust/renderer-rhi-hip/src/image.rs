@@ -93,6 +93,12 @@ impl Image {
         check(unsafe { mirhi_sys::mirhi_image_sampler(self.raw, &mut desc) })?;
         Ok(desc)
     }
+    /// A cube's seamless state (include/mirhi.h "The sampler"): lookups filter across face edges and corners, for draws recorded afterwards
+    /// and from the precompute passes' next call on.  Off by default; refused on anything but a cube image.
+    pub fn set_cube_seamless(&self, enable: bool) -> RhiResult<()> {
+        check(unsafe { mirhi_sys::mirhi_image_set_cube_seamless(self.raw, enable as u32) })
+    }
+    pub fn cube_seamless(&self) -> bool { unsafe { mirhi_sys::mirhi_image_cube_seamless(self.raw) != 0 } }
     pub fn default_sampler() -> mirhi_sys::mirhi_sampler_desc {
         let mut desc = mirhi_sys::mirhi_sampler_desc {
             address_u: mirhi_sys::MIRHI_ADDRESS_REPEAT, address_v: mirhi_sys::MIRHI_ADDRESS_REPEAT, mag_filter: mirhi_sys::MIRHI_SAMPLER_FILTER_LINEAR,

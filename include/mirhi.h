@@ -42,7 +42,8 @@ extern "C" {
                                     still 5 (new functions, one struct and one enum only; rasterization_samples = 4 accepted): mirhi_image_create_multisampled,
                                     mirhi_image_samples, mirhi_resolve_mode, mirhi_resolve_info, mirhi_cmd_begin_rendering_resolve;
                                     still 5 (two new functions and one struct only): mirhi_multiview_info, mirhi_multiview_info_default,
-                                    mirhi_cmd_begin_rendering_multiview */
+                                    mirhi_cmd_begin_rendering_multiview;
+                                    still 5 (two new functions only): mirhi_image_set_cube_seamless, mirhi_image_cube_seamless */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -241,9 +242,19 @@ mirhi_result mirhi_image_destroy(mirhi_image* img);
  *   Cube lookup, TextureCube.SampleLevel(LinearSampler, dir, lod): face and (s, t) by the Vulkan specification's cube-map face selection table --
  *   major axis = the component of largest magnitude, ties prefer z, then y, then x; (sc, tc) = +X (-z, -y), -X (+z, -y), +Y (+x, +z), -Y (+x, -z),
  *   +Z (+x, -y), -Z (-x, -y); s = sc / (2 |ma|) + 1/2, t likewise -- which is the inverse of GetCubemapDirection.  Bilinear inside the selected face
- *   with clamp to edge, NOT seamless across faces: x = s n - 1/2, x0 = floor(x), fraction x - x0, the four texels at x0, x0 + 1 (and rows
+ *   with clamp to edge, not seamless across faces unless the cube's seamless state is on (below): x = s n - 1/2, x0 = floor(x), fraction x - x0, the four texels at x0, x0 + 1 (and rows
  *   likewise) each clamped to [0, n - 1].  lod is clamped to [0, levels - 1]; the levels floor(lod) and floor(lod) + 1 (clamped to the last)
  *   are each filtered so and lerped by lod's fraction.
+ *   Seamless cubes (mirhi_image_set_cube_seamless; the state `cube_seamless` of a cube image, 0 or 1, default 0; what Vulkan does by default).  At one
+ *   level with faces of n x n texels: face, s and t as above; x = s n - 1/2, y = t n - 1/2, i0 = floor(x), j0 = floor(y); the fractions and the four
+ *   taps (i0 + di, j0 + dj) as above but NOT clamped.  A tap with both indices in [0, n - 1] is that texel.  A tap with exactly one index outside (-1
+ *   or n) is an edge tap: the texel of the face on the other side of that edge, in that face's border row or column, at the same position along the
+ *   shared edge -- equivalently: extend the face plane to the tap's centre ((i + 1/2) / n, (j + 1/2) / n), take that point's direction
+ *   (GetCubemapDirection's table with |u| or |v| > 1), run the face selection on it and take the texel (floor(s' n), floor(t' n)) clamped to
+ *   [0, n - 1]; s' n stays 1 / (n + 1) away from an integer, so the two statements agree for every n up to 4096.  A tap with both indices outside is a
+ *   corner tap (at most one of the four): it has no texel, its value is the mean of the other three, (a + b + c) / 3.  The four values are weighted by
+ *   the fractions exactly as above; level selection and the lerp between levels are unchanged; n = 1 is legal.  Wherever all four taps lie in the face
+ *   the result is the clamped sampler's.
  *   2-D lookup of the equirectangular source, Texture2D.SampleLevel(LinearSampler, uv, 0): bilinear at level 0, u repeats (longitude wraps),
  *   v clamps to the edge.
  * Numerics: float32 throughout, not bit-exact against anything: the kernels contract, use the hardware reciprocal / square root / logarithm and
@@ -251,6 +262,16 @@ mirhi_result mirhi_image_destroy(mirhi_image* img);
  * Refused with InvalidHandle: a non-cube where a cube is due (and the other way round), any format but R32G32B32A32_SFLOAT, source == destination,
  * images of two devices. */
 mirhi_result mirhi_image_create_cube(mirhi_device* dev, uint32_t size, uint32_t levels, mirhi_format format, mirhi_image** out);
+/* The seamless state of a cube image ("The sampler" above; VkSamplerCreateInfo without NON_SEAMLESS_CUBE_MAP, the reference's sampler.rs is empty):
+ * enable 0 / 1, default 0.  Like mirhi_image_set_sampler it takes effect for draws recorded afterwards -- the state is latched when a draw is recorded
+ * and is part of what a recording is compared by.  It is read by mirhi_cmd_bind_ibl's set (the irradiance cube and the prefiltered cube each carry
+ * their own; the LUT is 2-D), by mirhi_cmd_bind_skybox's environment, and by mirhi_ibl_irradiance and mirhi_ibl_prefilter for `env`, the cube they
+ * READ (from their next call on; prefilter's single lookup for Roughness < 0.01 included).  mirhi_ibl_cube_generate_mips (a box filter inside a face)
+ * and mirhi_ibl_equirect_to_cube (a 2-D source) are unaffected.  The latched states are part of a scope's IBL set: the same three images under
+ * different states within one scope are two different IBL sets.  Refused with InvalidHandle: a non-cube ("not a cube image"), a multisampled image,
+ * enable > 1 (the message names the value).  mirhi_image_cube_seamless: the state; 0 for every non-cube and for NULL. */
+mirhi_result mirhi_image_set_cube_seamless(mirhi_image* cube, uint32_t enable);
+uint32_t     mirhi_image_cube_seamless(const mirhi_image* img);
 /* equirect_to_cubemap.hlsl:78-105: level 0 of `cube`, all four channels, from the 2-D image `src2d` (DirectionToEquirectUV :59-75) */
 mirhi_result mirhi_ibl_equirect_to_cube(mirhi_image* src2d, mirhi_image* cube);
 /* Levels 1.. of a cube from its level 0, face by face with a 2 x 2 box filter in float, ((a + b) + (c + d)) * 0.25 (exact operations in this
@@ -526,7 +547,7 @@ mirhi_result mirhi_cmd_bind_shadow_cascades_blended(mirhi_cmd* cmd, mirhi_image*
  *     the n x n image: x = NdotV n - 1/2 along a row, y = roughness n - 1/2 down the rows; only .rg is read.
  *   Numerics: float32, not bit-exact -- the ambient term contracts and is bounded against the float64 model of renderer-rs_amd/ibl.py; Lo
  *   keeps MODEL_PBR's exact sequences.  Where the two largest |components| of N or R tie, float32 may select another face than exact arithmetic, and the
- *   stated sampler is not seamless there.
+ *   stated sampler is not seamless there unless the cube's seamless state is on (then the lookup is continuous and the flip costs nothing).
  * Refused with InvalidHandle: `irradiance` or `prefiltered` that is no cube; a `brdf_lut` that is a cube, an array (or layer view), not square or not
  * R32G32B32A32_SFLOAT; some arguments NULL but not all; images of two devices or of another device than `cmd`.  At the draw: a MODEL_PBR_IBL draw with no
  * IBL set bound; with blending, fragment discard or a predicate depth state (the rule of the shadowed variants); a rendering scope whose MODEL_PBR_IBL

@@ -305,6 +305,8 @@ _SIGNATURES = {
     "mirhi_sampler_desc_default": (None, [C.c_void_p]),
     "mirhi_image_set_sampler": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_image_sampler": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mirhi_image_set_cube_seamless": (C.c_int32, [C.c_void_p, C.c_uint32]),
+    "mirhi_image_cube_seamless": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_mip_levels": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_width": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_height": (C.c_uint32, [C.c_void_p]),
@@ -611,14 +613,25 @@ class Image:
         return int(lib().mirhi_image_samples(self.handle))
 
     @classmethod
-    def create_cube(cls, device: Device, size: int, levels: int = 1, fmt: int = Format.R32G32B32A32_SFLOAT) -> "Image":
+    def create_cube(cls, device: Device, size: int, levels: int = 1, fmt: int = Format.R32G32B32A32_SFLOAT, seamless: bool = False) -> "Image":
         """mirhi_image_create_cube: six faces and `levels` mip levels in one allocation (R32G32B32A32_SFLOAT only); level-major, then
-        face-major (+X, -X, +Y, -Y, +Z, -Z), then row-major."""
+        face-major (+X, -X, +Y, -Y, +Z, -Z), then row-major.  seamless=True: set_cube_seamless(True) on the new cube."""
         h = C.c_void_p()
         check(lib().mirhi_image_create_cube(device.handle, size, levels, fmt, C.byref(h)))
         img = cls._adopt(h, device, size, size, fmt)
         img.is_cube = True
+        if seamless:
+            img.set_cube_seamless(True)
         return img
+
+    def set_cube_seamless(self, enable=True):
+        """mirhi_image_set_cube_seamless: lookups in this cube filter across face edges and corners (include/mirhi.h "The sampler"), for draws
+        recorded afterwards and for the precompute passes that read it from their next call on.  True / False, or 0 / 1 as the C call takes it."""
+        check(lib().mirhi_image_set_cube_seamless(self.handle, int(enable)))
+
+    @property
+    def cube_seamless(self) -> bool:
+        return bool(lib().mirhi_image_cube_seamless(self.handle))
 
     def cube_levels(self, packed=None):
         """The levels of a cube's packed chain (default: read it back) as views [6, n >> l, n >> l, 4] of that one array."""

@@ -491,6 +491,9 @@ struct mirhi_image {
     // Cube images (mirhi_image_create_cube): six faces and `levels` mip levels in one allocation, level-major, then face-major, then row-major; width =
     // height = the edge of level 0, layers = 6.  A cube is neither a 2-D image nor an array: only the mirhi_ibl_* passes, upload and read take one.
     bool is_cube = false;
+    // mirhi_image_set_cube_seamless: lookups in this cube filter across face edges and corners (include/mirhi.h "The sampler").  Read when a draw is recorded
+    // (mirhi_cmd_bind_ibl / _bind_skybox sets, latched per draw like the sampler state of a texture) and by mirhi_ibl_irradiance / _prefilter for the cube they read.
+    uint32_t cube_seamless = 0;
     // Multisampled images (mirhi_image_create_multisampled): samples = 4, the transient attachment of a multisampled scope.  It owns no memory
     // (ptr nullptr, owned false) and is nothing but an attachment: whatever would read or write its texels refuses it (refuse_multisampled).
     uint32_t samples = 1;
@@ -536,9 +539,10 @@ struct RecordedPass {
     struct IblSet {
         const uint8_t* irradiance = nullptr; const uint8_t* prefiltered = nullptr; const uint8_t* lut = nullptr;
         uint32_t irr_size = 0, pre_size = 0, pre_levels = 0, lut_size = 0;
+        uint32_t seamless = 0;             // the two cubes' seamless states when the draw was recorded (bit 0 irradiance, bit 1 prefiltered): part of the set's identity
         bool operator==(const IblSet& o) const {
             return irradiance == o.irradiance && prefiltered == o.prefiltered && lut == o.lut && irr_size == o.irr_size && pre_size == o.pre_size &&
-                   pre_levels == o.pre_levels && lut_size == o.lut_size;
+                   pre_levels == o.pre_levels && lut_size == o.lut_size && seamless == o.seamless;
         }
     } ibl;
     // A SKYBOX segment: the one SKYBOX draw it consists of, as PassParams takes it (the sky_ words), fixed when the draw was recorded -- push
@@ -550,6 +554,7 @@ struct RecordedPass {
         long long e0[3];
         float pos0[3], posx[3], posy[3];
         uint32_t depth_bits, compare, write, prim;
+        uint32_t seamless;                 // the environment's seamless state when the draw was recorded
         SkyDraw() { memset(this, 0, sizeof *this); }
         bool operator==(const SkyDraw& o) const { return memcmp(this, &o, sizeof *this) == 0; }
     } sky;
@@ -1318,7 +1323,8 @@ extern "C" mirhi_result mirhi_ibl_irradiance(mirhi_image* env, mirhi_image* out)
     mirhi_device* dev = out->dev;
     { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
     const uint32_t n = out->width;
-    hipLaunchKernelGGL(ibl_irradiance_kernel, dim3(6u * n * n), dim3(256), 0, dev->stream, ibl_cube_of(env), (float4*)out->ptr, n);
+    if (env->cube_seamless) hipLaunchKernelGGL(ibl_irradiance_kernel_seamless, dim3(6u * n * n), dim3(256), 0, dev->stream, ibl_cube_of(env), (float4*)out->ptr, n);
+    else hipLaunchKernelGGL(ibl_irradiance_kernel, dim3(6u * n * n), dim3(256), 0, dev->stream, ibl_cube_of(env), (float4*)out->ptr, n);
     return ibl_end(dev);
 }
 extern "C" mirhi_result mirhi_ibl_prefilter(mirhi_image* env, mirhi_image* out, uint32_t sample_count) {
@@ -1340,7 +1346,8 @@ extern "C" mirhi_result mirhi_ibl_prefilter(mirhi_image* env, mirhi_image* out, 
         blocks += (texels + 256u / lanes - 1u) / (256u / lanes);
     }
     plan.first_block[out->levels] = blocks;
-    hipLaunchKernelGGL(ibl_prefilter_kernel, dim3(blocks), dim3(256), (size_t)sample_count * sizeof(float4), dev->stream, ibl_cube_of(env), (float4*)out->ptr, plan);
+    if (env->cube_seamless) hipLaunchKernelGGL(ibl_prefilter_kernel_seamless, dim3(blocks), dim3(256), (size_t)sample_count * sizeof(float4), dev->stream, ibl_cube_of(env), (float4*)out->ptr, plan);
+    else hipLaunchKernelGGL(ibl_prefilter_kernel, dim3(blocks), dim3(256), (size_t)sample_count * sizeof(float4), dev->stream, ibl_cube_of(env), (float4*)out->ptr, plan);
     return ibl_end(dev);
 }
 extern "C" mirhi_result mirhi_ibl_brdf_lut(mirhi_image* out2d) {
@@ -1382,6 +1389,15 @@ extern "C" mirhi_result mirhi_image_set_sampler(mirhi_image* img, const mirhi_sa
     img->sampler = *desc;        // read when a draw is recorded, like max_anisotropy
     return MIRHI_OK;
 }
+extern "C" mirhi_result mirhi_image_set_cube_seamless(mirhi_image* cube, uint32_t enable) {
+    NULL_CHECK(cube, "image");
+    REFUSE_MULTISAMPLED(cube, "sampled (it has no sampler state)");
+    if (!cube->is_cube) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: not a cube image: seamless filtering is the state of a cube (mirhi_image_create_cube)");
+    if (enable > 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: cube seamless state %u is neither 0 nor 1", enable);
+    cube->cube_seamless = enable;      // read when a draw is recorded, like the sampler state of a texture; by the precompute passes when they are called
+    return MIRHI_OK;
+}
+extern "C" uint32_t mirhi_image_cube_seamless(const mirhi_image* img) { return (img && img->is_cube) ? img->cube_seamless : 0u; }
 extern "C" mirhi_result mirhi_image_sampler(const mirhi_image* img, mirhi_sampler_desc* out) {
     NULL_CHECK(img, "image");
     NULL_CHECK(out, "sampler desc");
@@ -2017,7 +2033,7 @@ static mirhi_result record_sky_draw(mirhi_cmd* cmd, bool indexed, uint32_t count
     pass.state = ds;
     RecordedPass::SkyDraw& k = pass.sky;
     k.on = 1u;
-    k.env = cmd->skybox->ptr; k.size = cmd->skybox->width; k.levels = cmd->skybox->levels;
+    k.env = cmd->skybox->ptr; k.size = cmd->skybox->width; k.levels = cmd->skybox->levels; k.seamless = cmd->skybox->cube_seamless;
     k.compare = ds.compare; k.write = ds.write; k.prim = pass.total_tris;
     const mirhi_viewport& vp = cmd->viewport;
     { float f = vp.max_depth; f = f > 0.0f ? (f < 1.0f ? f : 1.0f) : 0.0f; memcpy(&k.depth_bits, &f, 4); }
@@ -2265,6 +2281,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         RecordedPass::IblSet set;
         set.irradiance = cmd->ibl[0]->ptr; set.prefiltered = cmd->ibl[1]->ptr; set.lut = cmd->ibl[2]->ptr;
         set.irr_size = cmd->ibl[0]->width; set.pre_size = cmd->ibl[1]->width; set.pre_levels = cmd->ibl[1]->levels; set.lut_size = cmd->ibl[2]->width;
+        set.seamless = (cmd->ibl[0]->cube_seamless ? 1u : 0u) | (cmd->ibl[1]->cube_seamless ? 2u : 0u);      // (latched here; the LUT is 2-D and has no such state)
         if (pass.ibl.irradiance && !(pass.ibl == set))
             return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: MODEL_PBR_IBL draws recorded under two different IBL sets in one rendering scope");
         pass.ibl = set;
@@ -3046,10 +3063,11 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
     if (P.ibl) {
         P.ibl_irradiance = (const float*)pass.ibl.irradiance; P.ibl_prefiltered = (const float*)pass.ibl.prefiltered; P.ibl_lut = (const float*)pass.ibl.lut;
         P.ibl_irr_size = pass.ibl.irr_size; P.ibl_pre_size = pass.ibl.pre_size; P.ibl_pre_levels = pass.ibl.pre_levels; P.ibl_lut_size = pass.ibl.lut_size;
+        P.ibl_seamless = pass.ibl.seamless;
     }
     if (P.sky) {
         const RecordedPass::SkyDraw& k = pass.sky;
-        P.sky_visible = k.visible; P.sky_size = k.size; P.sky_levels = k.levels; P.sky_env = (const float*)k.env;
+        P.sky_visible = k.visible; P.sky_size = k.size; P.sky_levels = k.levels; P.sky_env = (const float*)k.env; P.sky_seamless = k.seamless;
         memcpy(P.sky_a, k.a, sizeof P.sky_a); memcpy(P.sky_b, k.b, sizeof P.sky_b); memcpy(P.sky_scissor, k.scissor, sizeof P.sky_scissor);
         for (int i = 0; i < 3; i++) P.sky_e0[i] = k.e0[i];
         memcpy(P.sky_pos0, k.pos0, sizeof P.sky_pos0); memcpy(P.sky_posx, k.posx, sizeof P.sky_posx); memcpy(P.sky_posy, k.posy, sizeof P.sky_posy);

@@ -287,6 +287,10 @@ struct PassParams {
     // The attachments are transient: `color` is the colour RESOLVE target (1x), `depth` the depth resolve target (sample 0; depth_store = 1) or nullptr,
     // `prim_out` an image of 4 * width x height texels, texel (4 px + s, py) the winner of sample s.  Behind everything else, like the area words.
     uint32_t samples, samples_pad;
+    // Seamless cube filtering (mirhi_image_set_cube_seamless), latched when the draw was recorded.  ibl_seamless: bit 0 the irradiance cube's
+    // state, bit 1 the prefiltered cube's (raster_kernel_ibl_seamless alone reads it; != 0 selects that kernel); sky_seamless: 1 = the SKYBOX segment's
+    // environment is seamless (selects sky_kernel_seamless; no kernel reads it).  Behind everything else, like the area words.
+    uint32_t ibl_seamless, sky_seamless;
 };
 static_assert(sizeof(PassParams) % 8 == 0, "PassParams holds pointers");
 

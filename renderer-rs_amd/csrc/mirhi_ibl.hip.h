@@ -124,6 +124,44 @@ __global__ void __launch_bounds__(256) ibl_irradiance_kernel(IblCube env, float4
                              ((part[0][2] + part[1][2]) + (part[2][2] + part[3][2])) * k, 1.0f);
     }
 }
+// ... reading a seamless environment (the state of env, the cube being READ: mirhi_image_set_cube_seamless).  The same kernel with the seamless lookup, as a copy:
+// a body shared through a template parameter moved ibl_irradiance_kernel's SGPR count (28 -> 29), and the kernels of a cube whose state is off stay what they were.
+__global__ void __launch_bounds__(256) ibl_irradiance_kernel_seamless(IblCube env, float4* __restrict__ out, uint32_t n) {
+    #pragma clang fp contract(fast)
+    __shared__ float2 sc_phi[IBL_IRR_PHI], sc_theta[IBL_IRR_THETA];
+    __shared__ float part[4][3];
+    const uint32_t tid = threadIdx.x, t = blockIdx.x;            // (grid = 6 n^2 exactly)
+    // the shader's float loops: phi += 0.025f while phi < 2 PI, theta += 0.025f while theta < PI / 2 (252 and 63 steps)
+    if (tid == 0u) { float a = 0.0f; for (uint32_t i = 0; i < IBL_IRR_PHI; i++) { sc_phi[i].x = a; a += 0.025f; } }
+    if (tid == 64u) { float a = 0.0f; for (uint32_t i = 0; i < IBL_IRR_THETA; i++) { sc_theta[i].x = a; a += 0.025f; } }
+    __syncthreads();
+    if (tid < IBL_IRR_PHI) { const float a = sc_phi[tid].x; sc_phi[tid] = make_float2(sinf(a), cosf(a)); }
+    if (tid < IBL_IRR_THETA) { const float a = sc_theta[tid].x; sc_theta[tid] = make_float2(sinf(a), cosf(a)); }
+    __syncthreads();
+    const uint32_t face = t / (n * n), py = (t / n) % n, px = t % n;
+    const float3 N = ibl_texel_direction(face, px, py, n);
+    float3 up = fabsf(N.y) < 0.999f ? make_float3(0.0f, 1.0f, 0.0f) : make_float3(1.0f, 0.0f, 0.0f);
+    const float3 right = ibl_normalize(ibl_cross(up, N));
+    up = ibl_normalize(ibl_cross(N, right));
+    IblCube env0 = env; env0.levels = 1u;
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    for (uint32_t s = tid; s < IBL_IRR_PHI * IBL_IRR_THETA; s += 256u) {
+        const float2 p = sc_phi[s / IBL_IRR_THETA], th = sc_theta[s % IBL_IRR_THETA];
+        const float tx = th.x * p.y, ty = th.x * p.x, tz = th.y;
+        const float4 c = ibl_sample_cube_seamless(env0, tx * right.x + ty * up.x + tz * N.x, tx * right.y + ty * up.y + tz * N.y,
+                                         tx * right.z + ty * up.z + tz * N.z, 0.0f);
+        const float w = th.y * th.x;
+        r += c.x * w; g += c.y * w; b += c.z * w;
+    }
+    r = ibl_lane_sum(r, 64u); g = ibl_lane_sum(g, 64u); b = ibl_lane_sum(b, 64u);
+    if ((tid & 63u) == 0u) { part[tid >> 6][0] = r; part[tid >> 6][1] = g; part[tid >> 6][2] = b; }
+    __syncthreads();
+    if (tid == 0u) {
+        const float k = IBL_PI / (float)(IBL_IRR_PHI * IBL_IRR_THETA);
+        out[t] = make_float4(((part[0][0] + part[1][0]) + (part[2][0] + part[3][0])) * k, ((part[0][1] + part[1][1]) + (part[2][1] + part[3][1])) * k,
+                             ((part[0][2] + part[1][2]) + (part[2][2] + part[3][2])) * k, 1.0f);
+    }
+}
 
 // ---- prefilter_map.hlsl:134-229, every level in one grid -----------------------------------------------------------------------------------
 // N = V = R, so in tangent space everything of a sample but the lookup is the same for every texel of a level: H, NdotH = HdotV = H.z,
@@ -137,7 +175,9 @@ struct IblPrefilterPlan {
     uint32_t first_block[IBL_MAX_LEVELS + 1u];      // blocks [first_block[l], first_block[l + 1]) work on level l
     uint32_t lanes[IBL_MAX_LEVELS];                 // lanes per texel
 };
-__global__ void __launch_bounds__(256) ibl_prefilter_kernel(IblCube env, float4* __restrict__ out, IblPrefilterPlan plan) {
+// SEAMLESS: the state of env (every lookup, the single one of a level with Roughness < 0.01 included; ibl_prefilter_kernel_seamless below)
+template <bool SEAMLESS>
+__device__ __forceinline__ void ibl_prefilter_body(const IblCube& env, float4* __restrict__ out, const IblPrefilterPlan& plan) {
     #pragma clang fp contract(fast)
     extern __shared__ float4 table[];               // sample_count entries
     __shared__ uint32_t wave_kept[4];
@@ -154,7 +194,7 @@ __global__ void __launch_bounds__(256) ibl_prefilter_kernel(IblCube env, float4*
     float4* dst = out + ibl_level_offset(plan.size, level) + tc;
     const float roughness = plan.levels > 1u ? (float)level / (float)(plan.levels - 1u) : 0.0f;
     if (roughness < 0.01f) {                         // :168-173 (block-uniform; lanes == 1 here)
-        const float4 c = ibl_sample_cube(env, N.x, N.y, N.z, 0.0f);
+        const float4 c = ibl_sample_cube_as<SEAMLESS>(env, N.x, N.y, N.z, 0.0f);
         if (live) *dst = make_float4(c.x, c.y, c.z, 1.0f);
         return;
     }
@@ -200,7 +240,7 @@ __global__ void __launch_bounds__(256) ibl_prefilter_kernel(IblCube env, float4*
     float r = 0.0f, g = 0.0f, b = 0.0f, wsum = 0.0f;
     for (uint32_t k = sub; k < count; k += lanes) {
         const float4 e = table[k];
-        const float4 c = ibl_sample_cube(env, T.x * e.x + B.x * e.y + N.x * e.z, T.y * e.x + B.y * e.y + N.y * e.z,
+        const float4 c = ibl_sample_cube_as<SEAMLESS>(env, T.x * e.x + B.x * e.y + N.x * e.z, T.y * e.x + B.y * e.y + N.y * e.z,
                                          T.z * e.x + B.z * e.y + N.z * e.z, e.w);
         r += c.x * e.z; g += c.y * e.z; b += c.z * e.z; wsum += e.z;
     }
@@ -210,6 +250,8 @@ __global__ void __launch_bounds__(256) ibl_prefilter_kernel(IblCube env, float4*
         *dst = make_float4(r * inv, g * inv, b * inv, 1.0f);
     }
 }
+__global__ void __launch_bounds__(256) ibl_prefilter_kernel(IblCube env, float4* __restrict__ out, IblPrefilterPlan plan) { ibl_prefilter_body<false>(env, out, plan); }
+__global__ void __launch_bounds__(256) ibl_prefilter_kernel_seamless(IblCube env, float4* __restrict__ out, IblPrefilterPlan plan) { ibl_prefilter_body<true>(env, out, plan); }
 
 // ---- brdf_lut.hlsl:116-206 ---------------------------------------------------------------------------------------------------------------
 // A workgroup works on 256 texels of one row (one roughness): the 1024 half vectors of ImportanceSampleGGX depend on the row alone and are built

@@ -123,6 +123,9 @@ struct RasterEntry { uint32_t id; const char* name; void (*kernel)(const PassPar
 #define OWN_A(FAMILY, KERNEL, K, T) {raster_kernel_id(FAMILY, 0, K, T, 1, 0, 4, 1), #KERNEL "<" #K ", " #T ", true>", KERNEL<K, T, true>}
 #define IBL_A(K, T, S) {raster_kernel_id(RASTER_IBL, S, K, T, 1, 0, 4, 1), "raster_kernel_ibl<" #K ", " #T ", " #S ", true>", raster_kernel_ibl<K, T, S, true>}
 #define PLAIN_A(P, K, T, M) {raster_kernel_id(RASTER_PLAIN, P, K, T, 1, M, 4, 1), "raster_kernel<" #P ", " #K ", " #T ", 1, " #M ", true>", raster_kernel<P, K, T, 1, M, true>}
+// ... and the seamless instantiations of the IBL family (RasterVariant::seamless), full-extent and AREA
+#define IBL_S(K, T, S) {raster_kernel_id(RASTER_IBL, S, K, T, 1, 0, 4, 0, 1), "raster_kernel_ibl_seamless<" #K ", " #T ", " #S ">", raster_kernel_ibl_seamless<K, T, S>}
+#define IBL_SA(K, T, S) {raster_kernel_id(RASTER_IBL, S, K, T, 1, 0, 4, 1, 1), "raster_kernel_ibl_seamless<" #K ", " #T ", " #S ", true>", raster_kernel_ibl_seamless<K, T, S, true>}
 #define MSAA(P, K) {raster_kernel_id(RASTER_MSAA, P, K, 0, 1, 0, 4), "raster_kernel_msaa<" #P ", " #K ">", raster_kernel_msaa<P, K>}
 static const RasterEntry k_raster_entries[] = {
     ORDERED(2), ORDERED(3), ORDERED(4), ORDERED(1),
@@ -166,7 +169,16 @@ static const RasterEntry k_raster_entries[] = {
     {raster_kernel_id(RASTER_TRANSFER, XFER_BLIT_NEAREST, 0, 0, 1, 0, 4), "transfer_blit_kernel<0>", transfer_blit_kernel<0>},
     {raster_kernel_id(RASTER_TRANSFER, XFER_BLIT_LINEAR, 0, 0, 1, 0, 4), "transfer_blit_kernel<1>", transfer_blit_kernel<1>},
     {raster_kernel_id(RASTER_TRANSFER, XFER_FILL, 0, 0, 1, 0, 4), "transfer_fill_kernel", transfer_fill_kernel},
+    // seamless cube filtering, behind every older row: the SKYBOX segment of a seamless environment, MODEL_PBR_IBL scopes whose set has a seamless
+    // cube (per key, triangle-parallel path and shadow term, as the rows of raster_kernel_ibl), their AREA forms
+    {raster_kernel_id(RASTER_SKY, 0, 0, 0, 1, 0, 4, 0, 1), "sky_kernel_seamless", sky_kernel_seamless},
+    IBL_S(0, 1, 0), IBL_S(1, 1, 0), IBL_S(0, 0, 0), IBL_S(1, 0, 0), IBL_S(0, 1, 1), IBL_S(1, 1, 1), IBL_S(0, 0, 1), IBL_S(1, 0, 1),
+    IBL_S(0, 1, 2), IBL_S(1, 1, 2), IBL_S(0, 0, 2), IBL_S(1, 0, 2), IBL_S(0, 1, 3), IBL_S(1, 1, 3), IBL_S(0, 0, 3), IBL_S(1, 0, 3),
+    IBL_SA(0, 1, 0), IBL_SA(1, 1, 0), IBL_SA(0, 0, 0), IBL_SA(1, 0, 0), IBL_SA(0, 1, 1), IBL_SA(1, 1, 1), IBL_SA(0, 0, 1), IBL_SA(1, 0, 1),
+    IBL_SA(0, 1, 2), IBL_SA(1, 1, 2), IBL_SA(0, 0, 2), IBL_SA(1, 0, 2), IBL_SA(0, 1, 3), IBL_SA(1, 1, 3), IBL_SA(0, 0, 3), IBL_SA(1, 0, 3),
 };
+#undef IBL_S
+#undef IBL_SA
 #undef MSAA
 #undef IBL
 #undef IBL_A
@@ -325,6 +337,30 @@ extern "C" int mirhi_debug_raster_choice(const uint32_t in[12], char* name, uint
     snprintf(name, name_len, "%s", b ? b->name : raster_entry(v)->name);
     grid_block[0] = v.grid[0]; grid_block[1] = v.grid[1]; grid_block[2] = b ? n : v.grid[2]; grid_block[3] = v.block;
     return 0;
+}
+
+// ... the same for a scope whose latched seamless states are given: ibl_seamless = PassParams::ibl_seamless (bit 0 irradiance, bit 1 prefiltered),
+// sky_seamless = PassParams::sky_seamless.  With both 0 it answers what mirhi_debug_raster_choice answers.
+extern "C" int mirhi_debug_raster_choice_seamless(const uint32_t in[12], uint32_t ibl_seamless, uint32_t sky_seamless, char* name, uint32_t name_len, uint32_t grid_block[4]) {
+    static TriRec some_recs;
+    PassParams P{};
+    P.tiles_x = 5u; P.tile_row_begin = 0u; P.tile_row_end = 4u; P.tile_row_step = 1u;
+    P.pred = in[2]; P.zflip = in[3]; P.zmask = in[4]; P.tp_max_area = in[5]; P.raster_teams = in[6]; P.raster_wide = in[7]; P.alpha_scope = in[8]; P.xcd_swizzle = in[9];
+    P.ordered_recs = in[10] ? &some_recs : nullptr;
+    P.ibl_seamless = ibl_seamless; P.sky_seamless = sky_seamless;
+    const RasterVariant v = raster_variant(P, in[0], in[1] != 0u);
+    const RasterEntry* e = raster_entry(v);
+    if (!e) return 1;
+    snprintf(name, name_len, "%s", e->name);
+    grid_block[0] = v.grid[0]; grid_block[1] = v.grid[1]; grid_block[2] = v.grid[2]; grid_block[3] = v.block;
+    return 0;
+}
+// The device's table of cube edge neighbours (ibl_seamless_tap, mirhi_ibl_sample.hip.h), as plain host code: tap (i, j) of `face` at a level of n x n texels ->
+// out[0] the texel's offset from the level's first texel, out[1] 1 for a corner tap.  A test compares it with the float64 model's re-projection.
+extern "C" void mirhi_debug_cube_edge_tap(uint32_t n, uint32_t face, int32_t i, int32_t j, uint32_t out[2]) {
+    bool corner = false;
+    out[0] = ibl_seamless_tap(n, face < 6u ? face : 5u, ibl_edge_row(face), (int)i, (int)j, true, corner);
+    out[1] = corner ? 1u : 0u;
 }
 
 #ifdef MIRHI_STAMPS

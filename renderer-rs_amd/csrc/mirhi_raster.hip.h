@@ -738,11 +738,12 @@ __device__ __forceinline__ void raster_list(const uint4* __restrict__ list, uint
 // the winner's depth (SV_Position.z) to the fragment program; again a variant of its own, raster_kernel_shadow keeps its registers.
 // SHADOWV = 3: ... with CalculateShadowCSMBlended for scopes with a blended cascaded draw (PassParams::shadowed = 3, raster_kernel_csm_blend).
 // IBLV (PROGS = 4, one team, four waves, with any SHADOWV): the scope has MODEL_PBR_IBL draws (raster_kernel_ibl); the fragment program reads the
-// IBL set from the parameter block.  Carries the other programs as every PROGS = 4 kernel does.
+// IBL set from the parameter block.  Carries the other programs as every PROGS = 4 kernel does.  IBLV = 2: ... and a cube of the set is seamless
+// (raster_kernel_ibl_seamless): the fragment program's cube lookups filter across face edges.
 // AREA: the scope has a partial render area: the launch spans a sub-range of the tile columns (RasterHead::tile_origin) and every
 // pixel is tested against the area's rectangle instead of the extent.  Variants of their own (one team of four waves: raster_mode), so that the
 // AREA = false instantiations are, instruction for instruction, what they were before there were areas.
-template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4, int SHADOWV = 0, bool IBLV = false, bool AREA = false>
+template <int PROGS, int KEYED, int TP, int TEAMS = 1, bool MASKEDV = false, int WPT = 4, int SHADOWV = 0, int IBLV = 0, bool AREA = false>
 #ifndef MIRHI_PROGS2_WAVES
 #define MIRHI_PROGS2_WAVES 5
 #endif
@@ -1082,8 +1083,8 @@ __device__ __forceinline__ void raster_body(const PassParams* __restrict__ param
                 DrawRef D = const_draws(P.draws)[__builtin_amdgcn_readfirstlane(mydraw)];
                 const uint32_t tri = prim - D.prim_base;
                 const float pxc = (float)px + 0.5f, pyc = (float)py + 0.5f;
-                if constexpr (IBLV) col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc)
-                                                            : shade_model_program<true, SHADOWV, true>(D, tri, pxc, pyc, SHADOWV >= 2 ? __uint_as_float(zkb ^ P.zflip) : 0.0f, R);
+                if constexpr (IBLV != 0) col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc)
+                                                                 : shade_model_program<true, SHADOWV, IBLV>(D, tri, pxc, pyc, SHADOWV >= 2 ? __uint_as_float(zkb ^ P.zflip) : 0.0f, R);
                 else if (PROGS == 1) col = shade_triangle_program(D, tri, pxc, pyc);
                 else if (PROGS == 2) col = shade_model_program<false>(D, tri, pxc, pyc);
                 else if (SHADOWV >= 2) col = (D.program == 0) ? shade_triangle_program(D, tri, pxc, pyc)      // (a cascaded draw has a depth key: zmask != 0)
@@ -1159,7 +1160,15 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void raster_kernel_csm_blend(con
 // (DESIGN.md 8e).
 template <int KEYED, int TP, int SHADOWV, bool AREA = false>
 __global__ __launch_bounds__(RASTER_THREADS, (SHADOWV >= 2 ? 2 : 3)) void raster_kernel_ibl(const PassParams* __restrict__ params, const RasterHead H) {
-    raster_body<4, KEYED, TP, 1, false, 4, SHADOWV, true, AREA>(params, H);
+    raster_body<4, KEYED, TP, 1, false, 4, SHADOWV, 1, AREA>(params, H);
+}
+// ... whose IBL set has a seamless cube (mirhi_image_set_cube_seamless, latched by the draw: PassParams::ibl_seamless != 0): instantiations of their own, as the
+// AREA ones are, so that raster_kernel_ibl runs what it ran before there was the state.  Two waves per SIMD for every shadow term: at three
+// (168 registers) the seamless taps of twelve cube texels made the SHADOWV = 0 / 1 forms spill 20 - 27 VGPRs to scratch (64 - 84 bytes per lane), which no
+// kernel here may use -- a queue of the native dispatcher has none set up; at two they need about 190 and spill nothing.
+template <int KEYED, int TP, int SHADOWV, bool AREA = false>
+__global__ __launch_bounds__(RASTER_THREADS, 2) void raster_kernel_ibl_seamless(const PassParams* __restrict__ params, const RasterHead H) {
+    raster_body<4, KEYED, TP, 1, false, 4, SHADOWV, 2, AREA>(params, H);
 }
 // up to MAX_BATCH independent rendering scopes of equal shape (the frames of one mirhi_queue_submit): grid (tiles_x, tile rows, scopes).
 // One launch instead of one per frame: the ramp-up and drain of a kernel (5 us of the 11 us an isolated 10k-triangle raster kernel

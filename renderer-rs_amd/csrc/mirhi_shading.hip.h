@@ -678,20 +678,66 @@ __device__ __forceinline__ f3 ibl_ambient(ParamsPtr R, f3 N, f3 V, const PbrMate
             (kD.y * (irradiance.y * m.albedo.y) + prefiltered.y * (F0.y * brdf.x + brdf.y)) * ao,
             (kD.z * (irradiance.z * m.albedo.z) + prefiltered.z * (F0.z * brdf.x + brdf.y)) * ao};
 }
+// ... in a scope whose IBL set has a seamless cube (PassParams::ibl_seamless != 0, raster_kernel_ibl_seamless): the same sequence -- every
+// address, then the sixteen loads, then the filters -- with the seamless taps of mirhi_ibl_sample.hip.h for the two cubes.  A function of its own, so that
+// ibl_ambient above stays, instruction for instruction, what the non-seamless kernels ran before.
+__device__ __forceinline__ f3 ibl_ambient_seamless(ParamsPtr R, f3 N, f3 V, const PbrMaterial& m, float ao) {
+    #pragma clang fp contract(fast)
+    const float4* const irr = reinterpret_cast<const float4*>(R->ibl_irradiance);
+    const float4* const pre = reinterpret_cast<const float4*>(R->ibl_prefiltered);
+    const float4* const lut = reinterpret_cast<const float4*>(R->ibl_lut);
+    const uint32_t irr_n = R->ibl_irr_size, pre_n = R->ibl_pre_size, pre_levels = R->ibl_pre_levels, lut_n = R->ibl_lut_size;
+    const uint32_t seam = R->ibl_seamless;      // (wave-uniform: bit 0 the irradiance cube's state, bit 1 the prefiltered cube's)
+    const float ndv_raw = dot3(N, V);
+    const float NdotV = max0(ndv_raw);                                                  // :359
+    const f3 Rv = {2.0f * ndv_raw * N.x - V.x, 2.0f * ndv_raw * N.y - V.y, 2.0f * ndv_raw * N.z - V.z};      // :259 reflect(-V, N)
+    // addresses
+    const IblFaceUV fn = ibl_select_face(N.x, N.y, N.z);                               // :369 (lod 0: the one level)
+    const IblSeamTaps ki = ibl_seamless_taps(irr_n, fn.face, fn.s, fn.t, (seam & 1u) != 0u);
+    const float4* const pi = irr;      // (a seamless tap's offset counts from the level's first texel: it may lie in another face)
+    const IblFaceUV fr = ibl_select_face(Rv.x, Rv.y, Rv.z);                            // :373-377
+    const float lod = fminf(fmaxf(m.roughness * 7.0f, 0.0f), (float)(pre_levels - 1u));    // MAX_REFLECTION_LOD pbr.hlsli:373; the sampler's clamp
+    const float l0f = floorf(lod), frac = lod - l0f;
+    const uint32_t l0 = min((uint32_t)(int)l0f, pre_levels - 1u), l1 = min(l0 + 1u, pre_levels - 1u);
+    const uint32_t n0 = pre_n >> l0, n1 = pre_n >> l1;
+    const IblSeamTaps k0 = ibl_seamless_taps(n0, fr.face, fr.s, fr.t, (seam & 2u) != 0u), k1 = ibl_seamless_taps(n1, fr.face, fr.s, fr.t, (seam & 2u) != 0u);
+    const float4* const p0 = pre + ibl_level_offset(pre_n, l0);
+    const float4* const p1 = pre + ibl_level_offset(pre_n, l1);
+    const IblTaps kl = ibl_bilinear_taps(lut_n, NdotV, m.roughness);                   // :380 (u = NdotV: column, v = roughness: row)
+    // the sixteen loads
+    const float4 ia = pi[ki.o00], ib = pi[ki.o10], ic = pi[ki.o01], id = pi[ki.o11];
+    const float4 pa = p0[k0.o00], pb = p0[k0.o10], pc = p0[k0.o01], pd = p0[k0.o11];
+    const float4 qa = p1[k1.o00], qb = p1[k1.o10], qc = p1[k1.o01], qd = p1[k1.o11];
+    const float4 la = lut[kl.o00], lb = lut[kl.o10], lc = lut[kl.o01], ld = lut[kl.o11];
+    // filters
+    const float4 irradiance = ibl_seamless_filter(ki, ia, ib, ic, id);
+    const float4 prefiltered = ibl_lerp4(ibl_seamless_filter(k0, pa, pb, pc, pd), ibl_seamless_filter(k1, qa, qb, qc, qd), frac);
+    const float4 brdf = ibl_bilinear_filter(kl, la, lb, lc, ld);
+    const f3 F0 = {0.04f + (m.albedo.x - 0.04f) * m.metallic, 0.04f + (m.albedo.y - 0.04f) * m.metallic, 0.04f + (m.albedo.z - 0.04f) * m.metallic};   // :356
+    const float o = 1.0f - saturatef(NdotV), o2 = o * o, p5 = o2 * o2 * o;              // FresnelSchlickRoughness pbr.hlsli:147-152
+    const float r1 = 1.0f - m.roughness, om = 1.0f - m.metallic;
+    const f3 F = {F0.x + (fmaxf(r1, F0.x) - F0.x) * p5, F0.y + (fmaxf(r1, F0.y) - F0.y) * p5, F0.z + (fmaxf(r1, F0.z) - F0.z) * p5};
+    const f3 kD = {(1.0f - F.x) * om, (1.0f - F.y) * om, (1.0f - F.z) * om};           // :365-366
+    return {(kD.x * (irradiance.x * m.albedo.x) + prefiltered.x * (F0.x * brdf.x + brdf.y)) * ao,      // :370, :381, :384
+            (kD.y * (irradiance.y * m.albedo.y) + prefiltered.y * (F0.y * brdf.x + brdf.y)) * ao,
+            (kD.z * (irradiance.z * m.albedo.z) + prefiltered.z * (F0.z * brdf.x + brdf.y)) * ao};
+}
 // pixel/model_pbr_ibl.hlsl:199-396 (SHADOW 0 / 1) and pixel/model_pbr_ibl_csm.hlsl (SHADOW 2): color = ambient + Lo + emissive (:393) -- no hemisphere
 // ambient, and Lo is NOT scaled by lerp(1, ao, 0.5), which is model_pbr.hlsl's alone
-template <int SHADOW>
+template <int SHADOW, bool SEAMLESS = false>
 __device__ __forceinline__ f4 shade_pbr_ibl(DrawRef D, ParamsPtr R, const float b[3], const uint32_t vi[3], float u, float v, f3 worldPos, f3 V, f3 N, const UvGrad& grad, float clipz) {
     const PbrSurface s = pbr_surface(D, b, vi, u, v, N, grad);
     const f3 Lo = pbr_direct_lighting<SHADOW>(D, worldPos, V, s.N, s.m, clipz);
-    const f3 ambient = ibl_ambient(R, s.N, V, s.m, s.ao);
+    f3 ambient;
+    if constexpr (SEAMLESS) ambient = ibl_ambient_seamless(R, s.N, V, s.m, s.ao);
+    else ambient = ibl_ambient(R, s.N, V, s.m, s.ao);
     const f3 col = add3(add3(ambient, Lo), s.emissive);
     return {col.x, col.y, col.z, s.alpha};
 }
 
 // FULL: the variant that also carries the Cook-Torrance program and mip-mapped (trilinear) sampling; SHADOW: and the shadow term (shade_pbr); IBL: and MODEL_PBR_IBL (shade_pbr_ibl,
-// R = the scope's parameter block, where the IBL set lives)
-template <bool FULL, int SHADOW = 0, bool IBL = false>
+// R = the scope's parameter block, where the IBL set lives; IBL = 2: with the seamless cube lookups, ibl_ambient_seamless)
+template <bool FULL, int SHADOW = 0, int IBL = 0>
 __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3], float pxc, float pyc, float clipz = 0.0f, ParamsPtr R = nullptr) {
     f4 c[3];
     const bool full = D.program >= 2;
@@ -744,7 +790,7 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
         grad.dudy = ((by[0] * uvk[0][0] + by[1] * uvk[1][0]) + by[2] * uvk[2][0]) - u;
         grad.dvdy = ((by[0] * uvk[0][1] + by[1] * uvk[1][1]) + by[2] * uvk[2][1]) - v;
     }
-    if constexpr (IBL) { if (D.program == 5) return shade_pbr_ibl<SHADOW>(D, R, b, vi, u, v, worldPos, V, N, grad, clipz); }
+    if constexpr (IBL != 0) { if (D.program == 5) return shade_pbr_ibl<SHADOW, IBL == 2>(D, R, b, vi, u, v, worldPos, V, N, grad, clipz); }
     if (FULL && D.program == 3) return shade_pbr<SHADOW>(D, b, vi, u, v, worldPos, V, N, grad, clipz);
     // pixel/model_full.hlsl:85-150
     const f4 baseColor = {ldcf(cb(D.material), 0), ldcf(cb(D.material), 4), ldcf(cb(D.material), 8), ldcf(cb(D.material), 12)};
@@ -816,7 +862,7 @@ __device__ __forceinline__ f4 shade_model_program(DrawRef D, const uint32_t vi[3
     return {col.x, col.y, col.z, albedoSample.w * baseColor.w};
 }
 
-template <bool FULL, int SHADOW = 0, bool IBL = false>
+template <bool FULL, int SHADOW = 0, int IBL = 0>
 __device__ __forceinline__ f4 shade_model_program(DrawRef D, uint32_t tri, float pxc, float pyc, float clipz = 0.0f, ParamsPtr R = nullptr) {
     uint32_t vin[3];
     fetch_triangle_indices(D, tri, vin);

@@ -11,6 +11,9 @@
 // Nothing of the workspace is touched: no counter, no page table, no status word (DESIGN.md 8f "Workspace parity").
 #pragma once
 
+template <bool SEAMLESS> struct SkyTaps { typedef IblTaps type; };
+template <> struct SkyTaps<true> { typedef IblSeamTaps type; };
+
 __device__ __forceinline__ bool sky_depth_passes(uint32_t op, float frag, float stored) {
     switch (op) {      // mirhi_compare_op; wave-uniform
         case 1u: return frag < stored;
@@ -26,7 +29,11 @@ __device__ __forceinline__ bool sky_depth_passes(uint32_t op, float frag, float 
 
 // Four workgroups per CU are asked for: sixteen float4 texels in flight (four pixels x four taps) beside the addresses and fractions must fit, and the
 // kernel waits on gathers, not on arithmetic.  What the compiler makes of it (VGPRs, occupancy; no spill, scratch or LDS) is DESIGN.md 8f's table.
-__global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams* __restrict__ params, const RasterHead H) {
+// SEAMLESS: the environment's seamless state was on when the draw was recorded (PassParams::sky_seamless, sky_kernel_seamless): the four
+// taps cross face edges (ibl_seamless_taps: offsets from level 0's first texel) and a corner tap is the mean of the other three.  The shape stays:
+// every address, then the sixteen loads, then the filters.  SEAMLESS = false is sky_kernel as it was.
+template <bool SEAMLESS>
+__device__ __forceinline__ void sky_body(const PassParams* __restrict__ params, const RasterHead& H) {
     ParamsRef P = *(ParamsPtr)(uintptr_t)params;
     const uint32_t tid = threadIdx.x;
     const uint32_t tx = blockIdx.x + (H.tile_origin >> 16), ty = (H.tile_origin & 0xFFFFu) + blockIdx.y * H.tile_row_step;      // (the render area's tile columns)
@@ -69,11 +76,11 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams
         const uint32_t n = P.sky_size;
         const float4* const env = reinterpret_cast<const float4*>(P.sky_env);
         const float fx = (float)px + 0.5f;
-        IblTaps taps[4];
+        typename SkyTaps<SEAMLESS>::type taps[4];
         const float4* face[4];
 #pragma unroll
         for (int b = 0; b < 4; b++) {
-            taps[b] = IblTaps{0u, 0u, 0u, 0u, 0.0f, 0.0f}; face[b] = env;
+            taps[b] = {}; face[b] = env;
             if (!won[b]) continue;      // (behind geometry most pixels fail: their direction arithmetic is skipped, not only their loads)
             const float fy = (float)(py0 + 8u * (uint32_t)b) + 0.5f;
             // LocalPos: affine in the pixel centre (pixel/skybox.hlsl:11 takes the interpolated vertex output), then normalize (:24)
@@ -82,8 +89,11 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams
             const float lz = __builtin_fmaf(P.sky_posy[2], fy, __builtin_fmaf(P.sky_posx[2], fx, P.sky_pos0[2]));
             const float inv = __builtin_amdgcn_rsqf(__builtin_fmaf(lz, lz, __builtin_fmaf(ly, ly, lx * lx)));
             const IblFaceUV f = ibl_select_face(lx * inv, ly * inv, lz * inv);
-            taps[b] = ibl_bilinear_taps(n, f.s, f.t);
-            face[b] = env + f.face * n * n;      // (level 0 starts the chain; face < 6 and every tap offset < n * n whatever the direction holds)
+            if constexpr (SEAMLESS) taps[b] = ibl_seamless_taps(n, f.face, f.s, f.t, true);      // (face[b] stays the level's base: every tap offset < 6 n * n)
+            else {
+                taps[b] = ibl_bilinear_taps(n, f.s, f.t);
+                face[b] = env + f.face * n * n;      // (level 0 starts the chain; face < 6 and every tap offset < n * n whatever the direction holds)
+            }
         }
         float4 t[4][4];
 #pragma unroll
@@ -93,7 +103,9 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams
         }
 #pragma unroll
         for (int b = 0; b < 4; b++) {
-            const float4 c = ibl_bilinear_filter(taps[b], t[b][0], t[b][1], t[b][2], t[b][3]);
+            float4 c;
+            if constexpr (SEAMLESS) c = ibl_seamless_filter(taps[b], t[b][0], t[b][1], t[b][2], t[b][3]);
+            else c = ibl_bilinear_filter(taps[b], t[b][0], t[b][1], t[b][2], t[b][3]);
             col[b] = {c.x, c.y, c.z, c.w};
         }
     }
@@ -115,3 +127,7 @@ __global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams
         if (store_depth && ((won[b] && write_depth) || !load_depth)) P.depth[pix] = __uint_as_float((won[b] && write_depth) ? P.sky_depth_bits : zorig[b]);
     }
 }
+
+__global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel(const PassParams* __restrict__ params, const RasterHead H) { sky_body<false>(params, H); }
+// the SKYBOX segment of a seamless environment cube
+__global__ __launch_bounds__(RASTER_THREADS, 4) void sky_kernel_seamless(const PassParams* __restrict__ params, const RasterHead H) { sky_body<true>(params, H); }

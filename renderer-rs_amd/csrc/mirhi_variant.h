@@ -29,8 +29,8 @@ enum RasterFamily : uint32_t { RASTER_PLAIN, RASTER_WIDE, RASTER_DEPTH, RASTER_S
 constexpr RasterFamily RASTER_DEPTH_VIEWS = (RasterFamily)(RASTER_MSAA + 1u);
 
 // the kernel instantiation alone (no launch shape) as one word
-constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves, uint32_t area = 0u) {
-    return family | progs << 4 | keyed << 8 | tp << 12 | teams << 16 | masked << 20 | waves << 24 | area << 30;
+constexpr uint32_t raster_kernel_id(uint32_t family, uint32_t progs, uint32_t keyed, uint32_t tp, uint32_t teams, uint32_t masked, uint32_t waves, uint32_t area = 0u, uint32_t seamless = 0u) {
+    return family | progs << 4 | keyed << 8 | tp << 12 | teams << 16 | masked << 20 | waves << 24 | area << 30 | seamless << 31;
 }
 
 // One raster launch: the kernel family and its template arguments, the grid and the block.  Equal values <=> the same kernel
@@ -46,7 +46,8 @@ struct RasterVariant {
     uint32_t grid[3], block;
     uint32_t batched_form;    // 1: a raster_kernel_batch instantiation exists for it and the scope may take it (plain tile order, no wide plan)
     uint32_t area;            // 1: the AREA instantiation (a partial render area); the ordered, sky and transfer kernels have one form
-    constexpr uint32_t kernel_id() const { return raster_kernel_id(family, progs, keyed, tp, teams, masked, waves, area); }
+    uint32_t seamless;        // 1: the SEAMLESS instantiation (RASTER_IBL: a cube of the scope's IBL set is seamless; RASTER_SKY: the environment is); 0 for every other family
+    constexpr uint32_t kernel_id() const { return raster_kernel_id(family, progs, keyed, tp, teams, masked, waves, area, seamless); }
     bool operator==(const RasterVariant& o) const {
         return kernel_id() == o.kernel_id() && grid[0] == o.grid[0] && grid[1] == o.grid[1] && grid[2] == o.grid[2] && block == o.block && batched_form == o.batched_form;
     }
@@ -58,7 +59,8 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
     const uint32_t cols = launch_cols(P);      // (the render area's tile columns: all of them unless the area is partial)
     if (programs == PROGS_SKY) {
         // a SKYBOX segment: one 256-thread workgroup per tile of the owned rows, always the 2-D grid; no key, no bins, no batched form
-        return RasterVariant{RASTER_SKY, 0u, 0u, 0u, 1u, 0u, 4u, {cols, rows, 1u}, (uint32_t)RASTER_THREADS, 0u, 0u};
+        // (the environment's seamless state, latched by the draw: sky_kernel_seamless)
+        return RasterVariant{RASTER_SKY, 0u, 0u, 0u, 1u, 0u, 4u, {cols, rows, 1u}, (uint32_t)RASTER_THREADS, 0u, 0u, P.sky_seamless ? 1u : 0u};
     }
     if (programs == PROGS_TRANSFER) {
         // a transfer entry: its kernel by what it is (progs = XFER_*), a 1-D grid of PassParams::tiles_x workgroups (the host's count: a blit's tiles, the
@@ -90,6 +92,7 @@ inline RasterVariant raster_variant(const PassParams& P, uint32_t programs, bool
         // ordered key), one kernel per shadow term of its draws
         v.family = RASTER_IBL;
         v.progs = (programs & PROGS_CSM_BLEND) ? 3u : ((programs & PROGS_CASCADED) ? 2u : ((programs & PROGS_SHADOWED) ? 1u : 0u));
+        v.seamless = P.ibl_seamless ? 1u : 0u;      // a cube of the set was seamless when the draws were recorded: raster_kernel_ibl_seamless
     } else if (programs == PROGS_DEPTH_ONLY || (programs & PROGS_SHADOWED)) {
         // depth-only scopes and scopes with a shadowed draw have variants of their own, whatever the selectors below would pick (the host keeps
         // them on one team of four waves, single-list bins and the plain tile order; their key is an ordered one, never a predicate)

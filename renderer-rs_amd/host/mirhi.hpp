@@ -315,6 +315,10 @@ public:
     // the rest of the sampler state (include/mirhi.h mirhi_image_set_sampler): address modes, mag / min filters, mip mode; for draws recorded afterwards
     void set_sampler(const SamplerDesc& s) { check(mirhi_image_set_sampler(h_, &s)); }
     SamplerDesc sampler() const { SamplerDesc s; check(mirhi_image_sampler(h_, &s)); return s; }
+    // a cube's seamless state (include/mirhi.h "The sampler"): lookups filter across face edges and corners; for draws recorded afterwards and the
+    // precompute passes' next call
+    void set_cube_seamless(bool enable) { check(mirhi_image_set_cube_seamless(h_, enable ? 1u : 0u)); }
+    bool cube_seamless() const { return mirhi_image_cube_seamless(h_) != 0u; }
 private:
     Image(std::shared_ptr<Device> device, mirhi_image* raw, uint32_t w, uint32_t h, Format f) : device_(std::move(device)), h_(raw), w_(w), h_px_(h), f_(f) {}
     std::shared_ptr<Device> device_;

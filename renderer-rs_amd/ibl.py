@@ -126,15 +126,85 @@ def _bilinear_face(level, face, s, t, dtype):
     return top * (one - fy) + bot * fy
 
 
-def sample_cube(levels, d, lod=0.0, dtype=np.float64):
+def edge_neighbour(n: int, face, i, j):
+    """The texel an edge tap stands for (include/mirhi.h "The sampler", seamless cubes): tap (i, j) of `face` at a level of n x n texels, exactly
+    one of i, j outside [0, n - 1].  By projection, with no table of neighbours: the face plane is extended to the tap's centre ((i + 1/2) / n,
+    (j + 1/2) / n), that point's direction (GetCubemapDirection's table with |u| or |v| > 1) goes through the face selection, and the texel is
+    (floor(s' n), floor(t' n)) clamped to [0, n - 1].  Always in float64, whatever the dtype of the lookup: s' n stays 1 / (n + 1) away from an
+    integer, which float64 resolves for every n up to 4096 and float32 would not -- and a float32 run of the model has to read the same texels.
+    Returns (face', i', j')."""
+    i = np.asarray(i, dtype=np.int64)
+    j = np.asarray(j, dtype=np.int64)
+    uv = np.stack([(i.astype(np.float64) + 0.5) / float(n), (j.astype(np.float64) + 0.5) / float(n)], axis=-1)
+    f2, s2, t2 = select_face(cube_direction(face, uv, np.float64), np.float64)
+    i2 = np.clip(np.floor(s2 * float(n)).astype(np.int64), 0, n - 1)
+    j2 = np.clip(np.floor(t2 * float(n)).astype(np.int64), 0, n - 1)
+    return f2, i2, j2
+
+
+def seamless_taps(n: int, face, s, t, dtype=np.float64):
+    """The four taps of a seamless lookup: texel indices into the flattened level [6 n n] (order (i0, j0), (i0 + 1, j0), (i0, j0 + 1),
+    (i0 + 1, j0 + 1)), a bool per tap "corner tap" (both indices outside: no texel, index of the clamped texel as a placeholder), a bool per tap
+    "edge tap", and the fractions fx, fy."""
+    T = np.dtype(dtype).type
+    x = np.asarray(s * T(n) - T(0.5))
+    y = np.asarray(t * T(n) - T(0.5))
+    face = np.broadcast_to(np.asarray(face), x.shape)
+    x0 = np.floor(x)
+    y0 = np.floor(y)
+    fx = x - x0
+    fy = y - y0
+    i0 = x0.astype(np.int64)
+    j0 = y0.astype(np.int64)
+    idx, corner, edge = [], [], []
+    for dj in (0, 1):
+        for di in (0, 1):
+            i, j = i0 + di, j0 + dj
+            ox = (i < 0) | (i > n - 1)
+            oy = (j < 0) | (j > n - 1)
+            ic, jc = np.clip(i, 0, n - 1), np.clip(j, 0, n - 1)
+            is_edge = ox ^ oy
+            # (an in-face tap is its texel; a corner tap gets the clamped texel as a placeholder and is replaced by the mean of the other three)
+            k = np.array((face * n + jc) * n + ic, dtype=np.int64)
+            if is_edge.any():
+                f2, i2, j2 = edge_neighbour(n, face[is_edge], i[is_edge], j[is_edge])
+                k[is_edge] = (f2 * n + j2) * n + i2
+            idx.append(k)
+            corner.append(ox & oy)
+            edge.append(is_edge)
+    return idx, corner, edge, fx, fy
+
+
+def _bilinear_face_seamless(level, face, s, t, dtype):
+    """Bilinear across faces (seamless_taps): the four unclamped taps, a corner tap = the mean of the other three ((a + b + c) / 3 in tap
+    order), weighted by the fractions exactly as _bilinear_face does."""
+    T = np.dtype(dtype).type
+    n = level.shape[1]
+    flat = level.reshape(-1, level.shape[-1])
+    idx, corner, _, fx, fy = seamless_taps(n, face, s, t, dtype)
+    v = [flat[k] for k in idx]
+    for c in range(4):
+        o = [v[k] for k in range(4) if k != c]
+        v[c] = np.where(corner[c][..., None], ((o[0] + o[1]) + o[2]) / T(3.0), v[c])
+    fx, fy = fx[..., None], fy[..., None]
+    one = T(1.0)
+    top = v[0] * (one - fx) + v[1] * fx
+    bot = v[2] * (one - fx) + v[3] * fx
+    return top * (one - fy) + bot * fy
+
+
+def sample_cube(levels, d, lod=0.0, dtype=np.float64, seamless=False):
     """TextureCube.SampleLevel(LinearSampler, d, lod): lod clamped to [0, levels - 1], the levels floor(lod) and floor(lod) + 1
-    (clamped) each filtered bilinearly in the selected face and lerped by the fraction."""
+    (clamped) each filtered bilinearly in the selected face and lerped by the fraction.  seamless: the cube's seamless state
+    (mirhi_image_set_cube_seamless) -- each level is filtered across face edges and corners instead (_bilinear_face_seamless); level
+    selection and the lerp between levels are the same."""
     T = np.dtype(dtype).type
     levels = [np.asarray(l, dtype=dtype) for l in levels]
     d = np.asarray(d, dtype=dtype)
     face, s, t = select_face(d, dtype)
+    bilinear = _bilinear_face_seamless if seamless else _bilinear_face
     if len(levels) == 1:                     # lod clamps to 0: the one level, weight exactly 1
-        return _bilinear_face(levels[0], face, s, t, dtype)
+        return bilinear(levels[0], face, s, t, dtype)
     lod = np.clip(np.broadcast_to(np.asarray(lod, dtype=dtype), s.shape), T(0.0), T(len(levels) - 1))
     l0 = np.floor(lod)
     f = (lod - l0)[..., None]
@@ -147,7 +217,7 @@ def sample_cube(levels, d, lod=0.0, dtype=np.float64):
         need = use0 | use1
         if not need.any():
             continue
-        c = _bilinear_face(levels[k], face[need], s[need], t[need], dtype)
+        c = bilinear(levels[k], face[need], s[need], t[need], dtype)
         w = np.where(use0[need][..., None], T(1.0) - f[need], T(0.0)) + np.where((l1 == k)[need][..., None], f[need], T(0.0))
         # (l0 == l1 at the last level: the two weights add up to 1 there, as lerp(a, a, f) does up to rounding)
         out[need] += c * w
@@ -235,8 +305,8 @@ def _serial_add(acc, terms):
     return np.cumsum(np.concatenate([acc[:, None], terms], axis=1), axis=1)[:, -1]
 
 
-def irradiance(env_levels, size: int, dtype=np.float64):
-    """irradiance_map.hlsl:63-143: [6, size, size, 4] = (rgb, 1); lookups at level 0 of env."""
+def irradiance(env_levels, size: int, dtype=np.float64, seamless=False):
+    """irradiance_map.hlsl:63-143: [6, size, size, 4] = (rgb, 1); lookups at level 0 of env (seamless: env's seamless state)."""
     T = np.dtype(dtype).type
     env0 = [np.asarray(env_levels[0], dtype=dtype)[..., :3]]
     N = texel_directions(size, dtype).reshape(-1, 3)
@@ -251,7 +321,7 @@ def irradiance(env_levels, size: int, dtype=np.float64):
         tx = sin_t * np.cos(phi)
         ty = sin_t * np.sin(phi)
         vec = tx[None, :, None] * right[:, None, :] + ty[None, :, None] * up[:, None, :] + cos_t[None, :, None] * N[:, None, :]
-        col = sample_cube(env0, vec, 0.0, dtype)
+        col = sample_cube(env0, vec, 0.0, dtype, seamless)
         acc = _serial_add(acc, col * cos_t[None, :, None] * sin_t[None, :, None])
     count = T(len(phis) * len(thetas))
     out = np.ones((N.shape[0], 4), dtype=dtype)
@@ -290,12 +360,12 @@ def importance_sample_ggx(xi_x, xi_y, N, roughness, dtype=np.float64):
     return _normalize(vec)
 
 
-def _prefilter_level(env_rgb, m: int, roughness, sample_count: int, dtype):
+def _prefilter_level(env_rgb, m: int, roughness, sample_count: int, dtype, seamless=False):
     T = np.dtype(dtype).type
     R = texel_directions(m, dtype).reshape(-1, 3)
     out = np.ones((R.shape[0], 4), dtype=dtype)
     if roughness < T(0.01):                                # prefilter_map.hlsl:168-173
-        out[:, :3] = sample_cube(env_rgb, R, 0.0, dtype)
+        out[:, :3] = sample_cube(env_rgb, R, 0.0, dtype, seamless)
         return out.reshape(6, m, m, 4)
     xs, ys = hammersley(sample_count, dtype)
     acc = np.zeros((R.shape[0], 3), dtype=dtype)
@@ -320,7 +390,7 @@ def _prefilter_level(env_rgb, m: int, roughness, sample_count: int, dtype):
             mip = np.maximum(T(0.0), T(0.5) * np.log2(sa_sample / sa_texel))
         keep = ndl > 0
         mip = np.where(keep, mip, T(0.0))
-        col = sample_cube(env_rgb, L, mip, dtype)
+        col = sample_cube(env_rgb, L, mip, dtype, seamless)
         w = np.where(keep, ndl, T(0.0))
         acc = _serial_add(acc, col * w[..., None])
         wsum = _serial_add(wsum, w)
@@ -329,15 +399,15 @@ def _prefilter_level(env_rgb, m: int, roughness, sample_count: int, dtype):
     return out.reshape(6, m, m, 4)
 
 
-def prefilter(env_levels, size: int, levels: int, sample_count: int = 1024, dtype=np.float64):
+def prefilter(env_levels, size: int, levels: int, sample_count: int = 1024, dtype=np.float64, seamless=False):
     """prefilter_map.hlsl:134-229 run once per level: MipSize = size >> l, Roughness = l / (levels - 1) (0 for one level); the
-    lookups use the whole chain of env (trilinear at mipLevel).  Returns the list of levels, each (rgb, 1)."""
+    lookups use the whole chain of env (trilinear at mipLevel; seamless: env's seamless state).  Returns the list of levels, each (rgb, 1)."""
     T = np.dtype(dtype).type
     env_rgb = [np.asarray(l, dtype=dtype)[..., :3] for l in env_levels]
     out = []
     for l in range(levels):
         rough = T(l) / T(levels - 1) if levels > 1 else T(0.0)
-        out.append(_prefilter_level(env_rgb, size >> l, rough, sample_count, dtype))
+        out.append(_prefilter_level(env_rgb, size >> l, rough, sample_count, dtype, seamless))
     return out
 
 
@@ -408,10 +478,11 @@ def reflect(V, N):
     return np.asarray(2.0, dtype=N.dtype) * _dot(N, V)[..., None] * N - V
 
 
-def ambient(irradiance_levels, prefiltered_levels, lut, N, V, albedo, metallic, roughness, ao, dtype=np.float64):
+def ambient(irradiance_levels, prefiltered_levels, lut, N, V, albedo, metallic, roughness, ao, dtype=np.float64, irradiance_seamless=False, prefiltered_seamless=False):
     """model_pbr_ibl.hlsl:355-384: (kD * irradiance * albedo + prefiltered * (F0 * brdf.x + brdf.y)) * ao for unit vectors N, V [..., 3],
     albedo [..., 3] and metallic, roughness, ao [...]; `roughness` is the material's, ClampRoughness (:262) is applied here.  The cubes
-    are lists of levels [6, n, n, C >= 3] (level 0 of the irradiance cube is the one sampled), lut [n, n, C >= 2]."""
+    are lists of levels [6, n, n, C >= 3] (level 0 of the irradiance cube is the one sampled), lut [n, n, C >= 2].  Each cube carries its
+    own seamless state (mirhi_cmd_bind_ibl latches both); the LUT is 2-D and has none."""
     T = np.dtype(dtype).type
     N, V, albedo = (np.asarray(a, dtype=dtype) for a in (N, V, albedo))
     metallic, ao = (np.broadcast_to(np.asarray(a, dtype=dtype), N.shape[:-1]) for a in (metallic, ao))
@@ -420,8 +491,8 @@ def ambient(irradiance_levels, prefiltered_levels, lut, N, V, albedo, metallic, 
     ndv = np.maximum(_dot(N, V), T(0.0))                                                        # :359
     F = fresnel_schlick_roughness(ndv, F0, rough, dtype)                                        # :362
     kD = (T(1.0) - F) * (T(1.0) - metallic)[..., None]                                          # :365-366
-    irr = sample_cube([np.asarray(irradiance_levels[0], dtype=dtype)[..., :3]], N, 0.0, dtype)  # :369
-    pre = sample_cube([np.asarray(l, dtype=dtype)[..., :3] for l in prefiltered_levels], reflect(V, N), rough * T(MAX_REFLECTION_LOD), dtype)   # :373-377
+    irr = sample_cube([np.asarray(irradiance_levels[0], dtype=dtype)[..., :3]], N, 0.0, dtype, irradiance_seamless)  # :369
+    pre = sample_cube([np.asarray(l, dtype=dtype)[..., :3] for l in prefiltered_levels], reflect(V, N), rough * T(MAX_REFLECTION_LOD), dtype, prefiltered_seamless)   # :373-377
     brdf = sample_lut(np.asarray(lut, dtype=dtype)[..., :2], ndv, rough, dtype)                 # :380
     spec = pre * (F0 * brdf[..., 0:1] + brdf[..., 1:2])                                         # :381
     return (kD * (irr * albedo) + spec) * ao[..., None]                                         # :370, :384
@@ -464,9 +535,9 @@ def skybox_directions(inv_view_proj, viewport, width: int, height: int, dtype=np
     return _normalize(skybox_local_pos(inv_view_proj, viewport, width, height, dtype)).astype(dtype)
 
 
-def skybox(levels, inv_view_proj, viewport, width: int, height: int, dtype=np.float64):
+def skybox(levels, inv_view_proj, viewport, width: int, height: int, dtype=np.float64, seamless=False):
     """The sky frame [height, width, 4]: the cube lookup at lod 0 along skybox_directions (the stated deviation: `Sample` without derivatives)."""
-    return sample_cube(levels[:1], skybox_directions(inv_view_proj, viewport, width, height, dtype), 0.0, dtype)
+    return sample_cube(levels[:1], skybox_directions(inv_view_proj, viewport, width, height, dtype), 0.0, dtype, seamless)
 
 
 def skybox_coverage(viewport, scissor, width: int, height: int, cull_mode: int = 0, front_face: int = 0):

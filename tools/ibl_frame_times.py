@@ -2,7 +2,9 @@
 """Per-dispatch device times (mirhi_device_timeline, the method of tools/shadow_times.py) of the lit scope of cascaded_ground_case at
 1920 x 1080 under MODEL_PBR and under MODEL_PBR_IBL (raster_kernel_ibl; irradiance 32^2, prefiltered 128^2 x 8, LUT 512^2 made by the precompute
 passes), each with the shadow term none / a single 2048^2 map / four 2048^2 cascades.  Prints one JSON object (median microseconds per dispatch
-over the timed repeats) with the build id."""
+over the timed repeats) with the build id.  "seamless": the MODEL_PBR_IBL lit scope per shadow term with both cubes' seamless state off and on
+(mirhi_image_set_cube_seamless, raster_kernel_ibl against raster_kernel_ibl_seamless), three rounds interleaved in this one process, the lit scope's raster
+medians of each round and the ratio of their means."""
 import dataclasses
 import json
 import os
@@ -39,6 +41,20 @@ def main():
             t = st.per_kernel(st.timed(dev, res.render), n_scopes=n_scopes)
             res.destroy()
             out[f"{prog_name}_{shadow}"] = {k: v for k, v in t.items() if n_scopes == 1 or k.endswith(f"[{n_scopes - 1}]")}
+    rounds = {shadow: {"clamped": [], "seamless": []} for shadow in ("none", "single_map", "cascades")}
+    for _ in range(3):
+        for state, on in (("clamped", False), ("seamless", True)):
+            irr.set_cube_seamless(on); pre.set_cube_seamless(on)      # (latched when SceneResources records)
+            for shadow, sc, n_scopes in (("none", plain, 1), ("single_map", single, 2), ("cascades", scene, 5)):
+                sc2 = dataclasses.replace(sc, draws=[dataclasses.replace(d, program=S.PROGRAM_MODEL_PBR_IBL) if d.program == S.PROGRAM_MODEL_PBR else d for d in sc.draws])
+                res = m.SceneResources(dev, sc2, m.Format.B8G8R8A8_SRGB, ibl_images=(irr, pre, lut))
+                t = st.per_kernel(st.timed(dev, res.render), n_scopes=n_scopes)
+                res.destroy()
+                rounds[shadow][state].append(t.get("raster", t.get(f"raster[{n_scopes - 1}]")))
+    irr.set_cube_seamless(False); pre.set_cube_seamless(False)
+    for r in rounds.values():
+        r["ratio"] = round(sum(r["seamless"]) / sum(r["clamped"]), 3)
+    out["seamless"] = rounds
     for im in (src, env, irr, pre, lut):
         im.destroy()
     dev.destroy()

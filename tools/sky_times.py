@@ -2,7 +2,9 @@
 """Per-dispatch device times (mirhi_device_timeline, the method of tools/shadow_times.py) of the SKYBOX segment (sky_kernel) at 1920 x 1080 on
 B8G8R8A8_SRGB, environment 512^2 x 1: the sky alone (CLEAR), the sky behind cascaded_ground_case WITHOUT its four cascade scopes (shadow term 1) under MODEL_PBR_IBL
 (LESS_OR_EQUAL, no write: it reads the lit segment's depth), and the same lit scope without the sky.  Prints one JSON object: median microseconds
-per dispatch over the timed repeats, in dispatch order, with the build id."""
+per dispatch over the timed repeats, in dispatch order, with the build id.  "seamless": the sky alone and the sky behind the lit scope with the environment's
+seamless state off and on (mirhi_image_set_cube_seamless, sky_kernel against sky_kernel_seamless), three rounds interleaved in this one process, the raster
+medians of each round and the ratio of their means."""
 import dataclasses
 import json
 import os
@@ -36,6 +38,19 @@ def main():
         res = m.SceneResources(dev, scene, m.Format.B8G8R8A8_SRGB, ibl_images=(irr, pre, lut), want_depth=(name != "sky_alone"))
         out[name] = st.per_kernel(st.timed(dev, res.render), n_scopes=n)
         res.destroy()
+    rounds = {"sky_alone": {"clamped": [], "seamless": []}, "lit_with_sky": {"clamped": [], "seamless": []}}
+    for _ in range(3):
+        for state, on in (("clamped", False), ("seamless", True)):
+            env.set_cube_seamless(on)      # (latched when SceneResources records)
+            for name, scene, n in (("sky_alone", sky_alone, 1), ("lit_with_sky", dataclasses.replace(lit, sky=spec), 2)):
+                res = m.SceneResources(dev, scene, m.Format.B8G8R8A8_SRGB, ibl_images=(irr, pre, lut), want_depth=(name != "sky_alone"))
+                t = st.per_kernel(st.timed(dev, res.render), n_scopes=n)
+                res.destroy()
+                rounds[name][state].append(t.get("raster", t.get(f"raster[{n - 1}]")))
+    env.set_cube_seamless(False)
+    for name, r in rounds.items():
+        r["ratio"] = round(sum(r["seamless"]) / sum(r["clamped"]), 3)
+    out["seamless"] = rounds
     for im in (env, irr, pre, lut):
         im.destroy()
     dev.destroy()
