@@ -53,6 +53,10 @@ impl Image {
     pub const DEFAULT_PREFILTER_SAMPLES: u32 = 1024;
     /// equirect_to_cubemap.hlsl: level 0 of this cube from a 2-D equirectangular image.
     pub fn ibl_equirect_to_cube(&self, src2d: &Image) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_ibl_equirect_to_cube(src2d.raw, self.raw) }) }
+    /// The same pass from a 2-D R8G8B8A8_UNORM image holding Radiance RGBE bytes (R, G, B, E): each tap is decoded before the blend.
+    pub fn ibl_equirect_to_cube_rgbe(&self, rgbe8: &Image) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_ibl_equirect_to_cube_rgbe(rgbe8.raw, self.raw) }) }
+    /// This 2-D R32G32B32A32_SFLOAT image receives the exact float texels of the RGBE image of the same extent.
+    pub fn expand_rgbe(&self, rgbe8: &Image) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_image_expand_rgbe(rgbe8.raw, self.raw) }) }
     /// Levels 1.. of this cube from its level 0 (2 x 2 box filter per face).
     pub fn ibl_cube_generate_mips(&self) -> RhiResult<()> { check(unsafe { mirhi_sys::mirhi_ibl_cube_generate_mips(self.raw) }) }
     /// irradiance_map.hlsl: level 0 of this cube from the environment cube.

@@ -43,7 +43,8 @@ extern "C" {
                                     mirhi_image_samples, mirhi_resolve_mode, mirhi_resolve_info, mirhi_cmd_begin_rendering_resolve;
                                     still 5 (two new functions and one struct only): mirhi_multiview_info, mirhi_multiview_info_default,
                                     mirhi_cmd_begin_rendering_multiview;
-                                    still 5 (two new functions only): mirhi_image_set_cube_seamless, mirhi_image_cube_seamless */
+                                    still 5 (two new functions only): mirhi_image_set_cube_seamless, mirhi_image_cube_seamless;
+                                    still 5 (new functions only): mirhi_image_expand_rgbe, mirhi_ibl_equirect_to_cube_rgbe */
 
 /* ---- errors: one code per RhiError variant (crates/rhi/src/error.rs:6-50) ------------------------ */
 typedef int32_t mirhi_result;
@@ -274,6 +275,17 @@ mirhi_result mirhi_image_set_cube_seamless(mirhi_image* cube, uint32_t enable);
 uint32_t     mirhi_image_cube_seamless(const mirhi_image* img);
 /* equirect_to_cubemap.hlsl:78-105: level 0 of `cube`, all four channels, from the 2-D image `src2d` (DirectionToEquirectUV :59-75) */
 mirhi_result mirhi_ibl_equirect_to_cube(mirhi_image* src2d, mirhi_image* cube);
+/* Radiance RGBE sources.  An RGBE image on the device is an ordinary 2-D R8G8B8A8_UNORM image whose four bytes are (R, G, B, E) -- what
+ * mires_hdr_decode (include/miresources.h) yields, made with mirhi_image_create and filled with mirhi_image_upload: no new format, no new upload path, a
+ * quarter of the float form's bytes.  Both calls are immediate passes like the others; an `rgbe8` with a mip chain is accepted and its level 0 is read.
+ * InvalidHandle: an rgbe8 that is a cube, an array, a layer view or multisampled ("the RGBE source must be a 2-D image"), of any other format
+ * (R8G8B8A8_SRGB included: the bytes are no colours), a destination of another extent, images of two devices.
+ * level 0 of the 2-D R8G8B8A8_UNORM image `rgbe8`, read as Radiance RGBE, into the 2-D R32G32B32A32_SFLOAT image `dst` of the same extent:
+ * E = 0 -> (0,0,0,1), else (R,G,B) * 2^(E-136), alpha 1.  Exact. */
+mirhi_result mirhi_image_expand_rgbe(mirhi_image* rgbe8, mirhi_image* dst);
+/* mirhi_ibl_equirect_to_cube with an RGBE source: level 0 of `cube` from `rgbe8`, each of the four taps decoded as above before the
+ * bilinear blend; the same uv, wrap (u repeats, v clamps) and blend as the float path. */
+mirhi_result mirhi_ibl_equirect_to_cube_rgbe(mirhi_image* rgbe8, mirhi_image* cube);
 /* Levels 1.. of a cube from its level 0, face by face with a 2 x 2 box filter in float, ((a + b) + (c + d)) * 0.25 (exact operations in this
  * order).  The build's own definition: the reference never builds the chain that prefilter_map.hlsl:212 samples. */
 mirhi_result mirhi_ibl_cube_generate_mips(mirhi_image* cube);

@@ -293,6 +293,8 @@ _SIGNATURES = {
     "mirhi_image_samples": (C.c_uint32, [C.c_void_p]),
     "mirhi_image_create_cube": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mirhi_ibl_equirect_to_cube": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mirhi_image_expand_rgbe": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mirhi_ibl_equirect_to_cube_rgbe": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_ibl_cube_generate_mips": (C.c_int32, [C.c_void_p]),
     "mirhi_ibl_irradiance": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "mirhi_ibl_prefilter": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -645,6 +647,25 @@ class Image:
     def ibl_equirect_to_cube(self, src2d: "Image"):
         """equirect_to_cubemap.hlsl: level 0 of this cube from the 2-D equirectangular image."""
         check(lib().mirhi_ibl_equirect_to_cube(src2d.handle, self.handle))
+
+    def ibl_equirect_to_cube_rgbe(self, rgbe8: "Image"):
+        """mirhi_ibl_equirect_to_cube_rgbe: level 0 of this cube from a 2-D R8G8B8A8_UNORM image holding Radiance RGBE bytes (Image.from_hdr)."""
+        check(lib().mirhi_ibl_equirect_to_cube_rgbe(rgbe8.handle, self.handle))
+
+    def expand_rgbe(self, rgbe8: "Image"):
+        """mirhi_image_expand_rgbe: this 2-D R32G32B32A32_SFLOAT image receives the exact float texels of the RGBE image of the same extent."""
+        check(lib().mirhi_image_expand_rgbe(rgbe8.handle, self.handle))
+
+    @classmethod
+    def from_hdr(cls, device: Device, hdr) -> "Image":
+        """The R8G8B8A8_UNORM image of an images.HdrImage's RGBE bytes (images.decode_hdr / load_hdr), uploaded."""
+        img = cls(device, hdr.width, hdr.height, Format.R8G8B8A8_UNORM)
+        try:
+            img.upload(np.ascontiguousarray(hdr.rgbe, dtype=np.uint8))
+        except Exception:
+            img.destroy()
+            raise
+        return img
 
     def ibl_cube_generate_mips(self):
         check(lib().mirhi_ibl_cube_generate_mips(self.handle))
@@ -1493,3 +1514,37 @@ class SceneResources:
             if o is not None and owned:
                 o.destroy()
         self.objs = []
+
+
+def load_environment(device: Device, path_or_bytes, env_size: int, irradiance_size: int = 32, prefiltered_size: int = 128, prefilter_samples: int = 1024,
+                     lut_size: int = 512, seamless: bool = False):
+    """A Radiance .hdr file (a path, or the file's bytes) to the images of an IBL set: host decode (images.load_hdr / decode_hdr), upload of the RGBE
+    bytes, ibl_equirect_to_cube_rgbe, the cube's mip chain, irradiance, prefilter and the BRDF LUT.  Returns (environment, irradiance, prefiltered,
+    brdf_lut): the environment cube (env_size, full chain; what bind_skybox takes) and the three images of bind_ibl.  The defaults are the reference's
+    sizes (irradiance 32, prefiltered 128 with its full chain and 1024 samples, LUT 512).  seamless=True sets set_cube_seamless on the three cubes before
+    the passes that read them run.  The caller destroys the four images."""
+    from . import images
+    hdr = images.decode_hdr(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else images.load_hdr(os.fspath(path_or_bytes))
+    made = []
+    try:
+        src = Image.from_hdr(device, hdr)
+        made.append(src)
+        env = Image.create_cube(device, env_size, int(env_size).bit_length(), seamless=seamless)
+        made.append(env)
+        irr = Image.create_cube(device, irradiance_size, 1, seamless=seamless)
+        made.append(irr)
+        pre = Image.create_cube(device, prefiltered_size, int(prefiltered_size).bit_length(), seamless=seamless)
+        made.append(pre)
+        lut = Image(device, lut_size, lut_size, Format.R32G32B32A32_SFLOAT)
+        made.append(lut)
+        env.ibl_equirect_to_cube_rgbe(src)
+        env.ibl_cube_generate_mips()
+        irr.ibl_irradiance(env)
+        pre.ibl_prefilter(env, prefilter_samples)
+        lut.ibl_brdf_lut()
+    except Exception:
+        for img in made:
+            img.destroy()
+        raise
+    src.destroy()
+    return env, irr, pre, lut

@@ -1304,6 +1304,36 @@ extern "C" mirhi_result mirhi_ibl_equirect_to_cube(mirhi_image* src2d, mirhi_ima
     hipLaunchKernelGGL(ibl_equirect_kernel, dim3((texels + 255u) / 256u), dim3(256), 0, dev->stream, (const float4*)src2d->ptr, src2d->width, src2d->height, (float4*)cube->ptr, n);
     return ibl_end(dev);
 }
+// a Radiance RGBE source: an ordinary 2-D R8G8B8A8_UNORM image whose bytes are (R, G, B, E); with a mip chain, level 0 is read
+static mirhi_result rgbe_source_arg(const mirhi_image* img) {
+    if (!img) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the RGBE source is null");
+    if (img->samples != 1u || img->is_cube || img->is_array || img->parent) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the RGBE source must be a 2-D image");
+    if (img->format != MIRHI_FORMAT_R8G8B8A8_UNORM)      // (R8G8B8A8_SRGB too: the bytes are no colours)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the RGBE source must be R8G8B8A8_UNORM (format %d)", (int)img->format);
+    return MIRHI_OK;
+}
+extern "C" mirhi_result mirhi_image_expand_rgbe(mirhi_image* rgbe8, mirhi_image* dst) {
+    { mirhi_result r = rgbe_source_arg(rgbe8); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_2d_arg(dst, "the destination"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_pair(rgbe8, dst); if (r != MIRHI_OK) return r; }
+    if (dst->width != rgbe8->width || dst->height != rgbe8->height)
+        return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the destination must have the source's extent (%ux%u, got %ux%u)", rgbe8->width, rgbe8->height, dst->width, dst->height);
+    mirhi_device* dev = dst->dev;
+    { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
+    const uint32_t texels = dst->width * dst->height;          // (at most 16384^2 = 2^28)
+    hipLaunchKernelGGL(rgbe_expand_kernel, dim3((texels + RGBE_EXPAND_PER_BLOCK - 1u) / RGBE_EXPAND_PER_BLOCK), dim3(256), 0, dev->stream, (const uint32_t*)rgbe8->ptr, (float4*)dst->ptr, texels);
+    return ibl_end(dev);
+}
+extern "C" mirhi_result mirhi_ibl_equirect_to_cube_rgbe(mirhi_image* rgbe8, mirhi_image* cube) {
+    { mirhi_result r = rgbe_source_arg(rgbe8); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_cube_arg(cube, "the destination"); if (r != MIRHI_OK) return r; }
+    { mirhi_result r = ibl_pair(rgbe8, cube); if (r != MIRHI_OK) return r; }
+    mirhi_device* dev = cube->dev;
+    { mirhi_result r = ibl_begin(dev); if (r != MIRHI_OK) return r; }
+    const uint32_t n = cube->width, texels = 6u * n * n;
+    hipLaunchKernelGGL(ibl_equirect_rgbe_kernel, dim3((texels + 255u) / 256u), dim3(256), 0, dev->stream, (const uint32_t*)rgbe8->ptr, rgbe8->width, rgbe8->height, (float4*)cube->ptr, n);
+    return ibl_end(dev);
+}
 extern "C" mirhi_result mirhi_ibl_cube_generate_mips(mirhi_image* cube) {
     { mirhi_result r = ibl_cube_arg(cube, "the image"); if (r != MIRHI_OK) return r; }
     mirhi_device* dev = cube->dev;

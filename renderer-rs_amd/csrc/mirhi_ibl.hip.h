@@ -50,10 +50,11 @@ __device__ inline float ibl_lane_sum(float v, uint32_t width) {
 }
 
 // ---- equirect_to_cubemap.hlsl:78-105: one thread per texel of level 0 --------------------------------------------------------------------
-__global__ void __launch_bounds__(256) ibl_equirect_kernel(const float4* __restrict__ src, uint32_t sw, uint32_t sh, float4* __restrict__ cube, uint32_t n) {
+// Everything of a texel but its four fetches: the direction, DirectionToEquirectUV, the tap indices and the blend weights.  Shared by the float
+// source (ibl_equirect_kernel) and the RGBE source (ibl_equirect_rgbe_kernel), which differ in how a tap is fetched and in nothing else.
+struct IblEquirectTaps { uint32_t i00, i01, i10, i11; float fx, fy; };      // texel indices of (j0, i0), (j0, i1), (j1, i0), (j1, i1); x - x0, y - y0
+__device__ __forceinline__ IblEquirectTaps ibl_equirect_taps(uint32_t t, uint32_t n, uint32_t sw, uint32_t sh) {
     #pragma clang fp contract(fast)
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= 6u * n * n) return;
     const uint32_t face = t / (n * n), py = (t / n) % n, px = t % n;
     const float3 d = ibl_texel_direction(face, px, py, n);
     const float phi = atan2f(d.z, d.x), theta = asinf(fminf(fmaxf(d.y, -1.0f), 1.0f));        // DirectionToEquirectUV :59-75
@@ -65,9 +66,57 @@ __global__ void __launch_bounds__(256) ibl_equirect_kernel(const float4* __restr
     i0 = min(max(i0, 0), (int)sw - 1);
     const int i1 = i0 + 1 == (int)sw ? 0 : i0 + 1;
     const int j0 = min(max((int)y0, 0), (int)sh - 1), j1 = min(max((int)y0 + 1, 0), (int)sh - 1);
-    const float4 a = src[(uint32_t)j0 * sw + (uint32_t)i0], b = src[(uint32_t)j0 * sw + (uint32_t)i1];
-    const float4 c = src[(uint32_t)j1 * sw + (uint32_t)i0], e = src[(uint32_t)j1 * sw + (uint32_t)i1];
-    cube[t] = ibl_lerp4(ibl_lerp4(a, b, x - x0), ibl_lerp4(c, e, x - x0), y - y0);
+    return IblEquirectTaps{(uint32_t)j0 * sw + (uint32_t)i0, (uint32_t)j0 * sw + (uint32_t)i1, (uint32_t)j1 * sw + (uint32_t)i0, (uint32_t)j1 * sw + (uint32_t)i1,
+                           x - x0, y - y0};
+}
+__global__ void __launch_bounds__(256) ibl_equirect_kernel(const float4* __restrict__ src, uint32_t sw, uint32_t sh, float4* __restrict__ cube, uint32_t n) {
+    #pragma clang fp contract(fast)
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= 6u * n * n) return;
+    const IblEquirectTaps k = ibl_equirect_taps(t, n, sw, sh);
+    const float4 a = src[k.i00], b = src[k.i01];
+    const float4 c = src[k.i10], e = src[k.i11];
+    cube[t] = ibl_lerp4(ibl_lerp4(a, b, k.fx), ibl_lerp4(c, e, k.fx), k.fy);
+}
+
+// ---- Radiance RGBE texels: an R8G8B8A8_UNORM image whose four bytes are (R, G, B, E), read as little-endian words ----------------
+// m * 2^(E - 136), built from integer operations alone, so that the result does not depend on the wave's denormal mode: with p the position of m's
+// top bit the value is 1.xxx * 2^(p + E - 136), biased exponent p + E - 9; below 1 the result is a denormal whose bits are m * 2^(E - 136) / 2^-149
+// = m << (E + 13).  Exact for all 2^16 (m, E) pairs: m has 8 significant bits, the largest value is 255 * 2^119, the smallest 2^-135.
+__device__ __forceinline__ float rgbe_channel(uint32_t m, uint32_t e) {
+    if (m == 0u) return 0.0f;
+    const uint32_t p = 31u - (uint32_t)__clz((int)m);
+    const int be = (int)(p + e) - 9;
+    const uint32_t bits = be >= 1 ? ((uint32_t)(be - 1) << 23) + (m << (23u - p))      // (m's top bit lands on bit 23 and carries into the exponent)
+                                  : m << (e + 13u);
+    return __uint_as_float(bits);
+}
+__device__ __forceinline__ float4 rgbe_decode(uint32_t w) {
+    const uint32_t e = w >> 24;
+    if (e == 0u) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    return make_float4(rgbe_channel(w & 0xFFu, e), rgbe_channel((w >> 8) & 0xFFu, e), rgbe_channel((w >> 16) & 0xFFu, e), 1.0f);
+}
+// mirhi_image_expand_rgbe: a pure stream, 4 bytes in and 16 bytes out per texel.  A lane works on one texel at a time, so that a wave's accesses are
+// whole lines (256 B loaded, 1 KiB stored per instruction: the stores are four fifths of the traffic and are as wide as a lane's store gets), and on
+// four texels 256 apart, whose loads are issued together before the first store.
+#define RGBE_EXPAND_PER_BLOCK 1024u
+__global__ void __launch_bounds__(256) rgbe_expand_kernel(const uint32_t* __restrict__ src, float4* __restrict__ dst, uint32_t texels) {
+    const uint32_t base = blockIdx.x * RGBE_EXPAND_PER_BLOCK + threadIdx.x;
+    uint32_t w[4];
+    #pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) { const uint32_t t = base + k * 256u; w[k] = t < texels ? src[t] : 0u; }
+    #pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) { const uint32_t t = base + k * 256u; if (t < texels) dst[t] = rgbe_decode(w[k]); }
+}
+// mirhi_ibl_equirect_to_cube_rgbe: ibl_equirect_kernel with each of the four taps decoded from its RGBE word before the blend
+__global__ void __launch_bounds__(256) ibl_equirect_rgbe_kernel(const uint32_t* __restrict__ src, uint32_t sw, uint32_t sh, float4* __restrict__ cube, uint32_t n) {
+    #pragma clang fp contract(fast)
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= 6u * n * n) return;
+    const IblEquirectTaps k = ibl_equirect_taps(t, n, sw, sh);
+    const float4 a = rgbe_decode(src[k.i00]), b = rgbe_decode(src[k.i01]);
+    const float4 c = rgbe_decode(src[k.i10]), e = rgbe_decode(src[k.i11]);
+    cube[t] = ibl_lerp4(ibl_lerp4(a, b, k.fx), ibl_lerp4(c, e, k.fx), k.fy);
 }
 
 // ---- cube mip chain: one thread per texel of the destination level, 2 x 2 box filter per face, ((a + b) + (c + d)) * 0.25 (bit-exact) --------

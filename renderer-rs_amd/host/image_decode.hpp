@@ -16,12 +16,17 @@
 //                in tests/test_image_decode_cpu.py).  Arithmetic coding, lossless / hierarchical modes, 12-bit and CMYK
 //                files are refused with a message, never decoded approximately.
 //
+//   decode_hdr   Radiance .hdr (RGBE, flat / old-style / new-style RLE scanlines) -> RGBE8 rows and hdr_to_float (further down;
+//                DESIGN.md 8p).  Not part of decode_image's sniffing: its texels are no RGBA8 colours.
+//
 // Header-only, no dependency (own inflate).  Errors throw ImageError; nothing here touches the GPU.
 #ifndef MIRHI_IMAGE_DECODE_HPP
 #define MIRHI_IMAGE_DECODE_HPP
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <stdexcept>
@@ -835,6 +840,177 @@ inline ImageData load_image(const std::string& path) {
     std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     try { return decode_image(bytes.data(), bytes.size()); }
     catch (const ImageError& e) { throw ImageError(path + ": " + e.what()); }
+}
+
+// ------------------------------------------------------------------ Radiance .hdr -> RGBE8 rows
+// What the reference's IBL starts from (assets/environments/*.hdr through the `image` crate's `hdr` feature), read as that crate's
+// decoder reads it in its non-strict mode.  The texels stay in the file's own form, 4 bytes (R, G, B, E): that is what
+// mirhi_image_upload takes into an R8G8B8A8_UNORM image and what mirhi_image_expand_rgbe / mirhi_ibl_equirect_to_cube_rgbe read on
+// the device.  decode_image() does not sniff this format: an .hdr file is no RGBA8 texture.
+struct HdrData {
+    uint32_t width = 0, height = 0;
+    float exposure = 1.0f;              // the product of the header's EXPOSURE= lines: reported, never applied to the texels
+    std::vector<uint8_t> rgbe;          // width*height*4 (R, G, B, E), row-major, top row first
+};
+
+namespace detail {
+struct HdrReader {
+    const uint8_t* p; size_t n, pos = 0;
+    // the bytes up to the next '\n' (which is consumed and dropped); false at the end of the data
+    bool line(std::string& out) {
+        if (pos >= n) return false;
+        size_t e = pos;
+        while (e < n && p[e] != '\n') e++;
+        out.assign((const char*)p + pos, e - pos);
+        pos = e < n ? e + 1 : n;
+        return true;
+    }
+    void need(size_t bytes, uint32_t y) const {
+        if (n - pos < bytes) throw ImageError("Radiance: truncated data in scanline " + std::to_string(y));
+    }
+};
+inline std::string hdr_trim(const std::string& s) {
+    size_t a = 0, b = s.size();
+    while (a < b && (s[a] == ' ' || s[a] == '\t' || s[a] == '\r')) a++;
+    while (b > a && (s[b - 1] == ' ' || s[b - 1] == '\t' || s[b - 1] == '\r')) b--;
+    return s.substr(a, b - a);
+}
+// a resolution line's number: decimal digits only, saturating far above every limit
+inline bool hdr_number(const std::string& s, uint64_t& v) {
+    if (s.empty()) return false;
+    v = 0;
+    for (char c : s) { if (c < '0' || c > '9') return false; if (v < (1ull << 40)) v = v * 10 + (uint64_t)(c - '0'); }
+    return true;
+}
+}  // namespace detail
+
+inline HdrData decode_hdr(const uint8_t* p, size_t n) {
+    using namespace detail;
+    HdrReader r{p, n};
+    std::string ln;
+    if (!r.line(ln) || (ln.rfind("#?RADIANCE", 0) != 0 && ln.rfind("#?RGBE", 0) != 0))
+        throw ImageError("Radiance: bad signature (the first line must be #?RADIANCE or #?RGBE)");
+    HdrData out;
+    for (;;) {                                                      // header lines up to the first empty one
+        if (!r.line(ln)) throw ImageError("Radiance: the data ends inside the header (no resolution line)");
+        if (ln.empty()) break;
+        if (ln.rfind("FORMAT=", 0) == 0) {
+            const std::string f = hdr_trim(ln.substr(7));
+            if (f == "32-bit_rle_xyze") throw ImageError("Radiance: FORMAT=32-bit_rle_xyze (XYZE texels) is not supported");
+            if (f != "32-bit_rle_rgbe") throw ImageError("Radiance: unknown FORMAT=" + f.substr(0, 40));
+        } else if (ln.rfind("EXPOSURE=", 0) == 0) {
+            const std::string v = hdr_trim(ln.substr(9));
+            char* end = nullptr;
+            const float e = strtof(v.c_str(), &end);
+            if (!v.empty() && end == v.c_str() + v.size()) out.exposure *= e;       // (an unreadable value is ignored, like every other line)
+        }
+    }
+    if (!r.line(ln)) throw ImageError("Radiance: missing resolution line");
+    {
+        std::string tok[4]; int nt = 0; bool extra = false;
+        for (size_t i = 0; i < ln.size();) {
+            while (i < ln.size() && (ln[i] == ' ' || ln[i] == '\t' || ln[i] == '\r')) i++;
+            size_t e = i;
+            while (e < ln.size() && ln[e] != ' ' && ln[e] != '\t' && ln[e] != '\r') e++;
+            if (e > i) { if (nt < 4) tok[nt++] = ln.substr(i, e - i); else extra = true; }
+            i = e;
+        }
+        auto axis = [](const std::string& t, char a) { return t.size() == 2 && (t[0] == '-' || t[0] == '+') && t[1] == a; };
+        uint64_t a = 0, b = 0;
+        const bool yx = axis(tok[0], 'Y') && axis(tok[2], 'X'), xy = axis(tok[0], 'X') && axis(tok[2], 'Y');
+        if (nt != 4 || extra || !(yx || xy) || !hdr_number(tok[1], a) || !hdr_number(tok[3], b))
+            throw ImageError("Radiance: missing or malformed resolution line (expected -Y <height> +X <width>)");
+        if (!(tok[0] == "-Y" && tok[2] == "+X"))
+            throw ImageError("Radiance: unsupported orientation '" + tok[0] + " " + tok[1] + " " + tok[2] + " " + tok[3] + "' (only -Y <height> +X <width> is read)");
+        if (b < 1 || b > 65536) throw ImageError("Radiance: width " + std::to_string(b) + " is outside [1, 65536]");
+        if (a < 1 || a > 65536) throw ImageError("Radiance: height " + std::to_string(a) + " is outside [1, 65536]");
+        if (a * b > (1ull << 28)) throw ImageError("Radiance: " + std::to_string(b) + " x " + std::to_string(a) + " exceeds 2^28 texels");
+        out.width = (uint32_t)b; out.height = (uint32_t)a;
+    }
+    const uint32_t W = out.width, H = out.height;
+    const size_t row_bytes = (size_t)W * 4, total = row_bytes * H;
+    // memory follows the rows that really decode: the reservation is bounded by what the remaining bytes could expand to
+    // (two bytes of a new-style run give 127), whatever the header claims, and each row is added when its turn comes
+    { const size_t most = (n - r.pos) * 64 + row_bytes; out.rgbe.reserve(total < most ? total : most); }
+    std::vector<uint8_t> planes;
+    for (uint32_t y = 0; y < H; y++) {
+        out.rgbe.resize((size_t)(y + 1) * row_bytes);
+        uint8_t* row = out.rgbe.data() + (size_t)y * row_bytes;
+        if (W < 8 || W > 32767) {                                   // flat pixels
+            r.need(row_bytes, y);
+            memcpy(row, p + r.pos, row_bytes); r.pos += row_bytes;
+            continue;
+        }
+        r.need(4, y);
+        uint8_t px[4] = {p[r.pos], p[r.pos + 1], p[r.pos + 2], p[r.pos + 3]};
+        r.pos += 4;
+        if (px[0] == 2 && px[1] == 2 && px[2] < 128) {              // new-style RLE: four component planes in turn
+            const uint32_t len = ((uint32_t)px[2] << 8) | px[3];
+            if (len != W) throw ImageError("Radiance: scanline " + std::to_string(y) + " declares length " + std::to_string(len) + ", the width is " + std::to_string(W));
+            planes.resize(row_bytes);
+            for (uint32_t c = 0; c < 4; c++) {
+                uint8_t* pl = planes.data() + (size_t)c * W;
+                for (uint32_t x = 0; x < W;) {
+                    r.need(1, y);
+                    const uint32_t cnt = p[r.pos++];
+                    if (cnt > 128) {
+                        const uint32_t run = cnt - 128;
+                        r.need(1, y);
+                        const uint8_t v = p[r.pos++];
+                        if (run > W - x) throw ImageError("Radiance: a run passes the end of a component plane in scanline " + std::to_string(y));
+                        memset(pl + x, v, run); x += run;
+                    } else {
+                        if (cnt == 0) throw ImageError("Radiance: run count 0 in scanline " + std::to_string(y));
+                        if (cnt > W - x) throw ImageError("Radiance: a literal passes the end of a component plane in scanline " + std::to_string(y));
+                        r.need(cnt, y);
+                        memcpy(pl + x, p + r.pos, cnt); r.pos += cnt; x += cnt;
+                    }
+                }
+            }
+            for (uint32_t x = 0; x < W; x++) {
+                row[4 * x] = planes[x]; row[4 * x + 1] = planes[(size_t)W + x]; row[4 * x + 2] = planes[2 * (size_t)W + x]; row[4 * x + 3] = planes[3 * (size_t)W + x];
+            }
+            continue;
+        }
+        // old-style RLE: px is the line's first pixel; (1, 1, 1, n) repeats the pixel before it n << shift times
+        uint32_t shift = 0;
+        for (uint32_t x = 0;;) {
+            if (px[0] == 1 && px[1] == 1 && px[2] == 1) {
+                if (x == 0 && y == 0) throw ImageError("Radiance: an old-style repeat marker with no pixel before it");
+                const uint64_t count = shift >= 32 ? (px[3] ? ~0ull : 0ull) : (uint64_t)px[3] << shift;
+                if (count > W - x) throw ImageError("Radiance: an old-style repeat passes the end of scanline " + std::to_string(y));
+                const uint8_t* prev = row + 4 * (size_t)x - 4;      // (x == 0: the last pixel of the row above, contiguous in rgbe)
+                for (uint64_t k = 0; k < count; k++) memcpy(row + 4 * ((size_t)x + k), prev, 4);
+                x += (uint32_t)count;
+                if (shift < 32) shift += 8;
+            } else {
+                memcpy(row + 4 * (size_t)x, px, 4); x++;
+                shift = 0;
+            }
+            if (x >= W) break;
+            r.need(4, y);
+            memcpy(px, p + r.pos, 4); r.pos += 4;
+        }
+    }
+    return out;                                                     // (bytes behind the last scanline are ignored)
+}
+
+inline HdrData load_hdr(const std::string& path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw ImageError("File not found: " + path);
+    std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    try { return decode_hdr(bytes.data(), bytes.size()); }
+    catch (const ImageError& e) { throw ImageError(path + ": " + e.what()); }
+}
+
+// RGBE -> float RGBA: E = 0 gives (0, 0, 0), otherwise m * 2^(E - 136) per channel (no + 0.5, as the `image` crate); alpha 1.
+// Every value is exact in binary32: the largest is 255 * 2^119, the smallest 2^-135 (a denormal).
+inline void hdr_to_float(const uint8_t* rgbe, size_t texels, float* rgba) {
+    for (size_t i = 0; i < texels; i++, rgbe += 4, rgba += 4) {
+        const int e = rgbe[3];
+        for (int c = 0; c < 3; c++) rgba[c] = e ? ldexpf((float)rgbe[c], e - 136) : 0.0f;
+        rgba[3] = 1.0f;
+    }
 }
 
 }  // namespace resources

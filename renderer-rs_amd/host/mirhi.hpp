@@ -295,6 +295,15 @@ public:
     static uint64_t cube_level_offset(uint32_t size, uint32_t level) { uint64_t o = 0; for (uint32_t k = 0; k < level; k++) o += 6ull * (size >> k) * (size >> k); return o; }
     // the IBL precompute passes (include/mirhi.h "IBL precompute"; shaders/hlsl/compute/): immediate, finished on return; `this` is the destination
     void ibl_equirect_to_cube(const Image& src2d) const { check(mirhi_ibl_equirect_to_cube(src2d.h_, h_)); }
+    // Radiance RGBE sources: `rgbe8` is a 2-D R8G8B8A8_UNORM image whose bytes are (R, G, B, E), e.g. from_rgbe of what
+    // resources::decode_hdr (image_decode.hpp) returns.  expand_rgbe: this 2-D float image receives the exact texels; the fused pass needs no float copy.
+    void ibl_equirect_to_cube_rgbe(const Image& rgbe8) const { check(mirhi_ibl_equirect_to_cube_rgbe(rgbe8.h_, h_)); }
+    void expand_rgbe(const Image& rgbe8) const { check(mirhi_image_expand_rgbe(rgbe8.h_, h_)); }
+    static Image from_rgbe(std::shared_ptr<Device> device, uint32_t w, uint32_t h, const uint8_t* rgbe) {
+        Image img(std::move(device), w, h, Format::R8G8B8A8_UNORM);
+        img.upload(rgbe);
+        return img;
+    }
     void ibl_cube_generate_mips() const { check(mirhi_ibl_cube_generate_mips(h_)); }
     void ibl_irradiance(const Image& env) const { check(mirhi_ibl_irradiance(env.h_, h_)); }
     void ibl_prefilter(const Image& env, uint32_t sample_count = 1024) const { check(mirhi_ibl_prefilter(env.h_, h_, sample_count)); }
