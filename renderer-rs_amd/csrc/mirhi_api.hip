@@ -513,38 +513,49 @@ struct mirhi_pipeline {
     mirhi_depth_bias bias;       // the factors of depth_bias_enable (0, 0, 0 through mirhi_pipeline_create: the builder's defaults, pipeline.rs:665-667)
 };
 
+// What a rendering scope IS, as opposed to what one of its segments holds (RecordedPass): attachments as they resolved, load / store ops, clear values,
+// render area, sample count, views, IBL set.  Zero-filled on construction and without padding bytes, all bytes defined: cut_segment carries it into the
+// segment that continues the scope with one assignment and same_recording compares it with one memcmp -- a new scope property is one member here.
+struct ScopeHeader {
+    // what an attachment resolved to when the scope was recorded: two recordings are the same frame shape only if these agree (an image handle may be a
+    // new image at an old address).  zero: always 0 (it fills the struct).
+    struct Target { const uint8_t* ptr; uint32_t width, height, format, zero; };
+    // the IBL set the scope's MODEL_PBR_IBL draws were recorded under (mirhi_cmd_bind_ibl; one per scope, all its segments): resolved like the targets
+    struct IblSet {
+        const uint8_t *irradiance, *prefiltered, *lut;
+        uint32_t irr_size, pre_size, pre_levels, lut_size;
+        uint32_t seamless, zero;           // the two cubes' seamless states when the draw was recorded (bit 0 irradiance, bit 1 prefiltered): part of the set's identity
+        bool operator==(const IblSet& o) const { return memcmp(this, &o, sizeof *this) == 0; }
+    };
+    // a multisampled scope (mirhi_cmd_begin_rendering_resolve): the ops and targets name its RESOLVE images; a multiview scope: depth is the ARRAY's base
+    // with ONE layer's extent; a depth-only scope: color has the depth image's extent, no address and format UNDEFINED
+    Target color, depth, prim;
+    IblSet ibl;
+    const uint8_t* view_base;              // view v of a multiview scope reads its light matrix at view_base + v * view_stride (the constants buffer's address + view_offset)
+    int32_t color_load_op, color_store_op, depth_load_op, depth_store_op;
+    float clear_color[4], clear_depth;     // (compared by their bits)
+    int32_t area[4];                       // the render area, the full extent spelled out (take_render_area)
+    uint32_t depth_only;                   // no colour attachment: SHADOW draws into the depth image (raster_kernel_depth)
+    uint32_t samples;                      // 1, or 4: a multisampled scope
+    uint32_t view_mask, view_stride, zero; // a multiview depth scope (mirhi_cmd_begin_rendering_multiview): view_mask != 0; depth_only is set
+    ScopeHeader() { memset(this, 0, sizeof *this); samples = 1u; }
+    bool operator==(const ScopeHeader& o) const { return memcmp(this, &o, sizeof *this) == 0; }
+};
+static_assert(sizeof(ScopeHeader::Target) == sizeof(void*) + 4 * 4 && sizeof(ScopeHeader::IblSet) == 3 * sizeof(void*) + 6 * 4, "no padding bytes: memcmp compares them");
+static_assert(sizeof(ScopeHeader) == 3 * sizeof(ScopeHeader::Target) + sizeof(ScopeHeader::IblSet) + sizeof(void*) + (4 + 5 + 4 + 5) * 4, "no padding bytes: memcmp compares headers");
+
+// One segment of a rendering scope (a scope is cut where its pipelines change the depth state: cut_segment), or one transfer command.
 struct RecordedPass {
-    mirhi_rendering_info info;
-    // what the attachments resolved to when the scope was recorded: two recordings are the same frame shape only if these agree
-    // (an image handle may be a new image at an old address)
-    struct Target { const uint8_t* ptr; uint32_t width, height, format; };
-    Target color_t{nullptr, 0, 0, 0}, depth_t{nullptr, 0, 0, 0}, prim_t{nullptr, 0, 0, 0};
+    ScopeHeader scope;
+    // the attachments' handles: what for_each_attachment orders across lanes, no part of what a recording is (a multiview scope's depth: the ARRAY)
+    struct Images { mirhi_image* color = nullptr; mirhi_image* depth = nullptr; mirhi_image* prim_id = nullptr; } images;
+    DepthState state;                      // depth / blend state of the segment's draws (mirhi_scope.h)
     std::vector<DrawDesc> draws;
     std::vector<uint64_t> draw_vb_bytes;   // bytes of the bound vertex buffer range per draw (vertex pre-pass extent)
     uint32_t total_tris = 0;
-    DepthState state;                      // depth / blend state of the segment's draws (mirhi_scope.h)
-    // a scope whose pipelines change the depth state is continued in a new segment: colour is kept (LOAD), depth is
-    // carried through the depth attachment or, without one, a transient buffer of the workspace
     uint32_t first_tri = 0;                // primitive ids continue across the segments of a scope
-    bool carry_in = false, carry_out = false;
-    int32_t area[4] = {0, 0, 0, 0};
-    bool depth_only = false;               // color_image NULL: SHADOW draws into the depth image (raster_kernel_depth)
-    uint32_t samples = 1;                  // 4: a multisampled scope (mirhi_cmd_begin_rendering_resolve): info / color_t / depth_t name its RESOLVE images
-    // A multiview depth scope (mirhi_cmd_begin_rendering_multiview): view_mask != 0; depth_only is set, info.depth_image is the ARRAY and depth_t its
-    // base with ONE layer's extent; view v reads its light matrix at view_base + v * view_stride (view_base: the constants buffer's address + view_offset)
-    uint32_t view_mask = 0, view_stride = 0;
-    const uint8_t* view_base = nullptr;
+    bool carry_in = false, carry_out = false;      // depth is carried through the depth attachment or, without one, a transient buffer of the workspace
     std::vector<mirhi_image*> sampled;     // shadow maps the scope's draws sample (MIRHI_TEXTURE_SHADOW_MAP): ordered like attachments
-    // the IBL set the scope's MODEL_PBR_IBL draws were recorded under (mirhi_cmd_bind_ibl; one per scope, all its segments): resolved like the targets
-    struct IblSet {
-        const uint8_t* irradiance = nullptr; const uint8_t* prefiltered = nullptr; const uint8_t* lut = nullptr;
-        uint32_t irr_size = 0, pre_size = 0, pre_levels = 0, lut_size = 0;
-        uint32_t seamless = 0;             // the two cubes' seamless states when the draw was recorded (bit 0 irradiance, bit 1 prefiltered): part of the set's identity
-        bool operator==(const IblSet& o) const {
-            return irradiance == o.irradiance && prefiltered == o.prefiltered && lut == o.lut && irr_size == o.irr_size && pre_size == o.pre_size &&
-                   pre_levels == o.pre_levels && lut_size == o.lut_size && seamless == o.seamless;
-        }
-    } ibl;
     // A SKYBOX segment: the one SKYBOX draw it consists of, as PassParams takes it (the sky_ words), fixed when the draw was recorded -- push
     // constants, viewport, scissor and the environment are latched per draw.  All bytes defined (memcmp compares two recordings).
     struct SkyDraw {
@@ -1705,33 +1716,49 @@ extern "C" mirhi_result mirhi_cmd_reset(mirhi_cmd* cmd) {
         if ((cmd)->state != CMD_RECORDING) return fail(MIRHI_ERR_DEVICE, "Vulkan error: command buffer is not in the recording state"); \
     } while (0)
 
-// A draw's scissor (inclusive corners) cut to the scope's render area: what a draw may cover lies inside the area, so the geometry kernel bins
-// nothing into a tile the scope does not launch.  A full-extent scope's scissor stays as the attachment's far edges left it.
-// The callers compute scissor_partial AFTER this cut: every draw of a partial-area scope is scissor-partial, so every triangle that crosses the area's
-// edge is a cut one and goes to the big list (correct -- the per-pixel box test is what keeps its fragments inside -- and the reason such scopes are
-// kept off the triangle-parallel variants by density: ScopePlan::density_tiles).
-static void clamp_to_render_area(const RecordedPass& pass, int64_t& sx0, int64_t& sy0, int64_t& sx1, int64_t& sy1) {
-    const int32_t* a = pass.area;
-    if (a[0] == 0 && a[1] == 0 && a[2] == (int32_t)pass.color_t.width && a[3] == (int32_t)pass.color_t.height) return;
-    sx0 = std::max<int64_t>(sx0, a[0]); sy0 = std::max<int64_t>(sy0, a[1]);
-    sx1 = std::min<int64_t>(sx1, (int64_t)a[0] + a[2] - 1); sy1 = std::min<int64_t>(sy1, (int64_t)a[1] + a[3] - 1);
-}
-// The scope's render area as RecordedPass::area keeps it -- the full extent spelled out -- or the refusal (mirhi_scope.h render_area: the rectangle must
-// lie inside the width x height attachment; a partial one is refused on a split device: the band exchange moves whole tile rows)
-static mirhi_result take_render_area(const mirhi_cmd* cmd, const mirhi_rendering_info* info, uint32_t width, uint32_t height, int32_t area[4]) {
+// The scope's render area as ScopeHeader::area keeps it -- the full extent spelled out -- or the refusal (mirhi_scope.h render_area: the rectangle must
+// lie inside the width x height attachment).  A partial one is refused on a split device (the band exchange moves whole tile rows) -- unless the caller
+// takes `partial`: a multisampled and a multiview scope refuse a partial area in words and at a place of their own (msaa_ / multiview_scope_refusal).
+static mirhi_result take_render_area(const mirhi_cmd* cmd, const mirhi_rendering_info* info, uint32_t width, uint32_t height, int32_t area[4], bool* partial = nullptr) {
     const RenderArea a = render_area(width, height, info->render_area);
     if (!a.valid) {
         char msg[192];
         render_area_message(msg, sizeof msg, info->render_area, width, height);
         return fail(MIRHI_ERR_INVALID_HANDLE, "%s", msg);
     }
-    if (a.partial && cmd->dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a partial render area on a split device");
+    if (partial) *partial = a.partial;
+    else if (a.partial && cmd->dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a partial render area on a split device");
     area[0] = (int32_t)a.x; area[1] = (int32_t)a.y; area[2] = (int32_t)a.w; area[3] = (int32_t)a.h;
+    return MIRHI_OK;
+}
+#define REQUIRE_NO_SCOPE(cmd) do { if ((cmd)->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope"); } while (0)
+static ScopeHeader::Target target_of(const mirhi_image* img) {
+    return img ? ScopeHeader::Target{img->ptr, img->width, img->height, (uint32_t)img->format, 0u} : ScopeHeader::Target{nullptr, 0u, 0u, 0u, 0u};
+}
+// ops and clear values as the caller gave them; the area, samples and views are the opening function's to add
+static void take_ops(ScopeHeader& h, const mirhi_rendering_info* info) {
+    h.color_load_op = info->color_load_op; h.color_store_op = info->color_store_op; h.depth_load_op = info->depth_load_op; h.depth_store_op = info->depth_store_op;
+    memcpy(h.clear_color, info->clear_color, sizeof h.clear_color); h.clear_depth = info->clear_depth;
+}
+// Opens the scope of `p` (built in place: the frame loop records one per frame) on the images it writes (a multisampled scope: its resolve images).  Without
+// a colour image the scope is depth-only: the depth image's extent is the render area's frame, and there is no colour address or format.
+static mirhi_result open_scope(mirhi_cmd* cmd, RecordedPass& p, mirhi_image* color, mirhi_image* depth, mirhi_image* prim) {
+    ScopeHeader& h = p.scope;
+    h.depth_only = color ? 0u : 1u;
+    h.color = target_of(color ? color : depth);
+    if (!color) { h.color.ptr = nullptr; h.color.format = (uint32_t)MIRHI_FORMAT_UNDEFINED; }
+    h.depth = target_of(depth); h.prim = target_of(prim);
+    p.images.color = color; p.images.depth = depth; p.images.prim_id = prim;
+    cmd->passes.push_back(std::move(p));
+    cmd->in_rendering = true;
     return MIRHI_OK;
 }
 extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_rendering_info* info) {
     REQUIRE_RECORDING(cmd); NULL_CHECK(info, "rendering_info");
-    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
+    REQUIRE_NO_SCOPE(cmd);
+    RecordedPass p;
+    ScopeHeader& h = p.scope;
+    take_ops(h, info);
     for (const mirhi_image* img : {(const mirhi_image*)info->color_image, (const mirhi_image*)info->depth_image, (const mirhi_image*)info->prim_id_image})
         if (img && img->samples != 1u)
             return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a multisampled attachment needs a resolve target: mirhi_cmd_begin_rendering_resolve with a multisampled color_image");
@@ -1744,15 +1771,8 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
         if (info->prim_id_image) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: prim_id_image in a depth-only rendering scope");
         if (info->depth_store_op != MIRHI_STORE_OP_STORE)
             return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a depth-only rendering scope must store its depth (STORE)");
-        RecordedPass p;
-        p.info = *info;
-        p.depth_only = true;
-        p.color_t = {nullptr, di->width, di->height, (uint32_t)MIRHI_FORMAT_UNDEFINED};
-        p.depth_t = {di->ptr, di->width, di->height, (uint32_t)di->format};
-        { mirhi_result ra = take_render_area(cmd, info, di->width, di->height, p.area); if (ra != MIRHI_OK) return ra; }
-        cmd->passes.push_back(std::move(p));
-        cmd->in_rendering = true;
-        return MIRHI_OK;
+        { mirhi_result ra = take_render_area(cmd, info, di->width, di->height, h.area); if (ra != MIRHI_OK) return ra; }
+        return open_scope(cmd, p, nullptr, info->depth_image, nullptr);
     }
     NULL_CHECK(info->color_image, "color_image");
     const mirhi_image* ci = info->color_image;
@@ -1771,18 +1791,11 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering(mirhi_cmd* cmd, const mirhi_re
         if (info->prim_id_image->format != MIRHI_FORMAT_R32_UINT || info->prim_id_image->width != ci->width || info->prim_id_image->height != ci->height)
             return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: prim_id_image must be R32_UINT with the colour attachment's extent");
     }
-    RecordedPass p;
-    p.info = *info;
-    p.color_t = {ci->ptr, ci->width, ci->height, (uint32_t)ci->format};
-    if (info->depth_image) p.depth_t = {info->depth_image->ptr, info->depth_image->width, info->depth_image->height, (uint32_t)info->depth_image->format};
-    if (info->prim_id_image) p.prim_t = {info->prim_id_image->ptr, info->prim_id_image->width, info->prim_id_image->height, (uint32_t)info->prim_id_image->format};
-    { mirhi_result ra = take_render_area(cmd, info, ci->width, ci->height, p.area); if (ra != MIRHI_OK) return ra; }
-    cmd->passes.push_back(std::move(p));
-    cmd->in_rendering = true;
-    return MIRHI_OK;
+    { mirhi_result ra = take_render_area(cmd, info, ci->width, ci->height, h.area); if (ra != MIRHI_OK) return ra; }
+    return open_scope(cmd, p, info->color_image, info->depth_image, info->prim_id_image);
 }
-// A 4x multisampled scope.  What the scope WRITES are the resolve images: the recorded pass names them as its attachments (RecordedPass::info,
-// color_t, depth_t -- attachment ordering, the plan cache and fill_params then see a scope that stores colour and, with a depth resolve, depth), and samples = 4
+// A 4x multisampled scope.  What the scope WRITES are the resolve images: the recorded pass names them as its attachments (the header's targets
+// and the image handles -- attachment ordering, the plan cache and fill_params then see a scope that stores colour and, with a depth resolve, depth), and samples = 4
 // says that its kernels are geometry_kernel_msaa and raster_kernel_msaa.  The refusals are mirhi_scope.h's (msaa_scope_refusal).
 extern "C" void mirhi_resolve_info_default(mirhi_resolve_info* r) { if (r) memset(r, 0, sizeof *r); }
 extern "C" mirhi_result mirhi_cmd_begin_rendering_resolve(mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_resolve_info* resolve) {
@@ -1794,18 +1807,17 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering_resolve(mirhi_cmd* cmd, const 
         if (any_resolve) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a resolve needs a multisampled color_image (mirhi_image_create_multisampled)");
         return mirhi_cmd_begin_rendering(cmd, info);
     }
-    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
+    REQUIRE_NO_SCOPE(cmd);
     if (ci->dev != cmd->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the color_image belongs to another device than the command buffer");
     const mirhi_image* di = info->depth_image; const mirhi_image* pi = info->prim_id_image;
     const mirhi_image* cr = resolve ? resolve->color_resolve_image : nullptr; const mirhi_image* dr = resolve ? resolve->depth_resolve_image : nullptr;
     for (const mirhi_image* img : {cr, dr, pi})
         if (img && (img->is_cube || img->is_array)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a cube image or an image array is not an attachment (an array: use a layer view)");
-    const RenderArea area = render_area(ci->width, ci->height, info->render_area);
-    if (!area.valid) {
-        char msg[192];
-        render_area_message(msg, sizeof msg, info->render_area, ci->width, ci->height);
-        return fail(MIRHI_ERR_INVALID_HANDLE, "%s", msg);
-    }
+    RecordedPass p;
+    ScopeHeader& h = p.scope;
+    take_ops(h, info);
+    bool area_partial = false;
+    { mirhi_result ra = take_render_area(cmd, info, ci->width, ci->height, h.area, &area_partial); if (ra != MIRHI_OK) return ra; }
     MsaaScopeFacts f{};
     f.color_samples = ci->samples; f.color_format = (uint32_t)ci->format; f.color_w = ci->width; f.color_h = ci->height;
     f.color_load_op = info->color_load_op; f.color_store_op = info->color_store_op;
@@ -1819,21 +1831,12 @@ extern "C" mirhi_result mirhi_cmd_begin_rendering_resolve(mirhi_cmd* cmd, const 
     if (pi && pi->samples != 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the prim_id_image is multisampled itself");
     if (pi && pi->dev != ci->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the prim_id_image belongs to another device");
     if (di && di->dev != ci->dev) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the depth_image belongs to another device");
-    f.area_partial = area.partial; f.split_device = cmd->dev->split_world > 1; f.fragment_stats = (cmd->dev->profiling & MIRHI_PROFILE_FRAGMENTS) != 0;
+    f.area_partial = area_partial; f.split_device = cmd->dev->split_world > 1; f.fragment_stats = (cmd->dev->profiling & MIRHI_PROFILE_FRAGMENTS) != 0;
     if (const char* why = msaa_scope_refusal(f)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", why);
-    RecordedPass p;
-    p.info = *info;
-    p.samples = 4u;
-    p.info.color_image = resolve->color_resolve_image; p.info.color_store_op = MIRHI_STORE_OP_STORE;
-    p.info.depth_image = resolve->depth_resolve_image; p.info.depth_load_op = MIRHI_LOAD_OP_CLEAR;
-    p.info.depth_store_op = dr ? MIRHI_STORE_OP_STORE : MIRHI_STORE_OP_DONT_CARE;
-    p.color_t = {cr->ptr, cr->width, cr->height, (uint32_t)cr->format};
-    if (dr) p.depth_t = {dr->ptr, dr->width, dr->height, (uint32_t)dr->format};
-    if (pi) p.prim_t = {pi->ptr, pi->width, pi->height, (uint32_t)pi->format};
-    p.area[0] = 0; p.area[1] = 0; p.area[2] = (int32_t)ci->width; p.area[3] = (int32_t)ci->height;
-    cmd->passes.push_back(std::move(p));
-    cmd->in_rendering = true;
-    return MIRHI_OK;
+    h.samples = 4u;
+    h.color_store_op = MIRHI_STORE_OP_STORE; h.depth_load_op = MIRHI_LOAD_OP_CLEAR;
+    h.depth_store_op = dr ? MIRHI_STORE_OP_STORE : MIRHI_STORE_OP_DONT_CARE;
+    return open_scope(cmd, p, resolve->color_resolve_image, resolve->depth_resolve_image, info->prim_id_image);
 }
 // A multiview depth scope: ONE recorded pass -- a depth-only one whose depth target is the array's base with one layer's extent -- that carries
 // the view mask and where the views' matrices are.  Its draws are recorded once, like a single-view scope's; build_plan expands them to one parameter block per
@@ -1852,31 +1855,18 @@ static MultiviewFacts multiview_facts(const mirhi_cmd* cmd, const mirhi_renderin
 extern "C" void mirhi_multiview_info_default(mirhi_multiview_info* m) { if (m) { memset(m, 0, sizeof *m); m->view_stride = 64u; } }
 extern "C" mirhi_result mirhi_cmd_begin_rendering_multiview(mirhi_cmd* cmd, const mirhi_rendering_info* info, const mirhi_multiview_info* multiview) {
     REQUIRE_RECORDING(cmd); NULL_CHECK(info, "rendering_info"); NULL_CHECK(multiview, "multiview_info");
-    if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: begin_rendering inside an active rendering scope");
+    REQUIRE_NO_SCOPE(cmd);
     const mirhi_image* di = info->depth_image;
+    RecordedPass p;
+    ScopeHeader& h = p.scope;
+    take_ops(h, info);
     bool area_partial = false;
-    if (di && di->is_array) {
-        const RenderArea area = render_area(di->width, di->height, info->render_area);
-        if (!area.valid) {
-            char msg[192];
-            render_area_message(msg, sizeof msg, info->render_area, di->width, di->height);
-            return fail(MIRHI_ERR_INVALID_HANDLE, "%s", msg);
-        }
-        area_partial = area.partial;
-    }
+    if (di && di->is_array) { mirhi_result ra = take_render_area(cmd, info, di->width, di->height, h.area, &area_partial); if (ra != MIRHI_OK) return ra; }
     if (const char* why = multiview_scope_refusal(multiview_facts(cmd, info, multiview, area_partial))) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", why);
     if (di->dev != cmd->dev || multiview->view_constants->dev != cmd->dev)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: the depth array or the view constants belong to another device than the command buffer");
-    RecordedPass p;
-    p.info = *info;
-    p.depth_only = true;
-    p.color_t = {nullptr, di->width, di->height, (uint32_t)MIRHI_FORMAT_UNDEFINED};
-    p.depth_t = {di->ptr, di->width, di->height, (uint32_t)di->format};
-    p.area[0] = 0; p.area[1] = 0; p.area[2] = (int32_t)di->width; p.area[3] = (int32_t)di->height;
-    p.view_mask = multiview->view_mask; p.view_stride = multiview->view_stride; p.view_base = multiview->view_constants->ptr + multiview->view_offset;
-    cmd->passes.push_back(std::move(p));
-    cmd->in_rendering = true;
-    return MIRHI_OK;
+    h.view_mask = multiview->view_mask; h.view_stride = multiview->view_stride; h.view_base = multiview->view_constants->ptr + multiview->view_offset;
+    return open_scope(cmd, p, nullptr, info->depth_image, nullptr);
 }
 extern "C" mirhi_result mirhi_cmd_end_rendering(mirhi_cmd* cmd) {
     REQUIRE_RECORDING(cmd);
@@ -2017,16 +2007,51 @@ static void cut_segment(mirhi_cmd* cmd) {
     {
         RecordedPass& prev = cmd->passes.back();
         prev.carry_out = true;
-        next.info = prev.info;
-        next.color_t = prev.color_t; next.depth_t = prev.depth_t; next.prim_t = prev.prim_t;
-        next.depth_only = prev.depth_only; next.ibl = prev.ibl;
-        next.view_mask = prev.view_mask; next.view_stride = prev.view_stride; next.view_base = prev.view_base;
-        memcpy(next.area, prev.area, sizeof next.area);
-        next.info.color_load_op = MIRHI_LOAD_OP_LOAD;
+        next.scope = prev.scope;
+        next.images = prev.images;
+        next.scope.color_load_op = MIRHI_LOAD_OP_LOAD;
         next.carry_in = true;
         next.first_tri = next.total_tris = prev.total_tris;
     }
     cmd->passes.push_back(std::move(next));
+}
+
+// ---- what the two draw recorders (record_draw, record_sky_draw) share: each refusal at the place its recorder gives it ----
+// the depth test of a pipeline as a segment's state keeps it (Vulkan: no depth write without the depth test); record_draw adds blending and discard
+static DepthState depth_state_of(const mirhi_pipeline_desc& pd) {
+    DepthState ds;
+    ds.key_set = true;
+    ds.test = pd.depth_test_enable ? 1u : 0u;
+    ds.compare = ds.test ? (uint32_t)pd.depth_compare_op : (uint32_t)MIRHI_COMPARE_ALWAYS;
+    ds.write = ds.test && pd.depth_write_enable ? 1u : 0u;
+    return ds;
+}
+static mirhi_result require_dynamic_state(const mirhi_cmd* cmd) {
+    return cmd->has_viewport && cmd->has_scissor ? MIRHI_OK : fail(MIRHI_ERR_PIPELINE, "Pipeline error: viewport and scissor are dynamic state and must be set before drawing (pipeline.rs:697)");
+}
+static mirhi_result require_color_format(const mirhi_pipeline_desc& pd, const ScopeHeader& scope) {
+    if (pd.color_attachment_formats[0] == (int32_t)scope.color.format) return MIRHI_OK;
+    return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)scope.color.format);
+}
+static mirhi_result require_prim_ids(const RecordedPass& pass, uint32_t tri_count) {
+    return (uint64_t)pass.total_tris + tri_count > (uint64_t)MAX_PRIM_ID ? fail(MIRHI_ERR_DEVICE, "Vulkan error: too many primitives in one rendering scope") : MIRHI_OK;
+}
+// The current scissor as inclusive corners, cut to the scope's render area (which lies inside the attachment: a full-extent scope's scissor is cut to the
+// attachment's far edges): what a draw may cover lies inside the area, so the geometry kernel bins nothing into a tile the scope does not launch.
+// record_draw computes scissor_partial AFTER this cut: every draw of a partial-area scope is scissor-partial, so every triangle that crosses the area's
+// edge is a cut one and goes to the big list (correct -- the per-pixel box test is what keeps its fragments inside -- and the reason such scopes are
+// kept off the triangle-parallel variants by density: ScopePlan::density_tiles).  false: the scissor is empty, nothing can be covered.
+static bool draw_scissor(const mirhi_cmd* cmd, const ScopeHeader& scope, int32_t s[4]) {
+    const int32_t* a = scope.area;
+    const int64_t sx0 = std::max<int64_t>(cmd->scissor.x, a[0]), sy0 = std::max<int64_t>(cmd->scissor.y, a[1]);
+    const int64_t sx1 = std::min<int64_t>((int64_t)cmd->scissor.x + cmd->scissor.width, (int64_t)a[0] + a[2]) - 1;
+    const int64_t sy1 = std::min<int64_t>((int64_t)cmd->scissor.y + cmd->scissor.height, (int64_t)a[1] + a[3]) - 1;
+    s[0] = (int32_t)sx0; s[1] = (int32_t)sy0; s[2] = (int32_t)sx1; s[3] = (int32_t)sy1;
+    return sx0 <= sx1 && sy0 <= sy1;
+}
+// an image the segment's draws sample: ordered across lanes like an attachment (for_each_attachment)
+static void note_sampled(RecordedPass& pass, mirhi_image* img) {
+    if (std::find(pass.sampled.begin(), pass.sampled.end(), img) == pass.sampled.end()) pass.sampled.push_back(img);
 }
 
 // A SKYBOX draw (include/mirhi.h "SKYBOX"): always a segment of its own, set up here -- the triangle's edge functions, the three vertex values of
@@ -2035,24 +2060,19 @@ static void cut_segment(mirhi_cmd* cmd) {
 static mirhi_result record_sky_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, uint32_t instance_count, uint32_t first) {
     const mirhi_pipeline_desc& pd = cmd->pipeline->desc;
     if (indexed) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX pipeline draws with mirhi_cmd_draw(cmd, 3, 1, 0, 0): draw_indexed has nothing to index");
-    if (cmd->passes.back().depth_only) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX draw in a depth-only rendering scope (pixel/skybox.hlsl writes colour)");
-    if (cmd->passes.back().samples != 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a SKYBOX draw in a multisampled scope");
+    const ScopeHeader& scope = cmd->passes.back().scope;      // (for the refusals only: the cut below moves the segments)
+    if (scope.depth_only) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX draw in a depth-only rendering scope (pixel/skybox.hlsl writes colour)");
+    if (scope.samples != 1u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a SKYBOX draw in a multisampled scope");
     if (pd.blend_enable || pd.fragment_discard_enable) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a SKYBOX draw with blending or fragment discard");
     if (count != 3u || first != 0u || instance_count > 1u)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: a SKYBOX draw is vertex_count 3, first_vertex 0, instance_count 1 (got %u, %u, %u)", count, first, instance_count);
     if (!cmd->skybox) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: program %d (SKYBOX) needs an environment cube bound (mirhi_cmd_bind_skybox)", pd.fragment_program);
-    if (!cmd->has_viewport || !cmd->has_scissor) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: viewport and scissor are dynamic state and must be set before drawing (pipeline.rs:697)");
-    const RecordedPass::Target ci = cmd->passes.back().color_t;
-    if (pd.color_attachment_formats[0] != (int32_t)ci.format)
-        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)ci.format);
+    mirhi_result r;
+    if ((r = require_dynamic_state(cmd)) != MIRHI_OK || (r = require_color_format(pd, scope)) != MIRHI_OK) return r;
     if (instance_count == 0) return MIRHI_OK;
-    if ((uint64_t)cmd->passes.back().total_tris + 1u > (uint64_t)MAX_PRIM_ID) return fail(MIRHI_ERR_DEVICE, "Vulkan error: too many primitives in one rendering scope");
+    if ((r = require_prim_ids(cmd->passes.back(), 1u)) != MIRHI_OK) return r;
     if (pd.depth_test_enable && pd.depth_compare_op == MIRHI_COMPARE_NEVER) { cmd->passes.back().total_tris += 1u; return MIRHI_OK; }     // draws nothing, keeps its id
-    DepthState ds;
-    ds.key_set = true;
-    ds.test = pd.depth_test_enable ? 1u : 0u;
-    ds.compare = ds.test ? (uint32_t)pd.depth_compare_op : (uint32_t)MIRHI_COMPARE_ALWAYS;
-    ds.write = ds.test && pd.depth_write_enable ? 1u : 0u;
+    const DepthState ds = depth_state_of(pd);
     // a segment of its own, even when its depth state equals its neighbour's; a segment that holds no draw yet (nothing recorded, or only draws that
     // kept their ids and drew nothing: NEVER, an empty scissor) becomes the sky segment
     {
@@ -2088,13 +2108,7 @@ static mirhi_result record_sky_draw(mirhi_cmd* cmd, bool indexed, uint32_t count
         k.a[i] = -dy; k.b[i] = dx;
         k.e0[i] = (int64_t)k.a[i] * (128 - X[a]) + (int64_t)k.b[i] * (128 - Y[a]) + (topleft ? 0 : -1);      // E_i + bias at the centre of pixel (0, 0)
     }
-    int64_t sx0 = cmd->scissor.x, sy0 = cmd->scissor.y;
-    int64_t sx1 = sx0 + (int64_t)cmd->scissor.width - 1, sy1 = sy0 + (int64_t)cmd->scissor.height - 1;
-    if (sx1 > (int64_t)ci.width - 1) sx1 = (int64_t)ci.width - 1;
-    if (sy1 > (int64_t)ci.height - 1) sy1 = (int64_t)ci.height - 1;
-    clamp_to_render_area(cmd->passes.back(), sx0, sy0, sx1, sy1);
-    if (sx0 > sx1 || sy0 > sy1) { visible = false; sx0 = sy0 = 0; sx1 = sy1 = -1; }
-    k.scissor[0] = (int32_t)sx0; k.scissor[1] = (int32_t)sy0; k.scissor[2] = (int32_t)sx1; k.scissor[3] = (int32_t)sy1;
+    if (!draw_scissor(cmd, pass.scope, k.scissor)) { visible = false; k.scissor[0] = k.scissor[1] = 0; k.scissor[2] = k.scissor[3] = -1; }
     k.visible = visible ? 1u : 0u;
     // LocalPos = (M (x, -y, 1, 1)).xyz / .w per vertex (vertex/skybox.hlsl:40-42), M = push constants [0, 64) in CameraData.viewProjection's convention
     float M[16];
@@ -2114,7 +2128,7 @@ static mirhi_result record_sky_draw(mirhi_cmd* cmd, bool indexed, uint32_t count
         k.posx[r] = (float)dx; k.posy[r] = (float)dy;
         k.pos0[r] = (float)(L[0][r] + dx * ((double)hw - (double)cx) + dy * ((double)hh - (double)cy));
     }
-    if (std::find(pass.sampled.begin(), pass.sampled.end(), cmd->skybox) == pass.sampled.end()) pass.sampled.push_back(cmd->skybox);
+    note_sampled(pass, cmd->skybox);
     pass.total_tris += 1u;
     return MIRHI_OK;
 }
@@ -2123,12 +2137,14 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     REQUIRE_RECORDING(cmd);
     if (!cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: draw outside a rendering scope");
     if (!cmd->pipeline) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: no pipeline bound");
-    if (cmd->passes.back().view_mask)      // (a multiview scope refuses every program but SHADOW in its own words, ahead of the depth-only scope's)
+    const ScopeHeader& scope = cmd->passes.back().scope;      // (for the refusals only: a cut below moves the segments)
+    if (scope.view_mask)      // (a multiview scope refuses every program but SHADOW in its own words, ahead of the depth-only scope's)
         if (const char* why = multiview_program_refusal(cmd->pipeline->desc.vertex_program)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", why);
     if (cmd->pipeline->desc.vertex_program == MIRHI_PROGRAM_SKYBOX) return record_sky_draw(cmd, indexed, count, instance_count, first);
     if (!cmd->vb) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: no vertex buffer bound to binding 0");
     if (indexed && !cmd->ib) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: no index buffer bound");
-    if (!cmd->has_viewport || !cmd->has_scissor) return fail(MIRHI_ERR_PIPELINE, "Pipeline error: viewport and scissor are dynamic state and must be set before drawing (pipeline.rs:697)");
+    mirhi_result r;
+    if ((r = require_dynamic_state(cmd)) != MIRHI_OK) return r;
     if (instance_count > 1) {
         // The path has no instance-rate input (binding 0 is per-vertex, vertex.rs:35-41,130-136; no program reads SV_InstanceID): instance i
         // rasterizes the same triangles again, behind instance i - 1 in primitive order -- recorded as that many draws of one instance.
@@ -2142,27 +2158,20 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     const mirhi_pipeline_desc& pd = cmd->pipeline->desc;
     const bool shadow_prog = pd.vertex_program == MIRHI_PROGRAM_SHADOW;
     // (a multisampled scope refuses a SHADOW draw in its own words, ahead of the 1x scope's "needs a depth-only rendering scope")
-    if (cmd->passes.back().samples == 4u && shadow_prog) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", msaa_program_refusal(pd.fragment_program, false));
-    if (cmd->passes.back().depth_only && !shadow_prog)
+    if (scope.samples == 4u && shadow_prog) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", msaa_program_refusal(pd.fragment_program, false));
+    if (scope.depth_only && !shadow_prog)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: only SHADOW draws may be recorded in a depth-only rendering scope (program %d)", pd.vertex_program);
-    if (!cmd->passes.back().depth_only && shadow_prog)
+    if (!scope.depth_only && shadow_prog)
         return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: SHADOW draws need a depth-only rendering scope (color_image NULL, depth_image set)");
-    const RecordedPass::Target ci = cmd->passes.back().color_t;      // (a depth-only scope: the depth image's extent, format UNDEFINED)
-    if (pd.rasterization_samples != cmd->passes.back().samples)
-        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline rasterization_samples %u does not match the rendering scope's sample count %u", pd.rasterization_samples,
-                    cmd->passes.back().samples);
-    if (pd.color_attachment_formats[0] != (int32_t)ci.format)
-        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline colour format %d does not match the attachment format %d", pd.color_attachment_formats[0], (int)ci.format);
+    if (pd.rasterization_samples != scope.samples)
+        return fail(MIRHI_ERR_PIPELINE, "Pipeline error: pipeline rasterization_samples %u does not match the rendering scope's sample count %u", pd.rasterization_samples, scope.samples);
+    if ((r = require_color_format(pd, scope)) != MIRHI_OK) return r;      // (a depth-only scope: format UNDEFINED)
     // depth state must be uniform within a rendering scope (DESIGN.md "Depth key")
-    DepthState ds;
-    ds.key_set = true;
-    ds.test = pd.depth_test_enable ? 1u : 0u;
-    ds.compare = ds.test ? (uint32_t)pd.depth_compare_op : (uint32_t)MIRHI_COMPARE_ALWAYS;
-    ds.write = ds.test && pd.depth_write_enable ? 1u : 0u;       // Vulkan: no depth write without the depth test
+    DepthState ds = depth_state_of(pd);
     const bool never = pd.depth_test_enable && pd.depth_compare_op == MIRHI_COMPARE_NEVER;
     const uint32_t tri_count = count / 3u;
     if (instance_count == 0 || tri_count == 0) return MIRHI_OK;
-    if (never && cmd->passes.back().samples == 4u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", msaa_draw_refusal(ds, pd.fragment_program, false, false));      // (a predicate state)
+    if (never && scope.samples == 4u) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s", msaa_draw_refusal(ds, pd.fragment_program, false, false));      // (a predicate state)
     if (never) { cmd->passes.back().total_tris += tri_count; return MIRHI_OK; }     // draws nothing, but its primitives keep their ids
     if (pd.blend_enable) {
         uint32_t* blend = ds.blend;
@@ -2171,7 +2180,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         blend[7] = pd.color_write_mask & 0xFu;
     }
     ds.discard = pd.fragment_discard_enable ? 1u : 0u;
-    if (cmd->passes.back().samples == 4u) {
+    if (scope.samples == 4u) {
         // a multisampled scope is one segment of what raster_kernel_msaa takes: everything else is refused here, never drawn differently (mirhi_scope.h)
         const RecordedPass& mp = cmd->passes.back();
         const bool pbr_prog = pd.fragment_program == MIRHI_PROGRAM_MODEL_PBR || pd.fragment_program == MIRHI_PROGRAM_MODEL_PBR_IBL;
@@ -2208,7 +2217,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     }
     d.tri_count = tri_count;
     d.prim_base = pass.total_tris;
-    if ((uint64_t)pass.total_tris + tri_count > (uint64_t)MAX_PRIM_ID) return fail(MIRHI_ERR_DEVICE, "Vulkan error: too many primitives in one rendering scope");
+    if ((r = require_prim_ids(pass, tri_count)) != MIRHI_OK) return r;
     d.program = (uint32_t)pd.fragment_program;
     d.cull_mode = (uint32_t)pd.cull_mode; d.front_face = (uint32_t)pd.front_face;
     // uniforms required by the program (model.hlsl:5-19, model_full.hlsl:27-50)
@@ -2223,13 +2232,11 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         // ShadowConstants (vertex/shadow.hlsl:7-11) in b0: lightSpaceMatrix @0, model @64 -- the vertex pre-pass reads the model matrix as a MODEL
         // draw's object and the light matrix in place of viewProjection
         const uint8_t* p = nullptr;
-        mirhi_result r;
         if ((r = uptr(MIRHI_SLOT_CAMERA, 128, &p, "ShadowConstants (b0)")) != MIRHI_OK) return r;
         d.camera = (const float*)p;
         d.object = (const float*)(p + 64);
     } else if (d.program != MIRHI_PROGRAM_TRIANGLE) {
         const uint8_t* p = nullptr;
-        mirhi_result r;
         if ((r = uptr(MIRHI_SLOT_CAMERA, 208, &p, "CameraData (b0)")) != MIRHI_OK) return r;
         d.camera = (const float*)p;
         if ((r = uptr(MIRHI_SLOT_OBJECT, 128, &p, "ObjectData (b1)")) != MIRHI_OK) return r;
@@ -2298,25 +2305,20 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
     if (pd.depth_clamp_enable) d.depth_flags |= DEPTH_FLAG_CLAMP;
     d.gx = (GUARD_PX - std::fabs(d.cx)) / d.hw;
     d.gy = (GUARD_PX - std::fabs(d.cy)) / d.hh;
-    int64_t sx0 = cmd->scissor.x, sy0 = cmd->scissor.y;
-    int64_t sx1 = sx0 + (int64_t)cmd->scissor.width - 1, sy1 = sy0 + (int64_t)cmd->scissor.height - 1;
-    if (sx1 > (int64_t)ci.width - 1) sx1 = (int64_t)ci.width - 1;
-    if (sy1 > (int64_t)ci.height - 1) sy1 = (int64_t)ci.height - 1;
-    clamp_to_render_area(cmd->passes.back(), sx0, sy0, sx1, sy1);
-    d.sx0 = (int32_t)sx0; d.sy0 = (int32_t)sy0; d.sx1 = (int32_t)sx1; d.sy1 = (int32_t)sy1;
-    d.scissor_partial = (sx0 > 0 || sy0 > 0 || sx1 < (int64_t)ci.width - 1 || sy1 < (int64_t)ci.height - 1) ? 1u : 0u;
-    if (sx0 > sx1 || sy0 > sy1) return MIRHI_OK;    // empty scissor: nothing can be covered
+    int32_t sc[4];
+    if (!draw_scissor(cmd, pass.scope, sc)) return MIRHI_OK;    // empty scissor: nothing can be covered
+    d.sx0 = sc[0]; d.sy0 = sc[1]; d.sx1 = sc[2]; d.sy1 = sc[3];
+    d.scissor_partial = (sc[0] > 0 || sc[1] > 0 || sc[2] < (int32_t)pass.scope.color.width - 1 || sc[3] < (int32_t)pass.scope.color.height - 1) ? 1u : 0u;
     if (d.program == MIRHI_PROGRAM_MODEL_PBR_IBL) {
         // the set is per scope (PassParams): every MODEL_PBR_IBL draw of the scope, in all its segments, is recorded under the same three images
-        RecordedPass::IblSet set;
+        ScopeHeader::IblSet set{};
         set.irradiance = cmd->ibl[0]->ptr; set.prefiltered = cmd->ibl[1]->ptr; set.lut = cmd->ibl[2]->ptr;
         set.irr_size = cmd->ibl[0]->width; set.pre_size = cmd->ibl[1]->width; set.pre_levels = cmd->ibl[1]->levels; set.lut_size = cmd->ibl[2]->width;
         set.seamless = (cmd->ibl[0]->cube_seamless ? 1u : 0u) | (cmd->ibl[1]->cube_seamless ? 2u : 0u);      // (latched here; the LUT is 2-D and has no such state)
-        if (pass.ibl.irradiance && !(pass.ibl == set))
+        if (pass.scope.ibl.irradiance && !(pass.scope.ibl == set))
             return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: MODEL_PBR_IBL draws recorded under two different IBL sets in one rendering scope");
-        pass.ibl = set;
-        for (mirhi_image* im : cmd->ibl)
-            if (std::find(pass.sampled.begin(), pass.sampled.end(), im) == pass.sampled.end()) pass.sampled.push_back(im);
+        pass.scope.ibl = set;
+        for (mirhi_image* im : cmd->ibl) note_sampled(pass, im);
     }
     if (d.shadow_map) {
         // one raster variant per scope: CalculateShadow (raster_kernel_shadow) or CalculateShadowCSM (raster_kernel_csm; raster_kernel_csm_blend when some
@@ -2324,8 +2326,7 @@ static mirhi_result record_draw(mirhi_cmd* cmd, bool indexed, uint32_t count, ui
         for (const DrawDesc& o : pass.draws)
             if (o.shadow_map && (o.shadow_layers != 0u) != (d.shadow_layers != 0u))
                 return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: draws with a single shadow map and draws with shadow cascades in one rendering scope");
-        mirhi_image* sm = d.shadow_layers ? cmd->cascades : cmd->textures[MIRHI_TEXTURE_SHADOW_MAP];
-        if (std::find(pass.sampled.begin(), pass.sampled.end(), sm) == pass.sampled.end()) pass.sampled.push_back(sm);
+        note_sampled(pass, d.shadow_layers ? cmd->cascades : cmd->textures[MIRHI_TEXTURE_SHADOW_MAP]);
     }
     pass.draws.push_back(d);
     pass.draw_vb_bytes.push_back(vb_bytes);
@@ -2443,7 +2444,6 @@ static mirhi_result xfer_push(mirhi_cmd* cmd, const char* name, uint32_t kind, s
     uint64_t total = 0;
     for (size_t i = 0; i < regions.size(); i++) { regions[i].first = (uint32_t)total; total += units[i]; if (total >= (1ull << 31)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: %s: too much work for one command", name); }
     RecordedPass p;
-    memset(&p.info, 0, sizeof p.info);
     RecordedPass::Transfer& t = p.xfer;
     t.kind = kind; t.count = (uint32_t)regions.size(); t.src_format = src_format; t.dst_format = dst_format;
     if (color) memcpy(t.color, color, sizeof t.color);
@@ -2645,28 +2645,25 @@ static mirhi_result grow(T** ptr, size_t* have, size_t want_bytes) {
 static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit = false);
 static mirhi_result pblock_commit(Workspace& w, hipStream_t stream);
 
-static bool same_target(const RecordedPass::Target& a, const RecordedPass::Target& b) {
-    return a.ptr == b.ptr && a.width == b.width && a.height == b.height && a.format == b.format;
-}
-// Two recordings describe the same frame shape: same attachments, load / store ops, clear values, depth / blend state and, byte for
-// byte, the same draw descriptors (resolved device pointers, counts, viewport, scissor, state).  Buffer CONTENTS are not part of it:
-// the plan holds pointers, and a frame loop that rewrites its uniform buffer between frames records the same shape every time.
+// Two recordings describe the same frame shape: the same scopes (ScopeHeader: attachments as resolved, load / store ops, clear values, area, samples,
+// views, IBL set) and, segment by segment, the same depth / blend state and, byte for byte, the same draw descriptors (resolved device pointers,
+// counts, viewport, scissor, state).  Buffer CONTENTS are not part of it: the plan holds pointers, and a frame loop that rewrites its uniform buffer
+// between frames records the same shape every time.
 // any_color_address: the colour targets may sit at other addresses (same extent and format) -- the recording of a frame loop that cycles N + 1 swapchain images
 // through N command buffers (swapchain.rs:228-236, renderer.rs:377-390): everything the plan holds but PassParams::color is the same then
+static bool same_scope(const ScopeHeader& x, const ScopeHeader& y, bool any_color_address) {
+    if (!any_color_address) return x == y;
+    ScopeHeader a = x, b = y;      // the address replaced by "is set" on both sides
+    a.color.ptr = reinterpret_cast<const uint8_t*>((uintptr_t)(x.color.ptr != nullptr)); b.color.ptr = reinterpret_cast<const uint8_t*>((uintptr_t)(y.color.ptr != nullptr));
+    return a == b;
+}
 static bool same_recording(const std::vector<RecordedPass>& a, const std::vector<RecordedPass>& b, bool any_color_address = false) {
     if (a.size() != b.size()) return false;
     for (size_t i = 0; i < a.size(); i++) {
         const RecordedPass& x = a[i]; const RecordedPass& y = b[i];
-        if (any_color_address ? (x.color_t.width != y.color_t.width || x.color_t.height != y.color_t.height || x.color_t.format != y.color_t.format || !x.color_t.ptr != !y.color_t.ptr)
-                              : !same_target(x.color_t, y.color_t)) return false;
-        if (!same_target(x.depth_t, y.depth_t) || !same_target(x.prim_t, y.prim_t)) return false;
-        if (x.info.color_load_op != y.info.color_load_op || x.info.color_store_op != y.info.color_store_op || x.info.depth_load_op != y.info.depth_load_op ||
-            x.info.depth_store_op != y.info.depth_store_op || memcmp(x.info.clear_color, y.info.clear_color, sizeof x.info.clear_color) != 0 ||
-            memcmp(&x.info.clear_depth, &y.info.clear_depth, sizeof(float)) != 0) return false;
-        if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || !(x.state == y.state) ||
-            x.carry_in != y.carry_in || x.carry_out != y.carry_out || memcmp(x.area, y.area, sizeof x.area) != 0) return false;
-        if (x.samples != y.samples || x.view_mask != y.view_mask || x.view_stride != y.view_stride || x.view_base != y.view_base) return false;
-        if (x.depth_only != y.depth_only || x.sampled != y.sampled || !(x.ibl == y.ibl) || !(x.sky == y.sky)) return false;
+        if (!same_scope(x.scope, y.scope, any_color_address)) return false;
+        if (x.total_tris != y.total_tris || x.first_tri != y.first_tri || !(x.state == y.state) || x.carry_in != y.carry_in || x.carry_out != y.carry_out) return false;
+        if (x.sampled != y.sampled || !(x.sky == y.sky)) return false;
         if (!(x.xfer == y.xfer) || x.xfer_regions.size() != y.xfer_regions.size() ||
             (!x.xfer_regions.empty() && memcmp(x.xfer_regions.data(), y.xfer_regions.data(), x.xfer_regions.size() * sizeof(XferRegion)) != 0)) return false;
         if (x.draws.size() != y.draws.size() || x.draw_vb_bytes != y.draw_vb_bytes) return false;
@@ -2698,7 +2695,7 @@ static bool recording_reads(const std::vector<RecordedPass>& passes, const uint8
                 in(d.shadow_data)) return true;
         }
         // the view constants of a multiview scope (read when it executes): [view_base, the highest view's matrix]
-        if (pass.view_mask && pass.view_base < hi && lo < pass.view_base + (size_t)(31 - __builtin_clz(pass.view_mask)) * pass.view_stride + 64) return true;
+        if (pass.scope.view_mask && pass.scope.view_base < hi && lo < pass.scope.view_base + (size_t)(31 - __builtin_clz(pass.scope.view_mask)) * pass.scope.view_stride + 64) return true;
         // a transfer's buffers, read or written: a host write into either waits for it
         if (pass.xfer.kind && ((pass.xfer.span[0] && pass.xfer.span[0] < hi && lo < pass.xfer.span[1]) || (pass.xfer.span[2] && pass.xfer.span[2] < hi && lo < pass.xfer.span[3]))) return true;
     }
@@ -2727,57 +2724,52 @@ extern "C" void mirhi_debug_host_prof(void) { for (int k = 0; k < 8; k++) fprint
 #define HP(k) do {} while (0)
 #define HP_BEGIN do {} while (0)
 #endif
+// the plan stands for this device and workspace: no feedback of an earlier submission asks for clears, a bigger pool or another plan, and the tile split is
+// the one it was built for
+static bool plan_stands(const mirhi_cmd* cmd) {
+    const mirhi_device* dev = cmd->dev;
+    return cmd->plan_valid && !cmd->ws.grow_pool && !cmd->ws.replan && !cmd->ws.dirty && cmd->plan_split_rank == dev->split_rank && cmd->plan_split_world == dev->split_world &&
+           cmd->plan_split_layout == dev->split_layout;
+}
+// the recording is the planned one but for the addresses of its colour targets: the host copy and both parities of every scope in the parameter block get the new ones
+static mirhi_result retarget_color(mirhi_cmd* cmd) {
+    mirhi_device* dev = cmd->dev;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    hipStream_t stream = dev->lanes[cmd->lane < dev->lanes.size() ? cmd->lane : 0];
+    for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
+        uint8_t* target = const_cast<uint8_t*>(cmd->passes[pi].scope.color.ptr);
+        cmd->plan[pi].color = target;
+        for (size_t parity = 0; parity < 2; parity++) reinterpret_cast<PassParams*>(cmd->ws.pimage.data() + (2 * pi + parity) * sizeof(PassParams))->color = target;
+    }
+    const mirhi_result r = pblock_commit(cmd->ws, stream);
+    if (r != MIRHI_OK) { cmd->plan_valid = false; return r; }
+    if (!cmd->ws.pblock_direct) { cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true; }     // (the copy is in the lane's stream)
+    { std::lock_guard<std::mutex> lk(dev->mu); cmd->planned = cmd->passes; }
+    return MIRHI_OK;
+}
 extern "C" mirhi_result mirhi_cmd_end(mirhi_cmd* cmd) {
     HP_BEGIN;
     REQUIRE_RECORDING(cmd);
     if (cmd->in_rendering) return fail(MIRHI_ERR_DEVICE, "Vulkan error: end() inside an active rendering scope");
-    mirhi_device* dev = cmd->dev;
-    if (cmd->plan_valid && !cmd->ws.grow_pool && !cmd->ws.replan && !cmd->ws.dirty && cmd->plan_split_rank == dev->split_rank && cmd->plan_split_world == dev->split_world && cmd->plan_split_layout == dev->split_layout &&
-        same_recording(cmd->passes, cmd->planned)) {
-        HP(0);
-        // The frame recorded last time, recorded again: plan, workspace and parameter block are what they have to be.  No HIP call,
-        // no synchronisation, nothing uploaded; only the status words of the previous submission are handed over and re-armed.
+    // The frame recorded last time, recorded again: plan, workspace and parameter block are what they have to be.  No HIP call, no synchronisation,
+    // nothing uploaded.  Or the same frame into another swapchain image: the plan stands too, PassParams::color of every scope is rewritten.
+    const bool unchanged = plan_stands(cmd) && same_recording(cmd->passes, cmd->planned);
+    if (unchanged) HP(0);
+    if (unchanged || (plan_stands(cmd) && cmd->plan.size() == cmd->passes.size() && cmd->ws.pimage.size() >= cmd->passes.size() * 2 * sizeof(PassParams) &&
+                      same_recording(cmd->passes, cmd->planned, true))) {
+        // only the status words of the previous submission are handed over and re-armed (a submission that is still pending reads the workspace and the
+        // parameter block: wait for it -- a fenced loop has)
         mirhi_result r = settle_pending(cmd);
         if (r != MIRHI_OK) return r;
         HP(1);
-        if (cmd->ws.status_host && cmd->ws.any_status()) {
-            HP(2);
-            hand_over_status(cmd);
-            HP(3);
-            cmd->ws.clear_status();
-            HP(4);
-        }
-        if (!(cmd->ws.dirty || cmd->ws.replan || cmd->ws.grow_pool)) {      // (the status just handed over may have asked for clears or another plan: rebuild below)
+        bool stands = true;
+        if (cmd->ws.status_host && cmd->ws.any_status()) { HP(2); hand_over_status(cmd); HP(3); cmd->ws.clear_status(); HP(4); stands = plan_stands(cmd); }
+        if (stands) {      // (else the status just handed over asked for clears or another plan: rebuild)
+            if (!unchanged && (r = retarget_color(cmd)) != MIRHI_OK) return r;
             cmd->state = CMD_EXECUTABLE;
             return MIRHI_OK;
         }
     }
-    if (cmd->plan_valid && !cmd->ws.grow_pool && !cmd->ws.replan && !cmd->ws.dirty && cmd->plan_split_rank == dev->split_rank && cmd->plan_split_world == dev->split_world && cmd->plan_split_layout == dev->split_layout &&
-        cmd->plan.size() == cmd->passes.size() && cmd->ws.pimage.size() >= cmd->passes.size() * 2 * sizeof(PassParams) && same_recording(cmd->passes, cmd->planned, true)) {
-        // The same frame into another swapchain image: the plan stands, PassParams::color of every scope is rewritten (host copy, both parities in the parameter block).
-        mirhi_result r = settle_pending(cmd);                  // (the block is read by a submission that is still pending: wait for it -- a fenced loop has)
-        if (r != MIRHI_OK) return r;
-        if (cmd->ws.status_host && cmd->ws.any_status()) {
-            hand_over_status(cmd);
-            cmd->ws.clear_status();
-        }
-        if (cmd->ws.replan || cmd->ws.grow_pool || cmd->ws.dirty) goto rebuild;      // (the status just handed over asked for another plan)
-        {
-            HIP_TRY(hipSetDevice(dev->ordinal));
-            hipStream_t stream = dev->lanes[cmd->lane < dev->lanes.size() ? cmd->lane : 0];
-            for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
-                uint8_t* target = const_cast<uint8_t*>(cmd->passes[pi].color_t.ptr);
-                cmd->plan[pi].color = target;
-                for (size_t parity = 0; parity < 2; parity++) reinterpret_cast<PassParams*>(cmd->ws.pimage.data() + (2 * pi + parity) * sizeof(PassParams))->color = target;
-            }
-            if ((r = pblock_commit(cmd->ws, stream)) != MIRHI_OK) { cmd->plan_valid = false; return r; }
-            if (!cmd->ws.pblock_direct) { cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true; }     // (the copy is in the lane's stream)
-            { std::lock_guard<std::mutex> lk(dev->mu); cmd->planned = cmd->passes; }
-            cmd->state = CMD_EXECUTABLE;
-            return MIRHI_OK;
-        }
-    }
-rebuild:
     mirhi_result r = build_plan(cmd);
     if (r != MIRHI_OK) { cmd->plan_valid = false; return r; }
     cmd->state = CMD_EXECUTABLE;
@@ -2852,20 +2844,20 @@ struct ScopePlan {
 };
 static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, const Workspace& w, const PlanKnobs& knobs) {
     ScopePlan s;
-    s.tiles_x = (pass.color_t.width + TILE - 1) / TILE; s.tiles_y = (pass.color_t.height + TILE - 1) / TILE;
+    s.tiles_x = (pass.scope.color.width + TILE - 1) / TILE; s.tiles_y = (pass.scope.color.height + TILE - 1) / TILE;
     { uint32_t count; split_rows(dev->split_layout, dev->split_rank, dev->split_world, s.tiles_y, &s.r0, &s.rstep, &count); s.r1 = s.r0 + count; }
-    if (pass.depth_only) { s.r0 = 0; s.r1 = s.tiles_y; s.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
+    if (pass.scope.depth_only) { s.r0 = 0; s.r1 = s.tiles_y; s.rstep = 1; }      // every rank renders the whole depth image (include/mirhi.h, tile split)
     // (a transfer is not split: every rank moves what its own memory holds; one "tile" for the workspace's sizes, the launch's workgroups are fill_params')
     if (pass.xfer.kind) { s.tiles_x = 1u; s.tiles_y = 1u; s.r0 = 0u; s.r1 = 1u; s.rstep = 1u; }
     // The render area (validated by begin_rendering; never partial on a split device): its tile rows take the place of the band's -- bins, counters and
     // the raster grid are indexed by the owned row already --, its tile columns are a sub-range of the launch alone.  One evaluation per scope.
     s.area = RenderArea{};
     if (!pass.xfer.kind) {
-        s.area = render_area(pass.color_t.width, pass.color_t.height, pass.area);
+        s.area = render_area(pass.scope.color.width, pass.scope.color.height, pass.scope.area);
         if (s.area.partial) { s.r0 = s.area.row_begin; s.r1 = s.area.row_end; s.rstep = 1; }
     }
     s.tris = pass.total_tris - pass.first_tri;
-    s.cls = classify_scope(pass.state, pass.info.clear_depth, pass.draws.data(), pass.draws.size(), pass.depth_only, knobs, pass.sky.on != 0u, pass.xfer.kind != 0u, pass.samples);
+    s.cls = classify_scope(pass.state, pass.scope.clear_depth, pass.draws.data(), pass.draws.size(), pass.scope.depth_only, knobs, pass.sky.on != 0u, pass.xfer.kind != 0u, pass.scope.samples);
     s.mode = raster_mode(s.cls, s.density_tiles(), s.tris, w.spread, w.wide, knobs, s.area.partial);
     s.bins = bin_geometry(s.launched(), s.tris, pass.total_tris, s.mode.xcd_bins, w.pool_scale, knobs, s.tiles());
     return s;
@@ -2977,9 +2969,9 @@ static mirhi_result grow_scope_buffers(Workspace& w, const std::vector<RecordedP
     for (size_t pi = 0; pi < passes.size(); pi++) {
         const RecordedPass& pass = passes[pi];
         vs_bytes = std::max(vs_bytes, vertex[pi].out_bytes);
-        if ((pass.carry_in || pass.carry_out) && !pass.depth_t.ptr) carry = std::max(carry, (size_t)pass.color_t.width * pass.color_t.height * 4);
+        if ((pass.carry_in || pass.carry_out) && !pass.scope.depth.ptr) carry = std::max(carry, (size_t)pass.scope.color.width * pass.scope.color.height * 4);
         if (scopes[pi].cls.ordered) ord = std::max(ord, scopes[pi].tris * sizeof(TriRec));
-        if (scopes[pi].cls.tri_prog && pass.color_t.format == MIRHI_FORMAT_B8G8R8A8_SRGB) flat_tris = std::max<size_t>(flat_tris, pass.total_tris);
+        if (scopes[pi].cls.tri_prog && pass.scope.color.format == MIRHI_FORMAT_B8G8R8A8_SRGB) flat_tris = std::max<size_t>(flat_tris, pass.total_tris);
         if (pass.draws.size() > 1) pd = std::max(pd, scopes[pi].tris);
     }
     if ((r = grow(&w.vs_out, &w.vs_out_bytes, vs_bytes ? vs_bytes : 256)) != MIRHI_OK) return r;
@@ -2997,8 +2989,8 @@ static mirhi_result grow_multiview(mirhi_cmd* cmd, const std::vector<ScopePlan>&
     Workspace& w = cmd->ws;
     size_t slots = 0, pages = 0, tiles = 0, big = 0, vs = 0;
     for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
-        if (!cmd->passes[pi].view_mask) continue;
-        slots = std::max<size_t>(slots, multiview_count(cmd->passes[pi].view_mask));
+        if (!cmd->passes[pi].scope.view_mask) continue;
+        slots = std::max<size_t>(slots, multiview_count(cmd->passes[pi].scope.view_mask));
         pages = std::max(pages, scopes[pi].bins.pages); tiles = std::max(tiles, scopes[pi].tiles());
         big = std::max<size_t>(big, scopes[pi].bins.big_cap); vs = std::max(vs, vertex[pi].out_bytes);
     }
@@ -3043,7 +3035,7 @@ static mirhi_result grow_multiview(mirhi_cmd* cmd, const std::vector<ScopePlan>&
 
 // 4. one scope's parameters from its class, mode, bins and the workspace (the draws and vertex jobs are placed by build_plan)
 static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, const RasterMode& mode, const Workspace& w, size_t max_tiles, unsigned long long* frag_stats) {
-    const RecordedPass::Target& ci = pass.color_t;
+    const ScopeHeader::Target& ci = pass.scope.color;
     const size_t pool_pages = w.bin_pool_bytes / (BIN_PAGE_RECS * sizeof(BinRec));
     PassParams P;
     memset(&P, 0, sizeof P);
@@ -3055,26 +3047,26 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
     P.tile_col_begin = s.area.partial ? s.area.col_begin : 0u; P.tile_cols = s.area.partial ? s.area.col_end - s.area.col_begin : s.tiles_x;
     P.num_draws = (uint32_t)pass.draws.size(); P.total_tris = pass.total_tris;
     set_raster_choice(P, s.cls, mode, pass.state, w.ordered, pass.first_tri, pass.total_tris);
-    memcpy(P.clear_color, pass.info.clear_color, sizeof P.clear_color);
+    memcpy(P.clear_color, pass.scope.clear_color, sizeof P.clear_color);
     {   // sRGB OETF + UNORM8 of the clear colour, BGRA byte order (swapchain.rs:561-570)
         auto sat = [](float c) { return c > 0.0f ? (c < 1.0f ? c : 1.0f) : 0.0f; };
         auto enc = [&](float c) { c = sat(c); float e = c <= 0.0031308f ? 12.92f * c : 1.055f * std::pow(c, 1.0f / 2.4f) - 0.055f; return (uint32_t)std::nearbyint(sat(e) * 255.0f); };
         P.clear_packed = enc(P.clear_color[2]) | (enc(P.clear_color[1]) << 8) | (enc(P.clear_color[0]) << 16) |
                          ((uint32_t)std::nearbyint(sat(P.clear_color[3]) * 255.0f) << 24);
     }
-    P.color_load = pass.info.color_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
+    P.color_load = pass.scope.color_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
     P.color_format = ci.format;
     P.color = const_cast<uint8_t*>(ci.ptr);
-    if (pass.depth_t.ptr) {
-        P.depth = (float*)const_cast<uint8_t*>(pass.depth_t.ptr);
-        P.depth_load = pass.info.depth_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
-        P.depth_store = pass.info.depth_store_op == MIRHI_STORE_OP_STORE ? 1u : 0u;
+    if (pass.scope.depth.ptr) {
+        P.depth = (float*)const_cast<uint8_t*>(pass.scope.depth.ptr);
+        P.depth_load = pass.scope.depth_load_op == MIRHI_LOAD_OP_LOAD ? 1u : 0u;
+        P.depth_store = pass.scope.depth_store_op == MIRHI_STORE_OP_STORE ? 1u : 0u;
     } else if (pass.carry_in || pass.carry_out) {
         P.depth = w.carry_depth;               // no depth attachment: the segments of the scope hand depth over here
     }
     if (pass.carry_in) P.depth_load = 1u;
     if (pass.carry_out) P.depth_store = 1u;
-    P.prim_out = (uint32_t*)const_cast<uint8_t*>(pass.prim_t.ptr);
+    P.prim_out = (uint32_t*)const_cast<uint8_t*>(pass.scope.prim.ptr);
     P.bin_pool = w.bin_pool; P.bin_count = w.counters + CTR_BINS; P.bin_cap = s.bins.bin_cap;
     P.bin_table = w.bin_table; P.pool_next = w.counters + CTR_POOL;
     P.pool_dyn_base = s.bins.fixed_pages; P.pool_dyn_pages = (uint32_t)((pool_pages - s.bins.fixed_pages) / 8);      // per XCD
@@ -3085,15 +3077,15 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
     P.first_prim = pass.first_tri;
     P.prim_draw = pass.draws.size() > 1 ? w.prim_draw : nullptr;
     // (a multisampled scope averages linear colours: no packed flat colours)
-    P.flat_color = (s.cls.tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB && pass.samples == 1u) ? w.flat_color : nullptr;
+    P.flat_color = (s.cls.tri_prog && ci.format == MIRHI_FORMAT_B8G8R8A8_SRGB && pass.scope.samples == 1u) ? w.flat_color : nullptr;
     P.resolve_flat_only = (P.flat_color && !P.depth_load && P.color_format != 2u && !P.prim_out && !(P.depth && P.depth_store)) ? 1u : 0u;
     P.sub_cap = s.bins.sub_cap;                                       // (the bins are those the workspace was sized for: s.mode, not `mode`)
     P.count_stride = s.mode.xcd_bins ? (uint32_t)max_tiles : 0u;
-    P.depth_only = pass.depth_only ? 1u : 0u;
+    P.depth_only = pass.scope.depth_only ? 1u : 0u;
     if (P.ibl) {
-        P.ibl_irradiance = (const float*)pass.ibl.irradiance; P.ibl_prefiltered = (const float*)pass.ibl.prefiltered; P.ibl_lut = (const float*)pass.ibl.lut;
-        P.ibl_irr_size = pass.ibl.irr_size; P.ibl_pre_size = pass.ibl.pre_size; P.ibl_pre_levels = pass.ibl.pre_levels; P.ibl_lut_size = pass.ibl.lut_size;
-        P.ibl_seamless = pass.ibl.seamless;
+        P.ibl_irradiance = (const float*)pass.scope.ibl.irradiance; P.ibl_prefiltered = (const float*)pass.scope.ibl.prefiltered; P.ibl_lut = (const float*)pass.scope.ibl.lut;
+        P.ibl_irr_size = pass.scope.ibl.irr_size; P.ibl_pre_size = pass.scope.ibl.pre_size; P.ibl_pre_levels = pass.scope.ibl.pre_levels; P.ibl_lut_size = pass.scope.ibl.lut_size;
+        P.ibl_seamless = pass.scope.ibl.seamless;
     }
     if (P.sky) {
         const RecordedPass::SkyDraw& k = pass.sky;
@@ -3139,10 +3131,10 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         scopes.push_back(plan_scope(dev, pass, w, knobs));
         // (begin_rendering refuses it; a device split after the recording is met here)
         if (scopes.back().area.partial && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a partial render area on a split device");
-        if (pass.samples != 1u && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a multisampled scope on a split device");
-        if (pass.samples != 1u && (dev->profiling & MIRHI_PROFILE_FRAGMENTS)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: fragment statistics of a multisampled scope");
-        if (pass.view_mask && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a multiview scope on a split device");
-        if (pass.view_mask && (dev->profiling & MIRHI_PROFILE_FRAGMENTS)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: fragment statistics of a multiview scope");
+        if (pass.scope.samples != 1u && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a multisampled scope on a split device");
+        if (pass.scope.samples != 1u && (dev->profiling & MIRHI_PROFILE_FRAGMENTS)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: fragment statistics of a multisampled scope");
+        if (pass.scope.view_mask && dev->split_world > 1) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: a multiview scope on a split device");
+        if (pass.scope.view_mask && (dev->profiling & MIRHI_PROFILE_FRAGMENTS)) return fail(MIRHI_ERR_INVALID_HANDLE, "Invalid handle: unsupported: fragment statistics of a multiview scope");
         total_draws += pass.draws.size();
         total_regions += pass.xfer_regions.size();
         max_tiles = std::max(max_tiles, scopes.back().tiles());
@@ -3157,7 +3149,7 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     // read: [2 x PassParams per view slot][their draw descriptors][their vertex jobs]
     size_t mv_views = 0, mv_draws = 0, mv_jobs = 0;
     for (size_t pi = 0; pi < n; pi++)
-        if (const uint32_t views = multiview_count(cmd->passes[pi].view_mask)) { mv_views += views; mv_draws += views * cmd->passes[pi].draws.size(); mv_jobs += views * vertex[pi].jobs.size(); }
+        if (const uint32_t views = multiview_count(cmd->passes[pi].scope.view_mask)) { mv_views += views; mv_draws += views * cmd->passes[pi].draws.size(); mv_jobs += views * vertex[pi].jobs.size(); }
     const size_t params_bytes = n * 2 * sizeof(PassParams);
     w.draws_off = (params_bytes + 255) & ~(size_t)255;
     const size_t regions_off = (w.draws_off + total_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
@@ -3227,16 +3219,16 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
         // slot's shaded vertices are) alone.  (plan[pi] itself stays: the host's idea of the scope's launch shape; its device copies are not launched.)
         mirhi_cmd::ViewSet vset;
         const RecordedPass& pass = cmd->passes[pi];
-        if (pass.view_mask) {
+        if (pass.scope.view_mask) {
             MultiviewSlot slot[MAX_BATCH];
-            vset.count = multiview_slots(pass.view_mask, pass.color_t.width, pass.color_t.height, 0u, pass.view_stride, slot);
+            vset.count = multiview_slots(pass.scope.view_mask, pass.scope.color.width, pass.scope.color.height, 0u, pass.scope.view_stride, slot);
             vset.first = views_done;
             for (uint32_t j = 0; j < vset.count; j++) {
-                const float* matrix = reinterpret_cast<const float*>(pass.view_base + slot[j].matrix_offset);
+                const float* matrix = reinterpret_cast<const float*>(pass.scope.view_base + slot[j].matrix_offset);
                 uint8_t* const vs_base = w.mv_vs + (size_t)j * w.mv_vs_stride;
                 uint32_t* const ctr = w.mv_counters + (size_t)j * w.mv_counter_words;
                 PassParams V = P;
-                V.depth = reinterpret_cast<float*>(const_cast<uint8_t*>(pass.depth_t.ptr) + slot[j].layer_offset);
+                V.depth = reinterpret_cast<float*>(const_cast<uint8_t*>(pass.scope.depth.ptr) + slot[j].layer_offset);
                 V.bin_pool = w.mv_pool + (size_t)j * w.mv_pool_pages * BIN_PAGE_RECS;
                 V.bin_table = w.mv_table + (size_t)j * w.mv_tiles * BIN_TABLE_ROW;
                 V.bin_count = ctr + CTR_BINS; V.pool_next = ctr + CTR_POOL;
@@ -3465,7 +3457,7 @@ template <typename F>
 static void for_each_attachment(mirhi_device* dev, const mirhi_cmd* c, F&& f) {
     for (const RecordedPass& pass : c->planned) {
         // a layer view stands for its array: scopes that write layers and scopes that sample the array meet on one object (a live view's array is alive)
-        for (mirhi_image* img : {pass.info.color_image, pass.info.depth_image, pass.info.prim_id_image})
+        for (mirhi_image* img : {pass.images.color, pass.images.depth, pass.images.prim_id})
             if (img && std::find(dev->images.begin(), dev->images.end(), img) != dev->images.end()) f(img->parent ? img->parent : img);
         // the shadow maps the scope samples count as attachments: a read after another lane's write (the shadow scope) and a write after another lane's
         // read (the next frame's shadow scope behind this frame's lit one) are both ordered
