@@ -589,6 +589,55 @@ struct RecordedPass {
 constexpr uint32_t CTR_BIG = 0u, CTR_POOL = 32u, CTR_ACTIVE = CTR_POOL + 8u * (uint32_t)POOL_COUNTER_STRIDE,   // busy-tile counters: two parities x 8 x 32 words
                    CTR_BINS = CTR_ACTIVE + 2u * 8u * 32u + 32u;
 
+// A bin set: the five device buffers a rendering scope works against -- bin pool, page table, counter block, big-triangle list, vertex output -- as
+// `slots` equal slices, one hipMalloc per buffer.  A command buffer has two (Workspace): the scopes' own, of one slot, and the view slots' of its multiview
+// scopes, of up to MAX_BATCH, so that the views of a scope run side by side and leave the scopes' set alone.  The slices only grow, and the kernels
+// leave counters and tables re-armed; a slot's big-list parity flips when the slot is used, whatever the other slots and the other set do.
+struct BinSet {
+    BinRec* pool = nullptr; size_t pool_bytes = 0;              // pages of BIN_PAGE_RECS records: fixed first pages, then the dynamic ones
+    uint32_t* table = nullptr; size_t table_bytes = 0;          // [tiles][BIN_TABLE_ROW] page table, PAGE_EMPTY when idle
+    uint32_t* counters = nullptr; size_t counters_bytes = 0;    // CTR_*: two big-list counters, the pool counters, the busy-tile counters, the bin counts
+    BigRec* big = nullptr; size_t big_bytes = 0;
+    uint8_t* vs = nullptr; size_t vs_bytes = 0;
+    struct Strides { size_t pages = 0, tiles = 0, counter_words = 0, big_cap = 0, vs_bytes = 0; } stride;      // of one slot, in the units named
+    uint32_t slots = 0;
+    uint32_t parity = 0;                                        // bit j: which of slot j's two big-list counters its next scope appends to
+    bool dirty = true;                                          // counters / page table not known to be in their idle state: cleared at the next plan
+    // slot j's base pointers (and the pages of its pool): all that anything downstream of the growth knows of the slices
+    struct Slot { BinRec* pool; size_t pages; uint32_t* table; uint32_t* counters; BigRec* big; uint8_t* vs; };
+    Slot slot(size_t j) const {
+        return Slot{pool + j * stride.pages * BIN_PAGE_RECS, stride.pages, table + j * stride.tiles * BIN_TABLE_ROW, counters + j * stride.counter_words, big + j * stride.big_cap,
+                    vs + j * stride.vs_bytes};
+    }
+    uint32_t parity_of(uint32_t j) const { return (parity >> j) & 1u; }
+    uint32_t take_parity(uint32_t j) { const uint32_t p = parity_of(j); parity ^= 1u << j; return p; }      // the slot's current parity; its next scope gets the other
+    size_t bytes() const { return pool_bytes + table_bytes + counters_bytes + big_bytes + vs_bytes; }
+    void free_buffers() { for (void* p : {(void*)pool, (void*)table, (void*)counters, (void*)big, (void*)vs}) if (p) (void)hipFree(p); }
+};
+
+// Where the pieces of the parameter block start (bytes, each 256-aligned): [2 x PassParams per scope][draw descriptors][transfer regions][vertex jobs], and
+// behind them what the views of multiview scopes read: [2 x PassParams per view slot][their draw descriptors][their vertex jobs].  `bytes`: all of it (without
+// a multiview scope the block ends behind the scopes' vertex jobs).
+struct BlockLayout {
+    size_t draws = 0, regions = 0, jobs = 0, view_params = 0, view_draws = 0, view_jobs = 0, bytes = 0;
+    // the device copy of scope `pi` / of view slot `slot` of the plan (mirhi_cmd::ViewSet::first + j) for big-list parity `parity`
+    static size_t scope_params(size_t pi, uint32_t parity) { return (2 * pi + parity) * sizeof(PassParams); }
+    size_t slot_params(size_t slot, uint32_t parity) const { return view_params + (2 * slot + parity) * sizeof(PassParams); }
+};
+static BlockLayout block_layout(size_t scopes, size_t draws, size_t regions, size_t jobs, size_t views, size_t view_draws, size_t view_jobs) {
+    auto align256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    BlockLayout l;
+    l.draws = align256(scopes * 2 * sizeof(PassParams));
+    l.regions = align256(l.draws + draws * sizeof(DrawDesc));
+    l.jobs = align256(l.regions + regions * sizeof(XferRegion));
+    l.bytes = l.jobs + jobs * sizeof(VsJob);
+    l.view_params = align256(l.bytes);
+    l.view_draws = align256(l.view_params + views * 2 * sizeof(PassParams));
+    l.view_jobs = align256(l.view_draws + view_draws * sizeof(DrawDesc));
+    if (views) l.bytes = l.view_jobs + view_jobs * sizeof(VsJob);
+    return l;
+}
+
 struct Workspace {
     // Parameter block: everything the kernels read as "parameters" -- two PassParams per scope (big-list counter parity 0 / 1), the
     // draw descriptors, the vertex pre-pass jobs -- in ONE piece of fine-grained device memory that the host writes directly
@@ -599,10 +648,8 @@ struct Workspace {
     bool foreign = false;                                                             // the block went up through a copy engine (fallback): the next scope acquires at system scope
     uint8_t* pstage = nullptr; size_t pstage_bytes = 0;                                // pinned staging for the fallback (hipMemcpyAsync on the lane)
     std::vector<uint8_t> pshadow, pimage;                                              // what the block holds / what it should hold
-    size_t draws_off = 0, jobs_off = 0, draws_count = 0;
-    bool dirty = true;                                         // counters / page table not known to be in their idle state: cleared at the next plan
-    BinRec* bin_pool = nullptr; size_t bin_pool_bytes = 0;     // pages of BIN_PAGE_RECS records: fixed first pages, then the dynamic ones
-    uint32_t* bin_table = nullptr; size_t bin_table_bytes = 0; // [tiles][BIN_TABLE_ROW] page table, PAGE_EMPTY when idle
+    BlockLayout layout;                                                                // where its pieces start
+    BinSet scope_bins, view_bins;                              // the scopes' bins (one slot) and those of the multiview scopes' view slots
     uint32_t pool_scale = 1;                                   // doubled whenever a scope exhausted the pool (applied at the next submit)
     bool grow_pool = false;
     // Feedback on the two-team mesh mode (raster_mode picks it from the triangle count alone: 'few triangles per tile' is a mesh
@@ -619,12 +666,9 @@ struct Workspace {
     uint64_t spread_tris = 0;                                  // triangles of the command buffer when `spread` was measured: forgotten when the
                                                                // recorded frame is another one (more than twice / less than half as many)
     uint32_t xcd_tiles_last = 0;                               // tiles of the command buffer's last scope if it uses per-XCD bins, else 0
-    uint32_t* counters = nullptr; size_t counters_words = 0;   // [8 * tiles] bin counts, two big-list counters, the pool counter
-    BigRec* big_recs = nullptr; size_t big_recs_bytes = 0;
     float* carry_depth = nullptr; size_t carry_depth_bytes = 0;   // depth hand-over between the segments of a scope without a depth attachment
     TriRec* ordered = nullptr; size_t ordered_bytes = 0;          // slot t = triangle t of an ordered segment (blending)
     PassParams* params = nullptr;                            // = pblock: two copies per scope (big-list counter parity 0 / 1), read by the kernels
-    uint8_t* vs_out = nullptr; size_t vs_out_bytes = 0;
     uint32_t* flat_color = nullptr; size_t flat_color_bytes = 0;
     uint32_t* prim_draw = nullptr; size_t prim_draw_bytes = 0;     // per primitive: its draw (scopes with several draws)
     uint32_t* status_host = nullptr;                             // pinned, device-mapped: [status bits, big-list length]
@@ -635,27 +679,13 @@ struct Workspace {
     // status bits of the last submission: the scopes' own and those of every view slot
     uint32_t status_bits() const { uint32_t b = status_host[0]; for (uint32_t j = 0; j < (uint32_t)MAX_BATCH; j++) b |= status_host[STATUS_VIEWS + 4u * j]; return b; }
     bool any_status() const { uint32_t b = 0; for (uint32_t i = 0; i < STATUS_WORDS; i++) b |= status_host[i]; return b != 0; }
-    // Multiview depth scopes: view slot j has bins, page table, counters, big list and vertex output of its own -- the j-th slice of these
-    // buffers (strides in the units named) -- so that the views of a scope can run side by side; the single-view buffers above are not touched by such a scope.
-    // Like those, the slices only grow, and their counters and tables are left re-armed by the kernels; a slot's big-list parity (bit j of mv_parity) flips
-    // when the slot is used, whatever the other scopes of the command buffer do.
-    BinRec* mv_pool = nullptr; size_t mv_pool_bytes = 0, mv_pool_pages = 0;
-    uint32_t* mv_table = nullptr; size_t mv_table_bytes = 0, mv_tiles = 0;
-    uint32_t* mv_counters = nullptr; size_t mv_counters_bytes = 0, mv_counter_words = 0;
-    BigRec* mv_big = nullptr; size_t mv_big_bytes = 0, mv_big_cap = 0;
-    uint8_t* mv_vs = nullptr; size_t mv_vs_bytes = 0, mv_vs_stride = 0;
-    uint32_t mv_slots = 0, mv_parity = 0; bool mv_dirty = true;
-    size_t mv_params_off = 0;                                    // where the views' PassParams start in the parameter block (two per view slot: parity 0 / 1)
-    uint32_t* big_counts = nullptr;                              // two counters, used alternately (parity)
-    uint32_t parity = 0;
     // statistics pass (MIRHI_PROFILE_FRAGMENTS), built on first use: a primitive-id image of the workspace's own and copies
     // of the scopes' parameters that write it, so that the product kernels and parameters stay untouched
     uint32_t* stats_prim = nullptr; size_t stats_prim_bytes = 0;
     PassParams* stats_params = nullptr; size_t stats_params_bytes = 0; bool stats_params_valid = false;
-    size_t bytes() const {
-        return pblock_bytes + bin_pool_bytes + bin_table_bytes + counters_words * 4 + big_recs_bytes + vs_out_bytes + flat_color_bytes + mv_pool_bytes + mv_table_bytes +
-               mv_counters_bytes + mv_big_bytes + mv_vs_bytes;
-    }
+    // (what bench.py reports and test_gpu_parity bounds: the parameter block, the two bin sets and the flat colours -- carry_depth, ordered, prim_draw and the
+    // statistics buffers have never been counted)
+    size_t bytes() const { return pblock_bytes + scope_bins.bytes() + view_bins.bytes() + flat_color_bytes; }
 };
 
 enum CmdState { CMD_INITIAL = 0, CMD_RECORDING = 1, CMD_EXECUTABLE = 2 };
@@ -700,7 +730,7 @@ struct mirhi_cmd {
     std::vector<uint32_t> plan_programs;
     uint64_t plan_tris = 0;
     // multiview scopes of the plan: per entry of `plan` its view slots (count 0: a single-view scope) and where their parameters start -- `first` counts view
-    // slots of the whole plan: plan_view_params[first + j] is slot j's host copy, its two device copies are PassParams 2 * (first + j) + parity behind mv_params_off
+    // slots of the whole plan: plan_view_params[first + j] is slot j's host copy, its two device copies are at BlockLayout::slot_params(first + j, parity)
     struct ViewSet { uint32_t count = 0; size_t first = 0; };
     std::vector<ViewSet> plan_views;
     std::vector<PassParams> plan_view_params;
@@ -1601,19 +1631,14 @@ static void free_workspace(mirhi_cmd* c) {
     Workspace& w = c->ws;
     if (w.pblock) (void)hipFree(w.pblock);
     if (w.pstage) (void)hipHostFree(w.pstage);
-    if (w.bin_pool) (void)hipFree(w.bin_pool);
-    if (w.bin_table) (void)hipFree(w.bin_table);
-    if (w.counters) (void)hipFree(w.counters);
-    if (w.big_recs) (void)hipFree(w.big_recs);
+    w.scope_bins.free_buffers(); w.view_bins.free_buffers();
     if (w.carry_depth) (void)hipFree(w.carry_depth);
     if (w.ordered) (void)hipFree(w.ordered);
-    if (w.vs_out) (void)hipFree(w.vs_out);
     if (w.flat_color) (void)hipFree(w.flat_color);
     if (w.prim_draw) (void)hipFree(w.prim_draw);
     if (w.stats_prim) (void)hipFree(w.stats_prim);
     if (w.stats_params) (void)hipFree(w.stats_params);
     if (w.status_host) (void)hipHostFree(w.status_host);
-    for (void* p : {(void*)w.mv_pool, (void*)w.mv_table, (void*)w.mv_counters, (void*)w.mv_big, (void*)w.mv_vs}) if (p) (void)hipFree(p);
     w = Workspace();
 }
 
@@ -2728,7 +2753,7 @@ extern "C" void mirhi_debug_host_prof(void) { for (int k = 0; k < 8; k++) fprint
 // the one it was built for
 static bool plan_stands(const mirhi_cmd* cmd) {
     const mirhi_device* dev = cmd->dev;
-    return cmd->plan_valid && !cmd->ws.grow_pool && !cmd->ws.replan && !cmd->ws.dirty && cmd->plan_split_rank == dev->split_rank && cmd->plan_split_world == dev->split_world &&
+    return cmd->plan_valid && !cmd->ws.grow_pool && !cmd->ws.replan && !cmd->ws.scope_bins.dirty && cmd->plan_split_rank == dev->split_rank && cmd->plan_split_world == dev->split_world &&
            cmd->plan_split_layout == dev->split_layout;
 }
 // the recording is the planned one but for the addresses of its colour targets: the host copy and both parities of every scope in the parameter block get the new ones
@@ -2739,7 +2764,7 @@ static mirhi_result retarget_color(mirhi_cmd* cmd) {
     for (size_t pi = 0; pi < cmd->passes.size(); pi++) {
         uint8_t* target = const_cast<uint8_t*>(cmd->passes[pi].scope.color.ptr);
         cmd->plan[pi].color = target;
-        for (size_t parity = 0; parity < 2; parity++) reinterpret_cast<PassParams*>(cmd->ws.pimage.data() + (2 * pi + parity) * sizeof(PassParams))->color = target;
+        for (uint32_t parity = 0; parity < 2; parity++) reinterpret_cast<PassParams*>(cmd->ws.pimage.data() + BlockLayout::scope_params(pi, parity))->color = target;
     }
     const mirhi_result r = pblock_commit(cmd->ws, stream);
     if (r != MIRHI_OK) { cmd->plan_valid = false; return r; }
@@ -2863,35 +2888,76 @@ static ScopePlan plan_scope(const mirhi_device* dev, const RecordedPass& pass, c
     return s;
 }
 
-// 2. bins, page table, big list and counters for the largest scope; the previous submission's status handed over; everything re-armed.
+// 2. the bin sets: growth, idle check and clears, once for both (rearm_workspace: the scopes' set; grow_multiview: the view slots').
 // Buffers only ever grow, and a frame loop's do not: the steady state allocates nothing.  Counters and page table are cleared
-// when they are new (or after a frame that went wrong on the device: Workspace::dirty) -- never otherwise: every kernel leaves
+// when they are new (or after a frame that went wrong on the device: BinSet::dirty) -- never otherwise: every kernel leaves
 // them re-armed (raster_body: bin counters, table rows, pool counters, the other parity's big-list counter), and the fixed
 // words of the counter block do not move when the tile count changes (CTR_*).
+//
+// Growth to `slots` slices of at least the strides `want`.  What growth costs is where the two sets differ, and that is `together`:
+//   false (the scopes' set, one slot): each buffer grows on its own, and the set is dirty only when the table or the counters are new memory -- a
+//         bigger pool or big list moves nothing that the kernels left armed;
+//   true  (the view slots): a stride or the slot count that grew moves the slices, so all five buffers are sized anew and the set is dirty.
+// A buffer whose stride is 0 is not allocated (the scopes' vertex output is sized with the other buffers that the scopes' contents decide: grow_scope_buffers).
+static mirhi_result grow_bins(BinSet& b, size_t slots, const BinSet::Strides& want, bool together) {
+    BinSet::Strides& s = b.stride;
+    const bool grew = slots > b.slots || want.pages > s.pages || want.tiles > s.tiles || want.counter_words > s.counter_words || want.big_cap > s.big_cap || want.vs_bytes > s.vs_bytes;
+    b.slots = (uint32_t)std::max<size_t>(slots, b.slots);
+    s.pages = std::max(want.pages, s.pages); s.tiles = std::max(want.tiles, s.tiles); s.counter_words = std::max(want.counter_words, s.counter_words);
+    s.big_cap = std::max(want.big_cap, s.big_cap); s.vs_bytes = std::max(want.vs_bytes, s.vs_bytes);
+    const size_t n = b.slots, table_bytes = n * s.tiles * BIN_TABLE_ROW * sizeof(uint32_t), counters_bytes = n * s.counter_words * sizeof(uint32_t);
+    const bool had = b.table && b.table_bytes >= table_bytes && b.counters && b.counters_bytes >= counters_bytes;
+    if (together ? grew : !had) b.dirty = true;
+    mirhi_result r;
+    if ((r = grow(&b.pool, &b.pool_bytes, n * s.pages * BIN_PAGE_RECS * sizeof(BinRec))) != MIRHI_OK) return r;
+    if ((r = grow(&b.table, &b.table_bytes, table_bytes)) != MIRHI_OK) return r;
+    if ((r = grow(&b.counters, &b.counters_bytes, counters_bytes)) != MIRHI_OK) return r;
+    if ((r = grow(&b.big, &b.big_bytes, n * s.big_cap * sizeof(BigRec))) != MIRHI_OK) return r;
+    if (s.vs_bytes && (r = grow(&b.vs, &b.vs_bytes, n * s.vs_bytes)) != MIRHI_OK) return r;
+    return MIRHI_OK;
+}
+// ... and the set's idle state: checked on request where the plan relies on it, restored by two clears where it is not known.  `which`: "" / "multiview ".
+static mirhi_result rearm_bins(mirhi_cmd* cmd, BinSet& b, const char* which, hipStream_t stream, const PlanKnobs& knobs) {
+    if (!b.dirty && knobs.verify_idle.set) {
+        // Test hook: what the plan relies on instead of clearing -- every kernel leaves the workspace re-armed -- is checked here, on the
+        // host: all bin and pool counters zero, the big-list counter of every slot's next parity zero, every page-table entry PAGE_EMPTY.
+        HIP_TRY(hipStreamSynchronize(stream));
+        const size_t words = b.stride.counter_words;
+        std::vector<uint32_t> c(b.slots * words), t((size_t)b.slots * b.stride.tiles * BIN_TABLE_ROW);
+        HIP_TRY(hipMemcpy(c.data(), b.counters, c.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t.data(), b.table, t.size() * 4, hipMemcpyDeviceToHost));
+        size_t bad_c = 0, bad_t = 0;
+        for (uint32_t j = 0; j < b.slots; j++)
+            for (size_t i = 0; i < words; i++)       // (the last length of the slot's big list; the busy-tile counters of its last scope, read and re-armed by the next one)
+                bad_c += (c[j * words + i] != 0u && i != (size_t)(CTR_BIG + (b.parity_of(j) ^ 1u)) && !(i >= CTR_ACTIVE && i < CTR_ACTIVE + 2u * 8u * 32u)) ? 1 : 0;
+        for (uint32_t v : t) bad_t += v != PAGE_EMPTY ? 1 : 0;
+        if (bad_c || bad_t) return fail(MIRHI_ERR_DEVICE, "Vulkan error: %sworkspace not idle between frames: %zu counter words, %zu page-table entries left set", which, bad_c, bad_t);
+    }
+    if (b.dirty) {
+        HIP_TRY(hipMemsetAsync(b.table, 0xFF, b.table_bytes, stream));          // PAGE_EMPTY
+        HIP_TRY(hipMemsetAsync(b.counters, 0, b.counters_bytes, stream));
+        cmd->dev->foreign_writes++;
+        b.parity = 0;
+        b.dirty = false;
+        cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true;      // (a submit on another stream or queue waits for the clears)
+    }
+    return MIRHI_OK;
+}
+
+// The scopes' set for the largest scope; the previous submission's status handed over; everything re-armed.
 static mirhi_result rearm_workspace(mirhi_cmd* cmd, const std::vector<ScopePlan>& scopes, size_t max_tiles, hipStream_t stream, const PlanKnobs& knobs) {
     Workspace& w = cmd->ws;
     mirhi_result r;
     size_t max_pages = 0, max_big = 0;
     bool any_xcd_bins = false;
     for (const ScopePlan& s : scopes) { max_pages = std::max(max_pages, s.bins.pages); max_big = std::max<size_t>(max_big, s.bins.big_cap); any_xcd_bins |= s.mode.xcd_bins; }
-    if ((r = grow(&w.bin_pool, &w.bin_pool_bytes, (max_pages ? max_pages : 1) * BIN_PAGE_RECS * sizeof(BinRec))) != MIRHI_OK) return r;
-    {
-        const bool had = w.bin_table != nullptr && w.bin_table_bytes >= (max_tiles ? max_tiles : 1) * BIN_TABLE_ROW * sizeof(uint32_t);
-        if ((r = grow(&w.bin_table, &w.bin_table_bytes, (max_tiles ? max_tiles : 1) * BIN_TABLE_ROW * sizeof(uint32_t))) != MIRHI_OK) return r;
-        if (!had) w.dirty = true;
-    }
+    BinSet::Strides want;
+    want.pages = max_pages ? max_pages : 1; want.tiles = max_tiles ? max_tiles : 1; want.big_cap = max_big ? max_big : 1;
+    // fixed words (big-list and pool counters), then the bin counters: one per tile -- per tile and XCD in scopes with per-XCD bins -- 64 bytes apart
+    want.counter_words = CTR_BINS + (any_xcd_bins ? 8 : 1) * max_tiles * (size_t)BIN_COUNT_STRIDE;
+    if ((r = grow_bins(w.scope_bins, 1, want, false)) != MIRHI_OK) return r;
     w.xcd_tiles_last = (!scopes.empty() && scopes.back().mode.xcd_bins) ? (uint32_t)scopes.back().tiles() : 0u;
-    if ((r = grow(&w.big_recs, &w.big_recs_bytes, (max_big ? max_big : 1) * sizeof(BigRec))) != MIRHI_OK) return r;
-    {
-        size_t counter_bytes = w.counters_words * 4;
-        // fixed words (big-list and pool counters), then the bin counters: one per tile -- per tile and XCD in scopes with per-XCD bins -- 64 bytes apart
-        const size_t want_words = CTR_BINS + (any_xcd_bins ? 8 : 1) * max_tiles * (size_t)BIN_COUNT_STRIDE;
-        const bool had = w.counters && counter_bytes >= want_words * 4;
-        if ((r = grow(&w.counters, &counter_bytes, want_words * 4)) != MIRHI_OK) return r;
-        w.counters_words = counter_bytes / 4;
-        if (!had) w.dirty = true;
-    }
-    if (knobs.always_clear.set) w.dirty = true;             // (A/B runs: the round-2 behaviour, two memsets per recording)
+    if (knobs.always_clear.set) w.scope_bins.dirty = true;             // (A/B runs: the round-2 behaviour, two memsets per recording)
     if (!w.status_host) {
         HIP_TRY(hipHostMalloc((void**)&w.status_host, Workspace::STATUS_WORDS * 4u, hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(hipHostGetDevicePointer((void**)&w.status_dev, w.status_host, 0));
@@ -2900,29 +2966,9 @@ static mirhi_result rearm_workspace(mirhi_cmd* cmd, const std::vector<ScopePlan>
     hand_over_status(cmd);          // an earlier submission's status is not lost to the re-arm below (and may ask for a bigger pool: before the flags are cleared)
     w.grow_pool = false; w.replan = false;
     w.clear_status();
-    w.big_counts = w.counters + CTR_BIG;
-    if (!w.dirty && knobs.verify_idle.set) {
-        // Test hook: what the plan relies on instead of clearing -- every kernel leaves the workspace re-armed -- is checked here, on the
-        // host: all bin and pool counters zero, the big-list counter of the next parity zero, every page-table entry PAGE_EMPTY.
-        HIP_TRY(hipStreamSynchronize(stream));
-        std::vector<uint32_t> c(w.counters_words), t(w.bin_table_bytes / 4);
-        HIP_TRY(hipMemcpy(c.data(), w.counters, c.size() * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(t.data(), w.bin_table, t.size() * 4, hipMemcpyDeviceToHost));
-        size_t bad_c = 0, bad_t = 0;
-        for (size_t i = 0; i < c.size(); i++)       // (the busy-tile counters of the last scope are read and re-armed by the next one)
-            bad_c += (c[i] != 0u && i != (size_t)(CTR_BIG + (w.parity ^ 1u)) && !(i >= CTR_ACTIVE && i < CTR_ACTIVE + 2u * 8u * 32u)) ? 1 : 0;
-        for (uint32_t v : t) bad_t += v != PAGE_EMPTY ? 1 : 0;
-        if (bad_c || bad_t) return fail(MIRHI_ERR_DEVICE, "Vulkan error: workspace not idle between frames: %zu counter words, %zu page-table entries left set", bad_c, bad_t);
-    }
-    if (w.dirty) {
-        HIP_TRY(hipMemsetAsync(w.bin_table, 0xFF, w.bin_table_bytes, stream));          // PAGE_EMPTY
-        HIP_TRY(hipMemsetAsync(w.counters, 0, w.counters_words * 4, stream));
-        cmd->dev->foreign_writes++;
-        w.parity = 0;
-        w.dirty = false;
-        w.mv_dirty = true;      // (whatever asked for the clears asked for those of the view slots too: grow_multiview)
-        cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true;      // (a submit on another stream or queue waits for the clears)
-    }
+    const bool clears = w.scope_bins.dirty;
+    if ((r = rearm_bins(cmd, w.scope_bins, "", stream, knobs)) != MIRHI_OK) return r;
+    if (clears) w.view_bins.dirty = true;      // (whatever asked for the clears asked for those of the view slots too: grow_multiview)
     return MIRHI_OK;
 }
 
@@ -2974,7 +3020,8 @@ static mirhi_result grow_scope_buffers(Workspace& w, const std::vector<RecordedP
         if (scopes[pi].cls.tri_prog && pass.scope.color.format == MIRHI_FORMAT_B8G8R8A8_SRGB) flat_tris = std::max<size_t>(flat_tris, pass.total_tris);
         if (pass.draws.size() > 1) pd = std::max(pd, scopes[pi].tris);
     }
-    if ((r = grow(&w.vs_out, &w.vs_out_bytes, vs_bytes ? vs_bytes : 256)) != MIRHI_OK) return r;
+    if ((r = grow(&w.scope_bins.vs, &w.scope_bins.vs_bytes, vs_bytes ? vs_bytes : 256)) != MIRHI_OK) return r;
+    w.scope_bins.stride.vs_bytes = w.scope_bins.vs_bytes;      // (the one slot's)
     if (carry && (r = grow(&w.carry_depth, &w.carry_depth_bytes, carry)) != MIRHI_OK) return r;
     if (ord && (r = grow(&w.ordered, &w.ordered_bytes, ord)) != MIRHI_OK) return r;
     if (flat_tris && (r = grow(&w.flat_color, &w.flat_color_bytes, flat_tris * 4)) != MIRHI_OK) return r;
@@ -2982,9 +3029,9 @@ static mirhi_result grow_scope_buffers(Workspace& w, const std::vector<RecordedP
     return MIRHI_OK;
 }
 
-// ... and the view slots of the command buffer's multiview scopes (Workspace::mv_*): slices for the most views, each sized for the largest such scope.  A
-// slice that moves (any of the strides grew) or was never used is cleared; otherwise the kernels left it re-armed, which MIRHI_VERIFY_IDLE checks here as
-// rearm_workspace does for the single-view buffers.
+// ... and the view slots of the command buffer's multiview scopes (Workspace::view_bins): slices for the most views, each sized for the largest such scope.  A
+// slice that moves (any of the strides grew) or was never used is cleared; otherwise the kernels left it re-armed, which MIRHI_VERIFY_IDLE checks as it does
+// for the scopes' set.  A command buffer without a multiview scope leaves the set as it is.
 static mirhi_result grow_multiview(mirhi_cmd* cmd, const std::vector<ScopePlan>& scopes, const std::vector<VertexPlan>& vertex, hipStream_t stream, const PlanKnobs& knobs) {
     Workspace& w = cmd->ws;
     size_t slots = 0, pages = 0, tiles = 0, big = 0, vs = 0;
@@ -2995,48 +3042,20 @@ static mirhi_result grow_multiview(mirhi_cmd* cmd, const std::vector<ScopePlan>&
         big = std::max<size_t>(big, scopes[pi].bins.big_cap); vs = std::max(vs, vertex[pi].out_bytes);
     }
     if (!slots) return MIRHI_OK;
-    const size_t words = CTR_BINS + tiles * (size_t)BIN_COUNT_STRIDE;
-    vs = std::max<size_t>(256, (vs + 255) & ~(size_t)255);
+    // One bin counter per tile, without the scopes' set's factor of 8 for per-XCD bins: a multiview scope never has them.  It is depth-only (open_scope: no
+    // colour target), so classify_scope sets own_family (mirhi_scope.h:284, "c.own_family = depth_only || ..."), which makes raster_mode's mesh_only false
+    // (:316), which leaves teams at 1 whatever MIRHI_RASTER_TEAMS says (:318), and ":321  m.xcd_bins = m.teams == 2u && ..." is false.
+    BinSet::Strides want;
+    want.pages = pages; want.tiles = tiles; want.counter_words = CTR_BINS + tiles * (size_t)BIN_COUNT_STRIDE; want.big_cap = big;
+    want.vs_bytes = std::max<size_t>(256, (vs + 255) & ~(size_t)255);
     mirhi_result r;
-    if (slots > w.mv_slots || pages > w.mv_pool_pages || tiles > w.mv_tiles || words > w.mv_counter_words || big > w.mv_big_cap || vs > w.mv_vs_stride) {
-        w.mv_slots = (uint32_t)std::max<size_t>(slots, w.mv_slots); w.mv_pool_pages = std::max(pages, w.mv_pool_pages); w.mv_tiles = std::max(tiles, w.mv_tiles);
-        w.mv_counter_words = std::max(words, w.mv_counter_words); w.mv_big_cap = std::max(big, w.mv_big_cap); w.mv_vs_stride = std::max(vs, w.mv_vs_stride);
-        const size_t n = w.mv_slots;
-        if ((r = grow(&w.mv_pool, &w.mv_pool_bytes, n * w.mv_pool_pages * BIN_PAGE_RECS * sizeof(BinRec))) != MIRHI_OK) return r;
-        if ((r = grow(&w.mv_table, &w.mv_table_bytes, n * w.mv_tiles * BIN_TABLE_ROW * sizeof(uint32_t))) != MIRHI_OK) return r;
-        if ((r = grow(&w.mv_counters, &w.mv_counters_bytes, n * w.mv_counter_words * sizeof(uint32_t))) != MIRHI_OK) return r;
-        if ((r = grow(&w.mv_big, &w.mv_big_bytes, n * w.mv_big_cap * sizeof(BigRec))) != MIRHI_OK) return r;
-        if ((r = grow(&w.mv_vs, &w.mv_vs_bytes, n * w.mv_vs_stride)) != MIRHI_OK) return r;
-        w.mv_dirty = true;
-    }
-    if (!w.mv_dirty && knobs.verify_idle.set) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        const size_t cw = (size_t)w.mv_slots * w.mv_counter_words, tw = (size_t)w.mv_slots * w.mv_tiles * BIN_TABLE_ROW;
-        std::vector<uint32_t> c(cw), t(tw);
-        HIP_TRY(hipMemcpy(c.data(), w.mv_counters, cw * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(t.data(), w.mv_table, tw * 4, hipMemcpyDeviceToHost));
-        size_t bad_c = 0, bad_t = 0;
-        for (size_t j = 0; j < w.mv_slots; j++)
-            for (size_t i = 0; i < w.mv_counter_words; i++)       // (as in rearm_workspace: the last length of the slot's big list, the busy-tile counters)
-                bad_c += (c[j * w.mv_counter_words + i] != 0u && i != (size_t)(CTR_BIG + (((w.mv_parity >> j) & 1u) ^ 1u)) && !(i >= CTR_ACTIVE && i < CTR_ACTIVE + 2u * 8u * 32u)) ? 1 : 0;
-        for (uint32_t v : t) bad_t += v != PAGE_EMPTY ? 1 : 0;
-        if (bad_c || bad_t) return fail(MIRHI_ERR_DEVICE, "Vulkan error: multiview workspace not idle between frames: %zu counter words, %zu page-table entries left set", bad_c, bad_t);
-    }
-    if (w.mv_dirty) {
-        HIP_TRY(hipMemsetAsync(w.mv_table, 0xFF, w.mv_table_bytes, stream));          // PAGE_EMPTY
-        HIP_TRY(hipMemsetAsync(w.mv_counters, 0, w.mv_counters_bytes, stream));
-        cmd->dev->foreign_writes++;
-        w.mv_parity = 0;
-        w.mv_dirty = false;
-        cmd->last_stream = stream; cmd->last_native = nullptr; cmd->pending = true;      // (a submit on another stream or queue waits for the clears)
-    }
-    return MIRHI_OK;
+    if ((r = grow_bins(w.view_bins, slots, want, true)) != MIRHI_OK) return r;
+    return rearm_bins(cmd, w.view_bins, "multiview ", stream, knobs);
 }
 
-// 4. one scope's parameters from its class, mode, bins and the workspace (the draws and vertex jobs are placed by build_plan)
+// 4. one scope's parameters from its class, mode, bins and the workspace (the bin set's slot, the draws and the vertex jobs are placed by place_scope)
 static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, const RasterMode& mode, const Workspace& w, size_t max_tiles, unsigned long long* frag_stats) {
     const ScopeHeader::Target& ci = pass.scope.color;
-    const size_t pool_pages = w.bin_pool_bytes / (BIN_PAGE_RECS * sizeof(BinRec));
     PassParams P;
     memset(&P, 0, sizeof P);
     P.width = ci.width; P.height = ci.height;
@@ -3067,11 +3086,10 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
     if (pass.carry_in) P.depth_load = 1u;
     if (pass.carry_out) P.depth_store = 1u;
     P.prim_out = (uint32_t*)const_cast<uint8_t*>(pass.scope.prim.ptr);
-    P.bin_pool = w.bin_pool; P.bin_count = w.counters + CTR_BINS; P.bin_cap = s.bins.bin_cap;
-    P.bin_table = w.bin_table; P.pool_next = w.counters + CTR_POOL;
-    P.pool_dyn_base = s.bins.fixed_pages; P.pool_dyn_pages = (uint32_t)((pool_pages - s.bins.fixed_pages) / 8);      // per XCD
+    P.bin_cap = s.bins.bin_cap;
+    P.pool_dyn_base = s.bins.fixed_pages;
     P.fixed_recs = s.bins.fixed_per_tile * BIN_PAGE_RECS;
-    P.big_recs = w.big_recs; P.big_count = w.big_counts; P.big_count_next = w.big_counts + 1; P.big_cap = s.bins.big_cap;
+    P.big_cap = s.bins.big_cap;
     P.status = w.status_dev;
     P.frag_stats = frag_stats;
     P.first_prim = pass.first_tri;
@@ -3100,6 +3118,55 @@ static PassParams fill_params(const RecordedPass& pass, const ScopePlan& s, cons
         P.xfer = t.kind; P.xfer_count = t.count; P.xfer_src_format = t.src_format; P.xfer_dst_format = t.dst_format; P.xfer_groups = t.groups;
         memcpy(P.xfer_color, t.color, sizeof P.xfer_color);
         P.tiles_x = t.grid;      // the launch's workgroups (raster_variant: a 1-D grid)
+    }
+    return P;
+}
+
+// `P` for big-list parity `parity` of a slot's counter block (BinSet::Slot::counters): the scope appends large triangles to counter `parity` and counts its busy
+// tiles in that half, and re-arms the other ones for the scope that follows on the slot
+static PassParams with_parity(PassParams P, uint32_t* counters, uint32_t parity) {
+    P.big_count = counters + CTR_BIG + parity;
+    P.big_count_next = counters + CTR_BIG + (parity ^ 1u);
+    P.active = counters + CTR_ACTIVE + parity * 8u * 32u;
+    P.active_prev = counters + CTR_ACTIVE + (parity ^ 1u) * 8u * 32u;
+    return P;
+}
+
+// Places a scope -- or, with `camera`, one view of a multiview scope, which differs in the light matrix's address and the slot alone -- into the parameter
+// image: P bound to slot `b` of a bin set; the plan's draws with vs_out / vs_attr as pointers into the slot's vertex output and their slot_base; the vertex
+// jobs; and the two parity copies of P at `params_at` (the kernels read their parameters from the block).  `at`: where the draws and the jobs go (bytes
+// into the block), moved on behind them.  Returns P as the host keeps it.
+struct BlockCursor { size_t draws, jobs; };
+static PassParams place_scope(Workspace& w, PassParams P, const BinSet::Slot& b, const VertexPlan& v, const float* camera, size_t params_at, BlockCursor& at) {
+    P.bin_pool = b.pool; P.bin_table = b.table; P.bin_count = b.counters + CTR_BINS; P.pool_next = b.counters + CTR_POOL;
+    P.pool_dyn_pages = (uint32_t)((b.pages - P.pool_dyn_base) / 8);      // per XCD
+    P.big_recs = b.big; P.big_count = b.counters + CTR_BIG; P.big_count_next = b.counters + CTR_BIG + 1;
+    P.draws = reinterpret_cast<DrawDesc*>(w.pblock + at.draws);
+    DrawDesc* const img_draws = reinterpret_cast<DrawDesc*>(w.pimage.data() + at.draws);
+    uint32_t slots = 0;
+    for (size_t di = 0; di < v.draws.size(); di++) {
+        DrawDesc dd = v.draws[di];
+        if (camera) dd.camera = camera;
+        if (dd.vs_words) { dd.vs_out = b.vs + ((size_t)(uintptr_t)dd.vs_out - 1); dd.vs_attr = b.vs + ((size_t)(uintptr_t)dd.vs_attr - 1); }      // (vertex_jobs: offset + 1)
+        dd.slot_base = slots; slots += (dd.tri_count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
+        img_draws[di] = dd;
+    }
+    P.total_slots = slots;
+    at.draws += v.draws.size() * sizeof(DrawDesc);
+    P.vs_jobs = reinterpret_cast<VsJob*>(w.pblock + at.jobs);
+    P.num_vs_jobs = (uint32_t)v.jobs.size();
+    VsJob* const img_jobs = reinterpret_cast<VsJob*>(w.pimage.data() + at.jobs);
+    for (size_t k = 0; k < v.jobs.size(); k++) {
+        VsJob job = v.jobs[k];
+        if (camera) job.camera = camera;
+        job.out = b.vs + v.out_off[k];
+        P.vs_total_slots = job.slot_base + (job.count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
+        img_jobs[k] = job;
+    }
+    at.jobs += v.jobs.size() * sizeof(VsJob);
+    for (uint32_t parity = 0; parity < 2; parity++) {
+        const PassParams Q = with_parity(P, b.counters, parity);
+        memcpy(w.pimage.data() + params_at + parity * sizeof(PassParams), &Q, sizeof Q);
     }
     return P;
 }
@@ -3145,126 +3212,51 @@ static mirhi_result build_plan(mirhi_cmd* cmd, bool in_submit) {
     for (const RecordedPass& pass : cmd->passes) { vertex.push_back(vertex_jobs(pass)); jobs_total += vertex.back().jobs.size(); }
     if ((r = grow_scope_buffers(w, cmd->passes, scopes, vertex)) != MIRHI_OK) return r;
     if ((r = grow_multiview(cmd, scopes, vertex, stream, knobs)) != MIRHI_OK) return r;
-    // the parameter block: [2 x PassParams per scope][draw descriptors][transfer regions][vertex jobs], and behind them what the views of multiview scopes
-    // read: [2 x PassParams per view slot][their draw descriptors][their vertex jobs]
-    size_t mv_views = 0, mv_draws = 0, mv_jobs = 0;
+    // the parameter block (BlockLayout)
+    size_t view_slots = 0, view_draws = 0, view_jobs = 0;
     for (size_t pi = 0; pi < n; pi++)
-        if (const uint32_t views = multiview_count(cmd->passes[pi].scope.view_mask)) { mv_views += views; mv_draws += views * cmd->passes[pi].draws.size(); mv_jobs += views * vertex[pi].jobs.size(); }
-    const size_t params_bytes = n * 2 * sizeof(PassParams);
-    w.draws_off = (params_bytes + 255) & ~(size_t)255;
-    const size_t regions_off = (w.draws_off + total_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
-    w.jobs_off = (regions_off + total_regions * sizeof(XferRegion) + 255) & ~(size_t)255;
-    size_t block_bytes = w.jobs_off + jobs_total * sizeof(VsJob);
-    w.mv_params_off = (block_bytes + 255) & ~(size_t)255;
-    const size_t mv_draws_off = (w.mv_params_off + mv_views * 2 * sizeof(PassParams) + 255) & ~(size_t)255;
-    const size_t mv_jobs_off = (mv_draws_off + mv_draws * sizeof(DrawDesc) + 255) & ~(size_t)255;
-    if (mv_views) block_bytes = mv_jobs_off + mv_jobs * sizeof(VsJob);
-    if ((r = pblock_reserve(w, block_bytes ? block_bytes : 256)) != MIRHI_OK) return r;
+        if (const uint32_t views = multiview_count(cmd->passes[pi].scope.view_mask)) { view_slots += views; view_draws += views * cmd->passes[pi].draws.size(); view_jobs += views * vertex[pi].jobs.size(); }
+    const BlockLayout L = w.layout = block_layout(n, total_draws, total_regions, jobs_total, view_slots, view_draws, view_jobs);
+    if ((r = pblock_reserve(w, L.bytes ? L.bytes : 256)) != MIRHI_OK) return r;
     w.params = reinterpret_cast<PassParams*>(w.pblock);
-    DrawDesc* const dev_draws = reinterpret_cast<DrawDesc*>(w.pblock + w.draws_off);
-    VsJob* const dev_jobs = reinterpret_cast<VsJob*>(w.pblock + w.jobs_off);
-    w.pimage.assign(block_bytes, 0);
-    w.draws_count = total_draws;
+    w.pimage.assign(L.bytes, 0);
 
-    size_t draws_done = 0, jobs_done = 0, regions_done = 0, views_done = 0, mv_draws_done = 0, mv_jobs_done = 0;
+    size_t regions_at = L.regions, views_done = 0;
+    BlockCursor scope_at{L.draws, L.jobs}, view_at{L.view_draws, L.view_jobs};
     w.wide_eligible = false;
     cmd->plan.clear(); cmd->plan_programs.clear(); cmd->plan_tris = 0;
     cmd->plan_views.clear(); cmd->plan_view_params.clear();
     for (size_t pi = 0; pi < n; pi++) {
         const ScopePlan& s = scopes[pi];
-        VertexPlan& v = vertex[pi];
+        const VertexPlan& v = vertex[pi];
+        const RecordedPass& pass = cmd->passes[pi];
         // (the mode is evaluated again, not kept from step 1: hand_over_status in between may have changed w.spread / w.wide)
         const RasterMode mode = raster_mode(s.cls, s.density_tiles(), s.tris, w.spread, w.wide, knobs, s.area.partial);
         w.wide_eligible |= mode.wide_eligible;
-        PassParams P = fill_params(cmd->passes[pi], s, mode, w, max_tiles, dev->frag_stats);
-        P.draws = dev_draws + draws_done;
-        P.vs_jobs = dev_jobs + jobs_done;
-        P.num_vs_jobs = (uint32_t)v.jobs.size();
-        VsJob* const img_jobs = reinterpret_cast<VsJob*>(w.pimage.data() + w.jobs_off) + jobs_done;
-        for (size_t j = 0; j < v.jobs.size(); j++) {
-            v.jobs[j].out = w.vs_out + v.out_off[j];
-            P.vs_total_slots = v.jobs[j].slot_base + (v.jobs[j].count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
-            img_jobs[j] = v.jobs[j];
-        }
-        jobs_done += v.jobs.size();
-        uint32_t slots = 0;
-        for (DrawDesc& dd : v.draws) {
-            if (dd.vs_words) { dd.vs_out = w.vs_out + ((size_t)(uintptr_t)dd.vs_out - 1); dd.vs_attr = w.vs_out + ((size_t)(uintptr_t)dd.vs_attr - 1); }
-            dd.slot_base = slots; slots += (dd.tri_count + GEOM_THREADS - 1) / GEOM_THREADS * GEOM_THREADS;
-        }
-        P.total_slots = slots;
-        if (!v.draws.empty()) memcpy(w.pimage.data() + w.draws_off + draws_done * sizeof(DrawDesc), v.draws.data(), v.draws.size() * sizeof(DrawDesc));
-        draws_done += v.draws.size();
+        PassParams P = fill_params(pass, s, mode, w, max_tiles, dev->frag_stats);
         if (P.xfer) {
-            const std::vector<XferRegion>& regions = cmd->passes[pi].xfer_regions;
-            P.xfer_regions = reinterpret_cast<const XferRegion*>(w.pblock + regions_off) + regions_done;
-            memcpy(w.pimage.data() + regions_off + regions_done * sizeof(XferRegion), regions.data(), regions.size() * sizeof(XferRegion));
-            regions_done += regions.size();
+            P.xfer_regions = reinterpret_cast<const XferRegion*>(w.pblock + regions_at);
+            memcpy(w.pimage.data() + regions_at, pass.xfer_regions.data(), pass.xfer_regions.size() * sizeof(XferRegion));
+            regions_at += pass.xfer_regions.size() * sizeof(XferRegion);
         }
-        cmd->plan.push_back(P);
+        // copy `parity` of scope pi appends large triangles to counter `parity` and re-arms the other one for the scope that follows on the scopes' bins
+        cmd->plan.push_back(place_scope(w, P, w.scope_bins.slot(0), v, nullptr, L.scope_params(pi, 0), scope_at));
         cmd->plan_programs.push_back(s.cls.programs);
         cmd->plan_tris += s.tris;
-        // the kernels read their parameters from the block: copy 2*pi + parity of scope pi appends large triangles to counter
-        // `parity` and re-arms the other one for the scope that follows on this workspace
-        for (uint32_t parity = 0; parity < 2; parity++) {
-            PassParams Q = P;
-            Q.big_count = w.big_counts + parity;
-            Q.big_count_next = w.big_counts + (parity ^ 1u);
-            Q.active = w.counters + CTR_ACTIVE + parity * 8u * 32u;
-            Q.active_prev = w.counters + CTR_ACTIVE + (parity ^ 1u) * 8u * 32u;
-            memcpy(w.pimage.data() + (2 * pi + parity) * sizeof(PassParams), &Q, sizeof Q);
-        }
-        // A multiview scope: the parameters above once per view slot -- depth base = the view's layer, bins / page table / counters / big list / vertex output /
-        // status words = the slot's (Workspace::mv_*) -- with copies of the draws and vertex jobs that differ in the light matrix's address (and in where the
-        // slot's shaded vertices are) alone.  (plan[pi] itself stays: the host's idea of the scope's launch shape; its device copies are not launched.)
+        // A multiview scope: the same once per view slot -- depth base = the view's layer, status words and bins = the slot's (Workspace::view_bins), the light
+        // matrix = the view's.  (plan[pi] itself stays: the host's idea of the scope's launch shape; its device copies are not launched.)
         mirhi_cmd::ViewSet vset;
-        const RecordedPass& pass = cmd->passes[pi];
         if (pass.scope.view_mask) {
             MultiviewSlot slot[MAX_BATCH];
             vset.count = multiview_slots(pass.scope.view_mask, pass.scope.color.width, pass.scope.color.height, 0u, pass.scope.view_stride, slot);
             vset.first = views_done;
             for (uint32_t j = 0; j < vset.count; j++) {
-                const float* matrix = reinterpret_cast<const float*>(pass.scope.view_base + slot[j].matrix_offset);
-                uint8_t* const vs_base = w.mv_vs + (size_t)j * w.mv_vs_stride;
-                uint32_t* const ctr = w.mv_counters + (size_t)j * w.mv_counter_words;
+                const BinSet::Slot b = w.view_bins.slot(j);
                 PassParams V = P;
                 V.depth = reinterpret_cast<float*>(const_cast<uint8_t*>(pass.scope.depth.ptr) + slot[j].layer_offset);
-                V.bin_pool = w.mv_pool + (size_t)j * w.mv_pool_pages * BIN_PAGE_RECS;
-                V.bin_table = w.mv_table + (size_t)j * w.mv_tiles * BIN_TABLE_ROW;
-                V.bin_count = ctr + CTR_BINS; V.pool_next = ctr + CTR_POOL;
-                V.pool_dyn_pages = (uint32_t)((w.mv_pool_pages - s.bins.fixed_pages) / 8);
-                V.big_recs = w.mv_big + (size_t)j * w.mv_big_cap;
                 V.status = w.status_dev + Workspace::STATUS_VIEWS + 4u * j;
-                V.draws = reinterpret_cast<DrawDesc*>(w.pblock + mv_draws_off) + mv_draws_done;
-                DrawDesc* const img_draws = reinterpret_cast<DrawDesc*>(w.pimage.data() + mv_draws_off) + mv_draws_done;
-                for (size_t di = 0; di < v.draws.size(); di++) {
-                    DrawDesc c = v.draws[di];
-                    c.camera = matrix;
-                    if (c.vs_words) {
-                        c.vs_out = vs_base + (static_cast<const uint8_t*>(c.vs_out) - w.vs_out);
-                        c.vs_attr = vs_base + (static_cast<const uint8_t*>(c.vs_attr) - w.vs_out);
-                    }
-                    img_draws[di] = c;
-                }
-                mv_draws_done += v.draws.size();
-                V.vs_jobs = reinterpret_cast<VsJob*>(w.pblock + mv_jobs_off) + mv_jobs_done;
-                VsJob* const img_view_jobs = reinterpret_cast<VsJob*>(w.pimage.data() + mv_jobs_off) + mv_jobs_done;
-                for (size_t k = 0; k < v.jobs.size(); k++) {
-                    VsJob job = v.jobs[k];
-                    job.camera = matrix;
-                    job.out = vs_base + v.out_off[k];
-                    img_view_jobs[k] = job;
-                }
-                mv_jobs_done += v.jobs.size();
-                for (uint32_t parity = 0; parity < 2; parity++) {
-                    PassParams Q = V;
-                    Q.big_count = ctr + CTR_BIG + parity;
-                    Q.big_count_next = ctr + CTR_BIG + (parity ^ 1u);
-                    Q.active = ctr + CTR_ACTIVE + parity * 8u * 32u;
-                    Q.active_prev = ctr + CTR_ACTIVE + (parity ^ 1u) * 8u * 32u;
-                    if (parity == 0u) cmd->plan_view_params.push_back(Q);
-                    memcpy(w.pimage.data() + w.mv_params_off + (2 * (views_done + j) + parity) * sizeof(PassParams), &Q, sizeof Q);
-                }
+                V = place_scope(w, V, b, v, reinterpret_cast<const float*>(pass.scope.view_base + slot[j].matrix_offset), L.slot_params(views_done + j, 0), view_at);
+                cmd->plan_view_params.push_back(with_parity(V, b.counters, 0u));      // (the host's copy is the parity-0 one)
             }
             views_done += vset.count;
         }
@@ -3351,11 +3343,7 @@ static mirhi_result stats_params_for(mirhi_cmd* c) {
     std::vector<PassParams> copies;
     for (const PassParams& P0 : c->plan)
         for (uint32_t parity = 0; parity < 2; parity++) {
-            PassParams P = P0;
-            P.big_count = w.big_counts + parity;
-            P.big_count_next = w.big_counts + (parity ^ 1u);
-            P.active = w.counters + CTR_ACTIVE + parity * 8u * 32u;
-            P.active_prev = w.counters + CTR_ACTIVE + (parity ^ 1u) * 8u * 32u;
+            PassParams P = with_parity(P0, w.scope_bins.slot(0).counters, parity);      // (in the order of the block's copies: BlockLayout::scope_params)
             P.prim_out = w.stats_prim;
             P.resolve_flat_only = 0u;
             copies.push_back(P);
@@ -3629,9 +3617,9 @@ static mirhi_result issue_batch(Submit& s, uint32_t cmd_count, mirhi_cmd* const*
         mirhi_cmd* c = cmds[i];
         { const mirhi_result rc = claim_cmd(dev, c, stream, nullptr); if (rc != MIRHI_OK) return rc; }
         P[i] = &c->plan[0];
-        dp[i] = c->ws.params + c->ws.parity;
-        big[i] = c->ws.big_counts + c->ws.parity;
-        c->ws.parity ^= 1u;
+        const uint32_t parity = c->ws.scope_bins.take_parity(0);
+        dp[i] = c->ws.params + parity;
+        big[i] = c->ws.scope_bins.slot(0).counters + CTR_BIG + parity;
         dev->stats.frames_submitted++;
         dev->stats.triangles_submitted += c->plan[0].total_tris;
     }
@@ -3654,13 +3642,11 @@ static mirhi_result issue_multiview(Submit& s, mirhi_cmd* c, size_t pi, hipStrea
     const mirhi_cmd::ViewSet& vs = c->plan_views[pi];
     Workspace& w = c->ws;
     const PassParams* hp[MAX_BATCH]; const PassParams* dp[MAX_BATCH]; uint32_t* big[MAX_BATCH];
-    const PassParams* const dev_views = reinterpret_cast<const PassParams*>(w.pblock + w.mv_params_off);
     for (uint32_t j = 0; j < vs.count; j++) {
-        const uint32_t parity = (w.mv_parity >> j) & 1u;
+        const uint32_t parity = w.view_bins.take_parity(j);
         hp[j] = &c->plan_view_params[vs.first + j];
-        dp[j] = dev_views + 2 * (vs.first + j) + parity;
-        big[j] = hp[j]->big_count + parity;      // (the host copy is the parity-0 one)
-        w.mv_parity ^= 1u << j;
+        dp[j] = reinterpret_cast<const PassParams*>(w.pblock + w.layout.slot_params(vs.first + j, parity));
+        big[j] = w.view_bins.slot(j).counters + CTR_BIG + parity;
     }
     const PassParams& P = *hp[0];
     LaunchTiming tv{}, tg{}, tr{};
@@ -3696,9 +3682,10 @@ static mirhi_result issue_scope(Submit& s, mirhi_cmd* c, size_t pi, hipStream_t 
     mirhi_device* dev = s.dev;
     const PassParams& P = c->plan[pi];
     // alternate the big-list counter: the raster kernel zeroes the other one for the next scope
-    const PassParams* dp = c->ws.params + 2 * pi + c->ws.parity;
-    uint32_t* big_count = c->ws.big_counts + c->ws.parity;
-    if (flips_parity(P)) c->ws.parity ^= 1u;
+    BinSet& bins = c->ws.scope_bins;
+    const uint32_t parity = flips_parity(P) ? bins.take_parity(0) : bins.parity_of(0);
+    const PassParams* dp = reinterpret_cast<const PassParams*>(c->ws.pblock + BlockLayout::scope_params(pi, parity));
+    uint32_t* big_count = bins.slot(0).counters + CTR_BIG + parity;
     // ordered segment: slots of primitives that no draw of the segment covers (a Never draw keeps its ids) must read
     // as "no coverage" -- an all-zero record is a degenerate triangle whose edge functions are negative everywhere
     if (P.ordered_recs && P.ordered_count) HIP_TRY(hipMemsetAsync(P.ordered_recs, 0, (size_t)P.ordered_count * sizeof(TriRec), stream));
@@ -3864,7 +3851,7 @@ static mirhi_result status_of(mirhi_device* dev, mirhi_cmd* c) {
             if (want != cur && c->ws.wide_eligible && !PlanKnobs::read().raster_wide.set) { c->ws.wide = want; c->ws.replan = true; }
         }
         if (feedback && !c->ws.spread && c->ws.xcd_tiles_last && c->ws.status_host[2] > 2u * c->ws.xcd_tiles_last) { c->ws.spread = true; c->ws.replan = true; c->ws.spread_tris = c->plan_tris; }
-        if (bits & (STATUS_PAGE_TIMEOUT | STATUS_BIG_OVERFLOW)) c->ws.dirty = true;     // counters / page table are cleared before the next frame
+        if (bits & (STATUS_PAGE_TIMEOUT | STATUS_BIG_OVERFLOW)) c->ws.scope_bins.dirty = true;    // counters / page table are cleared before the next frame
         if (bits & STATUS_PAGE_TIMEOUT)
             r = fail(MIRHI_ERR_DEVICE, "Vulkan error: rasterizer bin page was never published; frame is incomplete");
         if (bits & STATUS_ALPHA_TEST_TEXTURED)
