@@ -23,6 +23,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <stdint.h>
+#include <atomic>
+#include <mutex>
+#include <string>
 
 #include "mirhi_device.h"
 #include "mirhi_launch.h"
@@ -113,6 +116,19 @@ hipError_t launch_geometry(const PassParams& P, const PassParams* dev_params, hi
 // ---- the raster launch: raster_variant (mirhi_variant.h) chooses, the two tables below turn the choice into a kernel entry --------
 // Each table names every instantiation of its kernels exactly once (nothing else in this file refers to them): the set of raster kernels in the code object
 // is the set of rows, and the code object holds them in the order of the rows.
+// A record of what the three raster launchers launched (mirhi_debug_raster_trace below; tests/test_gpu_variant_ledger.py): the chosen entry's name, appended
+// after the entry is found and before the launch, on either dispatch path.  Off: one relaxed load per raster launch; the mutex is taken only when on (the
+// submit thread launches too).
+static std::atomic<uint32_t> g_raster_trace_on{0u};
+static std::mutex g_raster_trace_mutex;
+static std::string g_raster_trace;          // the names, each followed by '\n'
+static uint32_t g_raster_trace_count = 0u;
+static inline void raster_trace(const char* name) {
+    if (!g_raster_trace_on.load(std::memory_order_relaxed)) return;
+    std::lock_guard<std::mutex> lock(g_raster_trace_mutex);
+    g_raster_trace += name; g_raster_trace += '\n'; g_raster_trace_count++;
+}
+
 struct RasterEntry { uint32_t id; const char* name; void (*kernel)(const PassParams*, const RasterHead); };      // id: RasterVariant::kernel_id
 #define ORDERED(P) {raster_kernel_id(RASTER_ORDERED, P, 0, 0, 1, 0, 4), "ordered_kernel<" #P ">", ordered_kernel<P>}
 #define OWN(FAMILY, KERNEL, K, T) {raster_kernel_id(FAMILY, 0, K, T, 1, 0, 4), #KERNEL "<" #K ", " #T ">", KERNEL<K, T>}
@@ -199,6 +215,7 @@ hipError_t launch_raster(const PassParams& P, const PassParams* dev_params, uint
     const RasterHead H = v.family == RASTER_ORDERED ? ordered_head(P, big_count) : raster_head(P, big_count);
     const RasterEntry* e = raster_entry(v);
     if (!e) return hipErrorInvalidDeviceFunction;       // (a variant without a kernel: the selector and the table disagree)
+    raster_trace(e->name);
     MIRHI_LAUNCH(e->kernel, dim3(v.grid[0], v.grid[1], v.grid[2]), dim3(v.block), stream, t, dev_params, H);
     return launch_result();
 }
@@ -250,6 +267,7 @@ hipError_t launch_raster_batch(const PassParams* const* Ps, const PassParams* co
     const RasterVariant v = raster_variant(P, programs, true);
     const RasterBatchEntry* e = raster_batch_entry(v);
     if (!e) return hipErrorInvalidDeviceFunction;
+    raster_trace(e->name);
     RasterBatch B{};
     for (uint32_t i = 0; i < n; i++) { B.params[i] = dev_params[i]; B.head[i] = raster_head(*Ps[i], big_count[i]); }
     MIRHI_LAUNCH(e->kernel, dim3(v.grid[0], v.grid[1], n), dim3(v.block), stream, t, B);
@@ -299,6 +317,7 @@ hipError_t launch_multiview_raster(const PassParams* const* Ps, const PassParams
     const RasterVariant v = multiview_variant(P, n);
     const RasterBatchEntry* e = raster_view_entry(v);
     if (!e) return hipErrorInvalidDeviceFunction;
+    raster_trace(e->name);
     RasterBatch B{};
     for (uint32_t i = 0; i < n; i++) { B.params[i] = dev_params[i]; B.head[i] = raster_head(*Ps[i], big_count[i]); }
     MIRHI_LAUNCH(e->kernel, dim3(v.grid[0], v.grid[1], v.grid[2]), dim3(v.block), stream, t, B);
@@ -354,6 +373,28 @@ extern "C" int mirhi_debug_raster_choice_seamless(const uint32_t in[12], uint32_
     snprintf(name, name_len, "%s", e->name);
     grid_block[0] = v.grid[0]; grid_block[1] = v.grid[1]; grid_block[2] = v.grid[2]; grid_block[3] = v.block;
     return 0;
+}
+// Outside the C ABI and without a HIP call: the name of row `row` of the launch tables above -- table 0 k_raster_entries, 1 k_raster_batch_entries,
+// 2 k_raster_view_entries.  Returns 1 past the end of the table (and for a table that does not exist).
+extern "C" int mirhi_debug_raster_table(uint32_t table, uint32_t row, char* name, uint32_t name_len) {
+    const char* n = nullptr;
+    if (table == 0u && row < sizeof k_raster_entries / sizeof k_raster_entries[0]) n = k_raster_entries[row].name;
+    if (table == 1u && row < sizeof k_raster_batch_entries / sizeof k_raster_batch_entries[0]) n = k_raster_batch_entries[row].name;
+    if (table == 2u && row < sizeof k_raster_view_entries / sizeof k_raster_view_entries[0]) n = k_raster_view_entries[row].name;
+    if (!n) return 1;
+    snprintf(name, name_len, "%s", n);
+    return 0;
+}
+// The record of raster launches (raster_trace above): on / off (turning it on or off keeps what is recorded), and read-and-clear -- returns the number of launches
+// since the last read and writes their entry names, '\n'-joined in launch order, as far as out_len allows (always terminated when out_len > 0).
+extern "C" void mirhi_debug_raster_trace(uint32_t enable) { g_raster_trace_on.store(enable ? 1u : 0u, std::memory_order_relaxed); }
+extern "C" uint32_t mirhi_debug_raster_trace_read(char* out, uint32_t out_len) {
+    std::lock_guard<std::mutex> lock(g_raster_trace_mutex);
+    if (!g_raster_trace.empty()) g_raster_trace.pop_back();      // (joined, not terminated)
+    if (out && out_len) snprintf(out, out_len, "%s", g_raster_trace.c_str());
+    const uint32_t n = g_raster_trace_count;
+    g_raster_trace.clear(); g_raster_trace_count = 0u;
+    return n;
 }
 // The device's table of cube edge neighbours (ibl_seamless_tap, mirhi_ibl_sample.hip.h), as plain host code: tap (i, j) of `face` at a level of n x n texels ->
 // out[0] the texel's offset from the level's first texel, out[1] 1 for a corner tap.  A test compares it with the float64 model's re-projection.
